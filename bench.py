@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- plots/s of one full training step of the PointNet2 hot path on synthetic 32k-point plots.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+    python bench.py --full                  (the headline plus every other figure: roofline, secondary legs, CPU baseline)
     python bench.py --gpus N ...            (no launcher: bench.py starts its N ranks itself, one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -12,9 +13,12 @@ A step = zero_grad -> PointNet2.forward -> project_to_plotwise_coverages -> loss
 -> backward -> [one RCCL all-reduce of the flat 60 KB gradient when N > 1] -> Adam step
 (the step of /root/reference/learning/train.py:52-66).  Plots are sharded over ranks (weak scaling), no other collective.
 
-Prints ONE JSON line on rank 0 with the contract's fields plus
+A plain run sets up, warms up, times the --steps steps and prints ONE JSON line on rank 0 with the contract's fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, loss, config).  --dump-outputs DIR also writes what the timed
+path computed in its last step (`dump_outputs`).  --full adds everything else, measured after the timed region:
   "roofline"     for the dominant entry point of the step (HIP-event timed inside the timed region),
   "kernels"      per-entry-point ms/step and algorithmic GB/s from one instrumented step after the timed region,
+  "unpipelined", "measured_peaks", "secondary" (the other BASELINE configurations and the reference's loops as written),
   "cpu_baseline" the oracle (CPU restatement of the reference path) timed on this host on a bounded sample.
 """
 import argparse
@@ -764,6 +768,43 @@ def secondary_legs(dev):
             "exchange_world1": lambda: exchange_leg(dev)}
 
 
+def _train_state_tensors(model, opt):
+    """Everything a training step reads and writes besides its batch: parameters (views of `opt.flat`), BatchNorm buffers,
+    the optimiser's moments and step words."""
+    return [opt.flat, opt.exp_avg, opt.exp_avg_sq, opt.step_words] + [b for _, b in model.named_buffers()]
+
+
+def train_state(model, opt):
+    return [t.detach().clone() for t in _train_state_tensors(model, opt)]
+
+
+def set_train_state(model, opt, saved):
+    with torch.no_grad():
+        for dst, src in zip(_train_state_tensors(model, opt), saved):
+            dst.copy_(src)
+
+
+def dump_outputs(path, loss, grad, model, opt):
+    """--dump-outputs: what the timed path's step computes, as a caller of the step receives it -- the loss, the flat parameter
+    gradient (`grad`), the model's state after the step (parameters and BatchNorm running statistics, `state.<key>`) and the
+    optimiser's state (`adam.*`) -- one DIR/<name>.npy each, float32 (float64 for the loss and the counters), ~0.3 MB in all.
+    main() takes these from one more execution of the timed path's own step (the same captured graph / loop) right after the
+    timed region, on the seeded state the run STARTED from and the batch of the next slot: the weights at the end of the
+    region are not the same from run to run -- the backward adds its weight gradients with float atomics (1e-6 relative,
+    DESIGN.md) and training amplifies that, a ReLU mask next to zero flips, and two runs of `--steps 20 --warmup 5` ended at
+    losses 0.3039 and 0.3092 -- while one step from the same weights and batch gives the same outputs up to rounding.  So two
+    runs, or two builds, can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss, "grad": grad, "adam.exp_avg": opt.exp_avg, "adam.exp_avg_sq": opt.exp_avg_sq,
+              "adam.step": opt.step_words[:1]}
+    arrays.update({f"state.{k}": v for k, v in model.state_dict().items()})
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype in (torch.float64, torch.int64, torch.int32) else t.float()
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    log(f"outputs of the timed step from the seeded start: {len(arrays)} arrays in {path}")
+
+
 def main():
     global N_POINTS
     ap = argparse.ArgumentParser()
@@ -772,7 +813,12 @@ def main():
     # start ran before the timer), ~0.5 ms that 50 steps showed as +0.012 ms per step
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what the headline does not need: the roofline and per-entry-point "
+                         "table, the unpipelined step, the chip's measured peaks, the secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--eager", action="store_true", help="do not capture the feature passes into hipGraphs")
     ap.add_argument("--serial", action="store_true",
                     help="headline = the unpipelined step (geometry and features of a batch back to back on one stream)")
@@ -803,9 +849,11 @@ def main():
                     help="run ONE secondary leg by name and print its JSON (no headline): config2_3sa_arch, config5_128k_f32, "
                          "config5_128k_bf16, config4_parcel_inference, config4_parcel_inference_bf16, dropin_eager -- for profiling and experiments")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs (BASELINE configs 2 (3sa-arch), 4, 5 and the eager drop-in loop) that a default "
+                    help="skip the secondary legs (BASELINE configs 2 (3sa-arch), 4, 5 and the eager drop-in loop) that a --full "
                          "single-GPU run of the metric's workload attaches under \"secondary\"")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -837,6 +885,8 @@ def main():
         legs = secondary_legs(dev)
         if a.only_leg not in legs:
             raise SystemExit(f"--only-leg: one of {sorted(legs)}")
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs writes the headline's outputs: not with --only-leg")
         emit_record({a.only_leg: legs[a.only_leg]()})
         return
     B, N_POINTS = a.plots, a.points
@@ -847,6 +897,7 @@ def main():
         a.exchange = "rccl"
     w = build_training(dev, local_rank, rank, world, B, N_POINTS, a.arch, a.dtype, n_slots, exchange=a.exchange)
     args, model, opt, slots, feature_step = w.args, w.model, w.opt, w.slots, w.feature_step
+    start_state = train_state(model, opt) if a.dump_outputs else None       # the seeded start (dump_outputs)
     data = slots[0]
 
     if hasattr(model, "geometry_fork"):
@@ -864,30 +915,38 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # ---- first step instrumented per entry point (also warms every kernel up)
-    log("inputs resident; first (instrumented) step")
-    with ops.timing() as t0:
-        step()
-    prof = t0.summary()
-    log("first step done: " + ", ".join(f"{k} {v[1]:.3f} ms" for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:6]))
-    step()
-    # which entry point gets the roofline: the longest one ON THE CRITICAL PATH of the timed mode.  Pipelined: the
-    # geometry passes (FPS, ball query, 3-NN) run on side streams under the feature pass, which is what bounds the step, so
-    # the candidates are the feature-pass entry points; serial: every entry point.  Measured on a second (warm) step.
-    # (the shortest of three warm steps per entry point: a single measurement once made the 8 us Adam kernel the "longest"
-    # entry point -- an event record that waited on something else)
-    prof = {}
-    for _ in range(3):
-        with ops.timing() as t1:
+    # ---- five unpipelined eager steps (they also warm every kernel up); with --full the first and the last three are
+    # instrumented per entry point.  A plain run takes the same five steps uninstrumented (the executor's one-call path: the
+    # same bits), so both start the timed region from the same weights.
+    dominant = longest_geometry = None
+    if not a.full:
+        log("inputs resident; five eager warm-up steps")
+        for _ in range(5):
             step()
-        for k, v in t1.summary().items():
-            if k not in prof or v[1] < prof[k][1]:
-                prof[k] = v
-    GEOMETRY = ("sn2_fps", "sn2_ball_query", "sn2_three_nn", "sn2_interp_index", "sn2_sa_order", "sn2_count_sum")
-    on_path = {k: v for k, v in prof.items() if a.serial or not k.startswith(GEOMETRY)}
-    dominant = max(on_path, key=lambda k: on_path[k][1]) if on_path else None
-    longest_geometry = max((k for k in prof if k.startswith(GEOMETRY)), key=lambda k: prof[k][1], default=None)
-    log(f"roofline entry point: {dominant}; longest geometry entry point: {longest_geometry}")
+    else:
+        log("inputs resident; first (instrumented) step")
+        with ops.timing() as t0:
+            step()
+        prof = t0.summary()
+        log("first step done: " + ", ".join(f"{k} {v[1]:.3f} ms" for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:6]))
+        step()
+        # which entry point gets the roofline: the longest one ON THE CRITICAL PATH of the timed mode.  Pipelined: the
+        # geometry passes (FPS, ball query, 3-NN) run on side streams under the feature pass, which is what bounds the step, so
+        # the candidates are the feature-pass entry points; serial: every entry point.  Measured on a second (warm) step.
+        # (the shortest of three warm steps per entry point: a single measurement once made the 8 us Adam kernel the "longest"
+        # entry point -- an event record that waited on something else)
+        prof = {}
+        for _ in range(3):
+            with ops.timing() as t1:
+                step()
+            for k, v in t1.summary().items():
+                if k not in prof or v[1] < prof[k][1]:
+                    prof[k] = v
+        GEOMETRY = ("sn2_fps", "sn2_ball_query", "sn2_three_nn", "sn2_interp_index", "sn2_sa_order", "sn2_count_sum")
+        on_path = {k: v for k, v in prof.items() if a.serial or not k.startswith(GEOMETRY)}
+        dominant = max(on_path, key=lambda k: on_path[k][1]) if on_path else None
+        longest_geometry = max((k for k in prof if k.startswith(GEOMETRY)), key=lambda k: prof[k][1], default=None)
+        log(f"roofline entry point: {dominant}; longest geometry entry point: {longest_geometry}")
 
     def capture_serial():
         """the whole unpipelined step as ONE hipGraph (single GPU only: no collective inside a graph); the three
@@ -961,10 +1020,13 @@ def main():
         for _ in range(a.steps):
             graph.replay()
         loss = loss_static
-    else:
+    elif a.full:
         with ops.timing({dominant}) as tdom:   # 2 event records per step on the dominant entry point only
             for _ in range(a.steps):
                 loss = step()
+    else:
+        for _ in range(a.steps):
+            loss = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
     barrier()
@@ -978,47 +1040,70 @@ def main():
         ops.fps_gave_up(dev)                     # (the region is over: reading the status word costs nothing now)
         ops.global_level_gave_up(dev)
     loss_value = float(loss.item())
-    if tdom is None:
-        # graph replays / side streams cannot carry the event records: time the dominant entry point over 5 unpipelined
-        # eager steps right after the timed region
-        with ops.timing({dominant, longest_geometry}) as tdom:
-            for _ in range(5):
-                step()
-    dom = tdom.summary()
+    geometry_passes = None if pipe is None else (pipe.issued - issued0) // pipe.group
+    if a.dump_outputs:
+        # the timed path's step once more, on the seeded state the run started from (dump_outputs says why); every rank takes
+        # it (the exchange is a collective), rank 0 writes; then the state the timed region left is put back
+        left = train_state(model, opt)
+        set_train_state(model, opt, start_state)
+        if pipe is not None:
+            dump_loss = pipe.step()
+            pipe.drain()
+            dump_grad = pipe.flat_grad[(pipe.done - 1) % pipe.slots]
+        elif graph is not None:
+            graph.replay()
+            dump_loss, dump_grad = loss_static, model._last_flat_grad
+        else:
+            dump_loss = step()
+            dump_grad = model._last_flat_grad
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, dump_loss, dump_grad, model, opt)
+        set_train_state(model, opt, left)
 
-    # ---- secondary figure (NOT `value`): the unpipelined step as one hipGraph, the latency of a single batch
-    serial_ms = None
-    if pipe is not None and world == 1 and not a.eager:
-        try:
-            g1, _ = capture_serial()
-            torch.cuda.synchronize()
-            t0s = time.perf_counter()
-            for _ in range(a.steps):
-                g1.replay()
-            torch.cuda.synchronize()
-            serial_ms = (time.perf_counter() - t0s) / a.steps * 1e3
-            log(f"unpipelined step (one hipGraph): {serial_ms:.3f} ms/step")
-        except Exception as exc:                     # noqa: BLE001
-            log(f"serial capture failed ({type(exc).__name__}: {exc})")
-            torch.cuda.synchronize()
+    # ---- --full only: the figures beside the headline
+    if a.full:
+        if tdom is None:
+            # graph replays / side streams cannot carry the event records: time the dominant entry point over 5 unpipelined
+            # eager steps right after the timed region
+            with ops.timing({dominant, longest_geometry}) as tdom:
+                for _ in range(5):
+                    step()
+        dom = tdom.summary()
 
-    # ---- one fully instrumented step for the per-entry-point table (after the timed region)
-    with ops.timing() as tall:
-        step()
-    table = tall.summary()
-    e1 = e2 = 0
-    with torch.no_grad():
-        _, _, saved = model._forward_impl(data["xyz"], data["cloud"], data["fps_start"], False)
-        e1, e2 = int(saved.tot1.item()), int(saved.tot2.item())
-        m1, m2 = saved.M1, saved.M2
+        # ---- secondary figure (NOT `value`): the unpipelined step as one hipGraph, the latency of a single batch
+        serial_ms = None
+        if pipe is not None and world == 1 and not a.eager:
+            try:
+                g1, _ = capture_serial()
+                torch.cuda.synchronize()
+                t0s = time.perf_counter()
+                for _ in range(a.steps):
+                    g1.replay()
+                torch.cuda.synchronize()
+                serial_ms = (time.perf_counter() - t0s) / a.steps * 1e3
+                log(f"unpipelined step (one hipGraph): {serial_ms:.3f} ms/step")
+            except Exception as exc:                     # noqa: BLE001
+                log(f"serial capture failed ({type(exc).__name__}: {exc})")
+                torch.cuda.synchronize()
 
-    peaks, dom_alone_ms = None, None
-    if rank == 0 and world == 1:
-        if dominant == "sn2_fp_backward:34+8->34":
-            dom_alone_ms = dominant_kernel_alone(step, dev, opt=opt)
-        log("measured peaks (stream copy / read, MFMA fp32 / bf16)")
-        peaks = measured_peaks(dev)
-        log("  " + json.dumps({k: v for k, v in peaks.items() if k.endswith(("GBps", "TFLOPs"))}))
+        # ---- one fully instrumented step for the per-entry-point table (after the timed region)
+        with ops.timing() as tall:
+            step()
+        table = tall.summary()
+        e1 = e2 = 0
+        with torch.no_grad():
+            _, _, saved = model._forward_impl(data["xyz"], data["cloud"], data["fps_start"], False)
+            e1, e2 = int(saved.tot1.item()), int(saved.tot2.item())
+            m1, m2 = saved.M1, saved.M2
+
+        peaks, dom_alone_ms = None, None
+        if rank == 0 and world == 1:
+            if dominant == "sn2_fp_backward:34+8->34":
+                dom_alone_ms = dominant_kernel_alone(step, dev, opt=opt)
+            log("measured peaks (stream copy / read, MFMA fp32 / bf16)")
+            peaks = measured_peaks(dev)
+            log("  " + json.dumps({k: v for k, v in peaks.items() if k.endswith(("GBps", "TFLOPs"))}))
     ranks_seen = world
     if world > 1:
         one = torch.ones(1, device=dev)
@@ -1026,44 +1111,6 @@ def main():
         ranks_seen = int(one.item())
     if rank == 0:
         ms = elapsed / a.steps * 1e3
-        kernels = []
-        for k, (c, tms) in sorted(table.items(), key=lambda kv: -kv[1][1]):
-            by = algorithmic_bytes(k, B, N_POINTS, m1, m2, e1, e2)
-            kernels.append({"entry": k, "ms": round(tms, 4),
-                            "alg_GBps": None if by is None else round(by / (tms * 1e-3) / 1e9, 1)})
-        CALLS_PER_STEP = {"sn2_interp_index": 3, "sn2_sa_order": 2}     # entry points whose byte model covers all their calls of a step
-
-        def roofline_of(entry, note):
-            if not entry or entry not in dom:
-                return None
-            c, tms = dom[entry]
-            avg_ms = tms / (c / CALLS_PER_STEP.get(entry, 1))
-            by = algorithmic_bytes(entry, B, N_POINTS, m1, m2, e1, e2)
-            ach = None if by is None else by / (avg_ms * 1e-3) / 1e9
-            traffic, tsrc = pmc_traffic(entry)
-            return {"kernel": entry, "dominant_device_kernel": DOMINANT_KERNEL.get(entry), "bound": "hbm",
-                    "achieved": None if ach is None else round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": None if ach is None else round(ach / HBM_PEAK_GBS, 6), "traffic": traffic,
-                    "traffic_source": tsrc, "avg_ms": round(avg_ms, 4), "algorithmic_bytes": by,
-                    "dominant_device_kernel_avg_ms_rocprof": rocprof_kernel_avg_ms(entry),
-                    "timing": ("HIP events inside the timed region" if mode == "serial/eager" else
-                               "HIP events over 5 unpipelined eager steps right after the timed region"), "note": note}
-        # ---- the whole step against both roofs: compulsory HBM bytes and dense-layer flops of ONE step
-        step_bytes, step_flops = step_model_figures(B, N_POINTS, m1, m2, e1, e2)
-        MFMA_PEAK = {"f32": 157.3e12, "bf16": 2.5e15}[a.dtype]
-        whole_step = {"compulsory_bytes": int(step_bytes), "hbm_frac": round(step_bytes / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4),
-                      "dense_flops": int(step_flops), "mfma_frac": round(step_flops / (ms * 1e-3) / MFMA_PEAK, 4),
-                      "mfma_peak_TFLOPs": MFMA_PEAK / 1e12,
-                      "what": "SURVEY.md 8d: compulsory HBM bytes (2.2 x forward) and dense-layer flops (3 x forward - 352 E1) of "
-                              "one step at the measured message counts, over the timed ms_per_step"}
-        roof = roofline_of(dominant, "longest entry point of the feature pass, the stream that bounds the pipelined step "
-                                     "(the geometry passes run beside it on side streams)" if not a.serial else
-                           "longest entry point of the step")
-        roof_geo = None if a.serial else roofline_of(
-            longest_geometry, "longest entry point overall, off the critical path: fps is a chain of arg-max rounds in one "
-                              "workgroup per plot (up to 8 exact samples per round; latency-bound: see us_per_sample and "
-                              "workgroups / compute_units); its HBM traffic is 12 B/point once, so the HBM fraction says "
-                              "nothing about it")
         out = {"metric": "plots/s fwd+bwd, 32k-pt synthetic plots, batch 16/GPU", "value": round(world * B / (ms * 1e-3), 2),
                "unit": "plots/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 4),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
@@ -1080,16 +1127,14 @@ def main():
                                           "ball query, 3-NN) of every batch run exactly once, for later batches on side "
                                           "streams" + (f", {pipe.group} consecutive batches per launch" if (pipe is not None and pipe.pair) else "") +
                                           "; distinct batches in the slots"),
-                          "plots_per_gpu": B, "points_per_plot": N_POINTS, "messages_sa1": e1, "messages_sa2": e2,
+                          "plots_per_gpu": B, "points_per_plot": N_POINTS,
                           "batches_per_geometry_pass": (pipe.group if pipe is not None else 1),
-                          "geometry_passes_launched_in_timed_region": (None if pipe is None else (pipe.issued - issued0) // pipe.group),
+                          "geometry_passes_launched_in_timed_region": geometry_passes,
                           "drain_ms_inside_timed_region": (None if drain_ms is None else round(drain_ms, 4)),
                           "exchange": w.exchange,
                           "parallelism": f"dp{world} (plots sharded; one 60 KB gradient all-reduce)" if world > 1 else "single GPU"},
-               "loss": round(loss_value, 6), "roofline": roof, "kernels": kernels,
+               "loss": round(loss_value, 6),
                "host_cores_of_this_rank": os.environ.get("SN2_BENCH_PINNED", f"all:{len(os.sched_getaffinity(0))}")}
-        if peaks is not None:
-            out["measured_peaks"] = peaks
         # what a SCALE record can be audited by: the library, the ranks that took part, the exchange that really ran
         try:
             from stratanet2_vegetation_coverage_maps_amd import rccl as _rccl
@@ -1098,69 +1143,112 @@ def main():
             out["config"]["rccl_version"] = f"unavailable ({type(exc).__name__})"
         out["config"]["ranks_seen"] = ranks_seen
         out["config"]["exchange_in_graph"] = bool(getattr(opt, "comm", None) is not None)
-        if roof is not None:
-            # ---- one record, scalar fields, each with ONE denominator:
-            #   frac / entry_point_frac : the ENTRY POINT's algorithmic bytes over its live HIP-event time (all its kernels), vs 8 TB/s
-            #   dominant_kernel_frac    : the named device kernel ALONE (its own bytes over its own live duration), vs 8 TB/s
-            #   *_of_measured_copy      : the same against the stream-copy rate measured in this run
-            #   whole_step_*            : SURVEY 8d's compulsory bytes / dense flops of one step over ms_per_step
-            roof["entry_point_frac"] = roof["frac"]
-            roof["entry_point_kernels"] = ENTRY_KERNELS.get(roof["kernel"], [DOMINANT_KERNEL.get(roof["kernel"])])
-            if dom_alone_ms is not None:
-                dk_bytes = (288 + 32 + 136) * N_POINTS * B      # h + dy rows, skip columns in, d pre-activation rows out
-                roof["dominant_kernel_ms"] = round(dom_alone_ms, 4)
-                roof["dominant_kernel_bytes"] = dk_bytes
-                roof["dominant_kernel_GBps"] = round(dk_bytes / (dom_alone_ms * 1e-3) / 1e9, 1)
-                roof["dominant_kernel_frac"] = round(dk_bytes / (dom_alone_ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)
-            roof["whole_step_hbm_frac"] = whole_step["hbm_frac"]
-            roof["whole_step_mfma_frac"] = whole_step["mfma_frac"]
-            roof["whole_step_compulsory_bytes"] = whole_step["compulsory_bytes"]
-            roof["whole_step_dense_flops"] = whole_step["dense_flops"]
+        if a.full:
+            kernels = []
+            for k, (c, tms) in sorted(table.items(), key=lambda kv: -kv[1][1]):
+                by = algorithmic_bytes(k, B, N_POINTS, m1, m2, e1, e2)
+                kernels.append({"entry": k, "ms": round(tms, 4),
+                                "alg_GBps": None if by is None else round(by / (tms * 1e-3) / 1e9, 1)})
+            CALLS_PER_STEP = {"sn2_interp_index": 3, "sn2_sa_order": 2}     # entry points whose byte model covers all their calls of a step
+
+            def roofline_of(entry, note):
+                if not entry or entry not in dom:
+                    return None
+                c, tms = dom[entry]
+                avg_ms = tms / (c / CALLS_PER_STEP.get(entry, 1))
+                by = algorithmic_bytes(entry, B, N_POINTS, m1, m2, e1, e2)
+                ach = None if by is None else by / (avg_ms * 1e-3) / 1e9
+                traffic, tsrc = pmc_traffic(entry)
+                return {"kernel": entry, "dominant_device_kernel": DOMINANT_KERNEL.get(entry), "bound": "hbm",
+                        "achieved": None if ach is None else round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": None if ach is None else round(ach / HBM_PEAK_GBS, 6), "traffic": traffic,
+                        "traffic_source": tsrc, "avg_ms": round(avg_ms, 4), "algorithmic_bytes": by,
+                        "dominant_device_kernel_avg_ms_rocprof": rocprof_kernel_avg_ms(entry),
+                        "timing": ("HIP events inside the timed region" if mode == "serial/eager" else
+                                   "HIP events over 5 unpipelined eager steps right after the timed region"), "note": note}
+            # ---- the whole step against both roofs: compulsory HBM bytes and dense-layer flops of ONE step
+            step_bytes, step_flops = step_model_figures(B, N_POINTS, m1, m2, e1, e2)
+            MFMA_PEAK = {"f32": 157.3e12, "bf16": 2.5e15}[a.dtype]
+            whole_step = {"compulsory_bytes": int(step_bytes), "hbm_frac": round(step_bytes / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4),
+                          "dense_flops": int(step_flops), "mfma_frac": round(step_flops / (ms * 1e-3) / MFMA_PEAK, 4),
+                          "mfma_peak_TFLOPs": MFMA_PEAK / 1e12,
+                          "what": "SURVEY.md 8d: compulsory HBM bytes (2.2 x forward) and dense-layer flops (3 x forward - 352 E1) of "
+                                  "one step at the measured message counts, over the timed ms_per_step"}
+            roof = roofline_of(dominant, "longest entry point of the feature pass, the stream that bounds the pipelined step "
+                                         "(the geometry passes run beside it on side streams)" if not a.serial else
+                               "longest entry point of the step")
+            roof_geo = None if a.serial else roofline_of(
+                longest_geometry, "longest entry point overall, off the critical path: fps is a chain of arg-max rounds in one "
+                                  "workgroup per plot (up to 8 exact samples per round; latency-bound: see us_per_sample and "
+                                  "workgroups / compute_units); its HBM traffic is 12 B/point once, so the HBM fraction says "
+                                  "nothing about it")
+            out["config"]["messages_sa1"], out["config"]["messages_sa2"] = e1, e2
+            out["roofline"], out["kernels"] = roof, kernels
             if peaks is not None:
-                cp = peaks["hbm_copy_GBps"]
-                roof["measured_copy_peak_GBps"] = cp
-                if roof["achieved"] is not None:
-                    roof["frac_of_measured_copy"] = round(roof["achieved"] / cp, 4)
+                out["measured_peaks"] = peaks
+            if roof is not None:
+                # ---- one record, scalar fields, each with ONE denominator:
+                #   frac / entry_point_frac : the ENTRY POINT's algorithmic bytes over its live HIP-event time (all its kernels), vs 8 TB/s
+                #   dominant_kernel_frac    : the named device kernel ALONE (its own bytes over its own live duration), vs 8 TB/s
+                #   *_of_measured_copy      : the same against the stream-copy rate measured in this run
+                #   whole_step_*            : SURVEY 8d's compulsory bytes / dense flops of one step over ms_per_step
+                roof["entry_point_frac"] = roof["frac"]
+                roof["entry_point_kernels"] = ENTRY_KERNELS.get(roof["kernel"], [DOMINANT_KERNEL.get(roof["kernel"])])
                 if dom_alone_ms is not None:
-                    roof["dominant_kernel_frac_of_measured_copy"] = round(roof["dominant_kernel_GBps"] / cp, 4)
-                roof["whole_step_hbm_frac_of_measured_copy"] = round(whole_step["compulsory_bytes"] / (ms * 1e-3) / (cp * 1e9), 4)
-                mp = peaks["mfma_bf16_TFLOPs" if a.dtype == "bf16" else "mfma_f32_TFLOPs"]
-                roof["whole_step_mfma_frac_of_measured"] = round(whole_step["dense_flops"] / (ms * 1e-3) / (mp * 1e12), 4)
-            roof["whole_step"] = whole_step
-        if roof_geo is not None:
-            if roof_geo["kernel"].startswith("sn2_fps"):
-                # farthest point sampling: M strictly sequential arg-max rounds per plot -- what describes it is the time per
-                # sample and how little of the chip it occupies, not a bandwidth
-                roof_geo["us_per_sample"] = round(roof_geo["avg_ms"] * 1e3 / max(1, m1 - 1), 4)
-                roof_geo["workgroups"] = B * 8           # the timed (unpipelined) form: eight workgroups per plot
-                roof_geo["compute_units"] = 256
-                roof_geo["bound"] = "latency"
-            out["roofline_off_critical_path"] = roof_geo
-        if serial_ms is not None:
-            out["unpipelined"] = {"ms_per_step": round(serial_ms, 4), "plots_per_s": round(B / (serial_ms * 1e-3), 2),
-                                  "what": "the same step with geometry and features of ONE batch back to back on one "
-                                          "stream, captured as one hipGraph (single-batch latency; not the headline value)"}
-        default_workload = (B, N_POINTS, a.arch, a.dtype) == (PLOTS_PER_GPU, 32768, "ref", "f32") and not (a.serial or a.eager or a.host_inputs)
-        if world == 1 and default_workload and not a.no_secondary:
-            # ---- the other configurations BASELINE.json names, driver-timed in the same run (compact legs; never `value`)
-            pipe = graph = None                         # the headline's pipeline, graphs and resident batches are done with
-            slots.clear()
-            torch.cuda.empty_cache()
-            sec = {}
-            for name, fn in secondary_legs(dev).items():
-                log(f"secondary leg: {name}")
-                try:
-                    sec[name] = fn()
-                    log(f"  {name}: " + json.dumps({k: v for k, v in sec[name].items() if k in ('ms_per_step', 'plots_per_s', 'seconds_per_parcel')}))
-                except Exception as exc:                     # noqa: BLE001  (a failed leg must not lose the headline line)
-                    sec[name] = {"error": f"{type(exc).__name__}: {exc}"}
-                    log(f"  {name} FAILED: {sec[name]['error']}")
-                    torch.cuda.synchronize()
-            out["secondary"] = sec
-        if world == 1 and not a.no_cpu_baseline:
-            log("cpu baseline (oracle on the host cores)")
-            out["cpu_baseline"] = cpu_baseline()
-            out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
+                    dk_bytes = (288 + 32 + 136) * N_POINTS * B      # h + dy rows, skip columns in, d pre-activation rows out
+                    roof["dominant_kernel_ms"] = round(dom_alone_ms, 4)
+                    roof["dominant_kernel_bytes"] = dk_bytes
+                    roof["dominant_kernel_GBps"] = round(dk_bytes / (dom_alone_ms * 1e-3) / 1e9, 1)
+                    roof["dominant_kernel_frac"] = round(dk_bytes / (dom_alone_ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)
+                roof["whole_step_hbm_frac"] = whole_step["hbm_frac"]
+                roof["whole_step_mfma_frac"] = whole_step["mfma_frac"]
+                roof["whole_step_compulsory_bytes"] = whole_step["compulsory_bytes"]
+                roof["whole_step_dense_flops"] = whole_step["dense_flops"]
+                if peaks is not None:
+                    cp = peaks["hbm_copy_GBps"]
+                    roof["measured_copy_peak_GBps"] = cp
+                    if roof["achieved"] is not None:
+                        roof["frac_of_measured_copy"] = round(roof["achieved"] / cp, 4)
+                    if dom_alone_ms is not None:
+                        roof["dominant_kernel_frac_of_measured_copy"] = round(roof["dominant_kernel_GBps"] / cp, 4)
+                    roof["whole_step_hbm_frac_of_measured_copy"] = round(whole_step["compulsory_bytes"] / (ms * 1e-3) / (cp * 1e9), 4)
+                    mp = peaks["mfma_bf16_TFLOPs" if a.dtype == "bf16" else "mfma_f32_TFLOPs"]
+                    roof["whole_step_mfma_frac_of_measured"] = round(whole_step["dense_flops"] / (ms * 1e-3) / (mp * 1e12), 4)
+                roof["whole_step"] = whole_step
+            if roof_geo is not None:
+                if roof_geo["kernel"].startswith("sn2_fps"):
+                    # farthest point sampling: M strictly sequential arg-max rounds per plot -- what describes it is the time per
+                    # sample and how little of the chip it occupies, not a bandwidth
+                    roof_geo["us_per_sample"] = round(roof_geo["avg_ms"] * 1e3 / max(1, m1 - 1), 4)
+                    roof_geo["workgroups"] = B * 8           # the timed (unpipelined) form: eight workgroups per plot
+                    roof_geo["compute_units"] = 256
+                    roof_geo["bound"] = "latency"
+                out["roofline_off_critical_path"] = roof_geo
+            if serial_ms is not None:
+                out["unpipelined"] = {"ms_per_step": round(serial_ms, 4), "plots_per_s": round(B / (serial_ms * 1e-3), 2),
+                                      "what": "the same step with geometry and features of ONE batch back to back on one "
+                                              "stream, captured as one hipGraph (single-batch latency; not the headline value)"}
+            default_workload = (B, N_POINTS, a.arch, a.dtype) == (PLOTS_PER_GPU, 32768, "ref", "f32") and not (a.serial or a.eager or a.host_inputs)
+            if world == 1 and default_workload and not a.no_secondary:
+                # ---- the other configurations BASELINE.json names, driver-timed in the same run (compact legs; never `value`)
+                pipe = graph = None                         # the headline's pipeline, graphs and resident batches are done with
+                slots.clear()
+                torch.cuda.empty_cache()
+                sec = {}
+                for name, fn in secondary_legs(dev).items():
+                    log(f"secondary leg: {name}")
+                    try:
+                        sec[name] = fn()
+                        log(f"  {name}: " + json.dumps({k: v for k, v in sec[name].items() if k in ('ms_per_step', 'plots_per_s', 'seconds_per_parcel')}))
+                    except Exception as exc:                     # noqa: BLE001  (a failed leg must not lose the headline line)
+                        sec[name] = {"error": f"{type(exc).__name__}: {exc}"}
+                        log(f"  {name} FAILED: {sec[name]['error']}")
+                        torch.cuda.synchronize()
+                out["secondary"] = sec
+            if world == 1 and not a.no_cpu_baseline:
+                log("cpu baseline (oracle on the host cores)")
+                out["cpu_baseline"] = cpu_baseline()
+                out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         emit_record(out)
     if getattr(opt, "comm", None) is not None:
         import gc

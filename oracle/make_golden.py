@@ -153,6 +153,9 @@ def main():
         for k, p in model64.named_parameters():
             out[f"grad64/{k}"] = p.grad.numpy()
         out["train64/coverages_pointwise"] = cov64.detach().numpy()
+        # the BatchNorm running statistics after that fp64 step, in a small file of their own (tests/test_oracle_golden.py)
+        bn64 = {f"sd_after64/{k}": v.numpy() for k, v in model64.state_dict().items() if "running_" in k or "num_batches" in k}
+        np.savez_compressed(os.path.join(OUT, f"{name}_bn64.npz"), **bn64)
         P.set_fps_start_provider(None)
         worst = max((float(np.abs(out[f"grad/{k}"] - out[f"grad64/{k}"]).max() / np.abs(out[f"grad64/{k}"]).max()), k)
                     for k, _ in model.named_parameters())

@@ -5,7 +5,7 @@ out=$1; pat=$2; shift 2
 root=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $root/$out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof -- python3 $root/bench.py --serial --eager --steps 20 --warmup 3 --no-cpu-baseline --no-secondary "$@" > $root/$out/prof.log 2>&1 || { tail -20 $root/$out/prof.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof -- python3 $root/bench.py --full --serial --eager --steps 20 --warmup 3 --no-cpu-baseline --no-secondary "$@" > $root/$out/prof.log 2>&1 || { tail -20 $root/$out/prof.log; exit 1; }
 cd $root
 find $out/prof -name "*kernel_stats.csv" | xargs -I{} cp {} $out/kstats.csv
 rm -rf $out/prof

@@ -5,7 +5,7 @@ out=$1; ctrs=$2; shift 2
 root=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $root/$out
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --pmc $ctrs --output-format csv -d $root/$out/pmc -- python3 $root/bench.py --serial --eager --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > $root/$out/pmc.log 2>&1 || { tail -20 $root/$out/pmc.log; exit 1; }
+timeout -k 10 300 rocprofv3 --pmc $ctrs --output-format csv -d $root/$out/pmc -- python3 $root/bench.py --full --serial --eager --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > $root/$out/pmc.log 2>&1 || { tail -20 $root/$out/pmc.log; exit 1; }
 cd $root
 cp $(find $out/pmc -name "*counter_collection.csv" | tail -1) $out/pmc_counters.csv
 rm -rf $out/pmc

@@ -1,9 +1,10 @@
 #!/bin/bash
 # rocprofv3 kernel stats of a short serial eager bench run; prints the top kernels (scratch tool for tuning sessions)
+bench=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_top
 rm -rf $out
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $GRAFT_REPO_ROOT/bench.py --serial --eager --steps 5 --warmup 2 --no-cpu-baseline "$@" > $out.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 "$bench" --full --serial --eager --steps 5 --warmup 2 --no-cpu-baseline "$@" > $out.log 2>&1
 cd $GRAFT_REPO_ROOT
 f=$(find gpurun_out/prof_top -name "*kernel_stats.csv" | tail -1)
 python - "$f" <<PY
