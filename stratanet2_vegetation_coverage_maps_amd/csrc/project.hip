@@ -450,7 +450,9 @@ __global__ __launch_bounds__(256) void projected_loss_finalize_kernel(const unsi
         for (int q = 0; q < 4; ++q)
             __hip_atomic_store(reinterpret_cast<unsigned*>(pred) + b * 4 + q, __float_as_uint(t[q] / n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(nocc + b, (int)t[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (atomicAdd(ticket, 1u) == (unsigned)B - 1u) ? 1 : 0;      // (the stores above are this thread's: program order)
+        // acq_rel at agent scope: the release orders this workgroup's pred / nocc stores before its ticket, the acquire makes
+        // every earlier workgroup's stores visible to the last one (a relaxed add orders neither)
+        s_last = (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)B - 1u) ? 1 : 0;
     }
     __syncthreads();
     if (!s_last) return;

@@ -203,6 +203,17 @@ class TrainPipeline:
         self.model._last_flat_grad = g
         self.opt.step()                           # all-reduce (world > 1) + Adam kernel
 
+    def _fold_pending_images(self):
+        """Split capture: the exchange and the Adam graph read `flat_grad[k]` (image 0 of the arena) and know nothing of the
+        backward's deferred images (FlatAdam(fold_gradient_images=True) leaves them for its own kernel, which the split path
+        does not run), so the backward graph folds them itself -- else the step trains on image 0 alone."""
+        pending = getattr(self.model, "_grad_images_pending", None)
+        if pending is None:
+            return
+        arena, replicas, stride = pending
+        self.model._grad_images_pending = None
+        ops.grad_reduce(arena, self.model._last_flat_grad.numel(), (replicas, stride))
+
     def capture(self):
         """Warm every slot eagerly (allocator, lazy loads), then capture each slot's feature pass.  Geometry of all
         slots must be valid while warming: computed here, and left valid for steps 0..slots-1."""
@@ -238,6 +249,8 @@ class TrainPipeline:
                 self.flat_grad[k] = self.model._last_flat_grad
                 if not self.split_exchange:
                     self._exchange_and_update(k)  # no exchange: Adam rides in the same graph
+                else:
+                    self._fold_pending_images()
             self.graph_fb[k] = g
             if self.split_exchange:
                 g2 = torch.cuda.CUDAGraph()

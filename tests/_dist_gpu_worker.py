@@ -55,12 +55,22 @@ def rank_main(rank, world, port, backend, q):
         q.put((rank, "error", traceback.format_exc(), 0.0, 0))
 
 
-def run_command(cmd, env, q):
-    """Run a command from a clean (never touched a GPU) process and hand back (rc, stdout, stderr)."""
+def run_command(cmd, env, q, timeout=540):
+    """Run a command from a clean (never touched a GPU) process and hand back (rc, stdout, stderr).  A command still running
+    after `timeout` seconds is killed with everything it started (its own session: bench.py --gpus N starts its ranks as
+    children) and reported as rc 124."""
+    import signal
     import subprocess
     e = dict(os.environ)
     e.update(env)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         e.pop(k, None)
-    r = subprocess.run(cmd, env=e, capture_output=True, text=True, cwd=ROOT)
-    q.put((r.returncode, r.stdout, r.stderr[-4000:]))
+    p = subprocess.Popen(cmd, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, start_new_session=True)
+    try:
+        out, err = p.communicate(timeout=timeout)
+        rc = p.returncode
+    except subprocess.TimeoutExpired:
+        os.killpg(p.pid, signal.SIGKILL)
+        out, err = p.communicate()
+        rc, err = 124, err + f"\n[run_command: killed after {timeout} s]"
+    q.put((rc, out, err[-4000:]))

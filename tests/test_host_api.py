@@ -82,7 +82,7 @@ def _run_clean(cmd, env, timeout=120):
         from _dist_gpu_worker import run_command
         ctx = mp.get_context("forkserver")
         q = ctx.Queue()
-        p = ctx.Process(target=run_command, args=(cmd, env, q))
+        p = ctx.Process(target=run_command, args=(cmd, env, q, max(1, timeout - 10)))
         p.start()
         rc, out, err = q.get(timeout=timeout)
         p.join(30)
