@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SN2_VERSION 100
+#define SN2_VERSION 101
 #define SN2_EINVAL (-1) /* bad size / null pointer             */
 #define SN2_ELIMIT (-2) /* size outside what the kernels cover */
 
@@ -195,6 +195,39 @@ int sn2_prepare_plots(const float *raw, long T, const int *offsets, const float 
 #define SN2_ZNORM_WS_WORDS(n, cells) ((size_t)5 * (n) + 3 * (size_t)(cells) + 8)
 int sn2_znorm(const float *x, const float *y, const float *z, int n, float radius, float x_min, float y_min, float x_max,
               float y_max, int *ws, float *zmin, float *z_out, void *stream);
+
+/* ---- a parcel's plots (csrc/parcel.hip; host side parcel.py): the discs of extract_cloud (inference/prepare_utils.py:47-53,
+ * scipy cKDTree.query_ball_point) around P plot centres and the per-plot z-normalisation of pre_transform
+ * (utils/load_data.py:228-249), for the whole parcel at once.
+ * cloud (10,T): the parcel in the reference's channel order and absolute metres.  centers (P,2) fp32.
+ * Membership of point i in disc p: fp64 dx*dx + dy*dy <= radius*radius, no contraction (scipy's inclusive test; exact for fp32
+ * inputs of similar magnitude).  The points of a plot are in ascending parcel index; the output bytes do not depend on the
+ * order in which waves run (integer counts only, no float atomics).  T < 2^31; the hits of all centres < 2^31.
+ * Centre grid: cells of side 1/cell_inv >= radius, cell of a position floor((v - g0) * cell_inv) in fp64; cell_start
+ * (GX*GY+1) and cell_items (centre ids, ascending inside a cell) are the CSR of the centres over the cells, row-major.
+ * Rows: a wave walks `L` consecutive points (one row, rows = ceil(T/L)); P*rows < 2^28.
+ *
+ * sn2_parcel_count: prefix (P*rows+1) = exclusive scan, plot-major, of the points of row r in disc p; prefix[P*rows] and
+ *   total[0] (int64) = all hits.  Plot p holds prefix[(p+1)*rows] - prefix[p*rows] points.  ws: sn2_parcel_count_ws_words.
+ * sn2_parcel_fill: writes point i of disc p (p kept: plot_base[p] != INT_MIN) to slot plot_base[p] + prefix[p*rows + r] +
+ *   its rank in the row: point_index[slot] = i, raw[c*sum_n + slot] = cloud[c*T + i] for every row c but z (c = 2).  prefix
+ *   is consumed (advanced).  sum_n = the slots of the kept plots.
+ * sn2_parcel_znorm: raw[2*sum_n + s] = fp32(z_i - min{ z_j : |xy_j - xy_i| <= radius, |xy_j - c_p| <= disc_radius }) for the
+ *   point i = point_index[s] of the plot p with offsets[p] <= s < offsets[p+1] (P plots, centres `centers`): the local
+ *   minimum of normalize_z_with_minz_in_a_radius over the plot's own points.  x_min..y_max: bounding box of the parcel;
+ *   the grid of cells of side radius has at most 2^26 cells.  ws: sn2_parcel_znorm_ws_words (0 = beyond that limit).
+ * ws must be 16-byte aligned. */
+size_t sn2_parcel_count_ws_words(int P, int rows);
+size_t sn2_parcel_znorm_ws_words(long T, float radius, float x_min, float y_min, float x_max, float y_max);
+int sn2_parcel_count(const float *cloud, long T, int L, int rows, const float *centers, int P, const int *cell_start,
+                     const int *cell_items, int GX, int GY, double gx0, double gy0, double cell_inv, float radius, int *ws,
+                     size_t ws_words, int *prefix, long long *total, void *stream);
+int sn2_parcel_fill(const float *cloud, long T, int L, int rows, const float *centers, int P, const int *cell_start,
+                    const int *cell_items, int GX, int GY, double gx0, double gy0, double cell_inv, float radius, int *prefix,
+                    const int *plot_base, long sum_n, float *raw, int *point_index, void *stream);
+int sn2_parcel_znorm(const float *cloud, long T, float x_min, float y_min, float x_max, float y_max, float radius,
+                     float disc_radius, const int *offsets, const float *centers, int P, const int *point_index, long sum_n,
+                     int *ws, size_t ws_words, float *raw, void *stream);
 
 /* ---- set abstraction: gather + shared MLP + BN + max -- SAModule/PointConv, model/point_net2.py:19,21-29 --- */
 typedef struct sn2_sa {

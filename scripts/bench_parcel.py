@@ -1,0 +1,150 @@
+"""Parcel -> plots -> mosaic on one GPU (parcel.py): synthetic parcels of 10 ha and 1 ha at 40 points/m^2.  Prints one JSON
+line: per parcel the device time of `prepare_parcel` (HIP events after warm-up, median of --repeat runs; the cloud's
+host-to-device copy separately), its entry points' times, `predict_parcel_cloud` + `finalize` end to end in plots/s, the
+prediction alone, the reference's CPU preparation (scipy discs + sklearn z-norm loop) timed on a sample of plots and
+EXTRAPOLATED to the parcel, the compulsory bytes of the count / fill passes against 8 TB/s, and the z-norm query's
+candidate tests per second.  Kernel times: run it under `rocprofv3 --kernel-trace --stats`.
+
+    python scripts/bench_parcel.py [--repeat 10] [--sample 6]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stratanet2_vegetation_coverage_maps_amd import PointNet2, hip_ops as ops, parcel  # noqa: E402
+from stratanet2_vegetation_coverage_maps_amd.synthetic import make_args, make_parcel  # noqa: E402
+
+HBM = 8e12
+
+
+def ev_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), out
+
+
+def reference_cpu(cloud, centers, sample, args, rng):
+    """The reference's rule on `sample` plots: cKDTree build (once), query_ball_point, sklearn radius_neighbors + the
+    per-point np.min loop (utils/load_data.py:237-249).  Returns (tree build s, mean s per plot)."""
+    from scipy.spatial import cKDTree
+    from sklearn.neighbors import NearestNeighbors
+    t = time.perf_counter()
+    tree = cKDTree(cloud[:2].T, 50)
+    build = time.perf_counter() - t
+    per = []
+    for k in rng.choice(len(centers), sample, replace=False):
+        t = time.perf_counter()
+        idx = tree.query_ball_point(centers[k], r=args.diam_meters // 2)
+        plot = cloud[:, idx].copy()
+        if plot.shape[1] >= 51:
+            xyz = plot[:3].T
+            _, neigh = NearestNeighbors(n_neighbors=500, algorithm="kd_tree").fit(xyz[:, :2]).radius_neighbors(xyz[:, :2], 1.5)
+            z = xyz[:, 2]
+            zmin = [np.min(z[neigh[n]]) for n in range(len(z))]
+            plot[2] = plot[2] - zmin
+        per.append(time.perf_counter() - t)
+    return build, float(np.mean(per))
+
+
+def znorm_candidates(cloud, plots):
+    """Candidate tests of the z-norm query: for every plot point, the parcel points in the 3 x 3 cells around its own
+    (cells as csrc/parcel.hip bins them)."""
+    x, y = cloud[0], cloud[1]
+    f32 = np.float32
+    inv = f32(1.0) / (f32(1.5) * f32(1.0001))
+    gx = int((x.max() - x.min()) * inv) + 1
+    gy = int((y.max() - y.min()) * inv) + 1
+    cx = np.clip(((x - x.min()) * inv).astype(np.int64), 0, gx - 1)
+    cy = np.clip(((y - y.min()) * inv).astype(np.int64), 0, gy - 1)
+    h = np.bincount(cy * gx + cx, minlength=gx * gy).reshape(gy, gx)
+    p = np.pad(h, 1)
+    box = sum(p[1 + dy:1 + dy + gy, 1 + dx:1 + dx + gx] for dy in (-1, 0, 1) for dx in (-1, 0, 1))
+    i = plots.point_index.cpu().numpy()
+    return int(box[cy[i], cx[i]].sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeat", type=int, default=10)
+    ap.add_argument("--sample", type=int, default=6)
+    ap.add_argument("--batch", type=int, default=64)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_parcel: needs the GPU")
+    dev = torch.device("cuda:0")
+    args = make_args(cuda=0)
+    torch.manual_seed(0)
+    model = PointNet2(args).eval()
+    rng = np.random.default_rng(0)
+    out = {}
+    for name, side in (("10ha", 316.3), ("1ha", 100.0)):
+        cloud = make_parcel(side, side, density=40.0, seed=1)
+        T = cloud.shape[1]
+        pinned = torch.from_numpy(cloud).pin_memory()
+        h2d, cloud_dev = ev_ms(lambda: pinned.to(dev, non_blocking=True))
+        for _ in range(2):
+            plots = parcel.prepare_parcel(cloud_dev, args)
+        torch.cuda.synchronize()
+        times = [ev_ms(lambda: parcel.prepare_parcel(cloud_dev, args))[0] for _ in range(a.repeat)]
+        with ops.timing({"sn2_parcel_count", "sn2_parcel_fill", "sn2_parcel_znorm"}) as tm:
+            plots = parcel.prepare_parcel(cloud_dev, args)
+        entries = {k: round(ms, 4) for k, (c, ms) in sorted(tm.summary().items())}
+        P, SN = len(plots), int(plots.n_points.sum())
+
+        def e2e():
+            mos, pl = parcel.predict_parcel_cloud(model, cloud_dev, args, batch_size=a.batch, fps_start=0)
+            res = mos.finalize()
+            torch.cuda.synchronize()
+            return res
+        e2e()
+        t = time.perf_counter()
+        e2e()
+        e2e_s = time.perf_counter() - t
+
+        def predict_only():
+            mos = parcel.parcel_mosaic(plots.centers_host, args, dev)
+            parcel.predict_parcel(model, plots.batches(args, a.batch, fps_start=0), mos, args)
+            torch.cuda.synchronize()
+        predict_only()
+        t = time.perf_counter()
+        predict_only()
+        pred_s = time.perf_counter() - t
+        centers = parcel.parcel_plot_centers(cloud[0].min(), cloud[0].max(), cloud[1].min(), cloud[1].max(), args)
+        build_s, per_plot_s = reference_cpu(cloud, centers, a.sample, args, rng)
+        count_fill_bytes = 2 * 8 * T + (9 * 4 + 4) * SN + 9 * 4 * SN           # x,y twice; member rows read + written
+        prep_ms = statistics.median(times)
+        cand = znorm_candidates(cloud, plots)
+        out[name] = {
+            "points": T, "plots": P, "plot_points": SN,
+            "h2d_ms": round(h2d, 3),
+            "prepare_ms_median": round(prep_ms, 3), "prepare_ms_min": round(min(times), 3),
+            "entry_ms": entries,
+            "predict_ms": round(pred_s * 1e3, 2),
+            "e2e_ms": round(e2e_s * 1e3, 2), "e2e_plots_per_s": round(P / e2e_s, 1),
+            "prepare_over_predict": round(prep_ms / (pred_s * 1e3), 3),
+            "reference_cpu_s_extrapolated": round(build_s + per_plot_s * P, 2),
+            "reference_cpu_sample_plots": a.sample,
+            "count_fill_compulsory_bytes": count_fill_bytes,
+            "count_fill_frac_of_8TBps": round(count_fill_bytes / HBM /
+                                              (1e-3 * (entries.get("sn2_parcel_count", 0) + entries.get("sn2_parcel_fill", 0))), 4),
+            "znorm_candidate_tests": cand,
+            "znorm_candidates_per_s_over_entry": round(cand / (1e-3 * entries.get("sn2_parcel_znorm", float("nan"))), 1),
+        }
+        print(f"[bench_parcel] {name}: {json.dumps(out[name])}", file=sys.stderr, flush=True)
+    ten = out["10ha"]
+    print(json.dumps({"metric": "10 ha parcel preparation on the device (prepare_parcel, median)", "value": ten["prepare_ms_median"],
+                      "unit": "ms", "n_gpus": 1, "target_met": ten["prepare_ms_median"] <= ten["predict_ms"], "parcels": out}))
+
+
+if __name__ == "__main__":
+    main()

@@ -7,7 +7,7 @@ from ctypes import POINTER, Structure, c_double, c_float, c_int, c_long, c_longl
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libstrata_hip.so")
 
-SN2_VERSION = 100
+SN2_VERSION = 101
 MAX_NEIGHBORS = 2000  # model/point_net2.py:24
 STAT_SLOTS = 1024     # SN2_STAT_SLOTS
 
@@ -127,6 +127,12 @@ SIGNATURES = {
                           c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p, c_void_p],
     "sn2_znorm": [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
                   c_void_p, c_void_p],
+    "sn2_parcel_count": [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_double,
+                         c_double, c_float, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],
+    "sn2_parcel_fill": [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_double,
+                        c_double, c_float, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
+    "sn2_parcel_znorm": [c_void_p, c_long, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int,
+                         c_void_p, c_long, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     "sn2_sa_order": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "sn2_sa_order_group": [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_sa_forward": [POINTER(SA), c_int, c_void_p],
@@ -182,6 +188,12 @@ SIGNATURES = {
     "sn2_net_backward": [POINTER(NetModel), POINTER(NetDims), POINTER(NetGeo), POINTER(NetAct), POINTER(NetBwd), c_void_p],
 }
 
+# workspace-size helpers: name -> argtypes; they return size_t (32-bit words; 0 = beyond what the kernels cover)
+SIZE_HELPERS = {
+    "sn2_parcel_count_ws_words": [c_int, c_int],
+    "sn2_parcel_znorm_ws_words": [c_long, c_float, c_float, c_float, c_float, c_float],
+}
+
 _lib = None
 
 
@@ -204,6 +216,10 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_int
+    for name, argtypes in SIZE_HELPERS.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = ctypes.c_size_t
     if lib.sn2_version() != SN2_VERSION:
         raise StrataHipError(f"libstrata_hip.so version {lib.sn2_version()} != binding {SN2_VERSION}: rebuild")
     _lib = lib

@@ -605,6 +605,87 @@ def znorm(xyz: torch.Tensor, radius: float):
     return zmin, zout
 
 
+# ---------------------------------------------------------------------------------------------- parcel plots
+def parcel_count_ws_words(P: int, rows: int) -> int:
+    """sn2_parcel_count_ws_words of include/strata_hip.h."""
+    return int(_lib.load().sn2_parcel_count_ws_words(int(P), int(rows)))
+
+
+def parcel_znorm_ws_words(T: int, radius: float, x_min: float, y_min: float, x_max: float, y_max: float) -> int:
+    """sn2_parcel_znorm_ws_words of include/strata_hip.h (0: the z-norm grid would exceed 2^26 cells)."""
+    return int(_lib.load().sn2_parcel_znorm_ws_words(int(T), float(radius), float(x_min), float(y_min), float(x_max),
+                                                     float(y_max)))
+
+
+def _chk_center_grid(grid, P: int):
+    """grid: (cell_start (GX*GY+1) i32, cell_items i32, GX, GY, gx0, gy0, cell_inv) -- the CSR of the plot centres over
+    square cells (parcel.center_grid)."""
+    start, items, GX, GY, gx0, gy0, inv = grid
+    _chk(start, I32, (GX * GY + 1,), "cell_start")
+    _chk(items, I32, None, "cell_items")
+    if items.dim() != 1 or items.numel() < 1 or items.numel() > P:
+        raise ValueError("cell_items: expected 1..P centre ids")
+    return start, items, int(GX), int(GY), float(gx0), float(gy0), float(inv)
+
+
+def parcel_count(cloud: torch.Tensor, centers: torch.Tensor, grid, radius: float, L: int, rows: int):
+    """include/strata_hip.h: sn2_parcel_count.  cloud (10,T) f32, centers (P,2) f32 -> (prefix (P*rows+1) i32: exclusive
+    starts of the (plot, row) counts, plot-major; total (1) i64: all hits)."""
+    _, T = cloud.shape
+    _chk(cloud, F32, (10, T), "cloud")
+    P = centers.shape[0]
+    _chk(centers, F32, (P, 2), "centers")
+    start, items, GX, GY, gx0, gy0, inv = _chk_center_grid(grid, P)
+    dev = cloud.device
+    nw = parcel_count_ws_words(P, rows)
+    ws = torch.empty(nw + 4, dtype=I32, device=dev)
+    prefix = torch.empty(P * rows + 1, dtype=I32, device=dev)
+    total = torch.empty(1, dtype=I64, device=dev)
+    _call("sn2_parcel_count", _ptr(cloud), T, int(L), int(rows), _ptr(centers), P, _ptr(start), _ptr(items), GX, GY, gx0, gy0,
+          inv, float(radius), _ptr(ws), nw, _ptr(prefix), _ptr(total), _stream())
+    return prefix, total
+
+
+def parcel_fill(cloud: torch.Tensor, centers: torch.Tensor, grid, radius: float, L: int, rows: int, prefix: torch.Tensor,
+                plot_base: torch.Tensor, sum_n: int):
+    """include/strata_hip.h: sn2_parcel_fill.  prefix: parcel_count's (consumed); plot_base (P) i32, INT_MIN = plot dropped.
+    -> raw (10,sum_n) f32 (z row not written: parcel_znorm), point_index (sum_n) i32."""
+    _, T = cloud.shape
+    _chk(cloud, F32, (10, T), "cloud")
+    P = centers.shape[0]
+    _chk(centers, F32, (P, 2), "centers")
+    start, items, GX, GY, gx0, gy0, inv = _chk_center_grid(grid, P)
+    _chk(prefix, I32, (P * rows + 1,), "prefix")
+    _chk(plot_base, I32, (P,), "plot_base")
+    dev = cloud.device
+    raw = torch.empty(10, sum_n, dtype=F32, device=dev)
+    pidx = torch.empty(sum_n, dtype=I32, device=dev)
+    _call("sn2_parcel_fill", _ptr(cloud), T, int(L), int(rows), _ptr(centers), P, _ptr(start), _ptr(items), GX, GY, gx0, gy0,
+          inv, float(radius), _ptr(prefix), _ptr(plot_base), int(sum_n), _ptr(raw), _ptr(pidx), _stream())
+    return raw, pidx
+
+
+def parcel_znorm(cloud: torch.Tensor, bbox, radius: float, disc_radius: float, offsets: torch.Tensor, centers: torch.Tensor,
+                 point_index: torch.Tensor, raw: torch.Tensor):
+    """include/strata_hip.h: sn2_parcel_znorm.  Writes raw's z row (in place): each plot point's z minus the least z within
+    `radius` among the points of its own disc.  bbox = (x_min, y_min, x_max, y_max) of the parcel (fp32 values)."""
+    _, T = cloud.shape
+    _chk(cloud, F32, (10, T), "cloud")
+    P = centers.shape[0]
+    _chk(centers, F32, (P, 2), "centers")
+    _chk(offsets, I32, (P + 1,), "offsets")
+    sum_n = point_index.shape[0]
+    _chk(point_index, I32, (sum_n,), "point_index")
+    _chk(raw, F32, (10, sum_n), "raw")
+    nw = parcel_znorm_ws_words(T, radius, *bbox)
+    if nw == 0:
+        raise ValueError("parcel_znorm: the parcel's extent needs more than 2^26 cells of the z-norm radius")
+    ws = torch.empty(nw + 4, dtype=I32, device=cloud.device)
+    _call("sn2_parcel_znorm", _ptr(cloud), T, *[float(v) for v in bbox], float(radius), float(disc_radius), _ptr(offsets),
+          _ptr(centers), P, _ptr(point_index), sum_n, _ptr(ws), nw, _ptr(raw), _stream())
+    return raw
+
+
 def sa_order_len(B: int, M: int) -> int:
     """SN2_SA_ORDER_WORDS of include/strata_hip.h."""
     return 4 * B * M + 16 * B * (M // 8 + 2) + 8

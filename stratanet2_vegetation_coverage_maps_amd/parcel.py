@@ -1,0 +1,262 @@
+"""A parcel point cloud -> its prepared plots on the device -> the parcel mosaic: the counterpart of the reference's
+`prepare.py` (`inference/prepare_utils.py:95-173`: plot centres, `extract_cloud_data`: discs and `pre_transform`) followed
+by `predict.py`, without the GIS file I/O.
+
+    plots = prepare_parcel(cloud, args, keep=polygon_keep([exterior, *holes], shape_buffer(args)))
+    for batch in plots.batches(args, 20): ...           # the dicts `inference.predict_parcel` takes
+    mosaic, plots = predict_parcel_cloud(model, cloud, args)
+
+Rules kept from the reference (the centres in `parcel_plot_centers`, the discs and the z-normalisation in
+csrc/parcel.hip):
+  - plot centres on a lattice of step 2 cos(pi/4) 10 - 20/diam_pix metres from the fp32 bounding box, the first centre
+    listed twice, centres kept by the parcel shape buffered by 20 + diam_meters//2, then cast to fp32;
+  - a plot is every point with fp64 dx*dx + dy*dy <= (diam_meters//2)^2 from its centre (scipy's inclusive test), and it is
+    kept iff it has at least 51 points (`< 50` gives None, prepare.py keeps `> 50`);
+  - z of a plot point = z - the least z of the PLOT's points within znorm_radius_in_meters (1.5 m, inclusive).
+Where it differs: a plot's points are in ascending parcel index (the reference returns kd-tree order; the order only
+decides which points a random subsample picks); `polygon_keep` restates shapely's buffer test with exact round joins
+(see there).
+"""
+import math
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import hip_ops as ops
+from .inference import ParcelMosaic, predict_parcel
+from .input_pipeline import draw_plot_randoms, fake_ground_xy
+
+MIN_POINTS = 51              # prepare_utils.py:67-69 (< 50: None) and prepare.py:93 (> 50)
+LAS_PARCEL_BUFFER = 20       # prepare_utils.py:148
+INT_MIN = -(2 ** 31)
+ROW_POINTS = 2048            # points per wave of the count / fill passes
+MAX_TABLE = 1 << 26          # (plot, row) entries of the count table before rows get longer
+
+
+def plot_movement(args) -> float:
+    """Lattice step (prepare_utils.py:115-128): 2 cos(45 deg) 10 - 20 / diam_pix (13.1421 m at diam_pix = 20)."""
+    return 2 * math.cos(math.pi / 4) * 10 - 1 * 20 / args.diam_pix
+
+
+def shape_buffer(args) -> int:
+    """The buffer of the parcel shape a centre must lie in (prepare_utils.py:148-151): 20 + diam_meters // 2."""
+    return LAS_PARCEL_BUFFER + args.diam_meters // 2
+
+
+def parcel_plot_centers(x_min, x_max, y_min, y_max, args, keep=None) -> np.ndarray:
+    """Plot centres of `divide_parcel_las_and_get_disk_centers` (prepare_utils.py:95-173) -> (P,2) float32.
+
+    x_min..y_max: the fp32 bounding box of the parcel (`get_xy_range`).  Dtypes as under the reference's numpy 1.x:
+    the extents are fp32 differences, nx = ceil(extent / movement) + 1 divides in fp64, and every lattice coordinate is
+    fp64 (an np.float32 scalar plus a python float is fp64 there).  Centres run x outer, y inner, after a first centre
+    equal to the lattice's first.  keep: None (all), or a callable taking the fp64 lattice (n,2) and returning a bool mask
+    (`polygon_keep`, or shapely's `shape.buffer(b).contains` where it is installed).  The survivors are cast to fp32."""
+    f32 = np.float32
+    x_min, x_max, y_min, y_max = f32(x_min), f32(x_max), f32(y_min), f32(y_max)
+    mv = plot_movement(args)
+    nx = math.ceil(float(f32(x_max - x_min)) / mv) + 1
+    ny = math.ceil(float(f32(y_max - y_min)) / mv) + 1
+    sx, sy = float(x_min) + mv / 4, float(y_min) + mv / 4
+    xs = sx + np.arange(nx, dtype=np.float64) * mv
+    ys = sy + np.arange(ny, dtype=np.float64) * mv
+    lattice = np.empty((1 + nx * ny, 2), dtype=np.float64)
+    lattice[0] = (sx, sy)
+    lattice[1:, 0] = np.repeat(xs, ny)
+    lattice[1:, 1] = np.tile(ys, nx)
+    if keep is not None:
+        mask = np.asarray(keep(lattice), dtype=bool).reshape(-1)
+        if mask.shape[0] != lattice.shape[0]:
+            raise ValueError("keep must return one bool per lattice point")
+        lattice = lattice[mask]
+    return lattice.astype(np.float32)
+
+
+def polygon_keep(rings, buffer_m: float):
+    """Host restatement of `shape.buffer(buffer_m).contains(Point(x, y))` for a polygon: rings = [exterior, *holes], each
+    a (V,2) array (closed or not).  A point is kept iff it is inside by the even-odd rule or its distance to the boundary
+    is < buffer_m (`contains` excludes the buffer's own boundary).
+
+    Deviation: shapely draws the round joins of a buffer with 16 segments per quarter circle, inside the true circle, so a
+    point within about 4 cm of the offset curve near a convex vertex (at a 30 m buffer) may be classed differently here."""
+    segs = []
+    for r in rings:
+        r = np.asarray(r, dtype=np.float64).reshape(-1, 2)
+        if len(r) > 1 and np.array_equal(r[0], r[-1]):
+            r = r[:-1]
+        if len(r) < 2:
+            raise ValueError("a ring needs at least two vertices")
+        segs.append(np.concatenate([r, np.roll(r, -1, axis=0)], 1))
+    seg = np.concatenate(segs, 0)
+    ax, ay, bx, by = (seg[:, k][None, :] for k in range(4))
+    dx, dy = bx - ax, by - ay
+    l2 = dx * dx + dy * dy
+    b2 = float(buffer_m) * float(buffer_m)
+
+    def keep(pts):
+        pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
+        out = np.empty(len(pts), dtype=bool)
+        for s in range(0, len(pts), 2048):
+            px, py = pts[s:s + 2048, :1], pts[s:s + 2048, 1:]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                crosses = (ay > py) != (by > py)
+                xint = ax + (py - ay) * dx / dy
+                inside = np.count_nonzero(crosses & (px < xint), axis=1) % 2 == 1
+                t = np.where(l2 > 0, ((px - ax) * dx + (py - ay) * dy) / l2, 0.0)
+            t = np.clip(t, 0.0, 1.0)
+            ex, ey = ax + t * dx - px, ay + t * dy - py
+            out[s:s + 2048] = inside | ((ex * ex + ey * ey).min(axis=1) < b2)
+        return out
+    return keep
+
+
+def plot_id(plot_idx: int, center) -> str:
+    """`define_plot_id(define_a_plot_name(plot_idx), center)` (prepare_utils.py:84-92)."""
+    return f"PP{str(int(plot_idx)).zfill(8)}_X{int(center[0])}_Y{int(center[1])}"
+
+
+def center_grid(centers: np.ndarray, radius: float, bbox):
+    """CSR of the centres that can reach the parcel's bounding box over square cells of side >= radius (host side of
+    csrc/parcel.hip): (cell_start (GX*GY+1), cell_items, GX, GY, gx0, gy0, cell_inv), or None when no centre is within
+    reach.  Cells grow beyond radius for very wide centre sets (at most 2048 per side)."""
+    c = centers.astype(np.float64)
+    x_min, y_min, x_max, y_max = (float(v) for v in bbox)
+    reach = float(radius) + 1.0
+    ids = np.nonzero((c[:, 0] >= x_min - reach) & (c[:, 0] <= x_max + reach) &
+                     (c[:, 1] >= y_min - reach) & (c[:, 1] <= y_max + reach))[0]
+    if len(ids) == 0:
+        return None
+    cx, cy = c[ids, 0], c[ids, 1]
+    gx0, gy0 = float(cx.min()), float(cy.min())
+    side = max(float(radius) * 1.001, max(float(cx.max()) - gx0, float(cy.max()) - gy0) / 2048)
+    inv = 1.0 / side
+    ix = np.floor((cx - gx0) * inv).astype(np.int64)          # the kernels' floor((v - g0) * inv), in fp64
+    iy = np.floor((cy - gy0) * inv).astype(np.int64)
+    GX, GY = int(ix.max()) + 1, int(iy.max()) + 1
+    cell = iy * GX + ix
+    order = np.lexsort((ids, cell))                            # by cell, ascending centre id inside a cell
+    start = np.zeros(GX * GY + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cell, minlength=GX * GY), out=start[1:])
+    return start.astype(np.int32), ids[order].astype(np.int32), GX, GY, gx0, gy0, inv
+
+
+@dataclass
+class ParcelPlots:
+    """The kept plots of a parcel, ragged and device resident: raw (10,ΣN) fp32 (z row normalised per plot, the other rows
+    the parcel's values), offsets (P+1) int32, point_index (ΣN) int32 (columns of the parcel), centers (P,2) fp32.  On the
+    host: n_points (P), plot_index (P) (the plot's index in the list of centres), plot_ids, centers_host (P,2) fp32."""
+    raw: torch.Tensor
+    offsets: torch.Tensor
+    point_index: torch.Tensor
+    centers: torch.Tensor
+    n_points: np.ndarray
+    plot_index: np.ndarray
+    plot_ids: List[str]
+    centers_host: np.ndarray
+
+    def __len__(self):
+        return len(self.n_points)
+
+    def batches(self, args, batch_size: int, rs=np.random, fps_start: Optional[int] = None):
+        """The input dicts of `inference.predict_parcel` ("cloud", "xyz", "plot_center"), built on the device from raw /
+        offsets by `sn2_prepare_plots` in eval mode.  Random draws: `draw_plot_randoms` per plot in plot order, so the
+        batches equal `input_pipeline.prepare_batch(plots, centers, args, train=False, rs=rs)` on the same plots and seed.
+        fps_start: None (the model draws the FPS starts) or one start index for every plot."""
+        dev = self.raw.device
+        fake = fake_ground_xy(args.diam_meters)
+        fake_dev = torch.from_numpy(fake).to(dev)
+        N = args.subsample_size
+        for b0 in range(0, len(self), batch_size):
+            b1 = min(len(self), b0 + batch_size)
+            draws = [draw_plot_randoms(int(n) + len(fake), N, False, rs, False) for n in self.n_points[b0:b1]]
+            idx = torch.from_numpy(np.stack([d["idx"] for d in draws])).to(dev)
+            with torch.cuda.device(dev):
+                cloud, xyz = ops.prepare_plots(self.raw, self.offsets[b0:b1 + 1], self.centers[b0:b1], fake_dev, idx, args.z_max)
+            d = {"cloud": cloud, "xyz": xyz, "plot_center": self.centers_host[b0:b1]}
+            if fps_start is not None:
+                d["fps_start"] = torch.full((2, b1 - b0), int(fps_start), dtype=torch.int64)
+            yield d
+
+
+def _empty(dev) -> ParcelPlots:
+    return ParcelPlots(torch.empty(10, 0, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                       torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, 2, dtype=torch.float32, device=dev),
+                       np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), [], np.zeros((0, 2), dtype=np.float32))
+
+
+def prepare_parcel(parcel_cloud, args, centers=None, keep=None, device=None) -> ParcelPlots:
+    """parcel_cloud: (10,T) float32, numpy or a device tensor, in the reference's channel order and absolute metres ->
+    the kept plots (>= 51 points) of the parcel, prepared on the device.  centers: None (the reference's lattice over the
+    parcel's bounding box, `parcel_plot_centers` with `keep`) or a (P,2) set of plot centres (any: duplicates and centres
+    without points included)."""
+    dev = torch.device(device) if device is not None else (
+        parcel_cloud.device if isinstance(parcel_cloud, torch.Tensor) and parcel_cloud.is_cuda else torch.device("cuda"))
+    cloud = torch.as_tensor(parcel_cloud).to(device=dev, dtype=torch.float32).contiguous()
+    if cloud.dim() != 2 or cloud.shape[0] != 10 or cloud.shape[1] == 0:
+        raise ValueError(f"parcel_cloud: expected (10,T) with T > 0, got {tuple(cloud.shape)}")
+    T = cloud.shape[1]
+    if T >= 2 ** 31:
+        raise ValueError("parcel_cloud: at most 2^31 - 1 points")
+    with torch.cuda.device(dev):
+        box = torch.cat([cloud[:2].min(1).values, cloud[:2].max(1).values]).cpu().numpy()   # fp32, get_xy_range
+        bbox = (box[0], box[1], box[2], box[3])                  # x_min, y_min, x_max, y_max
+        if centers is None:
+            centers = parcel_plot_centers(box[0], box[2], box[1], box[3], args, keep)
+        centers = np.ascontiguousarray(np.asarray(centers, dtype=np.float32).reshape(-1, 2))
+        P = len(centers)
+        radius = args.diam_meters // 2
+        grid = center_grid(centers, radius, bbox) if P else None
+        if grid is None:
+            return _empty(dev)
+        L = max(ROW_POINTS, -(-T * P // MAX_TABLE + 63) // 64 * 64)     # rows * P <= about MAX_TABLE
+        rows = -(-T // L)
+        cen = torch.from_numpy(centers).to(dev)
+        g = (torch.from_numpy(grid[0]).to(dev), torch.from_numpy(grid[1]).to(dev)) + grid[2:]
+        prefix, total = ops.parcel_count(cloud, cen, g, radius, L, rows)
+        starts = torch.cat([prefix[::rows].to(torch.int64), total]).cpu().numpy()
+        if starts[-1] >= 2 ** 31:
+            raise ValueError(f"prepare_parcel: {starts[-1]} plot points in all discs, at most 2^31 - 1")
+        starts = starts[:-1]
+        counts = np.diff(starts)
+        kept = counts >= MIN_POINTS
+        if not kept.any():
+            return _empty(dev)
+        n_points = counts[kept]
+        offsets = np.concatenate([[0], np.cumsum(n_points)])
+        base = np.full(P, INT_MIN, dtype=np.int64)
+        base[kept] = offsets[:-1] - starts[:-1][kept]
+        raw, pidx = ops.parcel_fill(cloud, cen, g, radius, L, rows, prefix, torch.from_numpy(base.astype(np.int32)).to(dev),
+                                    int(offsets[-1]))
+        offsets_dev = torch.from_numpy(offsets.astype(np.int32)).to(dev)
+        centers_kept = np.ascontiguousarray(centers[kept])
+        cen_kept = torch.from_numpy(centers_kept).to(dev)
+        ops.parcel_znorm(cloud, bbox, float(getattr(args, "znorm_radius_in_meters", 1.5)), radius, offsets_dev, cen_kept, pidx,
+                         raw)
+    plot_index = np.nonzero(kept)[0]
+    return ParcelPlots(raw, offsets_dev, pidx, cen_kept, n_points, plot_index,
+                       [plot_id(k, centers[k]) for k in plot_index], centers_kept)
+
+
+def parcel_mosaic(centers_host: np.ndarray, args, device) -> ParcelMosaic:
+    """The mosaic that holds every plot raster of the given centres: left = min cx - diam_meters//2, top = max cy +
+    diam_meters//2, pixels of diam_meters/diam_pix metres, plot windows placed as `ParcelMosaic.offsets` places them."""
+    half = args.diam_meters // 2
+    c = torch.as_tensor(np.asarray(centers_host), dtype=torch.float64).reshape(-1, 2)
+    left, top = float(c[:, 0].min()) - half, float(c[:, 1].max()) + half
+    pix = args.diam_meters / args.diam_pix
+    rows = torch.round((top - (c[:, 1] + half)) / pix)                # as ParcelMosaic.offsets
+    cols = torch.round(((c[:, 0] - half) - left) / pix)
+    return ParcelMosaic(left, top, int(rows.max()) + args.diam_pix, int(cols.max()) + args.diam_pix, args, device)
+
+
+def predict_parcel_cloud(model, parcel_cloud, args, batch_size: int = 20, rs=np.random, keep=None, prefetch: int = 3,
+                         centers=None, fps_start: Optional[int] = None):
+    """prepare_parcel + a mosaic sized to the plots + `inference.predict_parcel` -> (ParcelMosaic, ParcelPlots).  The mosaic
+    is None when the parcel has no kept plot.  `mosaic.finalize()` gives the coverage bands."""
+    plots = prepare_parcel(parcel_cloud, args, centers=centers, keep=keep)
+    if len(plots) == 0:
+        return None, plots
+    mosaic = parcel_mosaic(plots.centers_host, args, plots.raw.device)
+    predict_parcel(model, plots.batches(args, batch_size, rs, fps_start), mosaic, args, prefetch=prefetch)
+    return mosaic, plots

@@ -58,3 +58,74 @@ def make_batch(batch_size: int, n_points: int, first_plot: int = 0, base_seed: i
     gt = torch.rand(batch_size, 4, generator=g, dtype=torch.float64)
     pdf = 0.05 + 0.95 * torch.rand(batch_size * n_points, 3, generator=g, dtype=torch.float64)
     return {"cloud": torch.stack(clouds), "xyz": torch.stack(xyzs), "coverages": gt, "pdf_all": pdf}
+
+
+def make_parcel(width_m: float = 120.0, height_m: float = 100.0, density: float = 4.0, seed: int = 0, order: str = "scanline",
+                x0: float = 650000.0, y0: float = 6860000.0, args=None, plant: bool = True):
+    """A seeded parcel cloud (10,T) float32 in the reference's channel order and absolute Lambert-93-like metres, as
+    `load_las_file` makes it: integer centimetres / 100, cast to fp32 (spacing 1/16 m in x, 1/2 m in y at these values).
+
+    Mean density `density` points/m^2, four times higher on the left half than on the right, with an empty 50 m x 36 m
+    gap.
+    Four corner points fix the bounding box to (x0, y0, x0 + width_m, y0 + height_m), so the plot lattice is known; with
+    `plant`, inside the gap two lattice discs get exactly 50 and 51 points, and around a few lattice centres points are
+    planted at exactly 10 m (kept: the disc test is inclusive), pairs at exactly 1.5 m (the z-norm test is inclusive), and
+    a low point just outside a disc next to a point just inside (the per-plot z-norm differs there from a parcel-wide one).
+    order: "scanline" (sorted by 5 m strips, then y: flight lines) or "shuffled"."""
+    import numpy as np
+    from .parcel import parcel_plot_centers
+    args = args or make_args()
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    x0, y0 = float(f32(x0)), float(f32(y0))
+    area = width_m * height_m
+    n = int(rng.poisson(density * area))
+    u = rng.random((n, 2))
+    left = rng.random(n) < 0.8                                    # 4:1 between the halves
+    px = np.where(left, u[:, 0] * 0.5, 0.5 + u[:, 0] * 0.5) * width_m
+    py = u[:, 1] * height_m
+    gx, gy = 0.45 * width_m, 0.4 * height_m
+    out_gap = ~((px >= gx) & (px <= gx + 50) & (py >= gy) & (py <= gy + 36))
+    xy = np.stack([np.round((x0 + px[out_gap]) * 100) / 100, np.round((y0 + py[out_gap]) * 100) / 100], 1)
+    corners = np.array([[x0, y0], [x0 + width_m, y0 + height_m], [x0, y0 + height_m], [x0 + width_m, y0]])
+    pts = [np.concatenate([corners, xy])]
+    zs = [None]
+    cen = parcel_plot_centers(x0, f32(x0 + width_m), y0, f32(y0 + height_m), args).astype(np.float64)[1:]
+    if plant:
+        gap_lo, gap_hi = np.array([x0 + gx, y0 + gy]), np.array([x0 + gx + 50, y0 + gy + 36])
+        inner = np.all((cen >= gap_lo + 11) & (cen <= gap_hi - 11), axis=1)
+        sparse = cen[inner]
+        if len(sparse) < 2:
+            raise ValueError("make_parcel: the gap holds fewer than two lattice discs (parcel too small)")
+        for c, k in zip(sparse[:2], (50, 51)):                    # discs of exactly 50 and 51 points
+            a, r = rng.random(k) * 2 * np.pi, 3.0 * np.sqrt(rng.random(k))
+            pts.append(np.stack([c[0] + r * np.cos(a), c[1] + r * np.sin(a)], 1))
+        dense = cen[np.all((cen >= np.array([x0 + 15, y0 + 15])) & (cen <= np.array([x0 + gx - 15, y0 + height_m - 15])), 1)]
+        for c in dense[::3]:
+            c = c.astype(f32).astype(np.float64)                  # the fp32 centre the discs are cut around
+            pts.append(c + np.array([[6.0, 8.0], [-10.0, 0.0], [0.0, 10.0], [-6.0, -8.0]]))      # exactly 10 m
+            pts.append(c + np.array([[2.0, 2.0], [3.5, 2.0], [2.0, 3.5]]))                       # exactly 1.5 m apart
+            pts.append(c + np.array([[9.5, 0.0], [10.5, 0.0]]))                                  # in / out of the disc
+    xy = np.concatenate(pts).astype(f32)
+    T = len(xy)
+    z = np.round(np.where(rng.random(T) < 0.55, np.abs(0.05 * rng.standard_normal(T)),
+                          np.where(rng.random(T) < 0.5, 1.5 * rng.random(T), 1.5 + 18.5 * rng.random(T))) * 100) / 100
+    if plant:                                     # planted pairs: the second, 1.5 m away, and the out-of-disc point lower
+        k = T - 9 * len(dense[::3])
+        for j in range(len(dense[::3])):
+            b = k + 9 * j
+            z[b + 4], z[b + 5], z[b + 6] = 3.0, -2.0, 4.0
+            z[b + 7], z[b + 8] = 1.0, -5.0
+    z = z + 100.0                                 # absolute altitudes
+    feats = np.stack([rng.integers(0, 65536, T), rng.integers(0, 65536, T), rng.integers(0, 65536, T),
+                      rng.integers(0, 65536, T), rng.integers(0, 32768, T)]).astype(np.float64)
+    nret = rng.integers(1, 5, T)
+    ret = np.minimum(rng.integers(1, 5, T), nret)
+    cloud = np.concatenate([xy.T.astype(np.float64), z[None], feats, ret[None], nret[None]]).astype(f32)
+    if order == "shuffled":
+        perm = rng.permutation(T)
+    elif order == "scanline":
+        perm = np.lexsort((cloud[1], np.floor((cloud[0] - f32(x0)) / 5)))
+    else:
+        raise ValueError("order must be 'scanline' or 'shuffled'")
+    return np.ascontiguousarray(cloud[:, perm])
