@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SN2_VERSION 101
+#define SN2_VERSION 102
 #define SN2_EINVAL (-1) /* bad size / null pointer             */
 #define SN2_ELIMIT (-2) /* size outside what the kernels cover */
 
@@ -185,6 +185,43 @@ int sn2_three_nn_xy(const float *src_soa, int B, int S, const float *dst_soa, in
 int sn2_prepare_plots(const float *raw, long T, const int *offsets, const float *centers, const float *fake_xy, int n_fake,
                       const int *idx, int B, int N, int train, const double *rot, const int *flips, const float *noise,
                       const long *noise_offsets, long noise_T, float z_max, float *cloud, float *xyz, void *stream);
+
+/* ---- the subsample of every plot of a batch, drawn on the device (csrc/sample.hip): the DISTRIBUTION of the reference's
+ * sample_cloud (data_loader/loader.py:233-247), not numpy's draws.  idx (B,N) is what sn2_prepare_plots takes.
+ * Plot b has n_b = offsets[b+1] - offsets[b] + extra candidates, numbered 0 .. n_b-1 as sn2_prepare_plots numbers them (the
+ * plot's raw points, then the `extra` = n_fake appended ones).
+ *
+ * Generator: u(seed, key, i) is a 64-bit word from Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), all words 32-bit unsigned:
+ *   counter c = (c0, c1, c2, c3) = (i, 0, key & 0xffffffff, key >> 32)          (key: the plot's int64 key as 64 unsigned bits)
+ *   key     k = (k0, k1)         = (seed & 0xffffffff, seed >> 32)
+ *   ten times:  p0 = 0xD2511F53 * c0, p1 = 0xCD9E8D57 * c2                       (32 x 32 -> 64 bits)
+ *               c <- (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0))
+ *               and, after each of the ten rounds (the tenth's has no effect), k0 += 0x9E3779B9, k1 += 0xBB67AE85 (mod 2^32)
+ *   u = c0 << 32 | c1 of the final counter (the generator's first two output words, the first one on top).
+ * Row of plot b with key_b = plot_keys[b]:
+ *   n_b >  N: the N candidates i with the smallest pairs (u(seed, key_b, i), i), in ascending order of that pair.  The N smallest
+ *             of n independent uniform keys are a uniform N-subset in uniform order, as choice(n, N, replace=False) gives; two
+ *             equal keys (probability below n^2 / 2^65 per plot) are ordered by index.
+ *   n_b <= N: idx[b, j] = j for j < n_b, and idx[b, j] = floor(u(seed, key_b, j) * n_b / 2^64) for n_b <= j < N (the high 64 bits
+ *             of the 64 x 64 bit product; a value's probability is off from 1/n_b by less than 2^-64).
+ * So a row depends on (seed, key_b, n_b, N) alone: not on B, the plot's place in the batch or the form that ran; integer
+ * arithmetic only, and no atomic whose order could reach the output.
+ * n_max: the caller's bound on every n_b (it picks the form and sizes the workspace without a device read).  A plot with more
+ * candidates is sampled from its first n_max; a plot WITHOUT candidates (possible only with extra == 0) gets a row of zeros --
+ * a caller that knows its counts on the host refuses such a plot before the call.  extra < 0, n_max <= 0, N <= 0: SN2_EINVAL.
+ * form: 0 = by sn2_subsample_form(n_max, N); SN2_SUBSAMPLE_LDS = one workgroup per plot with the (key piece, index) pairs in
+ * LDS, n_max <= SN2_SUBSAMPLE_LDS_MAX (else SN2_ELIMIT); SN2_SUBSAMPLE_GLOBAL = four launches over the workspace, any n_max.
+ * | SN2_SUBSAMPLE_COARSE (tests): the pairs keep 2 key bits instead of 32, so nearly every comparison takes the path that
+ * recomputes the full keys.  Every form gives the same bytes.
+ * ws: 16-byte aligned, sn2_subsample_ws_words(B, n_max, N, form) 32-bit words (0 for the LDS form: ws may be NULL). */
+#define SN2_SUBSAMPLE_LDS 1
+#define SN2_SUBSAMPLE_GLOBAL 2
+#define SN2_SUBSAMPLE_COARSE 4
+#define SN2_SUBSAMPLE_LDS_MAX 16384
+int sn2_subsample_form(int n_max, int N); /* SN2_SUBSAMPLE_LDS or SN2_SUBSAMPLE_GLOBAL: what form 0 takes */
+size_t sn2_subsample_ws_words(int B, int n_max, int N, int form);
+int sn2_subsample(const int *offsets, int extra, int n_max, int B, int N, unsigned long long seed, const long long *plot_keys,
+                  int form, int *ws, size_t ws_words, int *idx, void *stream);
 
 /* z-normalisation of a raw plot (offline preparation): z_i - min{ z_j : |xy_i - xy_j| <= radius } --
  * normalize_z_with_minz_in_a_radius, utils/load_data.py:237-249 (sklearn kd-tree radius query in x,y + a python loop).

@@ -7,7 +7,7 @@ from ctypes import POINTER, Structure, c_double, c_float, c_int, c_long, c_longl
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libstrata_hip.so")
 
-SN2_VERSION = 101
+SN2_VERSION = 102
 MAX_NEIGHBORS = 2000  # model/point_net2.py:24
 STAT_SLOTS = 1024     # SN2_STAT_SLOTS
 
@@ -133,6 +133,9 @@ SIGNATURES = {
                         c_double, c_float, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
     "sn2_parcel_znorm": [c_void_p, c_long, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int,
                          c_void_p, c_long, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    "sn2_subsample_form": [c_int, c_int],
+    "sn2_subsample": [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_void_p, ctypes.c_size_t,
+                      c_void_p, c_void_p],
     "sn2_sa_order": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "sn2_sa_order_group": [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_sa_forward": [POINTER(SA), c_int, c_void_p],
@@ -192,6 +195,7 @@ SIGNATURES = {
 SIZE_HELPERS = {
     "sn2_parcel_count_ws_words": [c_int, c_int],
     "sn2_parcel_znorm_ws_words": [c_long, c_float, c_float, c_float, c_float, c_float],
+    "sn2_subsample_ws_words": [c_int, c_int, c_int, c_int],
 }
 
 _lib = None

@@ -587,6 +587,53 @@ def prepare_plots(raw, offsets, centers, fake_xy, idx, z_max: float, rot=None, f
     return cloud, xyz
 
 
+SUBSAMPLE_LDS, SUBSAMPLE_GLOBAL, SUBSAMPLE_COARSE = 1, 2, 4      # SN2_SUBSAMPLE_* of include/strata_hip.h
+SUBSAMPLE_LDS_MAX = 16384                                        # SN2_SUBSAMPLE_LDS_MAX
+
+
+def subsample_form(n_max: int, N: int) -> int:
+    """The form sn2_subsample takes for plots of at most n_max candidates when none is forced (sn2_subsample_form):
+    SUBSAMPLE_LDS (one workgroup per plot, pairs in LDS) or SUBSAMPLE_GLOBAL (four launches over a workspace)."""
+    return int(_lib.load().sn2_subsample_form(int(n_max), int(N)))
+
+
+def subsample_ws_words(B: int, n_max: int, N: int, form: int = 0) -> int:
+    """sn2_subsample_ws_words of include/strata_hip.h (0: the LDS form needs no workspace)."""
+    return int(_lib.load().sn2_subsample_ws_words(int(B), int(n_max), int(N), int(form)))
+
+
+def subsample(offsets, extra: int, N: int, seed: int, plot_keys, n_max: Optional[int] = None, form: int = 0):
+    """include/strata_hip.h: sn2_subsample.  offsets (B+1) i32, plot_keys (B) i64 -> idx (B,N) i32 for prepare_plots: per plot
+    the N candidates (of its offsets[b+1] - offsets[b] + extra) with the smallest Philox keys u(seed, plot_keys[b], i) in key
+    order, or all of them followed by draws with replacement.  n_max: the caller's host-side bound on a plot's candidates
+    (None: read from `offsets`, one small sync).  form: 0, or a SUBSAMPLE_* form for the tests (same bytes)."""
+    _chk(offsets, I32, None, "offsets")
+    if offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError("offsets: expected (B+1,) with B >= 1")
+    B = offsets.numel() - 1
+    _chk(plot_keys, I64, (B,), "plot_keys")
+    extra, N, seed, form = int(extra), int(N), int(seed), int(form)
+    if N <= 0 or extra < 0:
+        raise ValueError("subsample: N must be positive and extra non-negative")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("subsample: seed must fit 64 unsigned bits")
+    if n_max is None:
+        n_max = int((offsets[1:] - offsets[:-1]).max()) + extra
+    n_max = int(n_max)
+    if n_max <= 0 or n_max >= 2 ** 31:
+        raise ValueError("subsample: n_max must be in 1 .. 2^31 - 1 (a plot needs at least one candidate)")
+    if form not in (0, 1, 2, 5, 6):
+        raise ValueError("subsample: form must be 0, SUBSAMPLE_LDS or SUBSAMPLE_GLOBAL (| SUBSAMPLE_COARSE)")
+    if form & 3 == SUBSAMPLE_LDS and n_max > SUBSAMPLE_LDS_MAX:
+        raise ValueError(f"subsample: the LDS form takes at most {SUBSAMPLE_LDS_MAX} candidates per plot")
+    dev = offsets.device
+    nw = subsample_ws_words(B, n_max, N, form)
+    ws = torch.empty(nw + 4, dtype=I32, device=dev) if nw else None
+    idx = torch.empty(B, N, dtype=I32, device=dev)
+    _call("sn2_subsample", _ptr(offsets), extra, n_max, B, N, seed, _ptr(plot_keys), form, _ptr(ws), nw, _ptr(idx), _stream())
+    return idx
+
+
 def znorm(xyz: torch.Tensor, radius: float):
     """xyz (3,n) fp32 of ONE raw plot on the device -> (zmin (n), z - zmin (n)): the local-minimum z-normalisation of
     `normalize_z_with_minz_in_a_radius` (utils/load_data.py:237-249)."""

@@ -11,6 +11,11 @@ numpy code with a `deepcopy` per sample running in the training process.  Here t
 `noise="numpy"` draws the gaussian noise with `rs.randn` exactly where the reference does (bit-identical batches, used by
 the parity tests); `noise="device"` draws it with torch on the device (same distribution, no host work);
 `noise=None` leaves it out.
+
+`sampler="numpy"` (the default) draws every plot's subsample with `rs.choice` as the reference does; `sampler="device"` draws
+it on the device with `hip_ops.subsample` (csrc/sample.hip: the same distribution from a counter-based generator keyed by
+`seed` and one key per plot -- the same seed gives the same bytes, but not the reference's draws).  With `noise="device"` as
+well, no per-point work is left on the host.
 """
 import numpy as np
 import torch
@@ -30,10 +35,25 @@ def fake_ground_xy(diam_meters: int) -> np.ndarray:
     return np.stack([fx[keep], fy[keep]], 1).astype(np.float32)
 
 
-def draw_plot_randoms(n_points: int, subsample_size: int, train: bool, rs, noise: bool):
+SAMPLERS = ("numpy", "device")
+
+
+def check_sampler(sampler):
+    if sampler not in SAMPLERS:
+        raise ValueError("sampler must be 'numpy' or 'device'")
+    return sampler
+
+
+def draw_seed(rs) -> int:
+    """One 64-bit seed for `hip_ops.subsample` from the host generator (two 32-bit draws)."""
+    hi, lo = (int(v) for v in rs.randint(0, 2 ** 32, size=2, dtype=np.uint64))
+    return hi << 32 | lo
+
+
+def draw_plot_randoms(n_points: int, subsample_size: int, train: bool, rs, noise: bool, subsample: bool = True):
     """The random draws `load_cloud` makes for ONE plot of `n_points` points (fake points included), in its order:
     augment -> get_xyz_augmentation_params (:217-222), xy noise (:186-193), colour noise (:200-208); then sample_cloud
-    (:233-247)."""
+    (:233-247) unless `subsample` is False (the device sampler draws it)."""
     out = {}
     if train:
         flip_x = rs.random() > 0.5
@@ -47,6 +67,8 @@ def draw_plot_randoms(n_points: int, subsample_size: int, train: bool, rs, noise
             ncol = [np.clip(sigma * rs.randn(n_points), a_min=-clip_c, a_max=clip_c).astype(np.float32)   # sigma of x,y:
                     for _ in range(4)]                                                                      # loader.py:180,202
             out["noise"] = np.concatenate([nxy, np.stack(ncol)], 0)
+    if not subsample:
+        return out
     if n_points > subsample_size:
         idx = rs.choice(n_points, subsample_size, replace=False)
     else:
@@ -55,18 +77,34 @@ def draw_plot_randoms(n_points: int, subsample_size: int, train: bool, rs, noise
     return out
 
 
-def prepare_batch(raw_plots, centers, args, train: bool, rs=np.random, device="cuda:0", noise="numpy"):
+def prepare_batch(raw_plots, centers, args, train: bool, rs=np.random, device="cuda:0", noise="numpy", sampler="numpy",
+                  seed=None, plot_keys=None):
     """raw_plots: list of (10, n_i) float32 arrays/tensors (host or device); centers: (B,2).  Returns the `cloud_data`
-    dict the model takes: {"cloud": (B,10,N), "xyz": (B,3,N)} on the device."""
+    dict the model takes: {"cloud": (B,10,N), "xyz": (B,3,N)} on the device.
+    sampler="device": the subsample of plot b is `hip_ops.subsample`'s row for (seed, plot_keys[b]); seed: None = one 64-bit
+    seed drawn from `rs` per call (after the plots' augmentation draws); plot_keys: (B) integers, None = 0 .. B-1."""
+    check_sampler(sampler)
+    if sampler == "numpy" and (seed is not None or plot_keys is not None):
+        raise ValueError("seed and plot_keys belong to sampler='device'")
     dev = torch.device(device)
     B = len(raw_plots)
     N = args.subsample_size
     fake = fake_ground_xy(args.diam_meters)
     n_raw = [int(p.shape[1]) for p in raw_plots]
-    draws = [draw_plot_randoms(n + len(fake), N, train, rs, noise == "numpy") for n in n_raw]
+    if sampler == "device" and min(n_raw) + len(fake) <= 0:
+        raise ValueError("prepare_batch: a plot without points and no fake ground points to add")
+    draws = [draw_plot_randoms(n + len(fake), N, train, rs, noise == "numpy", sampler == "numpy") for n in n_raw]
     raw = torch.cat([torch.as_tensor(p, dtype=torch.float32).to(dev) for p in raw_plots], 1).contiguous()
     offsets = torch.tensor(np.concatenate([[0], np.cumsum(n_raw)]), dtype=torch.int32, device=dev)
-    idx = torch.from_numpy(np.stack([d["idx"] for d in draws])).to(dev)
+    if sampler == "numpy":
+        idx = torch.from_numpy(np.stack([d["idx"] for d in draws])).to(dev)
+    else:
+        keys = np.arange(B, dtype=np.int64) if plot_keys is None else np.asarray(plot_keys, dtype=np.int64).reshape(-1)
+        if keys.shape[0] != B:
+            raise ValueError("plot_keys: one key per plot")
+        with torch.cuda.device(dev):
+            idx = ops.subsample(offsets, len(fake), N, draw_seed(rs) if seed is None else seed, torch.from_numpy(keys).to(dev),
+                                n_max=max(n_raw) + len(fake))
     rot = flips = nz = noffs = None
     if train:
         rot = torch.tensor([[np.cos(d["angle"]), np.sin(d["angle"])] for d in draws], dtype=torch.float64, device=dev)
