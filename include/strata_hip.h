@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SN2_VERSION 102
+#define SN2_VERSION 102 /* unchanged by ADDED entry points (sn2_plot_losses): a binding that knows 102 still finds all it asks for */
 #define SN2_EINVAL (-1) /* bad size / null pointer             */
 #define SN2_ELIMIT (-2) /* size outside what the kernels cover */
 
@@ -548,6 +548,36 @@ int sn2_projected_loss_forward(const float *coverages, const int *pix, const flo
 int sn2_projected_loss_backward(const float *pred, const double *gt, int B, const float *proba, const double *pdf, int N, int D,
                                 double m, double e, const double *grad_total, const int *arg, const int *nocc, const int *pix,
                                 float *dcoverages, float *dproba, void *stream);
+
+/* Validation pass -- the per-plot losses of learning/test.py:evaluate (:52-79), which runs with batch_size = 1: its loss_abs,
+ * loss_log, loss_e and get_absolute_loss_by_strata are numbers of ONE plot each, averaged over plots afterwards.  For a batch
+ * of B plots of N points in one call (two launches, no backward, no arg / nocc):
+ *   coverages (B*N,4), proba (B*N,4) fp32; pix (B*N) the pixel ids of sn2_plot_pixels; pdf (B*N,3) fp64; gt (B,4) fp64;
+ *   pred (B,4) fp32 out: the plot-wise coverages, the bits of sn2_plot_project_forward_pix for the same inputs;
+ *   out (B,7) fp64, row b over plot b's N rows only: [total, absolute, NLL, entropy, abs_low, abs_med, abs_high] with
+ *     abs_s = sqrt((pred[b,s] - gt[b,s])^2 + 1e-4) for s = columns 0, 2, 3, absolute = their mean, NLL = -mean_i log(sum_k p_k
+ *     pdf_k) (p_ground = p0 + p1), entropy over columns 2, 3 as get_entropy_loss, total = absolute + m NLL + e entropy; absolute
+ *     and NLL in fp64, the entropy terms in fp32 (as sn2_loss_forward): row b equals what sn2_projected_loss_forward returns for
+ *     a batch that holds plot b alone, to fp64 re-association.
+ *   A switched-off term is SKIPPED as in sn2_loss_forward and its component is 0: m == 0: pdf may be NULL; e == 0: no entropy;
+ *   m == e == 0: proba may be NULL too.
+ *   ws: 8-byte aligned workspace of sn2_plot_losses_ws_words(B, N, D) 32-bit words, no initialisation.
+ * Contract:
+ *   - BATCH INVARIANCE: row b of out and pred depends on plot b's rows, N, D, m, e only -- the same plot at another position,
+ *     in a batch of another size, gives the same bytes.  (Every plot is cut into SN2_PLOT_LOSSES_SLICES(N) slices, a function
+ *     of N alone; a slice is summed by one workgroup in a fixed order, a plot's slices are added in ascending order by one
+ *     thread; no floating-point atomics, no partial sum shared between plots.)
+ *   - run-to-run identical bytes;
+ *   - a NaN (a height outside the KDE tables: sn2_kde_lookup marks it NaN) stays in its own plot's row;
+ *   - any B >= 1, N >= 1 with B*N < 2^31, D*D <= 2025 (as the other projection entry points); beyond: SN2_ELIMIT
+ *     (sn2_plot_losses_ws_words returns 0); NULL pointers, non-positive sizes: SN2_EINVAL -- both before anything is launched. */
+#define SN2_PLOT_LOSSES_SLICE_ROWS 2048
+#define SN2_PLOT_LOSSES_SLICES(N) \
+    (((N) + SN2_PLOT_LOSSES_SLICE_ROWS - 1) / SN2_PLOT_LOSSES_SLICE_ROWS < 1 ? 1 : \
+     (((N) + SN2_PLOT_LOSSES_SLICE_ROWS - 1) / SN2_PLOT_LOSSES_SLICE_ROWS > 64 ? 64 : ((N) + SN2_PLOT_LOSSES_SLICE_ROWS - 1) / SN2_PLOT_LOSSES_SLICE_ROWS))
+size_t sn2_plot_losses_ws_words(int B, int N, int D);
+int sn2_plot_losses(const float *coverages, const int *pix, const float *proba, const double *pdf, const double *gt, int B, int N,
+                    int D, double m, double e, void *ws, float *pred, double *out, void *stream);
 
 /* ---- optimiser step of the timed training step -- torch.optim.Adam as configured in learning/train.py:180-185
  * (L2 weight decay added to the gradient), on flat buffers; grad_scale multiplies the gradient first (1/world). */

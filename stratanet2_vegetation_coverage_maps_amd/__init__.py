@@ -4,6 +4,7 @@ Mirror of the reference's `model/` package for that path:
     from stratanet2_vegetation_coverage_maps_amd import PointNet2, project_to_plotwise_coverages, project_to_2d_rasters
 The HIP library (csrc/libstrata_hip.so) is loaded on first use and is mandatory: there is no CPU fallback.
 """
+from .evaluation import evaluate, plot_losses, plot_losses_torch  # noqa: F401
 from .hip_ops import subsample, subsample_form  # noqa: F401
 from .parcel import (ParcelPlots, parcel_plot_centers, polygon_keep, predict_parcel_cloud,  # noqa: F401
                      prepare_parcel)
@@ -12,4 +13,5 @@ from .project_to_2d import (project_batch_to_2d_rasters, project_to_2d_rasters, 
                             project_to_plotwise_coverages)
 
 __all__ = ["PointNet2", "project_to_plotwise_coverages", "project_to_2d_rasters", "project_batch_to_2d_rasters", "ParcelPlots",
-           "parcel_plot_centers", "polygon_keep", "prepare_parcel", "predict_parcel_cloud", "subsample", "subsample_form"]
+           "parcel_plot_centers", "polygon_keep", "prepare_parcel", "predict_parcel_cloud", "subsample", "subsample_form",
+           "evaluate", "plot_losses", "plot_losses_torch"]

@@ -7,7 +7,7 @@ from ctypes import POINTER, Structure, c_double, c_float, c_int, c_long, c_longl
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libstrata_hip.so")
 
-SN2_VERSION = 102
+SN2_VERSION = 102          # (added entry points keep the version: include/strata_hip.h)
 MAX_NEIGHBORS = 2000  # model/point_net2.py:24
 STAT_SLOTS = 1024     # SN2_STAT_SLOTS
 
@@ -178,6 +178,8 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_projected_loss_backward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_plot_losses": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
+                        c_void_p, c_void_p],
     "sn2_adam_step_images": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float,
                              c_void_p, c_float, c_void_p],
     "sn2_net_ctx_create": [POINTER(c_void_p)],
@@ -196,6 +198,7 @@ SIZE_HELPERS = {
     "sn2_parcel_count_ws_words": [c_int, c_int],
     "sn2_parcel_znorm_ws_words": [c_long, c_float, c_float, c_float, c_float, c_float],
     "sn2_subsample_ws_words": [c_int, c_int, c_int, c_int],
+    "sn2_plot_losses_ws_words": [c_int, c_int, c_int],
 }
 
 _lib = None

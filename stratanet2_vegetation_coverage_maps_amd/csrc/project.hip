@@ -579,6 +579,177 @@ extern "C" int sn2_projected_loss_backward(const float* pred, const double* gt, 
     SN2_RETURN_LAUNCH();
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Validation pass: the losses of EVERY PLOT of a batch on its own (learning/test.py:52-79 evaluates with batch_size = 1, so its
+// loss_abs / loss_log / loss_e / get_absolute_loss_by_strata are per-plot numbers that an AverageValueMeter then averages).
+//   launch 1  one workgroup per (plot, slice of PL_SLICE_ROWS rows): scatters its rows' coverages into its own key table
+//             (scatter_max_pix_kernel's body) AND sums the pointwise loss terms of the same rows (loss_point_kernel's body) -- the
+//             number of slices depends on N alone, so the pointwise pass of a single plot already is cdiv(N, 2048) workgroups;
+//   launch 2  one workgroup per plot: maximum over the slices and mean over occupied pixels (p2_finalize_kernel's arithmetic:
+//             the same pred bits), the plot's partial sums added slice 0, 1, 2, ... by one thread, the seven outputs.
+// Nothing crosses a plot's boundary and every sum has one fixed order that depends on N and D only: a plot's row is the same
+// bytes at any position of any batch, run after run, and a NaN stays in its plot.  No atomics outside LDS (integer maxima).
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int PL_SLICE_ROWS = SN2_PLOT_LOSSES_SLICE_ROWS;
+
+inline int plot_losses_slices(int N) { return SN2_PLOT_LOSSES_SLICES(N); }
+
+template <bool NLL, bool ENT>
+__global__ __launch_bounds__(1024) void plot_losses_scatter_kernel(const float4* __restrict__ vals, const int* __restrict__ pix,
+                                                                  const float4* __restrict__ proba, const double* __restrict__ pdf,
+                                                                  int N, int D, int parts, unsigned long long* __restrict__ keys_part,
+                                                                  double* __restrict__ partials) {
+    extern __shared__ unsigned long long s_keys[];  // D*D*3
+    __shared__ double s_part[2][16];
+    const int b = blockIdx.x / parts, part = blockIdx.x - b * parts;
+    const int ncell3 = D * D * 3;
+    for (int i = threadIdx.x; i < ncell3; i += 1024) s_keys[i] = 0ull;
+    __syncthreads();
+    const int per = (N + parts - 1) / parts;
+    const int lo = part * per, hi = min(N, lo + per);
+    double nll = 0.0, ent = 0.0;
+    for (int n = lo + threadIdx.x; n < hi; n += 1024) {
+        const size_t i = (size_t)b * N + n;
+        const int cell = pix[i];
+        const float4 v = vals[i];
+        const unsigned long long tag = (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
+        atomicMax(&s_keys[cell * 3 + 0], ((unsigned long long)f2ord(v.x) << 32) | tag);
+        atomicMax(&s_keys[cell * 3 + 1], ((unsigned long long)f2ord(v.z) << 32) | tag);
+        atomicMax(&s_keys[cell * 3 + 2], ((unsigned long long)f2ord(v.w) << 32) | tag);
+        if constexpr (NLL || ENT) {
+            const float4 p = proba[i];
+            if constexpr (NLL) {
+                const double f0 = pdf[3 * i], f1 = pdf[3 * i + 1], f2 = pdf[3 * i + 2];
+                const float pg = p.x + p.y;
+                const double lik = ((double)pg * f0 + (double)p.z * f1) + (double)p.w * f2;
+                nll -= log(lik);
+            }
+            if constexpr (ENT) {
+                const float e2 = p.z * logf(p.z + PL_EPS_F) + (1.f - p.z) * logf(1.f - p.z + PL_EPS_F);
+                const float e3 = p.w * logf(p.w + PL_EPS_F) + (1.f - p.w) * logf(1.f - p.w + PL_EPS_F);
+                ent -= (double)e2 + (double)e3;
+            }
+        }
+    }
+    if constexpr (NLL || ENT) {
+        nll = pl_wave_sum_f64(nll);
+        ent = pl_wave_sum_f64(ent);
+        const int w = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) s_part[0][w] = nll, s_part[1][w] = ent;
+    }
+    __syncthreads();
+    unsigned long long* g = keys_part + (size_t)blockIdx.x * ncell3;
+    for (int i = threadIdx.x; i < ncell3; i += 1024) g[i] = s_keys[i];
+    if constexpr (NLL || ENT) {
+        if (threadIdx.x == 0) {
+            double a = 0.0, c = 0.0;
+            for (int k = 0; k < 16; ++k) a += s_part[0][k], c += s_part[1][k];
+            partials[2 * (size_t)blockIdx.x] = a;
+            partials[2 * (size_t)blockIdx.x + 1] = c;
+        }
+    }
+}
+
+// out row: total, absolute, NLL, entropy, abs_low, abs_med, abs_high
+__global__ __launch_bounds__(256) void plot_losses_finalize_kernel(const unsigned long long* __restrict__ keys, int N, int D, int parts,
+                                                                   const double* __restrict__ gt, const double* __restrict__ partials,
+                                                                   int pointwise, double m, double e, float* __restrict__ pred,
+                                                                   double* __restrict__ out) {
+    __shared__ float s[5][4];
+    const int b = blockIdx.x;
+    const int ncell = D * D;
+    float lo = 0.f, so = 0.f, me = 0.f, hi = 0.f, cnt = 0.f;
+    for (int c = threadIdx.x; c < ncell; c += 256) {
+        const unsigned long long* kp = keys + ((size_t)b * parts * ncell + c) * 3;
+        unsigned long long k0 = kp[0], k1 = kp[1], k2 = kp[2];
+        for (int q = 1; q < parts; ++q) {
+            const unsigned long long* kq = kp + (size_t)q * ncell * 3;
+            const unsigned long long a0 = kq[0], a1 = kq[1], a2 = kq[2];
+            k0 = a0 > k0 ? a0 : k0;
+            k1 = a1 > k1 ? a1 : k1;
+            k2 = a2 > k2 ? a2 : k2;
+        }
+        if (k0) {
+            const float l = ord2f((uint32_t)(k0 >> 32));
+            lo += l;
+            so += 1.0f - l;
+            me += ord2f((uint32_t)(k1 >> 32));
+            hi += ord2f((uint32_t)(k2 >> 32));
+            cnt += 1.f;
+        }
+    }
+    lo = wave_sum(lo);
+    so = wave_sum(so);
+    me = wave_sum(me);
+    hi = wave_sum(hi);
+    cnt = wave_sum(cnt);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) s[0][w] = lo, s[1][w] = so, s[2][w] = me, s[3][w] = hi, s[4][w] = cnt;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float t[5];
+    for (int q = 0; q < 5; ++q) t[q] = (s[q][0] + s[q][1]) + (s[q][2] + s[q][3]);
+    const float n = fmaxf(t[4], 1.f);
+    float pv[4];
+    for (int q = 0; q < 4; ++q) pred[b * 4 + q] = pv[q] = t[q] / n;
+    double ab[3];
+    for (int c = 0; c < 3; ++c) {                       // strata low, medium, high = columns 0, 2, 3
+        const int col = c == 0 ? 0 : c + 1;
+        const double d = (double)pv[col] - gt[4 * b + col];
+        ab[c] = sqrt(d * d + PL_EPS_D);
+    }
+    double nll = 0.0, ent = 0.0;
+    if (pointwise) {
+        const double* pp = partials + 2 * (size_t)b * parts;
+        for (int q = 0; q < parts; ++q) nll += pp[2 * q], ent += pp[2 * q + 1];
+    }
+    const double l_abs = ((ab[0] + ab[1]) + ab[2]) / 3.0;
+    const double l_nll = pointwise ? nll / N : 0.0;
+    const double l_ent = pointwise ? (double)(float)(ent / (2.0 * N)) : 0.0;       // the reference's entropy is an fp32 tensor
+    double* o = out + 7 * (size_t)b;
+    o[0] = l_abs + m * l_nll + e * l_ent;
+    o[1] = l_abs;
+    o[2] = l_nll;
+    o[3] = l_ent;
+    o[4] = ab[0];
+    o[5] = ab[1];
+    o[6] = ab[2];
+}
+}  // namespace
+
+extern "C" size_t sn2_plot_losses_ws_words(int B, int N, int D) {
+    if (B <= 0 || N <= 0 || D <= 0 || D > 45 || D * D > MAX_CELLS || (long)B * N >= (1L << 31)) return 0;
+    const size_t slices = (size_t)B * plot_losses_slices(N);
+    return 2 * (slices * (size_t)D * D * 3 + slices * 2);          // u64 key tables, then two fp64 partial sums per slice
+}
+
+extern "C" int sn2_plot_losses(const float* coverages, const int* pix, const float* proba, const double* pdf, const double* gt,
+                               int B, int N, int D, double m, double e, void* ws, float* pred, double* out, void* stream) {
+    if (!coverages || !pix || !gt || !ws || !pred || !out || B <= 0 || N <= 0 || D <= 0) return SN2_EINVAL;
+    const bool nll = m != 0.0, ent = e != 0.0;
+    if ((nll || ent) && !proba) return SN2_EINVAL;
+    if (nll && !pdf) return SN2_EINVAL;
+    if (((uintptr_t)ws & 7) != 0) return SN2_EINVAL;
+    if (D > 45 || D * D > MAX_CELLS || (long)B * N >= (1L << 31)) return SN2_ELIMIT;
+    hipStream_t st = (hipStream_t)stream;
+    const int parts = plot_losses_slices(N);
+    const size_t slices = (size_t)B * parts;
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
+    double* partials = reinterpret_cast<double*>(keys + slices * (size_t)D * D * 3);
+    const size_t lds = (size_t)D * D * 3 * 8;
+    const float4* c4 = reinterpret_cast<const float4*>(coverages);
+    const float4* p4 = reinterpret_cast<const float4*>(proba);
+    const dim3 grid((unsigned)slices);
+    if (nll && ent) hipLaunchKernelGGL((plot_losses_scatter_kernel<true, true>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
+    else if (nll) hipLaunchKernelGGL((plot_losses_scatter_kernel<true, false>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
+    else if (ent) hipLaunchKernelGGL((plot_losses_scatter_kernel<false, true>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
+    else hipLaunchKernelGGL((plot_losses_scatter_kernel<false, false>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
+    hipLaunchKernelGGL(plot_losses_finalize_kernel, dim3(B), dim3(256), 0, st, (const unsigned long long*)keys, N, D, parts, gt,
+                       (const double*)partials, (nll || ent) ? 1 : 0, m, e, pred, out);
+    SN2_RETURN_LAUNCH();
+}
+
 extern "C" int sn2_plot_project_backward(const float* dpred, const int* arg, const int* nocc, const int* pix, int B, int N,
                                          int D, float* dpointwise, void* stream) {
     if (!dpred || !arg || !nocc || !pix || !dpointwise || B <= 0 || N <= 0 || D <= 0) return SN2_EINVAL;

@@ -1362,6 +1362,44 @@ def projected_loss_backward(pred, gt, proba, pdf, B: int, N: int, diam_pix: int,
     return dcov, dproba
 
 
+def plot_losses_ws_words(B: int, N: int, diam_pix: int) -> int:
+    """32-bit words of `plot_losses`' workspace (include/strata_hip.h: sn2_plot_losses_ws_words); 0 = beyond what the kernels cover."""
+    return int(_lib.load().sn2_plot_losses_ws_words(int(B), int(N), int(diam_pix)))
+
+
+def plot_losses(cov, pix, proba, pdf, gt, B: int, N: int, diam_pix: int, m: float, e: float, out=None, ws=None):
+    """include/strata_hip.h: sn2_plot_losses -> (out (B,7) fp64 = per plot total, absolute, NLL, entropy, abs_low, abs_med,
+    abs_high; pred (B,4) fp32).  pdf may be None when m == 0.  out = (out, pred): caller-owned buffers (rows of a larger table);
+    ws: caller-owned workspace of at least `plot_losses_ws_words` int32 words."""
+    R, D = B * N, int(diam_pix)
+    m, e = float(m), float(e)
+    _chk(cov, F32, (R, 4), "coverages")
+    _chk(pix, I32, (R,), "pix")
+    _chk(proba, F32, (R, 4), "proba")
+    if m != 0.0 or pdf is not None:
+        _chk(pdf, F64, (R, 3), "pdf")
+    _chk(gt, F64, (B, 4), "gt")
+    dev = cov.device
+    words = plot_losses_ws_words(B, N, D)
+    if words == 0:
+        raise StrataHipError(f"plot_losses: B={B}, N={N}, diam_pix={D} is outside what the kernels cover (SN2_ELIMIT)")
+    if ws is None:
+        ws = torch.empty(words, dtype=I32, device=dev)
+    else:
+        _chk(ws, I32, None, "ws")
+        if ws.numel() < words or ws.data_ptr() % 8:
+            raise ValueError(f"ws: need {words} int32 words, 8-byte aligned")
+    if out is None:
+        o, pred = torch.empty(B, 7, dtype=F64, device=dev), torch.empty(B, 4, dtype=F32, device=dev)
+    else:
+        o, pred = out
+        _chk(o, F64, (B, 7), "out")
+        _chk(pred, F32, (B, 4), "out pred")
+    _call("sn2_plot_losses", _ptr(cov), _ptr(pix), _ptr(proba), _ptr(pdf) if m != 0.0 else None, _ptr(gt), B, N, D, m, e, _ptr(ws),
+          _ptr(pred), _ptr(o), _stream())
+    return o, pred
+
+
 def adam_step_images(param, arena, replicas, stride, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step_dev, grad_scale=1.0):
     """include/strata_hip.h: sn2_adam_step_images -- fold the gradient's images and take the Adam step in one launch."""
     n = param.numel()
