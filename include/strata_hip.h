@@ -515,8 +515,8 @@ int sn2_mosaic_finalize(const float *mean, const float *wsum, int H, int W, int 
 /* ---- loss block of the timed training step: learning/loss_functions.py:9-57 combined as learning/train.py:58-62,
  *   total = get_absolute_loss(pred, gt) + m * get_NLL_loss(proba, pdf_all) + e * get_entropy_loss(proba)
  * pred (B,4) fp32 plot-wise coverages, gt (B,4) fp64, proba (R,4) fp32 pointwise class probabilities, pdf (R,3) fp64 the
- * KDE-mixture densities at the points' heights (the reference evaluates them on the CPU each step, :30-42; KDE fitting is
- * out of scope, so they are an input).  partials: 2*SN2_LOSS_BLOCKS fp64 workspace.  out[4] = total, absolute, NLL,
+ * KDE-mixture densities at the points' heights (the reference evaluates them on the CPU each step, :30-42; here sn2_kde_lookup
+ * over the tables of sn2_kde_fit or any other tables, so they are an input).  partials: 2*SN2_LOSS_BLOCKS fp64 workspace.  out[4] = total, absolute, NLL,
  * entropy.  Backward: grad_total = device scalar d(objective)/d(total); writes dpred (B,4), dproba (R,4).
  * A term that is switched off is SKIPPED (not multiplied by zero) and its inputs may be absent -- what the reference's loop,
  * which calls the three functions one by one (learning/train.py:58-60), needs: B = 0: no absolute term (pred, gt, dpred
@@ -526,9 +526,37 @@ int sn2_mosaic_finalize(const float *mean, const float *wsum, int H, int W, int 
  * interp1d(kind="linear") over one knot vector), which get_NLL_loss evaluates on the CPU for all B*N points every step
  * (learning/loss_functions.py:30-42).  cloud (B,C,N) fp32, height = cloud[:, z_channel, :] * z_max formed in fp32;
  * X (K) ascending knots and Y (3,K) the three tables, fp64; pdf (B*N,3) fp64 = what sn2_loss_* take.  Heights outside
- * [X[0], X[K-1]] (scipy raises there) give NaN.  Fitting the KDEs (KDEpy) is out of scope: the tables are an input. */
+ * [X[0], X[K-1]] (scipy raises there) give NaN.  The tables are an input: sn2_kde_fit's, or a reference-fitted mixture's. */
 int sn2_kde_lookup(const float *cloud, int B, int C, int N, int z_channel, float z_max, const double *X, const double *Y,
                    int K, double *pdf, void *stream);
+/* Fitting those tables -- KdeMixture.fit + evaluate_kdes, learning/kde_mixture.py:50-100 (three KDEpy FFTKDE(bw=0.1) over the
+ * symmetrised heights, evaluated on one grid of 5000 points, scaled by their weight sums and divided by their common maximum).
+ * KDEpy's FFTKDE is linear binning followed by a convolution with the sampled kernel; the estimator, with the grid margin and
+ * the kernel truncation written out (all arithmetic fp64, no fused multiply-add where an index or a fraction is decided):
+ *   z (n) fp32 heights in metres (cloud[2] before rescaling), all FINITE (the caller checks: a NaN or Inf is not detected here);
+ *   sample   {-z_i} u {z_i} (get_sym_sorted_z; the sort does not change the result and is not done);
+ *   weights  of a sample point, from a = |z| widened to fp64, strict inequalities (:54-58):
+ *              w1 = a < 0.5 ? 1 : 0.05;   w2 = 0.5 < a < 1.5 ? 1 : 0.05;   w3 = a > 1.5 ? 1 : a > 0.5 ? 0.5 : 0.05;
+ *   grid     zm = max |z|, A = zm + max(0.05 * 2 * zm, 5 bw), X = linspace(-A, A, K) (X[j] = j * dx - A, X[K-1] = A),
+ *            dx = 2A / (K-1): the grid covers every fitted height, so sn2_kde_lookup of one never gives NaN;
+ *   binning  a sample point s, t = (s - X[0]) / dx, j = min(floor(t), K-2), f = t - j: w (1-f) onto bin j, w f onto bin j+1;
+ *   kernel   g[d] = exp(-(d dx)^2 / (2 bw^2)) / (bw sqrt(2 pi)), |d| <= L = min(floor(5 bw / dx), K-1);
+ *   tables   Y[k][i] = sum_{|d| <= L, 0 <= i+d < K} bins_k[i+d] g[d], then all three divided by the one maximum over them
+ *            (the weight normalisation of FFTKDE and evaluate_kdes' multiplication by the weight sums cancel).
+ * X (K), Y (3,K) fp64 out, the layout sn2_kde_lookup takes.  ws: 8-byte aligned, SN2_KDE_FIT_WS_WORDS(K) 32-bit words, no
+ * initialisation.  Four or five launches on `stream`, nothing read back, no state outside ws (capturable, re-entrant with a ws per
+ * call).  DETERMINISTIC: no floating-point atomics -- the heights are cut into at most SN2_KDE_FIT_SLICES slices by n alone; a
+ * bin of a slice is summed by one workgroup, every thread over a fixed subsequence of the slice in order, the threads in a fixed
+ * tree, the slices in ascending order -- so the same z, bw, K give the same bytes on every call.  Against an fp64
+ * evaluation of the same estimator the tables differ by the re-association of sums of non-negative terms and a few ulp of exp.
+ * 1 <= n < 2^31, 2 <= K <= SN2_KDE_FIT_MAX_K (beyond: SN2_ELIMIT); bw > 0.  Every workgroup of the binning pass scans all n
+ * heights of its slice (K/8 workgroups per slice): 5e5 heights at K = 5000 is what it is sized for. */
+#define SN2_KDE_FIT_MAX_K 65536
+#define SN2_KDE_FIT_ABS_SLOTS 256
+#define SN2_KDE_FIT_SLICES 8
+#define SN2_KDE_FIT_WS_WORDS(K) \
+    (2 * ((4 + 3 * SN2_KDE_FIT_SLICES) * (size_t)(K) + 3 * (((size_t)(K) + 255) / 256)) + SN2_KDE_FIT_ABS_SLOTS)
+int sn2_kde_fit(const float *z, long n, double bw, int K, void *ws, double *X, double *Y, void *stream);
 #define SN2_LOSS_BLOCKS 1024
 int sn2_loss_forward(const float *pred, const double *gt, int B, const float *proba, const double *pdf, int R, double m,
                      double e, double *partials, double *out, void *stream);

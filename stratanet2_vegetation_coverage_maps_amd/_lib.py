@@ -168,6 +168,7 @@ SIGNATURES = {
                          c_int, c_int, c_int, c_int, c_void_p],
     "sn2_mosaic_finalize": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_kde_lookup": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "sn2_kde_fit": [c_void_p, c_long, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_loss_forward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,
                          c_void_p],
     "sn2_loss_backward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,

@@ -1304,6 +1304,32 @@ def kde_lookup(clouds_dev: torch.Tensor, z_max: float, X: torch.Tensor, Y: torch
     return pdf
 
 
+KDE_FIT_MAX_K = 65536                                            # SN2_KDE_FIT_MAX_K
+
+
+def kde_fit_ws_words(K: int) -> int:
+    """SN2_KDE_FIT_WS_WORDS of include/strata_hip.h (32-bit words)."""
+    K = max(int(K), 2)
+    return 2 * ((4 + 3 * 8) * K + 3 * ((K + 255) // 256)) + 256
+
+
+def kde_fit(z_dev: torch.Tensor, bw: float = 0.1, grid_points: int = 5000):
+    """include/strata_hip.h: sn2_kde_fit.  z (n) fp32 FINITE heights in metres on the device -> (X (K), Y (3,K)) fp64, the tables
+    `kde_lookup` takes: the reference's `KdeMixture.fit` + `evaluate_kdes`.  Four launches on the current stream and no read-back
+    (the finiteness check is the caller's: `losses.KdeTables.fit` makes it); the same input gives the same bytes.  n = 0, K < 2
+    and bw <= 0 are refused by the library (SN2_EINVAL), K > KDE_FIT_MAX_K too (SN2_ELIMIT)."""
+    _chk(z_dev, F32, None, "z")
+    if z_dev.dim() != 1:
+        raise ValueError(f"z: expected a 1-D tensor of heights, got {tuple(z_dev.shape)}")
+    K = int(grid_points)
+    dev = z_dev.device
+    ws = torch.empty(kde_fit_ws_words(K) // 2 + 1, dtype=F64, device=dev)
+    X = torch.empty(max(K, 2), dtype=F64, device=dev)
+    Y = torch.empty(3, max(K, 2), dtype=F64, device=dev)
+    _call("sn2_kde_fit", _ptr(z_dev) or None, z_dev.numel(), float(bw), K, _ptr(ws), _ptr(X), _ptr(Y), _stream())
+    return X, Y
+
+
 def loss_forward(pred, gt, proba, pdf, m: float, e: float):
     """-> out (4,) fp64 = [total, absolute, NLL, entropy] (include/strata_hip.h: sn2_loss_forward)."""
     B, R = pred.shape[0], proba.shape[0]

@@ -10,7 +10,9 @@ those launches were a fifth of the step.  `total_loss_torch` and the three `get_
 reference's loop calls are that node with two terms switched off on a HIP device, the torch forms elsewhere.
 
 Difference from the reference signature: `get_NLL_loss` takes the KDE-mixture densities `pdf_all (B*N,3)` directly
-instead of evaluating `args.kde_mixture` on the CPU each step (`loss_functions.py:30-42`; KDE fitting is out of scope).
+instead of evaluating `args.kde_mixture` on the CPU each step (`loss_functions.py:30-42`): `kde_densities` looks them up in
+`KdeTables`, which `KdeTables.fit` / `from_plots` fit on the device (`learning/kde_mixture.py:16-100`) or `from_mixture` copies
+from a mixture the reference fitted.
 """
 import torch
 
@@ -110,8 +112,9 @@ def get_entropy_loss(pred_pixels):
 
 class KdeTables:
     """The three linear-interpolation tables of the reference's `KdeMixture` (`learning/kde_mixture.py:62-70`: X and
-    y1, y2, y3 from `evaluate_kdes`, what `interp1d` holds) on the device.  Fitting (KDEpy FFTKDE) stays with the reference:
-    `KdeTables.from_mixture(args.kde_mixture, device)` copies the fitted tables."""
+    y1, y2, y3 from `evaluate_kdes`, what `interp1d` holds) on the device.  `KdeTables.fit(z, device)` fits them from heights on
+    the device (csrc/kde.hip: the estimator behind KDEpy's FFTKDE, written out in include/strata_hip.h), `from_plots` from a
+    dataset's plots; `KdeTables.from_mixture(args.kde_mixture, device)` copies the tables of a mixture the reference fitted."""
 
     def __init__(self, X, y1, y2, y3, device):
         import numpy as np
@@ -124,6 +127,67 @@ class KdeTables:
     @classmethod
     def from_mixture(cls, kde_mixture, device):
         return cls(kde_mixture.f1.x, kde_mixture.f1.y, kde_mixture.f2.y, kde_mixture.f3.y, device)
+
+
+    @classmethod
+    def fit(cls, z, device, bw=0.1, grid_points=5000):
+        """`KdeMixture.fit` + `evaluate_kdes` (`learning/kde_mixture.py:50-100`) on the device: z = heights in metres (`cloud[2]`
+        before rescaling), a host or device array of any shape, taken as fp32.  One finiteness check (the call's only
+        synchronisation): ValueError on a NaN or Inf.  The grid comes out ascending, so there is no host `argsort` as in
+        `__init__`.  The same heights give the same table bytes."""
+        if not isinstance(z, torch.Tensor):
+            import numpy as np
+            z = torch.from_numpy(np.array(z, dtype=np.float32))
+        z = z.detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+        if not z.is_cuda:
+            raise StrataHipError("losses.KdeTables.fit runs on the HIP device")
+        if not bool(torch.isfinite(z).all()):
+            raise ValueError("KdeTables.fit: the heights must be finite (found NaN or Inf)")
+        self = cls.__new__(cls)
+        with torch.cuda.device(z.device):
+            self.X, self.Y = ops.kde_fit(z, bw, grid_points)
+        return self
+
+    @classmethod
+    def from_plots(cls, plots, device, size=500_000, seed=0, bw=0.1, grid_points=5000, offsets=None):
+        """`get_fitted_kde_mixture_from_dataset` (`learning/kde_mixture.py:31-34`): `sample_heights` then `fit`."""
+        return cls.fit(sample_heights(plots, size=size, seed=seed, offsets=offsets, device=device), device, bw, grid_points)
+
+
+def sample_heights(plots, size=500_000, seed=0, offsets=None, device="cuda:0"):
+    """The counterpart of `sample_z_from_dataset` (`learning/kde_mixture.py:16-21`: concatenate every plot's `cloud[2]`, shuffle,
+    keep `size`): a uniform subset without replacement of all plots' heights, as (min(size, total),) fp32 on the device.
+    plots: a list of (C >= 3, n_i) arrays or tensors (host or device; row 2 = z in metres), or ONE (C, T) array of plots side by
+    side -- the resident `raw` of `input_pipeline.prepare_batch` -- with `offsets` (B+1) or None (all of it): the heights are
+    raw[2, offsets[0]:offsets[-1]].  Fewer than `size` heights: all of them, in their order, nothing drawn.
+    Drawn on the device with `hip_ops.subsample` (sn2_subsample) over ONE "plot" of key 0 spanning every height: the `size`
+    heights with the smallest Philox4x32-10 keys u(seed, 0, i), in key order -- distinct indices, integer arithmetic only, so
+    the same seed gives the same bytes (the distribution of the reference's shuffle, not numpy's draws).  Its limit is
+    total < 2^31 heights."""
+    dev = torch.device(device)
+    if isinstance(plots, (list, tuple)):
+        if offsets is not None:
+            raise ValueError("sample_heights: offsets go with ONE (C, T) array, not with a list of plots")
+        rows = [torch.as_tensor(p)[2].to(device=dev, dtype=torch.float32).reshape(-1) for p in plots]
+        z = torch.cat(rows) if rows else torch.empty(0, dtype=torch.float32, device=dev)
+    else:
+        z = torch.as_tensor(plots)[2].to(device=dev, dtype=torch.float32).reshape(-1)
+        if offsets is not None:
+            z = z[int(offsets[0]):int(offsets[-1])]
+    z = z.contiguous()
+    if not z.is_cuda:
+        raise StrataHipError("losses.sample_heights draws on the HIP device")
+    total, size = z.numel(), int(size)
+    if size <= 0:
+        raise ValueError("sample_heights: size must be positive")
+    if total <= size:
+        return z
+    if total >= 2 ** 31:
+        raise ValueError("sample_heights: sn2_subsample numbers a plot's candidates with int32: fewer than 2^31 heights")
+    with torch.cuda.device(dev):
+        span = torch.tensor([0, total], dtype=torch.int32, device=dev)
+        idx = ops.subsample(span, 0, size, int(seed), torch.zeros(1, dtype=torch.int64, device=dev), n_max=total)
+        return z[idx[0].long()]
 
 
 def kde_densities(clouds_dev, z_max, tables: KdeTables):
