@@ -448,7 +448,7 @@ int sn2_head_forward(const sn2_head *p, void *stream);
 int sn2_fp_head_eval(const sn2_fp *p, const sn2_head *hd, void *stream);
 int sn2_head_backward(const sn2_head *p, void *stream);
 /* After sn2_head_backward: the gradients of the BatchNorm whose output the head reads (FP1's), obtained from lin1's weight
- * and bias gradients instead of a pass over all rows (derivation in fp.hip).  gamma, beta, mean, invstd: that BatchNorm's
+ * and bias gradients instead of a pass over all rows (derivation in head.hip).  gamma, beta, mean, invstd: that BatchNorm's
  * parameters and saved batch statistics; dgamma, dbeta: ACCUMULATED, complete on return.  *ok (device int) = 1 when the
  * identity was used, 0 when some |gamma| <= 1e-4 made it unusable and the kernel summed over the rows itself (p->f = the
  * BatchNorm's input rows, p->dy = the gradient of its output).  Hand `ok` to the producer's sn2_fp_backward as bn_sums_done. */

@@ -1,15 +1,10 @@
 """Diagnostic: phase stamps of workgroup 0 of global_level_fwd_kernel inside a real training forward (16 x 32 768), from a
--DSN2_GL_STAMPS build of fp.hip made into gpurun_out/ (never shipped)."""
-import ctypes, os, subprocess, sys
+-DSN2_GL_STAMPS build of the library (global_level.hip) made into build/variants/ (never shipped)."""
+import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-csrc = os.path.join(ROOT, "stratanet2_vegetation_coverage_maps_amd/csrc")
-so = os.path.join(ROOT, "gpurun_out/libgl_dbg.so")
-os.makedirs(os.path.dirname(so), exist_ok=True)
-srcs = [os.path.join(csrc, f) for f in ("geometry.hip", "sa.hip", "sa_mfma.hip", "fp.hip", "project.hip", "loss.hip", "misc.hip")]
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", "-DSN2_GL_STAMPS"] + srcs + ["-o", so])
-from stratanet2_vegetation_coverage_maps_amd import _lib
-_lib.LIB_PATH = so
+from stratanet2_vegetation_coverage_maps_amd import _build, _lib
+_lib.LIB_PATH = _build.build_variant("libgl_dbg.so", ["-DSN2_GL_STAMPS"])
 import torch
 from stratanet2_vegetation_coverage_maps_amd import PointNet2
 from stratanet2_vegetation_coverage_maps_amd.synthetic import make_args, make_batch

@@ -7,7 +7,7 @@ import glob, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = "/tmp/sn2_isa"
 os.makedirs(out, exist_ok=True)
-for f in ("fp", "sa_mfma", "misc", "project", "loss", "sa", "geometry"):
+for f in ("fp", "head", "global_level", "interp_index", "sa_mfma", "misc", "project", "loss", "sa", "geometry"):
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", f"{out}/{f}.s",
                     f"{ROOT}/stratanet2_vegetation_coverage_maps_amd/csrc/{f}.hip"], check=True, stderr=subprocess.DEVNULL)
 filters = sys.argv[1:]

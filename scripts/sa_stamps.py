@@ -1,16 +1,12 @@
 """Diagnostic: per-wave phase stamps of sa_mfma_bwd_kernel<8, 2, 16, 16, 3> (SA1 backward, layer 1) inside a real training step
-(built with -DSN2_SA_STAMPS into gpurun_out/; never shipped).  Prints, over the waves that had work: when each phase ends
+(built with -DSN2_SA_STAMPS into build/variants/; never shipped).  Prints, over the waves that had work: when each phase ends
 relative to the kernel's first stamp (median / 90 % / max, in us at 2.4 GHz) and the items / steps per wave."""
-import ctypes, os, subprocess, sys
+import ctypes, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-csrc = os.path.join(ROOT, "stratanet2_vegetation_coverage_maps_amd/csrc")
-so = os.path.join(ROOT, "gpurun_out/libsa_dbg.so")
-srcs = [os.path.join(csrc, f) for f in ("geometry.hip", "sa.hip", "sa_mfma.hip", "fp.hip", "project.hip", "loss.hip", "misc.hip", "net.hip")]
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", "-DSN2_SA_STAMPS"] + srcs + ["-o", so])
-from stratanet2_vegetation_coverage_maps_amd import _lib
-_lib.LIB_PATH = so
+from stratanet2_vegetation_coverage_maps_amd import _build, _lib
+_lib.LIB_PATH = _build.build_variant("libsa_dbg.so", ["-DSN2_SA_STAMPS"])
 import torch
 from stratanet2_vegetation_coverage_maps_amd import PointNet2, project_to_plotwise_coverages, losses
 from stratanet2_vegetation_coverage_maps_amd.optim import FlatAdam, flatten_parameters

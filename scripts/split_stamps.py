@@ -1,14 +1,10 @@
 """Diagnostic: phase stamps of one workgroup of fp_bwd_split_kernel<64,32,64> (FP3 backward) inside a real training step
-(build with -DSN2_SPLIT_STAMPS into gpurun_out/; never shipped)."""
-import ctypes, os, subprocess, sys
+(build with -DSN2_SPLIT_STAMPS into build/variants/; never shipped)."""
+import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-csrc = os.path.join(ROOT, "stratanet2_vegetation_coverage_maps_amd/csrc")
-so = os.path.join(ROOT, "gpurun_out/libsplit_dbg.so")
-srcs = [os.path.join(csrc, f) for f in ("geometry.hip", "sa.hip", "sa_mfma.hip", "fp.hip", "project.hip", "loss.hip", "misc.hip", "net.hip")]
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", "-DSN2_SPLIT_STAMPS"] + srcs + ["-o", so])
-from stratanet2_vegetation_coverage_maps_amd import _lib
-_lib.LIB_PATH = so
+from stratanet2_vegetation_coverage_maps_amd import _build, _lib
+_lib.LIB_PATH = _build.build_variant("libsplit_dbg.so", ["-DSN2_SPLIT_STAMPS"])
 import torch
 from stratanet2_vegetation_coverage_maps_amd import PointNet2, project_to_plotwise_coverages, losses
 from stratanet2_vegetation_coverage_maps_amd.optim import FlatAdam, flatten_parameters

@@ -1,21 +1,15 @@
 """Diagnostic: FP1's forward (sn2_fp_forward, source-side form: table + row pass + finalisation) and backward alone on the chip at
 config 2's shapes (16 plots x 32 768 points, 1024 sources per plot, real 3-NN tables of synthetic plots), HIP events, for several
-builds of fp.hip:
+builds of the library (the row passes are in fp.hip):
     python scripts/time_fp1.py [-DSN2_FR_DIAG=<bits>] ...      bits of the row pass (both forms): 1 no h stores, 2 no table gathers, 4 no skip contraction, 8 (form 1) stores the compiler counts
-    SN2_GRID_MULT=2 python scripts/time_fp1.py                 (the row kernels' grids x 2)
-Each switch set is built into gpurun_out/ (never shipped).  Per-kernel durations: run it under scripts/kstats.sh."""
-import os, subprocess, sys
+Each switch set is built into build/variants/ (never shipped).  Per-kernel durations: run it under scripts/kstats.sh."""
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-csrc = os.path.join(ROOT, "stratanet2_vegetation_coverage_maps_amd/csrc")
 flags = [a for a in sys.argv[1:] if a.startswith("-D")]
 if flags:
-    so = os.path.join(ROOT, "gpurun_out/libfp1_dbg.so")
-    os.makedirs(os.path.dirname(so), exist_ok=True)
-    srcs = [os.path.join(csrc, f) for f in ("geometry.hip", "sa.hip", "sa_mfma.hip", "fp.hip", "project.hip", "loss.hip", "misc.hip", "net.hip")]
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared"] + flags + srcs + ["-o", so])
-    from stratanet2_vegetation_coverage_maps_amd import _lib
-    _lib.LIB_PATH = so
+    from stratanet2_vegetation_coverage_maps_amd import _build, _lib
+    _lib.LIB_PATH = _build.build_variant("libfp1_dbg.so", flags)
 import torch
 from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
 from stratanet2_vegetation_coverage_maps_amd.synthetic import make_batch
@@ -53,5 +47,5 @@ from stratanet2_vegetation_coverage_maps_amd import _lib as _l
 for form in (1, 0):
     _l.load().sn2_debug_fp_rows_form(form)
     t_f = timed(lambda: ops.fp_forward(fwd, 1))
-    print(f"{' '.join(flags) or 'shipped build'} (SN2_GRID_MULT={os.environ.get('SN2_GRID_MULT', '1')}), row pass form {form}: FP1 forward entry "
+    print(f"{' '.join(flags) or 'shipped build'}, row pass form {form}: FP1 forward entry "
           f"{t_f:.1f} us (table + row pass + finalisation) for {B} x {N} rows", flush=True)

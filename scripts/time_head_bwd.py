@@ -1,19 +1,14 @@
-"""Diagnostic: `sn2_head_backward` alone on the chip (524 288 rows = config 2), HIP events, for several builds of fp.hip:
+"""Diagnostic: `sn2_head_backward` alone on the chip (524 288 rows = config 2), HIP events, for several builds of the library (head.hip):
     python scripts/time_head_bwd.py [-DSWITCH ...]        e.g. -DSN2_NO_FLUSH, -DSN2_HB_DIAG=1 (no d-row stores), =2 (no arithmetic),
                                                           =3 (loads only), -DSN2_HB_STAMPS (phase stamps of one wave's second turn)
-Each switch set is built into gpurun_out/ (never shipped)."""
-import os, subprocess, sys
+Each switch set is built into build/variants/ (never shipped)."""
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-csrc = os.path.join(ROOT, "stratanet2_vegetation_coverage_maps_amd/csrc")
 flags = [a for a in sys.argv[1:] if a.startswith("-D")]
 if flags:
-    so = os.path.join(ROOT, "gpurun_out/libhb_dbg.so")
-    os.makedirs(os.path.dirname(so), exist_ok=True)
-    srcs = [os.path.join(csrc, f) for f in ("geometry.hip", "sa.hip", "sa_mfma.hip", "fp.hip", "project.hip", "loss.hip", "misc.hip")]
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared"] + flags + srcs + ["-o", so])
-    from stratanet2_vegetation_coverage_maps_amd import _lib
-    _lib.LIB_PATH = so
+    from stratanet2_vegetation_coverage_maps_amd import _build, _lib
+    _lib.LIB_PATH = _build.build_variant("libhb_dbg.so", flags)
 import torch
 from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
 

@@ -37,6 +37,10 @@ __device__ __forceinline__ int sn2_grad_image(int replicas, int stride) {
 
 static inline int sn2_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// plots of one sn2_global_level_forward launch (global_level.hip: the collected granules of all plots must fit its LDS; net.hip
+// takes the separate launches above it; hip_ops.GL_MAX_PLOTS mirrors it)
+constexpr int GL_MAX_PLOTS = 28;
+
 // ---- clearing a buffer.  Always a KERNEL, never hipMemsetAsync: every entry point may be captured into a hipGraph, and on
 // this runtime (ROCm 7.2) a captured memset NODE is only right on the FIRST replay -- from the second replay on it fills
 // the buffer with whatever its recycled argument block holds (scripts/debug_graph_d2h.py::memset_node: buf := 0; buf += 1

@@ -59,7 +59,7 @@ __device__ __forceinline__ f32x4 contract(f32x4 acc, FA a, FB b) {
 // the loads are s_load_dwordx* and the FMAs take SGPR operands.
 // ---- BatchNorm1d from the sums of a batch (torch defaults: eps 1e-5, momentum 0.1, biased variance to normalise, unbiased
 // variance into running_var -- model/point_net2.py:45-53): one channel.  Used by bn_finalize_kernel (misc.hip) and by the
-// kernels that finalise their own statistics (fp.hip: global_level_fwd_kernel).
+// kernels that finalise their own statistics (global_level.hip: global_level_fwd_kernel).
 __device__ __forceinline__ void sn2_bn_from_sums(double s1, double s2, double n, float gamma, float beta, float* running_mean,
                                                  float* running_var, float& a, float& c, float& mean, float& invstd) {
     const float eps = 1e-5f, mom = 0.1f;

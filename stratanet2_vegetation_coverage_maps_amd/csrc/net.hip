@@ -14,7 +14,6 @@ namespace {
 constexpr int WIDTHS[7] = {16, 16, 32, 64, 64, 34, 34};      // cout of sa1[0], sa1[1], sa2, sa3, fp3, fp2, fp1
 constexpr int WIDTH_SUM = 260;
 constexpr int GRAD_IMAGES = 32;                              // hip_ops.GRAD_IMAGES
-constexpr int GL_MAX_PLOTS_HOST = 28;                        // sn2_global_level_forward's limit (fp.hip: GL_MAX_PLOTS)
 
 // events of a forked geometry pass.  Chain b (level 2): FPS, ball query, work items [b_tables: all SA2 needs] -> the two small
 // 3-NN tables [b_nn: all FP3 / FP2 need] -> their inverted indices [b_done].  Chain c: the per-point 3-NN table [c_nn: all FP1
@@ -515,7 +514,7 @@ extern "C" int sn2_net_forward(const sn2_net_model* m, const sn2_net_dims* d, co
     sn2_fp p3, pf3;
     fp_desc(&p3, d, a, sa3_in(m, d, g, a), nograd);
     fp_desc(&pf3, d, a, fp3_in(m, d, g, a), nograd);
-    if (batch_stats && m->fuse_global_level && io->gl_xchg && io->gl_ctl && B <= GL_MAX_PLOTS_HOST && !m->sa3.mma_bf16 &&
+    if (batch_stats && m->fuse_global_level && io->gl_xchg && io->gl_ctl && B <= GL_MAX_PLOTS && !m->sa3.mma_bf16 &&
         !m->fp3.mma_bf16) {
         SN2_TRY(sn2_global_level_forward(&p3, &pf3, a->x3, a->arg3, io->gl_xchg, io->gl_ctl, cur));
     } else {

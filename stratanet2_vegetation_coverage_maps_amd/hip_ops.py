@@ -971,7 +971,7 @@ def plot_max_forward(h, a, c, B, R_per_plot, C):
     return out, arg
 
 
-GL_MAX_PLOTS = 28        # sn2_global_level_forward's limit (csrc/fp.hip: GL_MAX_PLOTS)
+GL_MAX_PLOTS = 28        # sn2_global_level_forward's limit (csrc/common.h: GL_MAX_PLOTS)
 _GLOBAL_WS = {}          # device index -> workspace of callers that name no owner
 _GLOBAL_WS_ALL = []      # weak references to every live workspace (global_level_gave_up looks at all of them)
 
