@@ -285,7 +285,15 @@ typedef struct sn2_sa {
     float *out;                     /* (B*M,cout) = a*ext + c : the module output x                             */
     const float *dout;              /* backward in : d loss / d out (B*M,cout)                                  */
     float *dfeat;                   /* backward out: ACCUMULATED d loss / d feat (B*Nsrc,cf) or NULL            */
+    float *bwd_ws;                  /* backward, nl = 2: SN2_SA_BWD_WS_WORDS floats, ZERO on entry (left non-zero), or
+                                       NULL.  Given, with dfeat = NULL and fp32 operands, the first block's dW/db come
+                                       out of the SAME message pass as the last block's (three sums the BatchNorm
+                                       backward is linear in + a one-workgroup combine kernel) instead of a pass of
+                                       their own; otherwise it is not touched                                   */
 } sn2_sa;
+/* sn2_sa.bwd_ws: replicas of the two 16 x 12 images [sum m xhat (x) in | sum m (x) in] of the nl = 2 module (MLP[11,16,16]) */
+#define SN2_SA_BWD_WS_REPLICAS 32
+#define SN2_SA_BWD_WS_WORDS (SN2_SA_BWD_WS_REPLICAS * 2 * 16 * 12)
 /* Work items of the SA passes (position-only: part of the geometry pass).  A wave step is four 16-message tiles; a plot's
  * centroids are ranked by DESCENDING neighbour count (ties by ascending id -- deterministic) and cut into classes:
  *   SOLO (n > SN2_SA_SOLO_MIN: all four tiles, 64 messages per step), QUAD (n > SN2_SA_QUAD_MIN: ranks 4k..4k+3 share the
@@ -703,6 +711,7 @@ typedef struct sn2_net_bwd {
     float *arena; long arena_words;
     int images, image_stride;
     float *dy2, *dy3, *dx1, *dx2, *dx3, *dy_sa3;
+    float *sa1_ws;                       /* sn2_sa.bwd_ws of SA1 (SN2_SA_BWD_WS_WORDS), the arena's last buffer */
     void *dy1, *du1;                     /* (B*N,36) rows of the activation type */
     float *du2, *du3;                    /* (B*M1,64), (B*M2,64) */
     int *bn_ok;                          /* 4 words */

@@ -29,7 +29,8 @@ class SA(Structure):  # sn2_sa
                 ("feat", c_void_p), ("feat_stride", c_int), ("spos", c_void_p), ("spos_stride", c_int),
                 ("cpos", c_void_p), ("nbr", c_void_p), ("cnt", c_void_p), ("total", c_void_p), ("order", c_void_p),
                 ("blk", Block * 2),
-                ("ext", c_void_p), ("arg", c_void_p), ("out", c_void_p), ("dout", c_void_p), ("dfeat", c_void_p)]
+                ("ext", c_void_p), ("arg", c_void_p), ("out", c_void_p), ("dout", c_void_p), ("dfeat", c_void_p),
+                ("bwd_ws", c_void_p)]
 
 
 class FP(Structure):  # sn2_fp
@@ -88,7 +89,7 @@ class NetAct(Structure):  # sn2_net_act
 class NetBwd(Structure):  # sn2_net_bwd
     _fields_ = [("dcov", c_void_p), ("dproba", c_void_p), ("arena", c_void_p), ("arena_words", c_long), ("images", c_int),
                 ("image_stride", c_int)] + [(n, c_void_p) for n in (
-                    "dy2", "dy3", "dx1", "dx2", "dx3", "dy_sa3", "dy1", "du1", "du2", "du3", "bn_ok", "src_ws1", "src_ws2")] + [
+                    "dy2", "dy3", "dx1", "dx2", "dx3", "dy_sa3", "sa1_ws", "dy1", "du1", "du2", "du3", "bn_ok", "src_ws1", "src_ws2")] + [
                         ("defer_grad_reduce", c_int), ("arena_is_zero", c_int), ("frozen_stats", c_int)]
 
 

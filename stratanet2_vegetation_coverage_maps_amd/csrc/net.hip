@@ -109,7 +109,7 @@ inline float* aux_row(const sn2_net_act* a, int k, int row) {      // row 0..3 =
 
 // PointNet2._sa1_desc / _sa2_desc
 void sa1_desc(sn2_sa* s, const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_geo* g, const sn2_net_act* a,
-              GradDst gd, const float* dout) {
+              GradDst gd, const float* dout, float* bwd_ws = nullptr) {
     memset(s, 0, sizeof(*s));
     s->B = d->B, s->Nsrc = d->N, s->M = d->M1, s->cap = d->cap1, s->cf = 8, s->nl = 2;
     s->feat = g->rows0, s->feat_stride = 12, s->spos = g->rows0 + 8, s->spos_stride = 12;
@@ -117,7 +117,7 @@ void sa1_desc(sn2_sa* s, const sn2_net_model* m, const sn2_net_dims* d, const sn
     fill_block(&s->blk[0], &m->sa1[0], 0, a, gd);
     fill_block(&s->blk[1], &m->sa1[1], 1, a, gd);
     s->ext = a->ext1, s->arg = a->arg1, s->out = a->x1;
-    s->dout = dout, s->dfeat = nullptr;
+    s->dout = dout, s->dfeat = nullptr, s->bwd_ws = bwd_ws;
 }
 void sa2_desc(sn2_sa* s, const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_geo* g, const sn2_net_act* a,
               GradDst gd, const float* dout, float* dfeat) {
@@ -413,6 +413,7 @@ extern "C" int sn2_net_bwd_carve(const sn2_net_model* m, const sn2_net_dims* d, 
     b->arena = ar, b->images = GRAD_IMAGES, b->image_stride = (int)stride;
     b->dy2 = take(B * M1 * 36), b->dy3 = take(B * M2 * 64), b->dx1 = take(B * M1 * 16), b->dx2 = take(B * M2 * 32);
     b->dx3 = take(B * 64), b->dy_sa3 = take(B * M2 * 64);
+    b->sa1_ws = take(SN2_SA_BWD_WS_WORDS);            // (inside the zero-filled arena: no fill launch of its own)
     b->arena_words = (long)o;
     *arena_bytes = o * sizeof(float);
     Carver c(scratch_base);
@@ -617,7 +618,7 @@ extern "C" int sn2_net_backward(const sn2_net_model* m, const sn2_net_dims* d, c
     sn2_sa sa;
     sa2_desc(&sa, m, d, g, a, gd, b->dx2, b->dx1);
     SN2_TRY(sn2_sa_backward(&sa, cur));
-    sa1_desc(&sa, m, d, g, a, gd, b->dx1);
+    sa1_desc(&sa, m, d, g, a, gd, b->dx1, b->sa1_ws);          // (NULL from a caller's own layout: the two-pass route)
     SN2_TRY(sn2_sa_backward(&sa, cur));
     // the images of (dW, db) -> image 0 (unless the optimiser step folds them itself: sn2_adam_step_images)
     if (b->defer_grad_reduce) return 0;

@@ -10,6 +10,13 @@
 //   max_e (a*h_e + c) = a * (a >= 0 ? max_e h_e : min_e h_e) + c, and sign(a) = sign(gamma) is known beforehand.
 //   backward: prep (dgamma/dbeta of the last BN from the B*M extremum rows) -> pass C (nl=2: last block's dW/db, first
 //             BN's dgamma/dbeta) -> pass D (first block's dW/db, input-feature gradient).
+//   backward, nl=2 with no feature gradient wanted and a workspace given (sn2_sa.bwd_ws; fp32 operands) -- SA1 in the network:
+//             prep -> pass C, which also sums the three C1 x (cin + 1) images the first block's dW/db is linear in
+//             (sa_mfma.hip: one-pass route) -> combine (one workgroup: the dgamma/dbeta terms, now complete).  No pass D: a
+//             message pass less.  S_x, S_m leave pass C through float atomics into SN2_SA_BWD_WS_REPLICAS zero-filled replicas
+//             (as the images of dW do: the choice), not through a slot per workgroup: 512 slots would be 0.8 MB for one
+//             workgroup to add.
+//             bf16 operands (sn2_block.mma_bf16) keep the two passes.
 // The E x C message tensors of the reference are never materialised: every pass re-gathers the 48/80-byte source rows
 // (L2-resident: a plot's rows are 1.5 MB) and recomputes the MLP in registers.
 #include "mlp.h"
@@ -18,7 +25,7 @@
 template <int CF, int NL, int C1, int C2, int PASS>
 int sa_mfma_launch_fwd(const sn2_sa* p, int training, hipStream_t st, int* nblocks_out);
 template <int CF, int NL, int C1, int C2, int PASS>
-int sa_mfma_launch_bwd(const sn2_sa* p, hipStream_t st);
+int sa_mfma_launch_bwd(const sn2_sa* p, float* ws, hipStream_t st);
 
 namespace {
 
@@ -68,6 +75,32 @@ __global__ __launch_bounds__(256) void sa_bwd_prep_kernel(const float* __restric
     }
 }
 
+// One-pass route, after pass C: image 0 of [dW0 | db0] -= dgamma0 / E * S_x' + dbeta0 / E * S_m', the primed sums = pass C's,
+// scaled by gamma0 invstd0 there, folded over the workspace's replicas in replica order.  One thread per element: C * (CIN + 1).
+__global__ __launch_bounds__(256) void sa_bwd_combine_kernel(const float* __restrict__ ws, const float* __restrict__ dgamma,
+                                                             const float* __restrict__ dbeta,
+                                                             const unsigned long long* __restrict__ total, int C, int CIN,
+                                                             float* __restrict__ dW, float* __restrict__ db) {
+    const int n = C * (CIN + 1), i = threadIdx.x;
+    if (i >= n) return;
+    float part[2][SN2_SA_BWD_WS_REPLICAS];
+#pragma unroll
+    for (int r = 0; r < SN2_SA_BWD_WS_REPLICAS; ++r) {          // (all loads in flight together)
+        part[0][r] = ws[(size_t)r * 2 * n + i];
+        part[1][r] = ws[(size_t)r * 2 * n + n + i];
+    }
+    const unsigned long long etot = *total;
+    const float invE = etot > 0 ? (float)(1.0 / (double)etot) : 0.f;
+    const int o = i / (CIN + 1), k = i - o * (CIN + 1);
+    const float dg = dgamma[o] * invE, de = dbeta[o] * invE;
+    float sx = 0.f, sm = 0.f;
+#pragma unroll
+    for (int r = 0; r < SN2_SA_BWD_WS_REPLICAS; ++r) sx += part[0][r], sm += part[1][r];
+    const float v = -fmaf(dg, sx, de * sm);
+    float* dst = k < CIN ? &dW[o * CIN + k] : &db[o];
+    *dst += v;
+}
+
 int check(const sn2_sa* p) {
     if (!p || p->B <= 0 || p->Nsrc <= 0 || p->M <= 0 || p->cap <= 0) return SN2_EINVAL;
     if (!p->feat || !p->spos || !p->cpos || !p->nbr || !p->cnt || !p->total || !p->ext || !p->arg || !p->out)
@@ -111,8 +144,20 @@ int backward_t(const sn2_sa* p, hipStream_t st) {
     if (pb > 256) pb = 256;      // (fewer workgroups = fewer same-address atomics, but slower: 8.7 / 9.8 / 16 us at 256 / 64 / 32)
     hipLaunchKernelGGL(sa_bwd_prep_kernel, dim3(pb), dim3(256), 0, st, p->dout, p->ext, p->arg, last->mean, last->invstd,
                        rows, C, last->dgamma, last->dbeta);
-    if constexpr (NL == 2) SN2_TRY((sa_mfma_launch_bwd<CF, NL, C1, C2, 2>(p, st)));
-    SN2_TRY((sa_mfma_launch_bwd<CF, NL, C1, C2, 3>(p, st)));
+    if constexpr (NL == 2) {
+        // the route follows from the descriptor: one message pass when nobody wants the feature gradient and a workspace is given
+        const sn2_block* k0 = &p->blk[0];
+        if (!p->dfeat && p->bwd_ws && !k0->mma_bf16) {
+            SN2_TRY((sa_mfma_launch_bwd<CF, NL, C1, C2, 2>(p, p->bwd_ws, st)));
+            if (k0->frozen_stats || last->frozen_stats) return 0;         // 1 / E := 0: nothing to combine
+            static_assert(C1 * (CF + 4) <= 256, "one thread per element of [dW0 | db0]");
+            hipLaunchKernelGGL(sa_bwd_combine_kernel, dim3(1), dim3((C1 * (CF + 4) + 63) / 64 * 64), 0, st, p->bwd_ws, k0->dgamma,
+                               k0->dbeta, p->total, C1, CF + 3, k0->dW, k0->db);
+            SN2_RETURN_LAUNCH();
+        }
+        SN2_TRY((sa_mfma_launch_bwd<CF, NL, C1, C2, 2>(p, nullptr, st)));
+    }
+    SN2_TRY((sa_mfma_launch_bwd<CF, NL, C1, C2, 3>(p, nullptr, st)));
     return 0;
 }
 

@@ -504,6 +504,7 @@ struct SaBwdArgs {
     float *dW0, *db0, *dW1, *db1, *dgamma0_out, *dbeta0_out;   // accumulated (atomics)
     int rep_k, rep_stride;                                     // images of (dW, db): sn2_block.grad_replicas
     float* dfeat;
+    float* ws;                                                 // pass C, one-pass route: sn2_sa.bwd_ws (else nullptr)
 };
 
 #ifdef SN2_SA_STAMPS
@@ -524,15 +525,44 @@ extern "C" int sn2_debug_sa_stamps(unsigned long long* out) {
 #define SACOUNT(i, v)
 #endif
 
-// PASS 2 = "C" (nl == 2): dW/db of block 1, dgamma/dbeta of block 0.   PASS 3 = "D": dW/db of block 0 (+ dfeat).
+// a wave's staging region: the pass's own images [64][PS] | [64][QS], and two more 16-column images where pass C's one-pass
+// round is compiled in (fp32 operands)
 template <int CF, int NL, int C1, int C2, int PASS, bool BF16>
-__global__ __launch_bounds__(256) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
+struct SaBwdLds {
+    static constexpr bool LAST2 = NL == 2 && PASS == 2;
+    static constexpr int OWN = OuterAcc<(LAST2 ? C2 : C1), (LAST2 ? C1 : CF + 4)>::LDS_FLOATS;
+    static constexpr int FLOATS = OWN + ((LAST2 && !BF16) ? 2 * 64 * 16 : 0);
+};
+
+// PASS 2 = "C" (nl == 2): dW/db of block 1, dgamma/dbeta of block 0.   PASS 3 = "D": dW/db of block 0 (+ dfeat).
+//
+// ONE-PASS ROUTE of pass C (a.ws given: no feature gradient wanted, fp32 operands).  Pass D exists as a launch of its own only
+// because block 0's BatchNorm backward needs the COMPLETE dgamma0, dbeta0, which pass C sums.  That backward is linear in them:
+// with m = [valid and h > 0], xhat = (h - mean0) invstd0, g = dy1 and in = [feat_j | pos_j - pos_i | 1] per message,
+//     [dW0 | db0] = diag(gamma0 invstd0) (S_g - diag(dgamma0 / E) S_x - diag(dbeta0 / E) S_m),
+//     S_g = sum m g (x) in,   S_x = sum m xhat (x) in,   S_m = sum m (x) in          (C1 x (CIN + 1) each)
+// and m, xhat, g, in are all in registers here.  The three sums ride in a SECOND contraction round of every step, over four
+// 16-column images of the wave-private region: m xhat and `in` are staged as soon as layer 1 is done (images of their own), m g
+// and m take the places of dp2 and y1 once the step's dp2 (x) y1 round has been read -- so only dy1 and the 16 mask bits stay in
+// registers across that round, and a workgroup needs 64 KB of LDS (two per CU, as before; six images side by side would be
+// 96 KB).  At the end the sums are scaled by gamma0 invstd0 (= the affine's a0, a per-lane constant of the D layout); S_g goes into the
+// dW0 / db0 images as pass D's result does, S_x and S_m are ADDED (float atomics) to replica blockIdx.x % SN2_SA_BWD_WS_REPLICAS of
+// a.ws, which must be zero on entry; sa_bwd_combine_kernel (sa.hip) finishes dW0 / db0 when dgamma0, dbeta0 are complete.  With
+// frozen statistics (1 / E := 0) S_x, S_m have no weight: they are not written and no combine kernel runs.  bf16 operands keep the
+// two passes: pass D rounds dp1 AFTER the three terms have cancelled, the sums would round m xhat before.
+template <int CF, int NL, int C1, int C2, int PASS, bool BF16>
+__global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
     constexpr int CIN = CF + 3, KB1 = CF / 4 + 1, TO1 = C1 / 16, TO2 = C2 / 16;
     constexpr bool LAST2 = NL == 2 && PASS == 2;             // this pass produces block 1's weight gradient
     constexpr int PO = LAST2 ? C2 : C1;                      // rows of the dW image
     constexpr int QK = LAST2 ? C1 : CIN + 1;                 // columns (block 0: inputs | bias)
     using Acc = OuterAcc<PO, QK>;
     constexpr int PS = Acc::PS, QS = Acc::QS, TP = Acc::TO, TQ = Acc::TK;
+    constexpr bool ONE = LAST2 && !BF16;                     // the one-pass route is compiled in (taken when a.ws is given)
+    static_assert(!ONE || (C1 == 16 && C2 == 16 && CIN + 1 <= 16), "one-pass round: 16-column images");
+    constexpr int QK0 = CIN + 1;
+    constexpr int WAVE_LDS = SaBwdLds<CF, NL, C1, C2, PASS, BF16>::FLOATS;          // a wave's staging region (floats)
+    const bool one = ONE && a.ws != nullptr;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, q = lane >> 4, c = lane & 15;
     const int wib = threadIdx.x >> 6;
@@ -540,10 +570,12 @@ __global__ __launch_bounds__(256) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
     const int nwaves = gridDim.x * 4;
     const int ncent = a.B * a.M;
     const SaFirst first = sa_first(a.order, a.cnt, a.B, a.M, wave);
-    float* lds_p = smem + wib * Acc::LDS_FLOATS;
+    float* lds_p = smem + wib * WAVE_LDS;
     float* lds_q = lds_p + 64 * PS;
+    float* lds_x0 = lds_p + Acc::LDS_FLOATS;                 // one-pass round: m xhat [64][16], then `in` [64][16];
+    float* lds_q0 = lds_x0 + 64 * 16;                        //   m g, m go where dp2 (lds_p), y1 (lds_q) were
     SASTAMP(0);
-    for (int i = lane; i < Acc::LDS_FLOATS; i += 64) lds_p[i] = 0.f;
+    for (int i = lane; i < WAVE_LDS; i += 64) lds_p[i] = 0.f;
 
     // (frozen: the forward ran BatchNorm on its running statistics -- no batch-mean / batch-variance terms: 1 / E := 0)
     const unsigned long long etot = *a.total;
@@ -624,6 +656,9 @@ __global__ __launch_bounds__(256) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
     for (int i = 0; i < TP; ++i)
 #pragma unroll
         for (int j = 0; j < TQ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc0[3];                                           // one-pass route: S_g, S_x, S_m (C1 rows x QK0 columns each)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) acc0[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dbias[LAST2 ? TO2 : 1][4], dbe0[TO1][4], dga0[TO1][4];   // block 1 bias gradient; block 0 BN gradients (pass C)
 #pragma unroll
     for (int i = 0; i < (LAST2 ? TO2 : 1); ++i)
@@ -710,6 +745,25 @@ __global__ __launch_bounds__(256) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
                     D1[io][t] = v;
+                }
+            }
+            unsigned onm = 0;    // one-pass route: bit 4 t + r = [valid and h > 0] of this lane's channel r, tile t
+            if constexpr (ONE) {
+                if (one) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        float mx[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float h = D1[0][t][r];
+                            const bool on = val[t] && h > 0.f;
+                            onm |= on ? 1u << (4 * t + r) : 0u;
+                            mx[r] = on ? (h - mu0[0][r]) * is0[0][r] : 0.f;
+                        }
+                        *reinterpret_cast<float4*>(lds_x0 + (16 * t + c) * 16 + 4 * q) = make_float4(mx[0], mx[1], mx[2], mx[3]);
+#pragma unroll
+                        for (int kb = 0; kb < 4; ++kb) lds_q0[(16 * t + c) * 16 + 4 * kb + q] = kb < KB1 ? bks[t][kb < KB1 ? kb : 0] : 0.f;
+                    }
                 }
             }
             f32x4 dy1[TO1][4];   // d loss / d (BN output of block 0)
@@ -868,6 +922,38 @@ __global__ __launch_bounds__(256) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             __builtin_amdgcn_wave_barrier();
+            if constexpr (ONE) {
+                if (one) {
+                    // ---- second round: [m g | m xhat | m] (x) in, contracted over the step's 64 messages
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        float mg[4], mm[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const bool on = (onm >> (4 * t + r)) & 1u;
+                            mg[r] = on ? dy1[0][t][r] : 0.f;
+                            mm[r] = on ? 1.f : 0.f;
+                        }
+                        *reinterpret_cast<float4*>(lds_p + (16 * t + c) * PS + 4 * q) = make_float4(mg[0], mg[1], mg[2], mg[3]);
+                        *reinterpret_cast<float4*>(lds_q + (16 * t + c) * QS + 4 * q) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    const float* rg = lds_p + q * PS + c;
+                    const float* rm = lds_q + q * QS + c;
+                    const float* rx = lds_x0 + q * 16 + c;
+                    const float* ri = lds_q0 + q * 16 + c;
+#pragma unroll 4
+                    for (int st = 0; st < 16; ++st) {
+                        const float vg = rg[st * 4 * PS], vx = rx[st * 4 * 16], vm = rm[st * 4 * QS], vi = ri[st * 4 * 16];
+                        acc0[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vg, vi, acc0[0], 0, 0, 0);
+                        acc0[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vx, vi, acc0[1], 0, 0, 0);
+                        acc0[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(vm, vi, acc0[2], 0, 0, 0);
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
         }
         if (n_items_dbg == 1) { SASTAMP(3); }
     }
@@ -878,7 +964,8 @@ __global__ __launch_bounds__(256) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
     // ---- workgroup-level reduction (every wave's image in its own staging region, plain stores, added in wave order: LDS
     // float atomics run at ~0.4 lane-adds per clock), then one global atomic per element
     constexpr int NW = PO * QK, NB = LAST2 ? C2 : 0, NG = LAST2 ? 2 * C1 : 0;
-    static_assert(NW + NB + NG <= Acc::LDS_FLOATS, "a wave's image fits its staging region");
+    constexpr int N0 = ONE ? C1 * QK0 : 0;                    // one-pass route: three more images [C1][CIN + 1]
+    static_assert(NW + NB + NG + 3 * N0 <= WAVE_LDS, "a wave's image fits its staging region");
     float* slab = lds_p;
 #pragma unroll
     for (int i = 0; i < TP; ++i)
@@ -908,13 +995,35 @@ __global__ __launch_bounds__(256) void sa_mfma_bwd_kernel(const SaBwdArgs a) {
                 }
             }
     }
+    if constexpr (ONE) {
+        if (one) {
+            // rows of the D layout = this lane's four channels: the scale gamma0 invstd0 (= a0) is a per-lane constant
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (c < QK0) slab[NW + NB + NG + (16 * i + 4 * q + r) * QK0 + c] = acc0[i][r] * a1v[0][r];
+        }
+    }
     SASTAMP(5);
     __syncthreads();
     SASTAMP(6);
     const int img = sn2_grad_image(a.rep_k, a.rep_stride);
-    for (int i = threadIdx.x; i < NW + NB + NG; i += 256) {
-        const float v = (smem[i] + smem[Acc::LDS_FLOATS + i]) + (smem[2 * Acc::LDS_FLOATS + i] + smem[3 * Acc::LDS_FLOATS + i]);
+    const int nred = NW + NB + NG + (one ? (a.frozen ? N0 : 3 * N0) : 0);
+    for (int i = threadIdx.x; i < nred; i += 256) {
+        const float v = (smem[i] + smem[WAVE_LDS + i]) + (smem[2 * WAVE_LDS + i] + smem[3 * WAVE_LDS + i]);
         if (v == 0.f) continue;
+        if (ONE && i >= NW + NB + NG) {
+            const int j = i - (NW + NB + NG);
+            if (j < N0) {                                       // S_g, scaled: the dW0 / db0 images, as pass D's result
+                const int o = j / QK0, k = j - o * QK0;
+                if (k < CIN) SN2_FLUSH_ADD(&a.dW0[img + o * CIN + k], v);
+                else SN2_FLUSH_ADD(&a.db0[img + o], v);
+            } else {                                            // S_x | S_m, scaled: the workspace
+                SN2_FLUSH_ADD(&a.ws[(size_t)(blockIdx.x % SN2_SA_BWD_WS_REPLICAS) * 2 * N0 + (j - N0)], v);
+            }
+            continue;
+        }
         if (i < NW) {
             if constexpr (LAST2) {
                 SN2_FLUSH_ADD(&a.dW1[img + i], v);
@@ -983,11 +1092,10 @@ template int sa_mfma_launch_fwd<8, 2, 16, 16, 1>(const sn2_sa*, int, hipStream_t
 template int sa_mfma_launch_fwd<16, 1, 32, 32, 1>(const sn2_sa*, int, hipStream_t, int*);
 template int sa_mfma_launch_fwd<32, 1, 64, 64, 1>(const sn2_sa*, int, hipStream_t, int*);   // third ball-query level (3sa-arch)
 
+// `ws`: pass C's one-pass route (sa.hip decides: sn2_sa.bwd_ws, no feature gradient, fp32 operands), else nullptr
 template <int CF, int NL, int C1, int C2, int PASS>
-int sa_mfma_launch_bwd(const sn2_sa* p, hipStream_t st) {
-    constexpr int CIN = CF + 3;
-    constexpr bool LAST2 = NL == 2 && PASS == 2;
-    using Acc = OuterAcc<(LAST2 ? C2 : C1), (LAST2 ? C1 : CIN + 1)>;
+int sa_mfma_launch_bwd(const sn2_sa* p, float* ws, hipStream_t st) {
+    if (ws && (PASS != 2 || NL != 2 || p->blk[0].mma_bf16)) return SN2_EINVAL;
     SaBwdArgs a;
     a.B = p->B; a.Nsrc = p->Nsrc; a.M = p->M; a.cap = p->cap; a.feat_stride = p->feat_stride; a.spos_stride = p->spos_stride;
     a.feat = p->feat; a.spos = p->spos; a.cpos = p->cpos; a.nbr = p->nbr; a.cnt = p->cnt; a.order = p->order; a.total = p->total;
@@ -1003,11 +1111,13 @@ int sa_mfma_launch_bwd(const sn2_sa* p, hipStream_t st) {
     a.dW0 = k0.dW; a.db0 = k0.db; a.dW1 = k1.dW; a.db1 = k1.db; a.dgamma0_out = k0.dgamma; a.dbeta0_out = k0.dbeta;
     a.rep_k = k0.grad_replicas; a.rep_stride = k0.grad_replica_stride;
     a.dfeat = p->dfeat;
+    a.ws = ws;
     int blocks = sn2_cdiv((long)p->B * p->M, 16);
     static const int occ_env = getenv("SN2_SA_BWD_OCC") ? atoi(getenv("SN2_SA_BWD_OCC")) : 0;
     const int occ = occ_env > 0 ? occ_env : (CF == 8 ? 2 : 1);            // workgroups per CU that are resident together
     if (blocks > sn2_cu_count() * occ) blocks = sn2_cu_count() * occ;
-    const size_t lds = (size_t)Acc::LDS_FLOATS * 4 * sizeof(float);
+    const size_t lds = (size_t)(p->blk[0].mma_bf16 ? SaBwdLds<CF, NL, C1, C2, PASS, true>::FLOATS
+                                                   : SaBwdLds<CF, NL, C1, C2, PASS, false>::FLOATS) * 4 * sizeof(float);
     auto kern = p->blk[0].mma_bf16 ? &sa_mfma_bwd_kernel<CF, NL, C1, C2, PASS, true> : &sa_mfma_bwd_kernel<CF, NL, C1, C2, PASS, false>;
     if (lds > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1015,7 +1125,7 @@ int sa_mfma_launch_bwd(const sn2_sa* p, hipStream_t st) {
     SN2_RETURN_LAUNCH();
 }
 
-template int sa_mfma_launch_bwd<8, 2, 16, 16, 2>(const sn2_sa*, hipStream_t);
-template int sa_mfma_launch_bwd<8, 2, 16, 16, 3>(const sn2_sa*, hipStream_t);
-template int sa_mfma_launch_bwd<16, 1, 32, 32, 3>(const sn2_sa*, hipStream_t);
-template int sa_mfma_launch_bwd<32, 1, 64, 64, 3>(const sn2_sa*, hipStream_t);
+template int sa_mfma_launch_bwd<8, 2, 16, 16, 2>(const sn2_sa*, float*, hipStream_t);
+template int sa_mfma_launch_bwd<8, 2, 16, 16, 3>(const sn2_sa*, float*, hipStream_t);
+template int sa_mfma_launch_bwd<16, 1, 32, 32, 3>(const sn2_sa*, float*, hipStream_t);
+template int sa_mfma_launch_bwd<32, 1, 64, 64, 3>(const sn2_sa*, float*, hipStream_t);

@@ -762,9 +762,14 @@ def sa_order_group(cnt: torch.Tensor, G: int, B: int, M: int, out_all: torch.Ten
     _call("sn2_sa_order_group", _ptr(cnt), G, B, M, _ptr(out_all), stride, _stream(), key="sn2_sa_order")
 
 
+SA_BWD_WS_WORDS = 32 * 2 * 16 * 12         # SN2_SA_BWD_WS_WORDS of include/strata_hip.h
+
+
 def sa_desc(blocks, feat, cf, spos, cpos_aos, nbr, cnt, total, B, Nsrc, M, ext, arg, out, dout=None, dfeat=None,
-            with_grads=False, order=None) -> SA:
-    """feat: (B*Nsrc, >=cf) row view; spos: (B*Nsrc, >=4) row view holding x,y,z,."""
+            with_grads=False, order=None, bwd_ws=None) -> SA:
+    """feat: (B*Nsrc, >=cf) row view; spos: (B*Nsrc, >=4) row view holding x,y,z,.
+    bwd_ws: (SA_BWD_WS_WORDS) f32, ZERO on entry -- sn2_sa.bwd_ws: a two-block module's backward without `dfeat` then takes
+    one message pass for both blocks' weight gradients instead of two."""
     cap = nbr.shape[1]
     cl = blocks[-1].cout
     feat_stride = _chk_rows(feat, F32, B * Nsrc, cf, "feat")
@@ -790,7 +795,9 @@ def sa_desc(blocks, feat, cf, spos, cpos_aos, nbr, cnt, total, B, Nsrc, M, ext, 
         _chk(dout, F32, (B * M, cl), "dout")
     if dfeat is not None:
         _chk(dfeat, F32, (B * Nsrc, cf), "dfeat")
-    d.dout, d.dfeat = _ptr(dout), _ptr(dfeat)
+    if bwd_ws is not None:
+        _chk(bwd_ws, F32, (SA_BWD_WS_WORDS,), "bwd_ws")
+    d.dout, d.dfeat, d.bwd_ws = _ptr(dout), _ptr(dfeat), _ptr(bwd_ws)
     return d
 
 

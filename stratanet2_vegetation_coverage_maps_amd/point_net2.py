@@ -745,9 +745,10 @@ class PointNet2(nn.Module):
         return cov, proba, s
 
     # ---- descriptors (shared by forward and backward; gradient views are attached for the backward call)
-    def _sa1_desc(self, s, dout=None, g=False):
+    def _sa1_desc(self, s, dout=None, g=False, bwd_ws=None):
         return ops.sa_desc(s.b_sa1, s.rows0[:, 0:8], 8, s.rows0[:, 8:12], s.pos1_aos, s.nbr1, s.cnt1, s.tot1, s.B, s.N,
-                           s.M1, s.ext1, s.arg1, s.x1, dout=dout, dfeat=None, with_grads=g, order=getattr(s, "ord1", None))
+                           s.M1, s.ext1, s.arg1, s.x1, dout=dout, dfeat=None, with_grads=g, order=getattr(s, "ord1", None),
+                           bwd_ws=bwd_ws)
 
     def _sa2_desc(self, s, dout=None, dfeat=None, g=False):
         return ops.sa_desc(s.b_sa2, s.x1, 16, s.pos1_aos, s.pos2_aos, s.nbr2, s.cnt2, s.tot2, s.B, s.M1, s.M2, s.ext2,
@@ -776,7 +777,7 @@ class PointNet2(nn.Module):
         params = self._params()
         # one zero-filled arena: flat parameter gradient + every accumulate-into buffer of the backward chain
         sizes = OrderedDict(dy2=B * M1 * 36, dy3=B * M2 * 64, dx1=B * M1 * 16, dx2=B * M2 * 32, dx3=B * 64,
-                            dy_sa3=B * M2 * 64)
+                            dy_sa3=B * M2 * 64, sa1_ws=ops.SA_BWD_WS_WORDS)
         flat, buf, views, images, arena = self._grad_arena(params, sizes, dev)
 
         def attach(bb):
@@ -828,7 +829,7 @@ class PointNet2(nn.Module):
         ops.fp_backward(self._sa3_desc(s, dy=dy_sa3, dsrc=dx2, with_grads=True, bn_sums_done=bn_ok[3:4]))
         # SA2 -> d x1 ; SA1
         ops.sa_backward(self._sa2_desc(s, dout=dx2, dfeat=dx1, g=True))
-        ops.sa_backward(self._sa1_desc(s, dout=dx1, g=True))
+        ops.sa_backward(self._sa1_desc(s, dout=dx1, g=True, bwd_ws=buf["sa1_ws"]))      # (both blocks in one message pass)
         if getattr(self, "defer_grad_reduce", False):
             self._grad_images_pending = (arena,) + tuple(images)       # FlatAdam folds the images inside its own kernel
         else:

@@ -312,7 +312,7 @@ class PointNet2ThreeSA(PointNet2):
         B, N, M1, M2, M3 = s.B, s.N, s.M1, s.M2, s.M3
         params = list(self.parameters())
         sizes = OrderedDict(dy2=B * M1 * 36, dy3=B * M2 * 64, dy4=B * M3 * 64, dx1=B * M1 * 16, dx2=B * M2 * 32,
-                            dx3=B * M3 * 64, dxg=B * 64, dy_sa4=B * M3 * 64)
+                            dx3=B * M3 * 64, dxg=B * 64, dy_sa4=B * M3 * 64, sa1_ws=ops.SA_BWD_WS_WORDS)
         flat, buf, views, images, arena = self._grad_arena(params, sizes, dev)
         for bb in s.b_sa1 + s.b_sa2 + s.b_sa3 + [s.b_sa4, s.b_fp4, s.b_fp3, s.b_fp2, s.b_fp1]:
             bb.grads = (views[id(bb.lin.weight)], views[id(bb.lin.bias)], views[id(bb.bn.weight)], views[id(bb.bn.bias)])
@@ -356,7 +356,7 @@ class PointNet2ThreeSA(PointNet2):
         ops.fp_backward(self._sa4_desc(s, dy=dy_sa4, dsrc=dx3, with_grads=True))
         ops.sa_backward(self._sa3l_desc(s, dout=dx3, dfeat=dx2, g=True))
         ops.sa_backward(self._sa2_desc(s, dout=dx2, dfeat=dx1, g=True))
-        ops.sa_backward(self._sa1_desc(s, dout=dx1, g=True))
+        ops.sa_backward(self._sa1_desc(s, dout=dx1, g=True, bwd_ws=buf["sa1_ws"]))
         ops.grad_reduce(arena, flat.numel(), images)
         s.flat_grad = flat
         self._last_flat_grad = flat
