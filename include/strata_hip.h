@@ -425,8 +425,29 @@ int sn2_global_pool_backward(const float *du, int du_stride, const int *arg, con
 #define SN2_GLOBAL_CTL_WORDS 8
 int sn2_global_level_forward(const sn2_fp *sa3, const sn2_fp *fp3, float *x3, int *arg3, unsigned long long *xchg,
                              unsigned *ctl, void *stream);
-/* tests only: the sweeps (~1 us each, default 2^18; 0 = back to it) an exchange wait of sn2_global_level_forward makes before
- * it gives up */
+/* The backward of that level in ONE launch (training mode, batch statistics, fp32 operands): FP3's BatchNorm sums (taken directly
+ * over the rows of dy), FP3's backward, the pool's backward, SA3's BatchNorm sums and SA3's backward -- what sn2_fp_bn_sums (FP3's),
+ * sn2_fp_backward(fp3, scatter_ready < 0), sn2_global_pool_backward and sn2_fp_backward(sa3) do in four launches.  One workgroup
+ * per plot; FP3 interpolates the plot's ONE source with weight 1, so d x3[b] = (sum_rows dp) W[:, 0:64] and no per-row input
+ * gradient of the interpolated part is formed; the gradient of SA3's output (B x 64 non-zeros) never reaches memory.
+ *   sa3, fp3: the descriptors of the forward with the backward fields of the separate calls: fp3->dy (B*M2,64), fp3->dsrc = d x3
+ *             (B,64, ACCUMULATED), fp3->dskip = sa3->dsrc = d x2 (B*M2,32, ACCUMULATED), blk.dW / db / dgamma / dbeta
+ *             (ACCUMULATED); plot b adds its dW | db into image b: blk.grad_replicas >= B.  du_scratch, scatter_ws, sa3->dy and
+ *             bn_sums_done are not used;  arg3 (B,64): the rows that attained the plot's max.
+ *   xchg: SN2_GLOBAL_BWD_XCHG_WORDS 64-bit words and ctl: SN2_GLOBAL_BWD_CTL_WORDS 32-bit words of its OWN (not the forward's), zero-
+ *         filled once and then left to the library, as above.
+ *   A wait is bounded as in the forward.  Every store to a result lies behind a workgroup's last wait, so a workgroup that gives up
+ *   has committed nothing; it counts itself in ctl[1] and the workgroup that leaves last finishes those plots alone: every result
+ *   is committed exactly once, with the bits of an undisturbed launch.  Two runs on the same inputs give the same bits (fixed-order
+ *   sums, no float atomics).
+ * SN2_ELIMIT for other shapes, bfloat16 operands, frozen statistics, more than 28 plots or fewer images than plots.
+ * sn2_net_backward takes it up to 256 rows per plot (one 64-row block per group: the measured instance), the four launches above. */
+#define SN2_GLOBAL_BWD_XCHG_WORDS ((size_t)2 * 28 * 128)
+#define SN2_GLOBAL_BWD_CTL_WORDS 64
+int sn2_global_level_backward(const sn2_fp *sa3, const sn2_fp *fp3, const int *arg3, unsigned long long *xchg, unsigned *ctl,
+                              void *stream);
+/* tests only: the sweeps (~1 us each, default 2^18; 0 = back to it) an exchange wait of sn2_global_level_forward /
+ * sn2_global_level_backward makes before it gives up */
 int sn2_debug_global_spin_limit(unsigned sweeps);
 
 /* ---- pointwise head: lin1+ReLU, lin2, softmax/sigmoid/product -- model/point_net2.py:141-151 ----------------
@@ -721,6 +742,8 @@ typedef struct sn2_net_bwd {
                                             touched it since: sn2_net_backward does not clear it again */
     int frozen_stats;                    /* set by the caller: the forward pass ran with io.training = SN2_BN_FROZEN_KEEP (every
                                             block's sn2_block.frozen_stats) */
+    unsigned long long *gl_xchg; unsigned *gl_ctl;   /* set by the caller: sn2_global_level_backward's exchange area (its own, not
+                                            sn2_net_io's), or NULL: the separate launches */
 } sn2_net_bwd;
 
 #define SN2_NET_FORK 1          /* geometry: level-2 chain on io.stream_b, per-point 3-NN chain on io.stream_c (needs io.ctx) */

@@ -90,7 +90,8 @@ class NetBwd(Structure):  # sn2_net_bwd
     _fields_ = [("dcov", c_void_p), ("dproba", c_void_p), ("arena", c_void_p), ("arena_words", c_long), ("images", c_int),
                 ("image_stride", c_int)] + [(n, c_void_p) for n in (
                     "dy2", "dy3", "dx1", "dx2", "dx3", "dy_sa3", "sa1_ws", "dy1", "du1", "du2", "du3", "bn_ok", "src_ws1", "src_ws2")] + [
-                        ("defer_grad_reduce", c_int), ("arena_is_zero", c_int), ("frozen_stats", c_int)]
+                        ("defer_grad_reduce", c_int), ("arena_is_zero", c_int), ("frozen_stats", c_int), ("gl_xchg", c_void_p),
+                        ("gl_ctl", c_void_p)]
 
 
 class NetIO(Structure):  # sn2_net_io
@@ -152,6 +153,7 @@ SIGNATURES = {
     "sn2_global_pool_backward": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p],
     "sn2_global_level_forward": [POINTER(FP), POINTER(FP), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_global_level_backward": [POINTER(FP), POINTER(FP), c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_debug_global_spin_limit": [ctypes.c_uint],
     "sn2_head_forward": [POINTER(Head), c_void_p],
     "sn2_fp_head_eval": [POINTER(FP), POINTER(Head), c_void_p],

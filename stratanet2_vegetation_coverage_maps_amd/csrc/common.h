@@ -40,6 +40,9 @@ static inline int sn2_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // plots of one sn2_global_level_forward launch (global_level.hip: the collected granules of all plots must fit its LDS; net.hip
 // takes the separate launches above it; hip_ops.GL_MAX_PLOTS mirrors it)
 constexpr int GL_MAX_PLOTS = 28;
+// rows per plot up to which the network's backward takes sn2_global_level_backward: one 64-row block per group of its workgroup,
+// the instance that has been measured against the four launches (the entry point itself takes any M2; hip_ops.GL_BWD_MAX_ROWS)
+constexpr int GL_BWD_MAX_ROWS = 256;
 
 // ---- clearing a buffer.  Always a KERNEL, never hipMemsetAsync: every entry point may be captured into a hipGraph, and on
 // this runtime (ROCm 7.2) a captured memset NODE is only right on the FIRST replay -- from the second replay on it fills

@@ -1,4 +1,4 @@
-// fp_rows.h -- what the dense-row units share (fp.hip, head.hip, global_level.hip, interp_index.hip): the accessors of a row of
+// fp_rows.h -- what the dense-row units share (fp.hip, head.hip, global_level.hip, global_level_bwd.hip, interp_index.hip): the accessors of a row of
 // per-point activations in either storage precision, the spelled-out interpolation arithmetic and the input stream of the
 // source-side row passes, the two source-table kernels with their launcher, the staging of a 64-row block's inputs, the host
 // view of the inverted interpolation index, and the small host helpers of the dispatch code.  Templates are instantiated

@@ -2,8 +2,9 @@
 // FP3 -> its BatchNorm (global_level_fwd_kernel with its exchange protocol, give-up and in-launch repair), the spin limit of
 // its waits (sn2_debug_global_spin_limit) and the entry point sn2_global_level_forward.  Replaces GlobalSAModule.forward and
 // the FPModule.forward behind it.  The blocks' tiles are those of fp_fwd_split_kernel (fp.hip); the staging of a block's
-// inputs is shared with it through fp_rows.h.
-#include "fp_rows.h"
+// inputs is shared with it through fp_rows.h; the exchange (granules, bounded collection, spin limit) with the backward kernel
+// of global_level_bwd.hip through global_level.h.
+#include "global_level.h"
 
 namespace {
 
@@ -37,8 +38,7 @@ extern "C" int sn2_debug_gl_stamps(unsigned long long* out) {
 #else
 #define GSTAMP(i)
 #endif
-typedef unsigned long long gl_u64;
-constexpr int GL_GROUPS = 4, GL_QS = OuterAcc<16, 36>::QS;       // 48: the staged rows [x2 (32) | pos2 (3) | 1] of SA3; FP3 reads the first 32
+constexpr int GL_QS = OuterAcc<16, 36>::QS;       // 48: the staged rows [x2 (32) | pos2 (3) | 1] of SA3; FP3 reads the first 32
 constexpr int GL_W3 = 64 * 35 + 64, GL_WF = 64 * 96 + 64;         // the two layers' [W | bias], copied into LDS once per workgroup
 constexpr int GL_FIXED_FLOATS = GL_GROUPS * 64 * GL_QS + GL_GROUPS * 128 + 128 + 64 + 2 * 1024 + 2 * 8 * 128 + GL_W3 + GL_WF;
 // (+ B * 4 * 128 floats of collected granules: 155 KB at GL_MAX_PLOTS = 28 plots, common.h)
@@ -93,37 +93,6 @@ struct GlArgs {
                             // launch has handled, [3] running statistics workgroup 0 updated in the last launch (bit 0 SA3, 1 FP3)
     unsigned spin_limit;
 };
-
-// all granules of a phase -> s_x (floats), every thread its share, eight loads in flight, swept until every tag matches (or
-// the limit runs out, or a publisher says that it gave up: the POISON tag = tag with the top bit flipped)
-constexpr unsigned GL_POISON = 0x80000000u;
-__device__ __forceinline__ bool gl_collect(const gl_u64* gx, int n, unsigned tag, float* s_x, unsigned spin_limit) {
-    bool ok = true;
-    for (int i0 = threadIdx.x; i0 < n; i0 += 8 * 1024) {
-        gl_u64 v[8];
-        unsigned spins = 0;
-        bool all, poisoned;
-        do {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + u * 1024;
-                v[u] = __hip_atomic_load(gx + (i < n ? i : i0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            all = true, poisoned = false;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                all = all && (unsigned)(v[u] >> 32) == tag;
-                poisoned = poisoned || (unsigned)(v[u] >> 32) == (tag ^ GL_POISON);
-            }
-            if (!all && !poisoned) __builtin_amdgcn_s_sleep(2);
-        } while (!all && !poisoned && ++spins < spin_limit);
-        if (!all) ok = false;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (i0 + u * 1024 < n) s_x[i0 + u * 1024] = __uint_as_float((unsigned)v[u]);
-    }
-    return ok;
-}
 
 // REPAIR = false: the launch proper, one workgroup per plot.  A workgroup whose wait for its peers' statistics runs out (HIP does
 // not promise that the B workgroups of a launch are resident together) or that finds a peer's POISON gives up: it counts itself
@@ -506,8 +475,8 @@ __global__ __launch_bounds__(1024) void global_level_fwd_kernel(GlArgs A) {
 
 }  // namespace
 
-// sweeps (~1 us each) before an exchange wait of global_level_fwd_kernel gives up; tests shorten it to provoke a give-up
-static unsigned g_gl_spin_limit = 1u << 18;
+// sweeps (~1 us each) before an exchange wait of global_level_fwd_kernel / global_level_bwd_kernel gives up; tests shorten it to provoke a give-up
+unsigned g_gl_spin_limit = 1u << 18;
 extern "C" int sn2_debug_global_spin_limit(unsigned sweeps) {       // (0 = back to the default)
     g_gl_spin_limit = sweeps ? sweeps : (1u << 18);
     return 0;

@@ -457,6 +457,9 @@ def backward(model, s, dcov, dproba):
     cb.defer_grad_reduce = int(defer)
     cb.arena_is_zero = int(pre_zeroed)
     cb.frozen_stats = int(bool(s.__dict__.get("frozen", False)))
+    if model.fuse_global_level and not cb.frozen_stats and plan.B <= ops.GL_MAX_PLOTS and plan.dims.M2 <= ops.GL_BWD_MAX_ROWS:
+        ws = ops.global_level_ws(dev, owner=model)
+        cb.gl_xchg, cb.gl_ctl = ws[3].data_ptr(), ws[4].data_ptr()
     _lib.check(lib.sn2_net_backward(byref(ms.c), byref(plan.dims), byref(geo_struct(s.geo)), byref(s.cact), byref(cb), ops._stream()),
                "sn2_net_backward")
     flat = arena[:ms.n_flat]

@@ -984,15 +984,17 @@ _GLOBAL_WS_ALL = []      # weak references to every live workspace (global_level
 
 
 class _GlobalWs(list):
-    """[exchange granules (int64), control words (int32), give-ups already reported]"""
+    """[exchange granules (int64), control words (int32), give-ups already reported, the backward's granules, its control words]"""
     __slots__ = ("__weakref__",)
 
 
 def global_level_ws(dev, B: int = GL_MAX_PLOTS, owner=None):
-    """The exchange area and control words of `global_level_forward` (zero-filled once, then the library's).
+    """The exchange areas and control words of `global_level_forward` (ws[0], ws[1]) and `global_level_backward` (ws[3], ws[4]:
+    its own), zero-filled once, then the library's.
     owner: the object whose training forwards use it (a PointNet2): the workspace lives on it, so two models that train on two
     streams of one process never share an exchange area; without an owner there is one per device.  Launches that share a
-    workspace must be on one stream at a time.  Allocated ONCE at the largest size the kernel takes (28 plots: 229 KB) and
+    workspace must be on one stream at a time.  Allocated ONCE at the largest size the kernels take (28 plots: 229 KB for the
+    forward's granules, 57 KB for the backward's, 8 + 64 control words) and
     never again: hipGraphs captured earlier hold its raw address and its launch epoch (round 4 reallocated it when a later call
     had more plots, under the feet of the graphs captured before)."""
     dev = torch.device(dev)
@@ -1006,7 +1008,8 @@ def global_level_ws(dev, B: int = GL_MAX_PLOTS, owner=None):
             # zero fills captured into a graph would run at every replay and reset the launch epoch under the other graphs
             raise StrataHipError("global_level_forward: its exchange area must exist before a stream capture starts -- run one "
                                  "eager training forward first (TrainPipeline.capture does) or call hip_ops.global_level_ws(dev, owner=model)")
-        ws = _GlobalWs([torch.zeros(2 * GL_MAX_PLOTS * 4 * 128, dtype=I64, device=dev), torch.zeros(8, dtype=I32, device=dev), 0])
+        ws = _GlobalWs([torch.zeros(2 * GL_MAX_PLOTS * 4 * 128, dtype=I64, device=dev), torch.zeros(8, dtype=I32, device=dev), 0,
+                        torch.zeros(2 * GL_MAX_PLOTS * 128, dtype=I64, device=dev), torch.zeros(64, dtype=I32, device=dev)])
         store[key] = ws
         import weakref
         _GLOBAL_WS_ALL[:] = [r for r in _GLOBAL_WS_ALL if r() is not None]
@@ -1024,10 +1027,31 @@ def global_level_forward(d_sa3: FP, d_fp3: FP, x3: torch.Tensor, arg3: torch.Ten
     _call("sn2_global_level_forward", d_sa3, d_fp3, _ptr(x3), _ptr(arg3), _ptr(ws[0]), _ptr(ws[1]), _stream())
 
 
+GL_BWD_MAX_ROWS = 256    # csrc/common.h: GL_BWD_MAX_ROWS
+
+
+def global_level_backward_fused(B: int, M2: int, frozen: bool, *blocks) -> bool:
+    """Does the backward of the global level take `global_level_backward`?  (The same rule as sn2_net_backward, csrc/net.hip:
+    at most 28 plots, batch statistics, fp32 operands, and at most 256 rows per plot -- the one-block-per-group instance of the
+    kernel, the one measured against the four launches; the entry point itself takes more rows.)"""
+    return B <= GL_MAX_PLOTS and M2 <= GL_BWD_MAX_ROWS and not frozen and not any(b.mma_bf16 for b in blocks)
+
+
+def global_level_backward(d_sa3: FP, d_fp3: FP, arg3: torch.Tensor, owner=None):
+    """FP3's BatchNorm sums, FP3 backward, the pool's backward, SA3's BatchNorm sums and SA3 backward in one launch (include/
+    strata_hip.h).  d_fp3: dy, dsrc = d x3, dskip = d x2; d_sa3: dsrc = the same d x2; both with_grads.  owner: see
+    `global_level_ws`."""
+    B = d_sa3.B
+    _chk(arg3, I32, (B, 64), "arg3")
+    ws = global_level_ws(arg3.device, B, owner=owner)
+    _call("sn2_global_level_backward", d_sa3, d_fp3, _ptr(arg3), _ptr(ws[3]), _ptr(ws[4]), _stream())
+
+
 def global_level_gave_up(dev, warn: bool = True) -> int:
-    """Exchange waits of `global_level_forward` that gave up on this device since the process started (a workgroup of a launch
-    was not resident within the spin limit: another stream or process held the CUs), over every live workspace.  Each such
-    launch was REPAIRED by the gated launch behind it (sn2_global_level_forward: the level is recomputed by one workgroup),
+    """Exchange waits of `global_level_forward` and `global_level_backward` that gave up on this device since the process
+    started (a workgroup of a launch was not resident within the spin limit: another stream or process held the CUs), over
+    every live workspace.  Each such launch was REPAIRED inside itself by the workgroup that left it last (the forward
+    recomputes the level, the backward finishes the plots whose workgroups had committed nothing: include/strata_hip.h),
     so the results are unaffected; a count that grew since the last call is reported once as a StrataHipWarning (the passes took
     longer; `PointNet2.fuse_global_level = False` runs the level as separate launches).  Reads device words: call it where the
     host synchronises anyway (TrainPipeline.drain, after a test)."""
@@ -1038,14 +1062,14 @@ def global_level_gave_up(dev, warn: bool = True) -> int:
         ws = r()
         if ws is None or ws[1].device.index != key:
             continue
-        n = int(ws[1][1].item())
+        n = int(ws[1][1].item()) + int(ws[4][1].item())
         total += n
         if n > ws[2]:
             seen, ws[2] = ws[2], n
             if warn:
                 import warnings
-                warnings.warn(f"global_level_forward: {n - seen} exchange wait(s) gave up on {dev}; those launches were repeated "
-                              "by the single-workgroup repair launch (results unaffected, the passes took longer); set "
+                warnings.warn(f"global_level_forward / backward: {n - seen} exchange wait(s) gave up on {dev}; those launches were finished "
+                              "by their last workgroup alone (results unaffected, the passes took longer); set "
                               "PointNet2.fuse_global_level = False where other kernels or processes share the device",
                               StrataHipWarning, stacklevel=2)
     return total

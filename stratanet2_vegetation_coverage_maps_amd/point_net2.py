@@ -812,21 +812,26 @@ class PointNet2(nn.Module):
         d2 = self._fp2_desc(s, dy=dy2, dsrc=dy3, dskip=dx1, du_scratch=torch.empty(B * M1, 64, dtype=F32, device=dev),
                             with_grads=True, interp_index=s.inv2, bn_sums_done=bn_ok[1:2])
         ops.fp_backward(d2)
-        bn3 = self.fp3_module.nn[0][2]      # and FP3's from FP2's
-        ops.fp_bn_sums(d2, bn3.weight.detach(), bn3.bias.detach(), s.b_fp3.aux[2], s.b_fp3.aux[3], views[id(bn3.weight)],
-                       views[id(bn3.bias)], bn_ok[2:3])
-        # FP3 -> d x2 and the per-row gradients of its interpolated part (left in du3: scatter_ready = -1); then the pool between
-        # FP3 and SA3 in one launch (hip_ops.global_pool_backward): d x3, its routing to the SA3 rows that attained the maximum, and
-        # SA3's BatchNorm sums over those B x 64 entries
         dx3, dx2 = buf["dx3"].view(B, 64), buf["dx2"].view(B * M2, 32)
-        du3 = torch.empty(B * M2, 64, dtype=F32, device=dev)
-        ops.fp_backward(self._fp3_desc(s, dy=dy3, dsrc=dx3, dskip=dx2, du_scratch=du3, with_grads=True,
-                                       interp_index=s.inv3, bn_sums_done=bn_ok[2:3], gather=False))
-        dy_sa3 = buf["dy_sa3"].view(B * M2, 64)
-        bn_sa3 = self.sa3_module.nn[0][2]
-        ops.global_pool_backward(du3, s.arg3, s.h_sa3, s.b_sa3.aux[2], s.b_sa3.aux[3], B, M2, dx3, dy_sa3,
-                                 views[id(bn_sa3.weight)], views[id(bn_sa3.bias)])
-        ops.fp_backward(self._sa3_desc(s, dy=dy_sa3, dsrc=dx2, with_grads=True, bn_sums_done=bn_ok[3:4]))
+        if self.fuse_global_level and ops.global_level_backward_fused(B, M2, getattr(s.b_fp3, "frozen", False), s.b_sa3, s.b_fp3):
+            # FP3's BatchNorm sums, FP3, the pool between FP3 and SA3, SA3's BatchNorm sums and SA3 in one launch
+            ops.global_level_backward(self._sa3_desc(s, dsrc=dx2, with_grads=True),
+                                      self._fp3_desc(s, dy=dy3, dsrc=dx3, dskip=dx2, with_grads=True), s.arg3, owner=self)
+        else:
+            bn3 = self.fp3_module.nn[0][2]      # and FP3's from FP2's
+            ops.fp_bn_sums(d2, bn3.weight.detach(), bn3.bias.detach(), s.b_fp3.aux[2], s.b_fp3.aux[3], views[id(bn3.weight)],
+                           views[id(bn3.bias)], bn_ok[2:3])
+            # FP3 -> d x2 and the per-row gradients of its interpolated part (left in du3: scatter_ready = -1); then the pool
+            # between FP3 and SA3 in one launch (hip_ops.global_pool_backward): d x3, its routing to the SA3 rows that attained
+            # the maximum, and SA3's BatchNorm sums over those B x 64 entries
+            du3 = torch.empty(B * M2, 64, dtype=F32, device=dev)
+            ops.fp_backward(self._fp3_desc(s, dy=dy3, dsrc=dx3, dskip=dx2, du_scratch=du3, with_grads=True,
+                                           interp_index=s.inv3, bn_sums_done=bn_ok[2:3], gather=False))
+            dy_sa3 = buf["dy_sa3"].view(B * M2, 64)
+            bn_sa3 = self.sa3_module.nn[0][2]
+            ops.global_pool_backward(du3, s.arg3, s.h_sa3, s.b_sa3.aux[2], s.b_sa3.aux[3], B, M2, dx3, dy_sa3,
+                                     views[id(bn_sa3.weight)], views[id(bn_sa3.bias)])
+            ops.fp_backward(self._sa3_desc(s, dy=dy_sa3, dsrc=dx2, with_grads=True, bn_sums_done=bn_ok[3:4]))
         # SA2 -> d x1 ; SA1
         ops.sa_backward(self._sa2_desc(s, dout=dx2, dfeat=dx1, g=True))
         ops.sa_backward(self._sa1_desc(s, dout=dx1, g=True, bwd_ws=buf["sa1_ws"]))      # (both blocks in one message pass)
