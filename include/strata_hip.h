@@ -114,7 +114,17 @@ int sn2_pack_rows(const float *cloud, const float *xyz, int B, int C, int N, flo
  * first B*N words: what sn2_fp.row_perm takes]) enabling the bucketed kernel (exact same result, several times
  * faster at N = 32768), or NULL for the brute-force kernel.  After the call the workspace describes the sorted point
  * set and can be handed to sn2_ball_query over the same sources. */
-#define SN2_FPS_WS_WORDS(B, N) (6L * (B) * (N) + (4104L + 4096L) * (B) + 32L)
+#define SN2_FPS_WS_GRID_WORDS 4104 /* cell-grid header of one plot */
+#define SN2_FPS_WS_XCHG_WORDS 4096 /* exchange area of one plot     */
+#define SN2_FPS_WS_CTL_WORDS 32    /* control words of the workspace: [1] = waits of the LAST pass that gave up */
+#define SN2_FPS_WS_GRID_OFFSET(B, N) (5L * (B) * (N))
+#define SN2_FPS_WS_CTL_OFFSET(B, N) (SN2_FPS_WS_GRID_OFFSET(B, N) + (long)(SN2_FPS_WS_GRID_WORDS + SN2_FPS_WS_XCHG_WORDS) * (B))
+#define SN2_FPS_WS_RANK_OFFSET(B, N) (SN2_FPS_WS_CTL_OFFSET(B, N) + SN2_FPS_WS_CTL_WORDS)
+#define SN2_FPS_WS_WORDS(B, N) (SN2_FPS_WS_RANK_OFFSET(B, N) + 1L * (B) * (N))
+size_t sn2_fps_ws_words(int B, int N);       /* = the macro of the same name, as every size_t sn2_*_words below: for hosts without a C compiler */
+size_t sn2_fps_ws_grid_offset(int B, int N);
+size_t sn2_fps_ws_ctl_offset(int B, int N);
+size_t sn2_fps_ws_rank_offset(int B, int N);
 int sn2_fps(const float *pos_soa, int B, int N, int M, const int *start, int *idx, float *cpos_soa,
             float *cpos_aos, int *order_ws, void *stream);
 /* The same with a choice of kernel for the bucketed path.  waves = 0 (what sn2_fps passes): the shortest pass -- the
@@ -160,17 +170,20 @@ int sn2_count_sum_group(const int *cnt, int G, int n, unsigned long long *total,
  * torch_geometric.nn.knn_interpolate, model/point_net2.py:63.
  * idx (B*T,3), w (B*T,3): w = 1/max(d2,1e-16); unused slots (k<3 or S<k) get w = 0 and idx = idx[0].
  * ws + dst_fps_ws (optional, both or neither): ws = 16-byte aligned workspace of SN2_THREE_NN_WS_WORDS(B,S) 32-bit words,
- * dst_fps_ws = the workspace sn2_fps filled for the TARGET points (same B, N = T > 2048).  With them (and 128 <= S <= 8192)
- * a wave takes 64 spatially adjacent targets and searches a per-plot x,y grid of the sources instead of scanning all S
- * (same result, bit for bit); results are still written at the targets' original positions. */
+ * dst_fps_ws = the workspace sn2_fps filled for the TARGET points (same B, N = T).  With them, where
+ * sn2_three_nn_uses_grid(S, T), a wave takes 64 spatially adjacent targets and searches a per-plot x,y grid of the sources
+ * instead of scanning all S (same result, bit for bit); results are still written at the targets' original positions. */
 #define SN2_THREE_NN_WS_WORDS(B, S) ((size_t)(B) * (4 * (size_t)(S) + 1032))
+size_t sn2_three_nn_ws_words(int B, int S);
 int sn2_three_nn(const float *src_soa, int B, int S, const float *dst_soa, int T, int k, int *idx, float *w,
                  void *ws, const int *dst_fps_ws, void *stream);
 /* The same search with the targets sorted by the source grid's x,y cells inside the call (a counting sort, one workgroup
  * per plot): every wave then holds 64 targets of one or two adjacent cells, whatever order the targets come in.
- * 128 <= S <= 8192; ws = 16-byte aligned workspace of SN2_THREE_NN_XY_WS_WORDS(B,S,T) 32-bit words.  Same results as
+ * 128 <= S <= 8192 (the S range of sn2_three_nn_uses_grid; else SN2_ELIMIT); ws = 16-byte aligned workspace of
+ * SN2_THREE_NN_XY_WS_WORDS(B,S,T) 32-bit words.  Same results as
  * sn2_three_nn, bit for bit. */
 #define SN2_THREE_NN_XY_WS_WORDS(B, S, T) ((size_t)(B) * (4 * (size_t)(S) + 5 * (size_t)(T) + 1032))
+size_t sn2_three_nn_xy_ws_words(int B, int S, int T);
 int sn2_three_nn_xy(const float *src_soa, int B, int S, const float *dst_soa, int T, int k, int *idx, float *w,
                     void *ws, void *stream);
 
@@ -230,6 +243,7 @@ int sn2_subsample(const int *offsets, int extra, int n_max, int B, int N, unsign
  * 32-bit words with cells = ((x_max-x_min)/radius + 2) * ((y_max-y_min)/radius + 2), 16-byte aligned.
  * zmin (n) and/or z_out (n) = fp32(z - zmin). */
 #define SN2_ZNORM_WS_WORDS(n, cells) ((size_t)5 * (n) + 3 * (size_t)(cells) + 8)
+size_t sn2_znorm_ws_words(int n, long cells);
 int sn2_znorm(const float *x, const float *y, const float *z, int n, float radius, float x_min, float y_min, float x_max,
               float y_max, int *ws, float *zmin, float *z_out, void *stream);
 
@@ -310,6 +324,7 @@ typedef struct sn2_sa {
 #define SN2_SA_OCT_FLAG 0x20000000
 #define SN2_SA_PACKED_ITEMS(M) ((M) / 8 + 2)
 #define SN2_SA_ORDER_WORDS(B, M) ((size_t)4 * (B) * (M) + (size_t)16 * (B) * SN2_SA_PACKED_ITEMS(M) + 8)
+size_t sn2_sa_order_words(int B, int M);
 int sn2_sa_order(const int *cnt, int B, int M, int *order, void *stream);
 /* G consecutive batches of B plots each in one launch pair: cnt (G*B*M), batch h's work items at order + h * stride_words
  * (stride_words >= SN2_SA_ORDER_WORDS(B,M)): what a geometry pass over several batches of a pipelined loop calls */
@@ -342,7 +357,7 @@ typedef struct sn2_fp {
                                        blk.dbeta already hold this BatchNorm's gradients, sn2_fp_backward launches no
                                        pass over the rows for them.  NULL: it does                                  */
     float *src_ws;                  /* workspace SN2_FP_SRC_WS_WORDS(B,R,S,cout) floats or NULL.  Given with knn_idx on a
-                                       layer of more than 64*SN2_STAT_SLOTS rows with cb % 4 == 0 (the per-point layer),
+                                       layer that sn2_fp_source_side(B*R, cb, 0) accepts (the per-point layer),
                                        everything linear in the interpolation is done once per SOURCE row: forward
                                        gathers rows of T = W_A (sa*src+sc) kept here; backward keeps the partial sums of G[s] = sum of
                                        w * d pre-activation over the rows interpolating s here, one row per 63 list
@@ -362,11 +377,14 @@ typedef struct sn2_fp {
  * source: every list's last chunk may be short) */
 #define SN2_INTERP_CHUNKS(R, S) ((3 * (size_t)(R) + 62) / 63 + (size_t)(S))
 #define SN2_FP_SRC_WS_WORDS(B, R, S, cout) ((size_t)(B) * SN2_INTERP_CHUNKS(R, S) * ((((cout) + 3) / 4) * 4))
+size_t sn2_interp_chunks(int R_per_plot, int S_per_plot);
+size_t sn2_fp_src_ws_words(int B, int R_per_plot, int S_per_plot, int cout);
 /* The transpose of knn_interpolate (its backward) is done as a gather through an inverted index of the 3-NN table:
  * source -> list of (target row, normalised weight).  The index depends on positions only, so it can be built ahead of
  * the backward pass (in the geometry pass) with sn2_interp_index; otherwise sn2_fp_backward builds it itself. */
 #define SN2_INTERP_WS_WORDS(B, R, S) \
     ((size_t)(B) * (S) * (((R) + 2047) / 2048 + 6) + 6 * (size_t)(B) * (R) + 64 + 4 * (size_t)(B) * SN2_INTERP_CHUNKS(R, S))
+size_t sn2_interp_ws_words(int B, int R_per_plot, int S_per_plot);
 /* src_pos: (B*S,4) x,y,z,- rows of the SOURCE positions or NULL.  Given, the index also holds the sources of every plot
  * in Morton order, and the source-side backward (sn2_fp.src_ws) walks them in that order, one stretch per XCD, so that
  * target rows shared by neighbouring sources stay in that XCD's L2. */
@@ -420,9 +438,12 @@ int sn2_global_pool_backward(const float *du, int du_stride, const int *arg, con
  *   undisturbed launch, bit for bit, whatever happened (torch's BatchNorm has no such failure mode: model/point_net2.py:45-53).
  *   An undisturbed launch pays one fence and one atomic per workgroup for it.  ctl[1] stays as a sticky count a host may read
  *   where it synchronises anyway, to learn that launches are being repeated.
- * SN2_ELIMIT for other shapes, bfloat16 operands or more than 28 plots: use the separate calls. */
+ * SN2_ELIMIT for other shapes, bfloat16 operands or more than SN2_GLOBAL_MAX_PLOTS plots (the collected granules of all plots
+ * must fit the workgroup's LDS): use the separate calls. */
+#define SN2_GLOBAL_MAX_PLOTS 28
 #define SN2_GLOBAL_XCHG_WORDS(B) ((size_t)2 * (size_t)(B) * 4 * 128)
 #define SN2_GLOBAL_CTL_WORDS 8
+size_t sn2_global_xchg_words(int B);
 int sn2_global_level_forward(const sn2_fp *sa3, const sn2_fp *fp3, float *x3, int *arg3, unsigned long long *xchg,
                              unsigned *ctl, void *stream);
 /* The backward of that level in ONE launch (training mode, batch statistics, fp32 operands): FP3's BatchNorm sums (taken directly
@@ -440,9 +461,12 @@ int sn2_global_level_forward(const sn2_fp *sa3, const sn2_fp *fp3, float *x3, in
  *   has committed nothing; it counts itself in ctl[1] and the workgroup that leaves last finishes those plots alone: every result
  *   is committed exactly once, with the bits of an undisturbed launch.  Two runs on the same inputs give the same bits (fixed-order
  *   sums, no float atomics).
- * SN2_ELIMIT for other shapes, bfloat16 operands, frozen statistics, more than 28 plots or fewer images than plots.
- * sn2_net_backward takes it up to 256 rows per plot (one 64-row block per group: the measured instance), the four launches above. */
-#define SN2_GLOBAL_BWD_XCHG_WORDS ((size_t)2 * 28 * 128)
+ * SN2_ELIMIT for other shapes, bfloat16 operands, frozen statistics, more than SN2_GLOBAL_MAX_PLOTS plots or fewer images than plots.
+ * The entry point takes any number of rows per plot; the network's backward takes it up to SN2_GLOBAL_BWD_MAX_ROWS rows per plot
+ * (one 64-row block per group of its workgroup: the instance measured against the four launches above) -- see
+ * sn2_global_level_backward_route. */
+#define SN2_GLOBAL_BWD_MAX_ROWS 256
+#define SN2_GLOBAL_BWD_XCHG_WORDS ((size_t)2 * SN2_GLOBAL_MAX_PLOTS * 128)
 #define SN2_GLOBAL_BWD_CTL_WORDS 64
 int sn2_global_level_backward(const sn2_fp *sa3, const sn2_fp *fp3, const int *arg3, unsigned long long *xchg, unsigned *ctl,
                               void *stream);
@@ -505,6 +529,7 @@ int sn2_plot_project_forward(const float *pred_pointwise, const float *cloud_xy,
  * rest of it from those ids -- keys: u64 workspace of SN2_P2_KEY_PARTS(N)*B*D*D*3 words (no initialisation: every slice of a
  * plot writes its own table, the finalisation takes their maximum), same arg / nocc / pred. */
 #define SN2_P2_KEY_PARTS(N) (((N) + 4095) / 4096 < 1 ? 1 : (((N) + 4095) / 4096 > 64 ? 64 : ((N) + 4095) / 4096))
+size_t sn2_p2_key_parts(int N);
 int sn2_plot_pixels(const float *cloud_xy, long plot_stride, int B, int N, int D, float *mm, int *pix, void *stream);
 int sn2_plot_project_forward_pix(const float *pred_pointwise, const int *pix, int B, int N, int D,
                                  unsigned long long *keys, int *arg, int *nocc, float *pred, void *stream);
@@ -585,6 +610,7 @@ int sn2_kde_lookup(const float *cloud, int B, int C, int N, int z_channel, float
 #define SN2_KDE_FIT_SLICES 8
 #define SN2_KDE_FIT_WS_WORDS(K) \
     (2 * ((4 + 3 * SN2_KDE_FIT_SLICES) * (size_t)(K) + 3 * (((size_t)(K) + 255) / 256)) + SN2_KDE_FIT_ABS_SLOTS)
+size_t sn2_kde_fit_ws_words(int K);
 int sn2_kde_fit(const float *z, long n, double bw, int K, void *ws, double *X, double *Y, void *stream);
 #define SN2_LOSS_BLOCKS 1024
 int sn2_loss_forward(const float *pred, const double *gt, int B, const float *proba, const double *pdf, int R, double m,
@@ -725,8 +751,9 @@ typedef struct sn2_net_act {
                                             backward pass is told so (sn2_net_bwd.arena_is_zero) */
 } sn2_net_act;
 
-/* The buffers of one backward pass: `arena` (zero-filled INSIDE sn2_net_backward) = 32 images of the flat parameter gradient,
- * image stride = n_flat rounded up to 64 floats, followed by the accumulate-into buffers; the rest is scratch. */
+/* The buffers of one backward pass: `arena` (zero-filled INSIDE sn2_net_backward) = SN2_NET_GRAD_IMAGES images of the flat
+ * parameter gradient, image stride = n_flat rounded up to 64 floats, followed by the accumulate-into buffers; the rest is scratch. */
+#define SN2_NET_GRAD_IMAGES 32
 typedef struct sn2_net_bwd {
     const float *dcov, *dproba;          /* IN (B*N,4) each, either may be NULL -- set by the caller */
     float *arena; long arena_words;
@@ -794,6 +821,29 @@ int sn2_net_backward(const sn2_net_model *m, const sn2_net_dims *d, const sn2_ne
 int sn2_adam_step_images(float *param, float *grad_images, int replicas, int stride, float *exp_avg, float *exp_avg_sq, int n,
                          float lr, float beta1, float beta2, float eps, float weight_decay, int *step_dev, float grad_scale,
                          void *stream);
+
+/* ==== Routes =================================================================================================
+ * Which kernel a size takes, and therefore which workspaces exist, stated ONCE: each predicate is host-only arithmetic (no HIP
+ * call, no device work; 0 or 1), lives beside the dispatch it governs, and is what that dispatch itself, sn2_net_* and the Python
+ * host all ask.  A caller still ANDs in its own settings and whether it holds the workspace. */
+/* sn2_fps* FILLS order_ws for these sizes (given a 16-byte aligned one): the bucketed kernels -- more than 2048 points per plot
+ * (at most 131 072), unless the plots are many (B > 32) and small (N <= 4096), M > 16, B*N a multiple of 4.  Otherwise the
+ * brute-force kernels run and the workspace is NOT touched: nobody may hand it to sn2_ball_query / sn2_three_nn. */
+int sn2_fps_fills_ws(int B, int N, int M);
+/* the grid search of sn2_three_nn_xy (and of sn2_three_nn with ws + dst_fps_ws) applies: 128 <= S <= 8192 sources and T > 2048
+ * targets; otherwise the full scan of sn2_three_nn runs */
+int sn2_three_nn_uses_grid(int S, int T);
+/* a dense-row block of R rows takes the 64-row matrix-core kernels of sn2_fp_forward / sn2_fp_backward in a TRAINING pass: its
+ * per-workgroup statistic slots bound the rows, ceil(R / 64) <= SN2_STAT_SLOTS.  Only those kernels take bfloat16 operands
+ * (sn2_block.mma_bf16). */
+int sn2_fp_rows_small(long R);
+/* sn2_fp.src_ws is used (the source-side form): 0 < cb <= 16, cb a multiple of 4, and more rows than sn2_fp_rows_small takes --
+ * or force != 0 (sn2_fp_head_eval, which has no other form).  Only this form keeps bfloat16 rows (sn2_fp.act_bf16). */
+int sn2_fp_source_side(long R, int cb, int force);
+/* sn2_net_forward / sn2_net_backward take the one-launch global level (bf16: either block has sn2_block.mma_bf16): at most
+ * SN2_GLOBAL_MAX_PLOTS plots, fp32 operands; backward also batch statistics (frozen == 0) and M2 <= SN2_GLOBAL_BWD_MAX_ROWS */
+int sn2_global_level_forward_route(int B, int bf16);
+int sn2_global_level_backward_route(int B, int M2, int frozen, int bf16);
 
 #ifdef __cplusplus
 }

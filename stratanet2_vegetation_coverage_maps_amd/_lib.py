@@ -1,15 +1,35 @@
 """ctypes binding of libstrata_hip.so (include/strata_hip.h).  No torch C++ extension, no fallback: if the library
 is missing the product path raises."""
 import ctypes
+import functools
 import os
 from ctypes import POINTER, Structure, c_double, c_float, c_int, c_long, c_longlong, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libstrata_hip.so")
 
-SN2_VERSION = 102          # (added entry points keep the version: include/strata_hip.h)
-MAX_NEIGHBORS = 2000  # model/point_net2.py:24
-STAT_SLOTS = 1024     # SN2_STAT_SLOTS
+# Every scalar constant of include/strata_hip.h that the Python host uses, under its macro's name.  tests/test_cabi.py prints
+# the macros with a C compiler and compares: this block is the only place a value of the header is written again.
+# (SN2_VERSION: added entry points keep the version.)
+CONSTANTS = {
+    "SN2_VERSION": 102, "SN2_EINVAL": -1, "SN2_ELIMIT": -2,
+    "SN2_MAX_NEIGHBORS": 2000, "SN2_STAT_SLOTS": 1024, "SN2_BN_FROZEN_KEEP": 2,
+    "SN2_FPS_WS_GRID_WORDS": 4104, "SN2_FPS_WS_CTL_WORDS": 32,
+    "SN2_SUBSAMPLE_LDS": 1, "SN2_SUBSAMPLE_GLOBAL": 2, "SN2_SUBSAMPLE_COARSE": 4, "SN2_SUBSAMPLE_LDS_MAX": 16384,
+    "SN2_SA_BWD_WS_WORDS": 32 * 2 * 16 * 12,
+    "SN2_GLOBAL_MAX_PLOTS": 28, "SN2_GLOBAL_CTL_WORDS": 8, "SN2_GLOBAL_BWD_MAX_ROWS": 256,
+    "SN2_GLOBAL_BWD_XCHG_WORDS": 2 * 28 * 128, "SN2_GLOBAL_BWD_CTL_WORDS": 64,
+    "SN2_MOSAIC_HIST_WORDS": 10004, "SN2_KDE_FIT_MAX_K": 65536, "SN2_LOSS_BLOCKS": 1024, "SN2_PROJECTED_LOSS_WS": 2 * 512 + 2,
+    "SN2_NET_GRAD_IMAGES": 32,
+    "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
+    "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256,
+}
+globals().update(CONSTANTS)
+# the names the package has used so far
+MAX_NEIGHBORS, STAT_SLOTS, BN_FROZEN_KEEP = CONSTANTS["SN2_MAX_NEIGHBORS"], CONSTANTS["SN2_STAT_SLOTS"], CONSTANTS["SN2_BN_FROZEN_KEEP"]
+(NET_FORK, NET_SHARED, NET_INVERTED, NET_DEFER_JOIN, NET_INPUT_ONLY, NET_HAS_ROWS0, NET_JOIN_PENDING, NET_WITH_GEOMETRY,
+ NET_HAS_INVERTED) = (CONSTANTS["SN2_NET_" + n] for n in ("FORK", "SHARED", "INVERTED", "DEFER_JOIN", "INPUT_ONLY", "HAS_ROWS0",
+                                                          "JOIN_PENDING", "WITH_GEOMETRY", "HAS_INVERTED"))
 
 
 class Block(Structure):  # sn2_block
@@ -19,9 +39,6 @@ class Block(Structure):  # sn2_block
                 ("dW", c_void_p), ("db", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p),
                 ("grad_replicas", c_int), ("grad_replica_stride", c_int), ("mma_bf16", c_int),
                 ("num_batches_tracked", c_void_p), ("frozen_stats", c_int)]
-
-
-BN_FROZEN_KEEP = 2          # SN2_BN_FROZEN_KEEP: the `training` argument of an eval-mode forward whose backward will be asked for
 
 
 class SA(Structure):  # sn2_sa
@@ -100,11 +117,7 @@ class NetIO(Structure):  # sn2_net_io
                 ("training", c_int)]
 
 
-NET_FORK, NET_SHARED, NET_INVERTED, NET_DEFER_JOIN, NET_INPUT_ONLY = 1, 2, 4, 8, 16          # SN2_NET_* of the header
-NET_HAS_ROWS0, NET_JOIN_PENDING, NET_WITH_GEOMETRY, NET_HAS_INVERTED = 32, 64, 128, 256
-
-
-# name -> argtypes; every entry point returns int (0 ok, >0 hipError_t, <0 argument error)
+# name -> argtypes; every entry point returns int (0 ok, >0 hipError_t, <0 argument error; the route predicates: 0 / 1)
 SIGNATURES = {
     "sn2_version": [],
     "sn2_debug_mfma_chain": [c_void_p, c_void_p, c_void_p, c_int, c_void_p],
@@ -195,10 +208,32 @@ SIGNATURES = {
     "sn2_net_geometry": [POINTER(NetModel), POINTER(NetDims), POINTER(NetGeo), POINTER(NetIO), c_void_p],
     "sn2_net_forward": [POINTER(NetModel), POINTER(NetDims), POINTER(NetGeo), POINTER(NetAct), POINTER(NetIO), c_void_p],
     "sn2_net_backward": [POINTER(NetModel), POINTER(NetDims), POINTER(NetGeo), POINTER(NetAct), POINTER(NetBwd), c_void_p],
+    # the route predicates ("Routes" of the header): host-only arithmetic, they return 0 / 1
+    "sn2_fps_fills_ws": [c_int, c_int, c_int],
+    "sn2_three_nn_uses_grid": [c_int, c_int],
+    "sn2_fp_rows_small": [c_long],
+    "sn2_fp_source_side": [c_long, c_int, c_int],
+    "sn2_global_level_forward_route": [c_int, c_int],
+    "sn2_global_level_backward_route": [c_int, c_int, c_int, c_int],
 }
 
-# workspace-size helpers: name -> argtypes; they return size_t (32-bit words; 0 = beyond what the kernels cover)
+# workspace-size and layout helpers: name -> argtypes; they return size_t (32-bit words unless the header says otherwise; 0 =
+# beyond what the kernels cover)
 SIZE_HELPERS = {
+    "sn2_fps_ws_words": [c_int, c_int],
+    "sn2_fps_ws_grid_offset": [c_int, c_int],
+    "sn2_fps_ws_ctl_offset": [c_int, c_int],
+    "sn2_fps_ws_rank_offset": [c_int, c_int],
+    "sn2_three_nn_ws_words": [c_int, c_int],
+    "sn2_three_nn_xy_ws_words": [c_int, c_int, c_int],
+    "sn2_znorm_ws_words": [c_int, c_long],
+    "sn2_sa_order_words": [c_int, c_int],
+    "sn2_interp_chunks": [c_int, c_int],
+    "sn2_interp_ws_words": [c_int, c_int, c_int],
+    "sn2_fp_src_ws_words": [c_int, c_int, c_int, c_int],
+    "sn2_global_xchg_words": [c_int],
+    "sn2_p2_key_parts": [c_int],
+    "sn2_kde_fit_ws_words": [c_int],
     "sn2_parcel_count_ws_words": [c_int, c_int],
     "sn2_parcel_znorm_ws_words": [c_long, c_float, c_float, c_float, c_float, c_float],
     "sn2_subsample_ws_words": [c_int, c_int, c_int, c_int],
@@ -235,6 +270,13 @@ def load():
         raise StrataHipError(f"libstrata_hip.so version {lib.sn2_version()} != binding {SN2_VERSION}: rebuild")
     _lib = lib
     return lib
+
+
+@functools.lru_cache(maxsize=4096)
+def host_value(name: str, *args) -> int:
+    """A route predicate or size helper of the library (SIGNATURES / SIZE_HELPERS: pure functions of their integer arguments),
+    remembered per argument tuple: several of them are asked once per launch on the per-call path."""
+    return getattr(load(), name)(*args)
 
 
 def check(rc: int, what: str):

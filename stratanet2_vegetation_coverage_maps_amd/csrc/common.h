@@ -37,12 +37,10 @@ __device__ __forceinline__ int sn2_grad_image(int replicas, int stride) {
 
 static inline int sn2_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// plots of one sn2_global_level_forward launch (global_level.hip: the collected granules of all plots must fit its LDS; net.hip
-// takes the separate launches above it; hip_ops.GL_MAX_PLOTS mirrors it)
-constexpr int GL_MAX_PLOTS = 28;
-// rows per plot up to which the network's backward takes sn2_global_level_backward: one 64-row block per group of its workgroup,
-// the instance that has been measured against the four launches (the entry point itself takes any M2; hip_ops.GL_BWD_MAX_ROWS)
-constexpr int GL_BWD_MAX_ROWS = 256;
+// plots of one sn2_global_level_forward / _backward launch (the collected granules of all plots must fit the workgroup's LDS) and
+// the rows per plot up to which the network's backward takes the one-launch form (sn2_global_level_backward_route)
+constexpr int GL_MAX_PLOTS = SN2_GLOBAL_MAX_PLOTS;
+constexpr int GL_BWD_MAX_ROWS = SN2_GLOBAL_BWD_MAX_ROWS;
 
 // ---- clearing a buffer.  Always a KERNEL, never hipMemsetAsync: every entry point may be captured into a hipGraph, and on
 // this runtime (ROCm 7.2) a captured memset NODE is only right on the FIRST replay -- from the second replay on it fills

@@ -1470,9 +1470,9 @@ int fp_forward_t(const sn2_fp* p, int mode, hipStream_t st) {
     // the matrix-core kernel (64 rows x 4 channel groups per workgroup): its per-workgroup statistic slots bound the rows of a
     // TRAINING pass; an eval pass writes no statistics, so any row count takes it (parcel inference: FP3 on 80 000 rows ran
     // the scalar-weight fallback below at 0.31 ms, 15 x what the contraction needs)
-    const bool small = sn2_cdiv(R, 64) <= SN2_STAT_SLOTS;
+    const bool small = sn2_fp_rows_small(R);
     bool src_side = false;                      // (the per-point layer keeps its source-side form in both modes)
-    if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16) src_side = !small && fp_source_side_ok<CA, CO>(p);
+    if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16) src_side = sn2_fp_source_side(R, CB, 0) && fp_source_side_ok<CA, CO>(p);
     if (small || (!keep && !src_side)) {
         if (p->act_bf16) return SN2_ELIMIT;
         const int grid = sn2_cdiv(R, 64);
@@ -1552,7 +1552,7 @@ int fp_backward_t(const sn2_fp* p, hipStream_t st) {
     // batch-mean and batch-variance terms of the BatchNorm backward vanish
     const float invR = p->blk.frozen_stats ? 0.f : 1.0f / (float)R;
     if (p->act_bf16 && !(p->bn_sums_done && p->src_ws && p->du_scratch && p->scatter_ws && p->dsrc && !p->dskip &&
-                         sn2_cdiv(R, 64) > SN2_STAT_SLOTS))
+                         !sn2_fp_rows_small(R)))
         return SN2_ELIMIT;                    // bfloat16 rows: the source-side form of the per-point layer only
     // bn_sums_done (non-NULL): dgamma / dbeta of this block's BatchNorm already came from sn2_head_bn_sums / sn2_fp_bn_sums
     if (p->bn_sums_done) {
@@ -1574,7 +1574,7 @@ int fp_backward_t(const sn2_fp* p, hipStream_t st) {
     if (KNN && !p->dsrc) du_out0 = nullptr;
     constexpr size_t lb = fp_split_lds_bytes<CI>(fp_split_du_seq<CI>() ? 1 : 4);
     static_assert(lb <= 150 * 1024, "fp_bwd_split_kernel staging must fit LDS");
-    const bool small = sn2_cdiv(R, 64) <= SN2_STAT_SLOTS;   // the 64-row x 4-channel-group kernel for small layers
+    const bool small = sn2_fp_rows_small(R);                // the 64-row x 4-channel-group kernel for small layers
     if (!small && p->blk.mma_bf16) return SN2_ELIMIT;       // bf16 operands: that kernel only
     if (small) {
         auto ks = p->blk.mma_bf16 ? &fp_bwd_split_kernel<CA, CB, CO, KNN, true> : &fp_bwd_split_kernel<CA, CB, CO, KNN, false>;
@@ -1590,7 +1590,7 @@ int fp_backward_t(const sn2_fp* p, hipStream_t st) {
         if (e != hipSuccess) return (int)e;
     }
     if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16) {
-        if (!small && fp_source_side_ok<CA, CO>(p) && p->dsrc && !p->dskip && p->du_scratch && p->scatter_ws) {
+        if (sn2_fp_source_side(R, CB, 0) && fp_source_side_ok<CA, CO>(p) && p->dsrc && !p->dskip && p->du_scratch && p->scatter_ws) {
             const int S = p->S_per_plot, Rp = p->R_per_plot, B = p->B, n_src = B * S;
             if (S > 8192) return SN2_ELIMIT;
             constexpr int NT = 512;                       // 2 workgroups x 8 waves per CU
@@ -1687,6 +1687,16 @@ int fp_backward_t(const sn2_fp* p, hipStream_t st) {
     } while (0)
 
 }  // namespace
+
+// Routes (include/strata_hip.h).  The templates above instantiate the source-side kernels for the blocks whose cb passes the
+// same test at compile time (`if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16)`).
+extern "C" int sn2_fp_rows_small(long R) { return sn2_cdiv(R, 64) <= SN2_STAT_SLOTS; }
+extern "C" int sn2_fp_source_side(long R, int cb, int force) {
+    return cb > 0 && cb <= 16 && cb % 4 == 0 && (!sn2_fp_rows_small(R) || force);
+}
+extern "C" size_t sn2_fp_src_ws_words(int B, int R_per_plot, int S_per_plot, int cout) {
+    return SN2_FP_SRC_WS_WORDS(B, R_per_plot, S_per_plot, cout);
+}
 
 extern "C" int sn2_fp_forward(const sn2_fp* p, int training, void* stream) {
     SN2_TRY(check_fp(p));

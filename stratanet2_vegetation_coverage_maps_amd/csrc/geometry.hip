@@ -152,11 +152,12 @@ __device__ __forceinline__ unsigned morton_cell(unsigned cx, unsigned cy, unsign
 }
 
 // grid header per plot (32-bit words): [0..4096] first sorted position of every Morton cell (+ end), then lo.xyz, scale.xyz
-constexpr int GRID_WORDS = ORDER_CELLS + 1 + 6 + 1;   // padded to an even count
+constexpr int GRID_WORDS = SN2_FPS_WS_GRID_WORDS;
+static_assert(GRID_WORDS == ORDER_CELLS + 1 + 6 + 1, "cell starts (+ end), lo.xyz, scale.xyz, padded to an even count");
 // exchange area of the multi-workgroup FPS (fps_cluster_kernel): per plot FPS_XCHG_WORDS words of tagged granules, then
 // FPS_CTL_WORDS control words per launch (ticket counter, timeout count).  Zeroed HERE, by the kernel in front of every FPS
 // launch (a kernel boundary: visible to every workgroup behind it; the tags count super-rounds from 1, so 0 = nothing yet).
-constexpr int FPS_XCHG_WORDS = 4096, FPS_CTL_WORDS = 32;
+constexpr int FPS_XCHG_WORDS = SN2_FPS_WS_XCHG_WORDS, FPS_CTL_WORDS = SN2_FPS_WS_CTL_WORDS;
 // One workgroup of 1024 threads per plot walks the points three times (bounding box, histogram, scatter); a trip fetches U = 16
 // points per thread before it touches the first (two trips per pass at N = 32 768; one DEPENDENT load per trip took 71 us,
 // all 32 points of a thread in registers at once spill at 1024 threads).  What is left (61 us) are the LDS atomics: 55 % of a
@@ -932,12 +933,13 @@ static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* s
     int* order = ws;                                               // B*N ints
     float4* sorted = reinterpret_cast<float4*>(ws + (size_t)B * N);   // B*N float4 (16-byte aligned: B*N*4 bytes offset
                                                                    // from a 16-byte aligned base with B*N % 4 == 0)
-    int* grid = ws + (size_t)5 * B * N;                              // B*GRID_WORDS ints
+    int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);                   // B*GRID_WORDS ints
     unsigned* xchg = reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS);      // B*FPS_XCHG_WORDS + FPS_CTL_WORDS
+    unsigned* ctl = reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N));
     // repair = this launch follows fps_cluster_kernel on the same workspace: the tables are there, and the kernel returns at once
     // unless the control words say that the multi-workgroup pass gave up
-    const unsigned* gate = repair ? xchg + (size_t)B * FPS_XCHG_WORDS : nullptr;
-    if (!repair) launch_spatial_order(pos, B, N, order, sorted, grid, xchg, xchg + (size_t)B * FPS_XCHG_WORDS, st);
+    const unsigned* gate = repair ? ctl : nullptr;
+    if (!repair) launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, st);
     if (speculate) {
         constexpr int K = SN2_FPS_K;
         const size_t lds = fps_spec_lds_bytes<SPW, NW, K>();
@@ -1651,9 +1653,9 @@ static int launch_fps_cluster(const float* pos, int B, int N, int M, const int* 
     constexpr int NBL = SPW * NW, NE = FC_TP * P;
     int* order = ws;
     float4* sorted = reinterpret_cast<float4*>(ws + (size_t)B * N);
-    int* grid = ws + (size_t)5 * B * N;
+    int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);
     unsigned* xchg = reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS);
-    unsigned* ctl = xchg + (size_t)B * FPS_XCHG_WORDS;
+    unsigned* ctl = reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N));
     launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, st);
     const int log_cap = M <= 4096 ? M : 0;           // the samples of a plot stay in LDS until the end (16 B each) when they fit
     const size_t lds0 = (size_t)NBL * 16 + 8 * 16 + 2 * (size_t)(NE + 16) * 16 + 2 * FC_TP * 16 + (size_t)NBL * 4 * 9 + 72 * 4 + 8 * 4 + 16 +
@@ -1706,6 +1708,27 @@ static int dispatch_fps_bucket16(const float* pos_soa, int B, int N, int M, cons
     return SN2_ELIMIT;
 }
 
+// Routes (include/strata_hip.h).  Many small plots (the parcel loop's level 2: 256 .. 512 plots of 2 500 points -> 625): the
+// bucketed kernel has 40 buckets to prune among and takes 2 us per sample with 16 waves per plot (1.1 ms at half of every CU's
+// wave slots); the brute-force kernel with the plot's points in the registers of FOUR waves takes the whole plot per round and
+// is shorter.  N <= 131 072: 128 bucket slots per wave, the largest single-workgroup kernel (dispatch_fps_bucket16) -- larger
+// plots are SN2_ELIMIT with or without a workspace: the brute-force kernels that sn2_fps_status falls through to end at
+// 32 768 points.
+static bool fps_many_small(int B, int N) { return N <= 4096 && B > 32; }
+extern "C" int sn2_fps_fills_ws(int B, int N, int M) {
+    return N > 2048 && !fps_many_small(B, N) && M > 16 && ((long)B * N) % 4 == 0 && N <= 131072;
+}
+static bool nn_grid_sources(int S) { return S >= 128 && S <= 8192; }      // what the per-plot x,y grid of three_nn_grid_kernel holds in LDS
+extern "C" int sn2_three_nn_uses_grid(int S, int T) { return nn_grid_sources(S) && T > 2048; }
+
+extern "C" size_t sn2_fps_ws_words(int B, int N) { return (size_t)SN2_FPS_WS_WORDS(B, N); }
+extern "C" size_t sn2_fps_ws_grid_offset(int B, int N) { return (size_t)SN2_FPS_WS_GRID_OFFSET(B, N); }
+extern "C" size_t sn2_fps_ws_ctl_offset(int B, int N) { return (size_t)SN2_FPS_WS_CTL_OFFSET(B, N); }
+extern "C" size_t sn2_fps_ws_rank_offset(int B, int N) { return (size_t)SN2_FPS_WS_RANK_OFFSET(B, N); }
+extern "C" size_t sn2_three_nn_ws_words(int B, int S) { return SN2_THREE_NN_WS_WORDS(B, S); }
+extern "C" size_t sn2_three_nn_xy_ws_words(int B, int S, int T) { return SN2_THREE_NN_XY_WS_WORDS(B, S, T); }
+extern "C" size_t sn2_znorm_ws_words(int n, long cells) { return SN2_ZNORM_WS_WORDS(n, cells); }
+
 extern "C" int sn2_fps_waves(const float* pos_soa, int B, int N, int M, const int* start, int* idx, float* cpos_soa,
                              float* cpos_aos, int* order_ws, int waves, void* stream) {
     return sn2_fps_status(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, order_ws, waves, nullptr, stream);
@@ -1729,12 +1752,7 @@ extern "C" int sn2_fps_status(const float* pos_soa, int B, int N, int M, const i
     }
     const bool spec = waves != 1;      // 1: the one-sample-per-round kernel (round 1's; cross-checks and timing comparisons)
     hipStream_t st = (hipStream_t)stream;
-    // Many small plots (the parcel loop's level 2: 256 .. 512 plots of 2 500 points -> 625): the bucketed kernel has 40 buckets to
-    // prune among and takes 2 us per sample with 16 waves per plot (1.1 ms at half of every CU's wave slots); the brute-force
-    // kernel with the plot's points in the registers of FOUR waves takes the whole plot per round and is shorter.  Mirrored by
-    // hip_ops.fps_fills_ws (no workspace is filled then: the ball query behind it scans the plot).
-    const bool many_small = N <= 4096 && B > 32;
-    if (order_ws && N > 2048 && !many_small && M > 16 && (((size_t)B * N) % 4 == 0) && (((size_t)order_ws) % 16 == 0)) {
+    if (order_ws && (((size_t)order_ws) % 16 == 0) && sn2_fps_fills_ws(B, N, M)) {
         // 32 + P / 64 + P: P = 2, 4 or 8 workgroups of 16 / 8 waves per plot (fps_cluster_kernel); needs at least two buckets
         // per wave and all B * P workgroups resident at once, else the single-workgroup kernel below runs
         if (cluster) {
@@ -1780,7 +1798,7 @@ extern "C" int sn2_fps_status(const float* pos_soa, int B, int N, int M, const i
     if (N <= 512) return launch_fps<2, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
     if (N <= 1024) return launch_fps<4, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
     if (N <= 2048) return launch_fps<2, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 4096 && many_small) return launch_fps<16, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
+    if (fps_many_small(B, N)) return launch_fps<16, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
     if (N <= 4096) return launch_fps<4, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
     if (N <= 8192) return launch_fps<8, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
     if (N <= 16384) return launch_fps<16, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
@@ -2597,7 +2615,7 @@ __global__ __launch_bounds__(NT) void nn_target_sort_chunk_kernel(const float* _
 extern "C" int sn2_three_nn_xy(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
                                void* ws, void* stream) {
     if (!src_soa || !dst_soa || !idx || !w || !ws || B <= 0 || S <= 0 || T <= 0 || k < 1 || k > 3) return SN2_EINVAL;
-    if (S < 128 || S > 8192 || (((size_t)ws) % 16) != 0) return SN2_ELIMIT;
+    if (!nn_grid_sources(S) || (((size_t)ws) % 16) != 0) return SN2_ELIMIT;
     hipStream_t st = (hipStream_t)stream;
     int G = (int)sqrtf((float)S / 4.f);   // about 4 sources per cell
     G = G < 2 ? 2 : (G > NN_GMAX ? NN_GMAX : G);
@@ -2634,7 +2652,7 @@ extern "C" int sn2_three_nn(const float* src_soa, int B, int S, const float* dst
     if (!src_soa || !dst_soa || !idx || !w || B <= 0 || S <= 0 || T <= 0 || k < 1 || k > 3) return SN2_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     // grid search: needs the targets in the spatial order sn2_fps built for them (workspace laid out as there)
-    if (ws && dst_fps_ws && S >= 128 && S <= 8192 && T > 2048 && (((size_t)B * T) % 4 == 0) && (((size_t)ws) % 16 == 0)) {
+    if (ws && dst_fps_ws && sn2_three_nn_uses_grid(S, T) && (((size_t)B * T) % 4 == 0) && (((size_t)ws) % 16 == 0)) {
         int G = (int)sqrtf((float)S / 4.f);   // about 4 sources per cell (2, 3, 8 and 12 per cell measured slower)
         G = G < 2 ? 2 : (G > NN_GMAX ? NN_GMAX : G);
         float4* tbl = reinterpret_cast<float4*>(ws);

@@ -482,6 +482,10 @@ extern "C" int sn2_debug_global_spin_limit(unsigned sweeps) {       // (0 = back
     return 0;
 }
 
+// Routes (include/strata_hip.h): what this launch takes besides the architecture's shapes
+extern "C" int sn2_global_level_forward_route(int B, int bf16) { return B <= GL_MAX_PLOTS && !bf16; }
+extern "C" size_t sn2_global_xchg_words(int B) { return SN2_GLOBAL_XCHG_WORDS(B); }
+
 extern "C" int sn2_global_level_forward(const sn2_fp* sa3, const sn2_fp* fp3, float* x3, int* arg3, unsigned long long* xchg,
                                         unsigned* ctl, void* stream) {
     if (!sa3 || !fp3 || !x3 || !arg3 || !xchg || !ctl) return SN2_EINVAL;
@@ -491,12 +495,12 @@ extern "C" int sn2_global_level_forward(const sn2_fp* sa3, const sn2_fp* fp3, fl
     if (!(sa3->ca == 32 && sa3->cb == 3 && sa3->blk.cin == 35 && sa3->blk.cout == 64 && fp3->ca == 64 && fp3->cb == 32 &&
           fp3->blk.cin == 96 && fp3->blk.cout == 64))
         return SN2_ELIMIT;
-    if (sa3->blk.mma_bf16 || fp3->blk.mma_bf16 || sa3->act_bf16 || fp3->act_bf16) return SN2_ELIMIT;
+    if (!sn2_global_level_forward_route(B, sa3->blk.mma_bf16 || fp3->blk.mma_bf16) || sa3->act_bf16 || fp3->act_bf16) return SN2_ELIMIT;
     if (sa3->knn_idx || sa3->src_a || !fp3->knn_idx || !fp3->knn_w || fp3->src_a) return SN2_EINVAL;
     if (!sa3->src || sa3->src_stride != 32 || !sa3->skip || sa3->skip_stride != 4 || !sa3->h || sa3->h_stride != 64) return SN2_EINVAL;
     if (fp3->src != x3 || fp3->src_stride != 64 || fp3->skip != sa3->src || fp3->skip_stride != 32 || !fp3->h || fp3->h_stride != 64)
         return SN2_EINVAL;
-    if (B > GL_MAX_PLOTS || (long)B * M2 >= (1L << 31) / 64) return SN2_ELIMIT;
+    if ((long)B * M2 >= (1L << 31) / 64) return SN2_ELIMIT;
     for (const sn2_block* k : {&sa3->blk, &fp3->blk})
         if (!k->W || !k->b || !k->gamma || !k->beta || !k->running_mean || !k->running_var || !k->a || !k->c || !k->mean || !k->invstd)
             return SN2_EINVAL;

@@ -519,6 +519,14 @@ __global__ __launch_bounds__(1024) void global_level_bwd_kernel(GbArgs A) {
 
 }  // namespace
 
+// Routes (include/strata_hip.h).  gl_bwd_covers: what the launch takes besides the architecture's shapes (any number of rows per
+// plot); the route of the network's backward is narrower ON PURPOSE: one 64-row block per group of the workgroup is the instance
+// that has been measured against the four separate launches.
+static bool gl_bwd_covers(int B, int frozen, int bf16) { return B <= GL_MAX_PLOTS && !frozen && !bf16; }
+extern "C" int sn2_global_level_backward_route(int B, int M2, int frozen, int bf16) {
+    return gl_bwd_covers(B, frozen, bf16) && M2 <= GL_BWD_MAX_ROWS;
+}
+
 extern "C" int sn2_global_level_backward(const sn2_fp* sa3, const sn2_fp* fp3, const int* arg3, unsigned long long* xchg,
                                          unsigned* ctl, void* stream) {
     if (!sa3 || !fp3 || !arg3 || !xchg || !ctl) return SN2_EINVAL;
@@ -527,7 +535,8 @@ extern "C" int sn2_global_level_backward(const sn2_fp* sa3, const sn2_fp* fp3, c
     if (!(sa3->ca == 32 && sa3->cb == 3 && sa3->blk.cin == 35 && sa3->blk.cout == 64 && fp3->ca == 64 && fp3->cb == 32 &&
           fp3->blk.cin == 96 && fp3->blk.cout == 64))
         return SN2_ELIMIT;
-    if (sa3->blk.mma_bf16 || fp3->blk.mma_bf16 || sa3->act_bf16 || fp3->act_bf16 || sa3->blk.frozen_stats || fp3->blk.frozen_stats)
+    if (!gl_bwd_covers(B, sa3->blk.frozen_stats || fp3->blk.frozen_stats, sa3->blk.mma_bf16 || fp3->blk.mma_bf16) || sa3->act_bf16 ||
+        fp3->act_bf16)
         return SN2_ELIMIT;
     if (sa3->knn_idx || sa3->src_a || !fp3->knn_idx || fp3->src_a) return SN2_EINVAL;
     if (!sa3->src || sa3->src_stride != 32 || !sa3->skip || sa3->skip_stride != 4 || !sa3->h || sa3->h_stride != 64) return SN2_EINVAL;
@@ -540,7 +549,7 @@ extern "C" int sn2_global_level_backward(const sn2_fp* sa3, const sn2_fp* fp3, c
     for (const sn2_block* k : {&sa3->blk, &fp3->blk})
         if (!k->W || !k->gamma || !k->mean || !k->invstd || !k->dW || !k->db || !k->dgamma || !k->dbeta) return SN2_EINVAL;
     // a plot adds its dW | db into an image of its own
-    if (B > GL_MAX_PLOTS || (long)B * M2 >= (1L << 31) / 64) return SN2_ELIMIT;
+    if ((long)B * M2 >= (1L << 31) / 64) return SN2_ELIMIT;
     if (sa3->blk.grad_replicas < B || fp3->blk.grad_replicas < B || sa3->blk.grad_replica_stride != fp3->blk.grad_replica_stride)
         return SN2_ELIMIT;
     GbArgs A;

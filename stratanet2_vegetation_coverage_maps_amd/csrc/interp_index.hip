@@ -280,6 +280,9 @@ int build_interp_index(const int* knn_idx, const float* knn_w, const float* src_
     SN2_RETURN_LAUNCH();
 }
 
+extern "C" size_t sn2_interp_chunks(int R_per_plot, int S_per_plot) { return SN2_INTERP_CHUNKS(R_per_plot, S_per_plot); }
+extern "C" size_t sn2_interp_ws_words(int B, int R_per_plot, int S_per_plot) { return SN2_INTERP_WS_WORDS(B, R_per_plot, S_per_plot); }
+
 extern "C" int sn2_interp_index(const int* knn_idx, const float* knn_w, const float* src_pos, int B, int R_per_plot,
                                 int S_per_plot, float* ws, void* stream) {
     if (!knn_idx || !knn_w || !ws || B <= 0 || R_per_plot <= 0 || S_per_plot <= 0) return SN2_EINVAL;

@@ -186,6 +186,8 @@ __global__ __launch_bounds__(256) void kde_norm_kernel(double* __restrict__ Y, i
 
 }  // namespace
 
+extern "C" size_t sn2_kde_fit_ws_words(int K) { return SN2_KDE_FIT_WS_WORDS(K); }
+
 extern "C" int sn2_kde_fit(const float* z, long n, double bw, int K, void* ws, double* X, double* Y, void* stream) {
     if (!z || !ws || !X || !Y || n <= 0 || K < 2 || !(bw > 0.0) || !(bw <= 1.7e308) || ((uintptr_t)ws & 7)) return SN2_EINVAL;
     if (n > 0x7fffffffL || K > SN2_KDE_FIT_MAX_K) return SN2_ELIMIT;

@@ -13,7 +13,7 @@ namespace {
 
 constexpr int WIDTHS[7] = {16, 16, 32, 64, 64, 34, 34};      // cout of sa1[0], sa1[1], sa2, sa3, fp3, fp2, fp1
 constexpr int WIDTH_SUM = 260;
-constexpr int GRAD_IMAGES = 32;                              // hip_ops.GRAD_IMAGES
+constexpr int GRAD_IMAGES = SN2_NET_GRAD_IMAGES;
 
 // events of a forked geometry pass.  Chain b (level 2): FPS, ball query, work items [b_tables: all SA2 needs] -> the two small
 // 3-NN tables [b_nn: all FP3 / FP2 need] -> their inverted indices [b_done].  Chain c: the per-point 3-NN table [c_nn: all FP1
@@ -23,16 +23,16 @@ struct NetCtx {
     hipEvent_t fork, b_tables, b_nn, b_done, c_nn, c_done, pack_fork, packed;
 };
 
-inline long rows_stat_limit() { return 64L * SN2_STAT_SLOTS; }
-
-inline bool fps_fills_ws(int B, int N, int m) {              // hip_ops.fps_fills_ws == the condition inside sn2_fps_status
-    const bool many_small = N <= 4096 && B > 32;
-    return N > 2048 && !many_small && m > 16 && ((long)B * N) % 4 == 0 && N <= 131072;
+// which kernels a shape takes, hence which workspaces exist: the predicates of the header's "Routes" section, and the model's
+// own settings
+inline bool fp_src_ws_wanted(const sn2_net_model* m, long R, int cb, bool force) {
+    return m->source_side && sn2_fp_source_side(R, cb, force);
 }
-inline bool three_nn_uses_grid(int S, int T) { return S >= 128 && S <= 8192 && T > 2048; }
-inline bool fp_src_ws_wanted(const sn2_net_model* m, long R, int cb, bool force) {   // hip_ops.fp_desc: d._src_ws
-    return m->source_side && cb > 0 && cb <= 16 && cb % 4 == 0 && (R > rows_stat_limit() || force);
+// eval: the per-point layer and the head in one pass (sn2_fp_head_eval), no (B*N,36) rows between them
+inline bool fused_eval_head(const sn2_net_model* m, const sn2_net_dims* d, int training) {
+    return !training && m->fuse_eval_head && !d->act_bf16 && m->source_side;
 }
+inline int gl_bf16(const sn2_net_model* m) { return m->sa3.mma_bf16 || m->fp3.mma_bf16; }
 
 // bump allocator over a caller-owned arena; base == nullptr: the "pointers" are offsets
 struct Carver {
@@ -149,7 +149,7 @@ void fp_desc(sn2_fp* p, const sn2_net_dims* d, const sn2_net_act* a, const FpIn&
     p->knn_idx = in.knn_idx, p->knn_w = in.knn_w;
     p->skip = in.cb > 0 ? in.skip : nullptr, p->skip_stride = in.cb > 0 ? in.skip_stride : 0;
     fill_block(&p->blk, in.L, in.k, a, gd);
-    if ((long)d->B * in.Rp > rows_stat_limit()) p->blk.mma_bf16 = 0;       // no bfloat16 kernel for that many rows
+    if (!sn2_fp_rows_small((long)d->B * in.Rp)) p->blk.mma_bf16 = 0;       // no bfloat16 kernel for that many rows
     p->h = static_cast<float*>(in.h), p->h_stride = (in.L->cout + 3) / 4 * 4;
     p->src_ws = in.src_ws;
     p->act_bf16 = in.act_bf16;
@@ -243,13 +243,13 @@ int check_geo(const sn2_net_dims* d, const sn2_net_geo* g) {
     return 0;
 }
 int check_geo_workspaces(const sn2_net_dims* d, const sn2_net_geo* g) {     // what only the geometry pass itself needs
-    if (three_nn_uses_grid(d->M2, d->M1) && !g->nn_ws2) return SN2_EINVAL;
-    if (three_nn_uses_grid(d->M1, d->N) && !g->nn_ws1) return SN2_EINVAL;
+    if (sn2_three_nn_uses_grid(d->M2, d->M1) && !g->nn_ws2) return SN2_EINVAL;
+    if (sn2_three_nn_uses_grid(d->M1, d->N) && !g->nn_ws1) return SN2_EINVAL;
     return 0;
 }
 
 int three_nn_any(const float* src, int B, int S, const float* dst, int T, int k, int* idx, float* w, int* ws, void* st) {
-    if (three_nn_uses_grid(S, T)) return sn2_three_nn_xy(src, B, S, dst, T, k, idx, w, ws, st);
+    if (sn2_three_nn_uses_grid(S, T)) return sn2_three_nn_xy(src, B, S, dst, T, k, idx, w, ws, st);
     return sn2_three_nn(src, B, S, dst, T, k, idx, w, nullptr, nullptr, st);
 }
 
@@ -262,8 +262,8 @@ int geometry_impl(const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_g
     const bool inverted = flags & SN2_NET_INVERTED;
     const int* start0 = io->fps_start;
     const int* start1 = io->fps_start ? io->fps_start + B : nullptr;
-    int* ws1 = fps_fills_ws(B, N, M1) ? g->ws1 : nullptr;
-    int* ws2 = fps_fills_ws(B, M1, M2) ? g->ws2 : nullptr;
+    int* ws1 = sn2_fps_fills_ws(B, N, M1) ? g->ws1 : nullptr;
+    int* ws2 = sn2_fps_fills_ws(B, M1, M2) ? g->ws2 : nullptr;
     int waves = 0;
     if (flags & SN2_NET_SHARED) waves = B > 32 ? m->fps_waves_many : m->fps_waves_shared;
     SN2_TRY(sn2_fps_status(g->xyz, B, N, M1, start0, g->idx1, g->pos1_soa, g->pos1_aos, ws1, waves, io->fps_status, cur));
@@ -352,11 +352,11 @@ extern "C" int sn2_net_geo_carve(const sn2_net_model* m, const sn2_net_dims* d, 
     memset(g, 0, sizeof(*g));
     Carver c(base);
     g->idx1 = c.take<int>(B * M1), g->pos1_soa = c.take<float>(B * 3 * M1), g->pos1_aos = c.take<float>(B * M1 * 4);
-    g->ws1 = fps_fills_ws(d->B, d->N, d->M1) ? c.take<int>((size_t)SN2_FPS_WS_WORDS(B, N)) : nullptr;
+    g->ws1 = sn2_fps_fills_ws(d->B, d->N, d->M1) ? c.take<int>((size_t)SN2_FPS_WS_WORDS(B, N)) : nullptr;
     g->nbr1 = c.take<int>(B * M1 * (size_t)d->cap1), g->cnt1 = c.take<int>(B * M1);
     g->tot1 = c.take<unsigned long long>(1), g->ord1 = c.take<int>(SN2_SA_ORDER_WORDS(B, M1));
     g->idx2 = c.take<int>(B * M2), g->pos2_soa = c.take<float>(B * 3 * M2), g->pos2_aos = c.take<float>(B * M2 * 4);
-    g->ws2 = fps_fills_ws(d->B, d->M1, d->M2) ? c.take<int>((size_t)SN2_FPS_WS_WORDS(B, M1)) : nullptr;
+    g->ws2 = sn2_fps_fills_ws(d->B, d->M1, d->M2) ? c.take<int>((size_t)SN2_FPS_WS_WORDS(B, M1)) : nullptr;
     g->nbr2 = c.take<int>(B * M2 * (size_t)d->cap2), g->cnt2 = c.take<int>(B * M2);
     g->tot2 = c.take<unsigned long long>(1), g->ord2 = c.take<int>(SN2_SA_ORDER_WORDS(B, M2));
     g->knn3_idx = c.take<int>(B * M2 * 3), g->knn3_w = c.take<float>(B * M2 * 3);
@@ -365,8 +365,8 @@ extern "C" int sn2_net_geo_carve(const sn2_net_model* m, const sn2_net_dims* d, 
     g->inv3 = c.take<float>(SN2_INTERP_WS_WORDS(B, M2, 1));
     g->inv2 = c.take<float>(SN2_INTERP_WS_WORDS(B, M1, M2));
     g->inv1 = c.take<float>(SN2_INTERP_WS_WORDS(B, N, M1));
-    g->nn_ws2 = three_nn_uses_grid(d->M2, d->M1) ? c.take<int>(SN2_THREE_NN_XY_WS_WORDS(B, M2, M1)) : nullptr;
-    g->nn_ws1 = three_nn_uses_grid(d->M1, d->N) ? c.take<int>(SN2_THREE_NN_XY_WS_WORDS(B, M1, N)) : nullptr;
+    g->nn_ws2 = sn2_three_nn_uses_grid(d->M2, d->M1) ? c.take<int>(SN2_THREE_NN_XY_WS_WORDS(B, M2, M1)) : nullptr;
+    g->nn_ws1 = sn2_three_nn_uses_grid(d->M1, d->N) ? c.take<int>(SN2_THREE_NN_XY_WS_WORDS(B, M1, N)) : nullptr;
     g->rows0 = c.take<float>(B * N * 12);
     if (d->p2_diam_pix > 0) g->p2_pix = c.take<int>(B * N), g->p2_mm = c.take<float>(B * 4);
     // xyz, pos3 (a constant zero vector) and rank1 (a view of ws1) are the caller's
@@ -387,7 +387,7 @@ extern "C" int sn2_net_act_carve(const sn2_net_model* m, const sn2_net_dims* d, 
     a->h_sa3 = c.take<float>(B * M2 * 64), a->h3 = c.take<float>(B * M2 * 64);
     a->x3 = c.take<float>(B * 64), a->arg3 = c.take<int>(B * 64);
     a->h2 = c.take<float>(B * M1 * 36);
-    const bool fused_eval = !training && m->fuse_eval_head && !d->act_bf16 && m->source_side;
+    const bool fused_eval = fused_eval_head(m, d, training);
     if (!fused_eval) a->h1 = d->act_bf16 ? (void*)c.take<unsigned short>(B * N * 36) : (void*)c.take<float>(B * N * 36);
     if (fp_src_ws_wanted(m, (long)B * N, 8, fused_eval)) a->src_ws1 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, N, M1, 34));
     if (fp_src_ws_wanted(m, (long)B * M1, 16, false)) a->src_ws2 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, M1, M2, 34));
@@ -457,7 +457,7 @@ extern "C" int sn2_net_forward(const sn2_net_model* m, const sn2_net_dims* d, co
     const int B = d->B, N = d->N, M2 = d->M2;
     hipStream_t cur = (hipStream_t)stream;
     NetCtx* ctx = static_cast<NetCtx*>(io->ctx);
-    const bool fused_eval = !training && m->fuse_eval_head && !d->act_bf16 && m->source_side;
+    const bool fused_eval = fused_eval_head(m, d, training);
     if (!fused_eval && !a->h1) return SN2_EINVAL;
     if (training && !(g->inv1 && g->inv2 && g->inv3)) return SN2_EINVAL;
     const GradDst nograd{nullptr, 0, 0};
@@ -515,8 +515,7 @@ extern "C" int sn2_net_forward(const sn2_net_model* m, const sn2_net_dims* d, co
     sn2_fp p3, pf3;
     fp_desc(&p3, d, a, sa3_in(m, d, g, a), nograd);
     fp_desc(&pf3, d, a, fp3_in(m, d, g, a), nograd);
-    if (batch_stats && m->fuse_global_level && io->gl_xchg && io->gl_ctl && B <= GL_MAX_PLOTS && !m->sa3.mma_bf16 &&
-        !m->fp3.mma_bf16) {
+    if (batch_stats && m->fuse_global_level && io->gl_xchg && io->gl_ctl && sn2_global_level_forward_route(B, gl_bf16(m))) {
         SN2_TRY(sn2_global_level_forward(&p3, &pf3, a->x3, a->arg3, io->gl_xchg, io->gl_ctl, cur));
     } else {
         SN2_TRY(sn2_fp_forward(&p3, mode, cur));
@@ -603,8 +602,7 @@ extern "C" int sn2_net_backward(const sn2_net_model* m, const sn2_net_dims* d, c
     pf3.dy = b->dy3, pf3.dsrc = b->dx3, pf3.dsrc_stride = 64, pf3.dskip = b->dx2, pf3.dskip_stride = 32;
     fp_desc(&p3, d, a, sa3_in(m, d, g, a), gd);
     p3.dsrc = b->dx2, p3.dsrc_stride = 32;
-    if (m->fuse_global_level && !b->frozen_stats && b->gl_xchg && b->gl_ctl && B <= GL_MAX_PLOTS && M2 <= GL_BWD_MAX_ROWS &&
-        !m->sa3.mma_bf16 && !m->fp3.mma_bf16) {
+    if (m->fuse_global_level && b->gl_xchg && b->gl_ctl && sn2_global_level_backward_route(B, M2, b->frozen_stats, gl_bf16(m))) {
         // FP3's BatchNorm sums, FP3, the pool between FP3 and SA3, SA3's BatchNorm sums and SA3 in one launch
         SN2_TRY(sn2_global_level_backward(&p3, &pf3, a->arg3, b->gl_xchg, b->gl_ctl, cur));
     } else {

@@ -287,6 +287,8 @@ extern "C" int sn2_plot_project_forward(const float* pred_pointwise, const float
     SN2_RETURN_LAUNCH();
 }
 
+extern "C" size_t sn2_p2_key_parts(int N) { return (size_t)SN2_P2_KEY_PARTS(N); }
+
 extern "C" int sn2_plot_pixels(const float* cloud_xy, long plot_stride, int B, int N, int D, float* mm, int* pix, void* stream) {
     if (!cloud_xy || !mm || !pix || B <= 0 || N <= 0 || D <= 0) return SN2_EINVAL;
     if (D * D > MAX_CELLS || plot_stride < 2L * N) return SN2_ELIMIT;

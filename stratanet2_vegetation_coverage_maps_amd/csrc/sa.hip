@@ -254,6 +254,8 @@ __global__ __launch_bounds__(1024) void sa_order_sort_kernel(const int* __restri
 }  // namespace
 
 static int sa_order_impl(const int* cnt, int G, int B, int M, int* order, size_t stride, hipStream_t st);
+extern "C" size_t sn2_sa_order_words(int B, int M) { return SN2_SA_ORDER_WORDS(B, M); }
+
 extern "C" int sn2_sa_order(const int* cnt, int B, int M, int* order, void* stream) {
     if (!cnt || !order || B <= 0 || M <= 0) return SN2_EINVAL;
     return sa_order_impl(cnt, 1, B, M, order, SN2_SA_ORDER_WORDS(B, M), (hipStream_t)stream);

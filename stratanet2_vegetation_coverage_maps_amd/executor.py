@@ -50,7 +50,7 @@ def _act_shapes(B, N, M1, M2, act_bf16):
         "ext2": (F32, (B * M2, 32)), "arg2": (I32, (B * M2, 32)), "x2": (F32, (B * M2, 32)),
         "h_sa3": (F32, (B * M2, 64)), "h3": (F32, (B * M2, 64)), "x3": (F32, (B, 64)), "arg3": (I32, (B, 64)),
         "h2": (F32, (B * M1, 36)), "h1": (BF16 if act_bf16 else F32, (B * N, 36)),
-        "src_ws1": (F32, (B * ops.interp_chunks(N, M1) * 36,)), "src_ws2": (F32, (B * ops.interp_chunks(M1, M2) * 36,)),
+        "src_ws1": (F32, (ops.fp_src_ws_words(B, N, M1, 34),)), "src_ws2": (F32, (ops.fp_src_ws_words(B, M1, M2, 34),)),
     }
 
 
@@ -98,6 +98,10 @@ class Plan:
         b = NetBwd()
         _lib.check(lib.sn2_net_bwd_carve(byref(ms), byref(d), _FAKE_BASE, _FAKE_BASE, byref(b), byref(sz), byref(sz2)), "sn2_net_bwd_carve")
         self.bwd_arena_words, self.bwd_scratch_bytes = int(sz.value) // 4, int(sz2.value)
+        # the one-launch global level, where the model's setting and the pass's BatchNorm mode allow it (the routes of
+        # sn2_net_forward / sn2_net_backward: asked once per plan, not per step)
+        self.gl_forward = ops.global_level_forward_fused(B, ms.sa3, ms.fp3)
+        self.gl_backward = ops.global_level_backward_fused(B, M2, False, ms.sa3, ms.fp3)
 
 
 _ZEROS = {}
@@ -415,7 +419,7 @@ def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None
         bwd_arena = torch.empty(plan.bwd_arena_words, dtype=F32, device=dev)
         ca.bwd_arena, ca.bwd_arena_words = bwd_arena.data_ptr(), plan.bwd_arena_words
     io = _io(model, dev, mode, flags, cloud=cloud, fps_start=fs, fork=fork)
-    if training and model.fuse_global_level:
+    if training and model.fuse_global_level and plan.gl_forward:
         ws = ops.global_level_ws(dev, owner=model)
         io.gl_xchg, io.gl_ctl = ws[0].data_ptr(), ws[1].data_ptr()
     _lib.check(lib.sn2_net_forward(byref(ms.c), byref(plan.dims), byref(cg), byref(ca), byref(io), ops._stream()), "sn2_net_forward")
@@ -457,7 +461,7 @@ def backward(model, s, dcov, dproba):
     cb.defer_grad_reduce = int(defer)
     cb.arena_is_zero = int(pre_zeroed)
     cb.frozen_stats = int(bool(s.__dict__.get("frozen", False)))
-    if model.fuse_global_level and not cb.frozen_stats and plan.B <= ops.GL_MAX_PLOTS and plan.dims.M2 <= ops.GL_BWD_MAX_ROWS:
+    if model.fuse_global_level and not cb.frozen_stats and plan.gl_backward:
         ws = ops.global_level_ws(dev, owner=model)
         cb.gl_xchg, cb.gl_ctl = ws[3].data_ptr(), ws[4].data_ptr()
     _lib.check(lib.sn2_net_backward(byref(ms.c), byref(plan.dims), byref(geo_struct(s.geo)), byref(s.cact), byref(cb), ops._stream()),

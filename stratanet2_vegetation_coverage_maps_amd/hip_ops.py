@@ -298,29 +298,37 @@ def pack_rows(cloud: torch.Tensor, xyz: torch.Tensor, out: Optional[torch.Tensor
     return rows0
 
 
+_host = _lib.host_value      # route predicates and size helpers of the library, remembered per argument tuple
+
+
 def fps_ws_words(B: int, N: int) -> int:
     """SN2_FPS_WS_WORDS of include/strata_hip.h."""
-    return 6 * B * N + (4104 + 4096) * B + 32
+    return _host("sn2_fps_ws_words", int(B), int(N))
+
+
+def fps_ws_grid(ws: torch.Tensor, B: int, N: int) -> torch.Tensor:
+    """The B cell-grid headers of a filled FPS workspace (cell starts, bounding boxes, pad words)."""
+    o = _host("sn2_fps_ws_grid_offset", int(B), int(N))
+    return ws[o:o + _lib.SN2_FPS_WS_GRID_WORDS * B]
 
 
 def fps_ws_ctl(ws: torch.Tensor, B: int, N: int) -> torch.Tensor:
     """The 32 control words of a filled FPS workspace ([1] = exchange waits of the multi-workgroup kernel that gave up in the LAST
     pass over this workspace; the process-wide running total is `fps_gave_up`)."""
-    o = 5 * B * N + (4104 + 4096) * B
-    return ws[o:o + 32]
+    o = _host("sn2_fps_ws_ctl_offset", int(B), int(N))
+    return ws[o:o + _lib.SN2_FPS_WS_CTL_WORDS]
 
 
 def fps_ws_rank(ws: torch.Tensor, B: int, N: int) -> torch.Tensor:
     """The (B*N) int32 view of a filled FPS workspace that holds every point's position in the plot's spatial (Morton) order."""
-    return ws[5 * B * N + (4104 + 4096) * B + 32:]
+    return ws[_host("sn2_fps_ws_rank_offset", int(B), int(N)):]
 
 
 def fps_fills_ws(B: int, N: int, m: int) -> bool:
     """Whether sn2_fps takes its bucketed path for these sizes, i.e. FILLS the workspace (Morton order, sorted table, cell
-    starts) that ball_query / three_nn may then walk.  Must mirror the condition in csrc/geometry.hip (sn2_fps): handing
-    those kernels a workspace nobody filled would send them through garbage cell lists."""
-    many_small = N <= 4096 and B > 32          # sn2_fps_status: many small plots take the brute-force kernel (no tables)
-    return N > 2048 and not many_small and m > 16 and (B * N) % 4 == 0 and N <= 131072
+    starts) that ball_query / three_nn may then walk (sn2_fps_fills_ws, the test sn2_fps_status itself makes): handing those
+    kernels a workspace nobody filled would send them through garbage cell lists."""
+    return bool(_host("sn2_fps_fills_ws", int(B), int(N), int(m)))
 
 
 _FPS_STATUS = {}          # device index -> [status word (1,) int32 on the device, count already reported]
@@ -452,19 +460,19 @@ def count_sum_group(cnt: torch.Tensor, G: int, n: int, totals: torch.Tensor, str
 
 def three_nn_ws_words(B: int, S: int, T: int = 0) -> int:
     """SN2_THREE_NN_XY_WS_WORDS (T > 0) / SN2_THREE_NN_WS_WORDS (T = 0) of include/strata_hip.h."""
-    return B * (4 * S + 5 * T + 1032)
+    return _host("sn2_three_nn_xy_ws_words", int(B), int(S), int(T)) if T else _host("sn2_three_nn_ws_words", int(B), int(S))
 
 
 def three_nn_uses_grid(S: int, T: int) -> bool:
-    """The grid search of sn2_three_nn_xy applies (otherwise the full scan runs)."""
-    return 128 <= S <= 8192 and T > 2048
+    """The grid search of sn2_three_nn_xy applies (otherwise the full scan runs): sn2_three_nn_uses_grid."""
+    return bool(_host("sn2_three_nn_uses_grid", int(S), int(T)))
 
 
 def three_nn(src_soa: torch.Tensor, dst_soa: torch.Tensor, k: int, out=None, grid: bool = True, ws=None,
              dst_fps_ws: Optional[torch.Tensor] = None):
     """-> idx (B*T,3) int32 local source indices, w (B*T,3) = 1/max(d2,1e-16) (0 on unused slots).
     out = (idx, w): caller-owned result buffers.
-    grid=True: for T > 2048 targets and 128..8192 sources the search walks a per-plot x,y grid of the sources, a wave taking
+    grid=True: where `three_nn_uses_grid(S, T)` the search walks a per-plot x,y grid of the sources, a wave taking
     64 targets of adjacent grid cells (sn2_three_nn_xy sorts the targets by cell itself; same result as the full scan, bit
     for bit); ws: caller-owned workspace of three_nn_ws_words(B, S, T) int32 for it (allocated here when None).
     dst_fps_ws (with grid=True): use the order `fps(..., return_ws=True)` left for the TARGET points instead of the
@@ -587,8 +595,8 @@ def prepare_plots(raw, offsets, centers, fake_xy, idx, z_max: float, rot=None, f
     return cloud, xyz
 
 
-SUBSAMPLE_LDS, SUBSAMPLE_GLOBAL, SUBSAMPLE_COARSE = 1, 2, 4      # SN2_SUBSAMPLE_* of include/strata_hip.h
-SUBSAMPLE_LDS_MAX = 16384                                        # SN2_SUBSAMPLE_LDS_MAX
+SUBSAMPLE_LDS, SUBSAMPLE_GLOBAL, SUBSAMPLE_COARSE = _lib.SN2_SUBSAMPLE_LDS, _lib.SN2_SUBSAMPLE_GLOBAL, _lib.SN2_SUBSAMPLE_COARSE
+SUBSAMPLE_LDS_MAX = _lib.SN2_SUBSAMPLE_LDS_MAX
 
 
 def subsample_form(n_max: int, N: int) -> int:
@@ -644,7 +652,7 @@ def znorm(xyz: torch.Tensor, radius: float):
     lo = xyz[:2].min(1).values.tolist()          # the caller usually has the bounding box already; here one small sync
     hi = xyz[:2].max(1).values.tolist()
     cells = (int((hi[0] - lo[0]) / radius) + 2) * (int((hi[1] - lo[1]) / radius) + 2)
-    ws = torch.empty(5 * n + 3 * cells + 8, dtype=I32, device=xyz.device)
+    ws = torch.empty(_host("sn2_znorm_ws_words", n, cells), dtype=I32, device=xyz.device)
     zmin = torch.empty(n, dtype=F32, device=xyz.device)
     zout = torch.empty(n, dtype=F32, device=xyz.device)
     _call("sn2_znorm", _ptr(xyz[0]), _ptr(xyz[1]), _ptr(xyz[2]), n, float(radius), lo[0], lo[1], hi[0], hi[1], _ptr(ws),
@@ -735,7 +743,7 @@ def parcel_znorm(cloud: torch.Tensor, bbox, radius: float, disc_radius: float, o
 
 def sa_order_len(B: int, M: int) -> int:
     """SN2_SA_ORDER_WORDS of include/strata_hip.h."""
-    return 4 * B * M + 16 * B * (M // 8 + 2) + 8
+    return _host("sn2_sa_order_words", int(B), int(M))
 
 
 def sa_order(cnt: torch.Tensor, B: int, M: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -762,7 +770,7 @@ def sa_order_group(cnt: torch.Tensor, G: int, B: int, M: int, out_all: torch.Ten
     _call("sn2_sa_order_group", _ptr(cnt), G, B, M, _ptr(out_all), stride, _stream(), key="sn2_sa_order")
 
 
-SA_BWD_WS_WORDS = 32 * 2 * 16 * 12         # SN2_SA_BWD_WS_WORDS of include/strata_hip.h
+SA_BWD_WS_WORDS = _lib.SN2_SA_BWD_WS_WORDS
 
 
 def sa_desc(blocks, feat, cf, spos, cpos_aos, nbr, cnt, total, B, Nsrc, M, ext, arg, out, dout=None, dfeat=None,
@@ -811,13 +819,27 @@ def sa_backward(d: SA):
 
 def interp_ws_words(B: int, R_per_plot: int, S_per_plot: int) -> int:
     """SN2_INTERP_WS_WORDS of include/strata_hip.h."""
-    return (B * S_per_plot * ((R_per_plot + 2047) // 2048 + 6) + 6 * B * R_per_plot + 64
-            + 4 * B * interp_chunks(R_per_plot, S_per_plot))
+    return _host("sn2_interp_ws_words", int(B), int(R_per_plot), int(S_per_plot))
 
 
 def interp_chunks(R_per_plot: int, S_per_plot: int) -> int:
     """SN2_INTERP_CHUNKS of include/strata_hip.h: slots of the per-plot chunk table of an inverted index."""
-    return (3 * R_per_plot + 62) // 63 + S_per_plot
+    return _host("sn2_interp_chunks", int(R_per_plot), int(S_per_plot))
+
+
+def fp_src_ws_words(B: int, R_per_plot: int, S_per_plot: int, cout: int) -> int:
+    """SN2_FP_SRC_WS_WORDS of include/strata_hip.h: floats of the source-side workspace of a dense-row block (sn2_fp.src_ws)."""
+    return _host("sn2_fp_src_ws_words", int(B), int(R_per_plot), int(S_per_plot), int(cout))
+
+
+def fp_rows_small(R: int) -> bool:
+    """sn2_fp_rows_small: a training pass over R rows takes the 64-row matrix-core kernels, the only ones with bfloat16 operands."""
+    return bool(_host("sn2_fp_rows_small", int(R)))
+
+
+def fp_source_side(R: int, cb: int, force: bool = False) -> bool:
+    """sn2_fp_source_side: a k-NN block of R rows with cb skip channels takes the source-side form where it is handed a workspace."""
+    return bool(_host("sn2_fp_source_side", int(R), int(cb), int(bool(force))))
 
 
 def interp_index(knn, B: int, R_per_plot: int, S_per_plot: int, out: Optional[torch.Tensor] = None,
@@ -870,8 +892,8 @@ def fp_desc(block: BlockBuffers, B, R_per_plot, S_per_plot, ca, cb, src, h, src_
             bn_sums_done=None, row_perm=None, force_src_ws=False, gather=True) -> FP:
     """src: (B*S_per_plot, >=ca) rows when knn is given, else (B*R_per_plot, >=ca); skip: (B*R_per_plot, >=cb) row view.
     h of dtype bfloat16 (then dy and du_scratch too): the per-point layer stores its three activation buffers in bfloat16
-    (include/strata_hip.h: sn2_fp.act_bf16; BASELINE config 5) -- only the source-side form of a layer of more than
-    64 * SN2_STAT_SLOTS rows has those kernels."""
+    (include/strata_hip.h: sn2_fp.act_bf16; BASELINE config 5) -- only the source-side form (`fp_source_side`) has those
+    kernels."""
     R = B * R_per_plot
     hs = (block.cout + 3) // 4 * 4
     AT = BF16 if (h is not None and h.dtype == BF16) else F32         # the storage type of h / dy / du_scratch
@@ -902,8 +924,8 @@ def fp_desc(block: BlockBuffers, B, R_per_plot, S_per_plot, ca, cb, src, h, src_
     else:
         d.skip, d.skip_stride = None, 0
     block.fill(d.blk, with_grads)
-    if R > 64 * _lib.STAT_SLOTS:
-        # bfloat16 operands exist on the matrix-core kernels of the layers over centroids (<= 64 * SN2_STAT_SLOTS rows);
+    if not fp_rows_small(R):
+        # bfloat16 operands exist on the matrix-core kernels of the layers over centroids only;
         # a block with more rows (FP2 at the reference's default ratio1 = 0.5: 262 144 rows) runs its fp32 row kernels
         d.blk.mma_bf16 = 0
     d.h, d.h_stride = _ptr(h), hs
@@ -920,8 +942,8 @@ def fp_desc(block: BlockBuffers, B, R_per_plot, S_per_plot, ca, cb, src, h, src_
     d.bn_sums_done = _ptr(bn_sums_done)
     # source-side workspace of the per-point layer (include/strata_hip.h: src_ws); scratch, so one per descriptor
     d._src_ws = None
-    if SOURCE_SIDE and knn is not None and 0 < cb <= 16 and cb % 4 == 0 and (R > 64 * _lib.STAT_SLOTS or force_src_ws):
-        d._src_ws = torch.empty(B * interp_chunks(R_per_plot, S_per_plot) * hs, dtype=F32, device=src.device)
+    if SOURCE_SIDE and knn is not None and fp_source_side(R, cb, force_src_ws):
+        d._src_ws = torch.empty(fp_src_ws_words(B, R_per_plot, S_per_plot, block.cout), dtype=F32, device=src.device)
     d.src_ws = _ptr(d._src_ws)
     d.row_perm = None
     if row_perm is not None and d._src_ws is not None and du_scratch is not None:
@@ -931,7 +953,7 @@ def fp_desc(block: BlockBuffers, B, R_per_plot, S_per_plot, ca, cb, src, h, src_
         d.row_perm = _ptr(row_perm)
     d.act_bf16 = int(AT == BF16)
     if d.act_bf16 and d._src_ws is None:
-        raise ValueError("fp: bfloat16 activation rows need the source-side form (a k-NN layer of more than 65 536 rows)")
+        raise ValueError("fp: bfloat16 activation rows need the source-side form (hip_ops.fp_source_side)")
     if du_scratch is not None:
         _chk(du_scratch, AT, (R, max(ca, hs)), "du_scratch")
         if knn is not None and dsrc is not None:
@@ -978,7 +1000,7 @@ def plot_max_forward(h, a, c, B, R_per_plot, C):
     return out, arg
 
 
-GL_MAX_PLOTS = 28        # sn2_global_level_forward's limit (csrc/common.h: GL_MAX_PLOTS)
+GL_MAX_PLOTS = _lib.SN2_GLOBAL_MAX_PLOTS        # sn2_global_level_forward's and _backward's limit
 _GLOBAL_WS = {}          # device index -> workspace of callers that name no owner
 _GLOBAL_WS_ALL = []      # weak references to every live workspace (global_level_gave_up looks at all of them)
 
@@ -993,8 +1015,8 @@ def global_level_ws(dev, B: int = GL_MAX_PLOTS, owner=None):
     its own), zero-filled once, then the library's.
     owner: the object whose training forwards use it (a PointNet2): the workspace lives on it, so two models that train on two
     streams of one process never share an exchange area; without an owner there is one per device.  Launches that share a
-    workspace must be on one stream at a time.  Allocated ONCE at the largest size the kernels take (28 plots: 229 KB for the
-    forward's granules, 57 KB for the backward's, 8 + 64 control words) and
+    workspace must be on one stream at a time.  Allocated ONCE at the largest size the kernels take (GL_MAX_PLOTS plots: 229 KB
+    for the forward's granules, 57 KB for the backward's, 8 + 64 control words) and
     never again: hipGraphs captured earlier hold its raw address and its launch epoch (round 4 reallocated it when a later call
     had more plots, under the feet of the graphs captured before)."""
     dev = torch.device(dev)
@@ -1008,13 +1030,21 @@ def global_level_ws(dev, B: int = GL_MAX_PLOTS, owner=None):
             # zero fills captured into a graph would run at every replay and reset the launch epoch under the other graphs
             raise StrataHipError("global_level_forward: its exchange area must exist before a stream capture starts -- run one "
                                  "eager training forward first (TrainPipeline.capture does) or call hip_ops.global_level_ws(dev, owner=model)")
-        ws = _GlobalWs([torch.zeros(2 * GL_MAX_PLOTS * 4 * 128, dtype=I64, device=dev), torch.zeros(8, dtype=I32, device=dev), 0,
-                        torch.zeros(2 * GL_MAX_PLOTS * 128, dtype=I64, device=dev), torch.zeros(64, dtype=I32, device=dev)])
+        ws = _GlobalWs([torch.zeros(_host("sn2_global_xchg_words", GL_MAX_PLOTS), dtype=I64, device=dev),
+                        torch.zeros(_lib.SN2_GLOBAL_CTL_WORDS, dtype=I32, device=dev), 0,
+                        torch.zeros(_lib.SN2_GLOBAL_BWD_XCHG_WORDS, dtype=I64, device=dev),
+                        torch.zeros(_lib.SN2_GLOBAL_BWD_CTL_WORDS, dtype=I32, device=dev)])
         store[key] = ws
         import weakref
         _GLOBAL_WS_ALL[:] = [r for r in _GLOBAL_WS_ALL if r() is not None]
         _GLOBAL_WS_ALL.append(weakref.ref(ws))
     return ws
+
+
+def global_level_forward_fused(B: int, *blocks) -> bool:
+    """Does a training forward of the global level take `global_level_forward`?  (sn2_global_level_forward_route, the rule of
+    sn2_net_forward: at most GL_MAX_PLOTS plots and fp32 operands in `blocks`; the caller ANDs in its own setting.)"""
+    return bool(_host("sn2_global_level_forward_route", int(B), int(any(b.mma_bf16 for b in blocks))))
 
 
 def global_level_forward(d_sa3: FP, d_fp3: FP, x3: torch.Tensor, arg3: torch.Tensor, owner=None):
@@ -1027,14 +1057,15 @@ def global_level_forward(d_sa3: FP, d_fp3: FP, x3: torch.Tensor, arg3: torch.Ten
     _call("sn2_global_level_forward", d_sa3, d_fp3, _ptr(x3), _ptr(arg3), _ptr(ws[0]), _ptr(ws[1]), _stream())
 
 
-GL_BWD_MAX_ROWS = 256    # csrc/common.h: GL_BWD_MAX_ROWS
+GL_BWD_MAX_ROWS = _lib.SN2_GLOBAL_BWD_MAX_ROWS
 
 
 def global_level_backward_fused(B: int, M2: int, frozen: bool, *blocks) -> bool:
-    """Does the backward of the global level take `global_level_backward`?  (The same rule as sn2_net_backward, csrc/net.hip:
-    at most 28 plots, batch statistics, fp32 operands, and at most 256 rows per plot -- the one-block-per-group instance of the
-    kernel, the one measured against the four launches; the entry point itself takes more rows.)"""
-    return B <= GL_MAX_PLOTS and M2 <= GL_BWD_MAX_ROWS and not frozen and not any(b.mma_bf16 for b in blocks)
+    """Does the backward of the global level take `global_level_backward`?  (sn2_global_level_backward_route, the rule of
+    sn2_net_backward: at most GL_MAX_PLOTS plots, batch statistics, fp32 operands, and at most GL_BWD_MAX_ROWS rows per plot --
+    the one-block-per-group instance of the kernel, the one measured against the four launches; the entry point itself takes
+    more rows.)"""
+    return bool(_host("sn2_global_level_backward_route", int(B), int(M2), int(bool(frozen)), int(any(b.mma_bf16 for b in blocks))))
 
 
 def global_level_backward(d_sa3: FP, d_fp3: FP, arg3: torch.Tensor, owner=None):
@@ -1149,7 +1180,7 @@ def head_desc(f, fa, fc, lin1, lin2, coverages=None, proba=None, dcov=None, dpro
     return d
 
 
-GRAD_IMAGES = 32       # images of the flat parameter gradient the backward kernels spread their atomics over
+GRAD_IMAGES = _lib.SN2_NET_GRAD_IMAGES       # images of the flat parameter gradient the backward kernels spread their atomics over
 
 
 def flat_layout(params):
@@ -1229,7 +1260,7 @@ def plot_project_forward(pred_pointwise: torch.Tensor, clouds_dev: torch.Tensor,
 
 def p2_key_parts(N: int) -> int:
     """SN2_P2_KEY_PARTS of include/strata_hip.h."""
-    return max(1, min(64, (N + 4095) // 4096))
+    return _host("sn2_p2_key_parts", int(N))
 
 
 def plot_pixels(clouds_dev: torch.Tensor, diam_pix: int, out=None):
@@ -1310,7 +1341,7 @@ def mosaic_finalize(mean: torch.Tensor, wsum: torch.Tensor):
     _chk(mean, F32, (3, H, W), "mean")
     _chk(wsum, F32, (H, W), "wsum")
     dev = mean.device
-    hist = torch.empty(10004, dtype=I32, device=dev)
+    hist = torch.empty(_lib.SN2_MOSAIC_HIST_WORDS, dtype=I32, device=dev)
     acc = torch.empty(1, dtype=F64, device=dev)
     thr = torch.empty(2, dtype=F32, device=dev)
     out = torch.empty(5, H, W, dtype=F32, device=dev)
@@ -1318,7 +1349,7 @@ def mosaic_finalize(mean: torch.Tensor, wsum: torch.Tensor):
     return out, thr
 
 
-LOSS_BLOCKS = 1024
+LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS
 
 
 def kde_lookup(clouds_dev: torch.Tensor, z_max: float, X: torch.Tensor, Y: torch.Tensor, z_channel: int = 2) -> torch.Tensor:
@@ -1335,13 +1366,12 @@ def kde_lookup(clouds_dev: torch.Tensor, z_max: float, X: torch.Tensor, Y: torch
     return pdf
 
 
-KDE_FIT_MAX_K = 65536                                            # SN2_KDE_FIT_MAX_K
+KDE_FIT_MAX_K = _lib.SN2_KDE_FIT_MAX_K
 
 
 def kde_fit_ws_words(K: int) -> int:
     """SN2_KDE_FIT_WS_WORDS of include/strata_hip.h (32-bit words)."""
-    K = max(int(K), 2)
-    return 2 * ((4 + 3 * 8) * K + 3 * ((K + 255) // 256)) + 256
+    return _host("sn2_kde_fit_ws_words", max(int(K), 2))
 
 
 def kde_fit(z_dev: torch.Tensor, bw: float = 0.1, grid_points: int = 5000):
@@ -1385,7 +1415,7 @@ def loss_backward(pred, gt, proba, pdf, m: float, e: float, grad_total):
     return dpred, dproba
 
 
-PROJECTED_LOSS_WS = 2 * 512 + 2      # SN2_PROJECTED_LOSS_WS
+PROJECTED_LOSS_WS = _lib.SN2_PROJECTED_LOSS_WS
 
 
 def projected_loss_forward(cov, pix, proba, pdf, gt, B: int, N: int, diam_pix: int, m: float, e: float):

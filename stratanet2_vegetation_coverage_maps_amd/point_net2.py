@@ -197,9 +197,9 @@ class PointNet2(nn.Module):
         """"fp32" (default: exact fp32 products, the reference's precision) or "bf16": the dense contractions of
         `BF16_BLOCKS` -- forward, input gradient, weight gradient -- take bfloat16 operands on v_mfma_f32_16x16x32_bf16 /
         16x16x16 with fp32 accumulation; ReLU, BatchNorm, statistics, every arg-max and all position-only kernels stay
-        fp32, so the index structures are the same bits in both modes.  A dense block with more than 64 * SN2_STAT_SLOTS
-        (65 536) rows -- FP2 at the reference's default ratio1 = 0.5 on 32 768-point plots -- has no bfloat16 kernel and
-        runs in fp32 (`hip_ops.fp_desc`)."""
+        fp32, so the index structures are the same bits in both modes.  A dense block with more rows than
+        `hip_ops.fp_rows_small` takes -- FP2 at the reference's default ratio1 = 0.5 on 32 768-point plots -- has no bfloat16
+        kernel and runs in fp32 (`hip_ops.fp_desc`)."""
         if dtype not in ("fp32", "bf16"):
             raise ValueError("mma_dtype must be 'fp32' or 'bf16'")
         self.mma_dtype = dtype
@@ -347,12 +347,12 @@ class PointNet2(nn.Module):
     def _fp1_source_side(rows):
         """Whether the per-point layer FP1 runs in its source-side form (hip_ops.fp_desc hands out `src_ws`): only that form
         keeps bfloat16 rows (`_act_dtype`) and a permuted d pre-activation buffer (`rank1`)."""
-        return bool(ops.SOURCE_SIDE) and rows > 64 * STAT_SLOTS
+        return bool(ops.SOURCE_SIDE) and ops.fp_source_side(rows, 8)
 
     def _act_dtype(self, rows):
         """Storage type of the three per-point activation buffers (FP1's output h1, the head's gradient dy1, FP1's
-        d pre-activation): bfloat16 under `mma_dtype = "bf16"` where the per-point layer takes its source-side form (more
-        than 64 * SN2_STAT_SLOTS rows), else fp32.  These 75 MB buffers are what the per-point kernels stream."""
+        d pre-activation): bfloat16 under `mma_dtype = "bf16"` where the per-point layer takes its source-side form
+        (`_fp1_source_side`), else fp32.  These 75 MB buffers are what the per-point kernels stream."""
         return torch.bfloat16 if (self.mma_dtype == "bf16" and self._fp1_source_side(rows)) else F32
 
     def _sizes(self, N):
@@ -711,7 +711,7 @@ class PointNet2(nn.Module):
         # ---- SA3: MLP[35,64] on cat[x2, pos2] -> per-plot max                    (:133, 37-42)
         s.h_sa3 = torch.empty(B * M2, 64, dtype=F32, device=dev)
         s.h3 = torch.empty(B * M2, 64, dtype=F32, device=dev)
-        if training and self.fuse_global_level and B <= 28 and not (s.b_sa3.mma_bf16 or s.b_fp3.mma_bf16):
+        if training and self.fuse_global_level and ops.global_level_forward_fused(B, s.b_sa3, s.b_fp3):
             # ... and its max, FP3 (k=1 from the plot's global feature) and both BatchNorms: one launch  (:133-137)
             s.x3 = torch.empty(B, 64, dtype=F32, device=dev)
             s.arg3 = torch.empty(B, 64, dtype=I32, device=dev)

@@ -7,9 +7,9 @@ import re
 from conftest import ROOT
 
 
-def _declared():
+def _declared(ret="int"):
     txt = open(os.path.join(ROOT, "include", "strata_hip.h")).read()
-    return sorted(set(re.findall(r"^int\s+(sn2_\w+)\s*\(", txt, flags=re.M)))
+    return sorted(set(re.findall(r"^%s\s+(sn2_\w+)\s*\(" % ret, txt, flags=re.M)))
 
 
 def test_header_declares_the_hot_path():
@@ -25,11 +25,12 @@ def test_library_builds_loads_and_exports_everything():
     path = _build.build(verbose=False)
     assert os.path.exists(path)
     raw = ctypes.CDLL(path)
-    for name in _declared():
+    for name in _declared() + _declared("size_t"):
         assert hasattr(raw, name), f"{name} declared in strata_hip.h but not exported"
     lib = _lib.load()
     assert lib.sn2_version() == _lib.SN2_VERSION
     assert set(_lib.SIGNATURES) == set(_declared()), "ctypes binding and header disagree"
+    assert set(_lib.SIZE_HELPERS) == set(_declared("size_t")), "ctypes binding and header disagree on the size helpers"
 
 
 def test_struct_layouts_match_the_header_abi():
@@ -48,6 +49,112 @@ def test_struct_layouts_match_the_header_abi():
         sizes = [int(x) for x in subprocess.check_output([exe]).split()]
     assert sizes == [ctypes.sizeof(c) for c in (_lib.Block, _lib.SA, _lib.FP, _lib.Head, _lib.NetLayer, _lib.NetModel, _lib.NetDims,
                                                 _lib.NetGeo, _lib.NetAct, _lib.NetBwd, _lib.NetIO)]
+
+
+# (B, N, M1, M2): the metric's shape and a tiny batch
+_SHAPES = [(16, 32768, 1024, 256), (2, 64, 16, 4)]
+
+
+def _size_cases(B, N, M1, M2):
+    """(helper of the library, its arguments, the header's macro call, the hip_ops function that wraps it or None)"""
+    from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
+    K, cells = (5000, 12345) if N > 1000 else (2, 4)
+    return [
+        ("sn2_fps_ws_words", (B, N), f"SN2_FPS_WS_WORDS({B},{N})", lambda: ops.fps_ws_words(B, N)),
+        ("sn2_fps_ws_grid_offset", (B, N), f"SN2_FPS_WS_GRID_OFFSET({B},{N})", None),
+        ("sn2_fps_ws_ctl_offset", (B, N), f"SN2_FPS_WS_CTL_OFFSET({B},{N})", None),
+        ("sn2_fps_ws_rank_offset", (B, N), f"SN2_FPS_WS_RANK_OFFSET({B},{N})", None),
+        ("sn2_three_nn_ws_words", (B, M1), f"SN2_THREE_NN_WS_WORDS({B},{M1})", lambda: ops.three_nn_ws_words(B, M1)),
+        ("sn2_three_nn_xy_ws_words", (B, M1, N), f"SN2_THREE_NN_XY_WS_WORDS({B},{M1},{N})", lambda: ops.three_nn_ws_words(B, M1, N)),
+        ("sn2_znorm_ws_words", (N, cells), f"SN2_ZNORM_WS_WORDS({N},{cells})", None),
+        ("sn2_sa_order_words", (B, M1), f"SN2_SA_ORDER_WORDS({B},{M1})", lambda: ops.sa_order_len(B, M1)),
+        ("sn2_interp_chunks", (N, M1), f"SN2_INTERP_CHUNKS({N},{M1})", lambda: ops.interp_chunks(N, M1)),
+        ("sn2_interp_ws_words", (B, N, M1), f"SN2_INTERP_WS_WORDS({B},{N},{M1})", lambda: ops.interp_ws_words(B, N, M1)),
+        ("sn2_interp_ws_words", (B, M2, 1), f"SN2_INTERP_WS_WORDS({B},{M2},1)", lambda: ops.interp_ws_words(B, M2, 1)),
+        ("sn2_fp_src_ws_words", (B, N, M1, 34), f"SN2_FP_SRC_WS_WORDS({B},{N},{M1},34)", lambda: ops.fp_src_ws_words(B, N, M1, 34)),
+        ("sn2_global_xchg_words", (B,), f"SN2_GLOBAL_XCHG_WORDS({B})", None),
+        ("sn2_p2_key_parts", (N,), f"SN2_P2_KEY_PARTS({N})", lambda: ops.p2_key_parts(N)),
+        ("sn2_kde_fit_ws_words", (K,), f"SN2_KDE_FIT_WS_WORDS({K})", lambda: ops.kde_fit_ws_words(K)),
+    ]
+
+
+def test_constants_and_size_helpers_match_the_header_macros():
+    """Header -> library -> Python, closed: a C compiler prints every scalar macro that `_lib.CONSTANTS` names and every size
+    macro at two shapes; the Python constants, the library's size helpers and the hip_ops functions over them must give
+    those numbers.  Every size helper the binding knows (but the four whose rule is no macro) is covered."""
+    import subprocess
+    import tempfile
+    from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
+    from stratanet2_vegetation_coverage_maps_amd import _lib
+    lib = _lib.load()
+    names = sorted(_lib.CONSTANTS)
+    cases = [c for shape in _SHAPES for c in _size_cases(*shape)]
+    assert {c[0] for c in cases} == set(_lib.SIZE_HELPERS) - {"sn2_parcel_count_ws_words", "sn2_parcel_znorm_ws_words",
+                                                              "sn2_subsample_ws_words", "sn2_plot_losses_ws_words"}
+    exprs = names + [c[2] for c in cases]
+    src = '#include <stdio.h>\n#include "strata_hip.h"\nint main(){\n' + "".join(
+        f'printf("%lld\\n", (long long)({e}));\n' for e in exprs) + "return 0;}\n"
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "m.c")
+        open(c, "w").write(src)
+        exe = os.path.join(d, "m")
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        vals = [int(x) for x in subprocess.check_output([exe]).split()]
+    assert len(vals) == len(exprs)
+    for n, v in zip(names, vals):
+        assert _lib.CONSTANTS[n] == v and getattr(_lib, n) == v, n
+    for (helper, args, macro, py), v in zip(cases, vals[len(names):]):
+        assert getattr(lib, helper)(*args) == v, macro
+        if py is not None:
+            assert py() == v, macro
+    # the names the package and its tests have always used are those constants
+    assert (ops.GL_MAX_PLOTS, ops.GL_BWD_MAX_ROWS, ops.GRAD_IMAGES, ops.SA_BWD_WS_WORDS, _lib.STAT_SLOTS, _lib.BN_FROZEN_KEEP) == tuple(
+        _lib.CONSTANTS[n] for n in ("SN2_GLOBAL_MAX_PLOTS", "SN2_GLOBAL_BWD_MAX_ROWS", "SN2_NET_GRAD_IMAGES", "SN2_SA_BWD_WS_WORDS",
+                                    "SN2_STAT_SLOTS", "SN2_BN_FROZEN_KEEP"))
+    assert (ops.LOSS_BLOCKS, ops.PROJECTED_LOSS_WS, ops.KDE_FIT_MAX_K, ops.SUBSAMPLE_LDS_MAX) == tuple(
+        _lib.CONSTANTS[n] for n in ("SN2_LOSS_BLOCKS", "SN2_PROJECTED_LOSS_WS", "SN2_KDE_FIT_MAX_K", "SN2_SUBSAMPLE_LDS_MAX"))
+    assert (_lib.NET_FORK, _lib.NET_HAS_INVERTED) == (_lib.CONSTANTS["SN2_NET_FORK"], _lib.CONSTANTS["SN2_NET_HAS_INVERTED"])
+
+
+def test_route_predicates_on_each_side_of_every_boundary():
+    """The route rules of the library (include/strata_hip.h, "Routes") against the rules as the commit before them stated them
+    in four languages, written out here as literals ON PURPOSE: this is the second statement that pins the first."""
+    from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
+    from stratanet2_vegetation_coverage_maps_amd import _lib
+    lib = _lib.load()
+    fps = {(1, 2048, 64): 0, (1, 2052, 64): 1, (1, 2052, 16): 0, (1, 2052, 17): 1, (1, 2049, 64): 0, (33, 4096, 64): 0,
+           (32, 4096, 64): 1, (33, 4100, 64): 1, (1, 131072, 64): 1, (1, 131076, 64): 0}
+    for a, want in fps.items():
+        assert lib.sn2_fps_fills_ws(*a) == want and ops.fps_fills_ws(*a) is bool(want), a
+    for a, want in {(127, 2049): 0, (128, 2049): 1, (128, 2048): 0, (8192, 2049): 1, (8193, 2049): 0}.items():
+        assert lib.sn2_three_nn_uses_grid(*a) == want and ops.three_nn_uses_grid(*a) is bool(want), a
+    assert lib.sn2_fp_rows_small(65536) == 1 and lib.sn2_fp_rows_small(65537) == 0
+    assert ops.fp_rows_small(65536) is True and ops.fp_rows_small(65537) is False
+    for cb, want in {0: 0, 3: 0, 20: 0, 4: 1, 8: 1, 16: 1}.items():
+        assert lib.sn2_fp_source_side(65537, cb, 0) == want and ops.fp_source_side(65537, cb) is bool(want), cb
+    assert lib.sn2_fp_source_side(65536, 8, 0) == 0 and lib.sn2_fp_source_side(65536, 8, 1) == 1
+    assert ops.fp_source_side(65536, 8) is False and ops.fp_source_side(65536, 8, True) is True
+    for a, want in {(28, 0): 1, (29, 0): 0, (28, 1): 0}.items():
+        assert lib.sn2_global_level_forward_route(*a) == want, a
+    for a, want in {(28, 256, 0, 0): 1, (28, 257, 0, 0): 0, (29, 256, 0, 0): 0, (28, 256, 1, 0): 0, (28, 256, 0, 1): 0}.items():
+        assert lib.sn2_global_level_backward_route(*a) == want, a
+
+    class Blk:
+        def __init__(self, bf16):
+            self.mma_bf16 = bf16
+    f32, b16 = Blk(False), Blk(True)
+    assert ops.global_level_forward_fused(28, f32, f32) is True and ops.global_level_forward_fused(29, f32, f32) is False
+    assert ops.global_level_forward_fused(28, f32, b16) is False
+    assert ops.global_level_backward_fused(28, 256, False, f32, f32) is True
+    assert ops.global_level_backward_fused(28, 257, False, f32, f32) is False and ops.global_level_backward_fused(28, 256, True, f32, f32) is False
+    assert ops.global_level_backward_fused(29, 256, False, f32, f32) is False and ops.global_level_backward_fused(28, 256, False, b16, f32) is False
+    # sn2_three_nn_xy refuses source counts outside the grid search's range before any device work (fake pointers: never dereferenced)
+    fake = 0x1000
+    for S, want in ((127, -2), (8193, -2)):
+        assert lib.sn2_three_nn_xy(fake, 1, S, fake, 4096, 3, fake, fake, fake, None) == want, S
+    # plots beyond the largest bucketed kernel: SN2_ELIMIT with a workspace as without one, before any device work
+    assert lib.sn2_fps_status(fake, 1, 131076, 64, None, fake, fake, fake, fake, 0, None, None) == -2
+    assert lib.sn2_fps_status(fake, 1, 131076, 64, None, fake, fake, fake, None, 0, None, None) == -2
 
 
 def test_argument_checks_return_before_any_device_work():

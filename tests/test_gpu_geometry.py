@@ -74,7 +74,7 @@ def test_bucketed_fps_equals_brute_force_and_oracle(B, N, M):
     if ops.fps_fills_ws(B, N, M):                     # (1 x 2049: no bucketed path, the workspace is not touched)
         wa, wb = _filled(0x01010101, 8), _filled(0x7E7E7E7E, 16)
         assert int((wa == 0x01010101).sum()) == 0 and int((wb == 0x7E7E7E7E).sum()) == 0
-        assert torch.equal(wa[5 * B * N:5 * B * N + 4104 * B], wb[5 * B * N:5 * B * N + 4104 * B])    # cell starts, bounding boxes, pad words
+        assert torch.equal(ops.fps_ws_grid(wa, B, N), ops.fps_ws_grid(wb, B, N))    # cell starts, bounding boxes, pad words
         assert torch.equal(wa[:B * N].view(B, N).sort(1).values, wb[:B * N].view(B, N).sort(1).values)    # a permutation of 0..N-1
         order, rank = wa[:B * N].view(B, N).long(), ops.fps_ws_rank(wa, B, N).view(B, N).long()               # and its inverse
         assert torch.equal(torch.gather(rank, 1, order), torch.arange(N, device=DEV).expand(B, N))
@@ -305,6 +305,34 @@ def test_fps_workspace_is_only_handed_out_when_filled():
         assert torch.equal(cnt, cnt_f)
         ref = P.fps_batched(xyz.permute(0, 2, 1).contiguous(), M, torch.zeros(B, dtype=torch.long))
         assert torch.equal(idx.cpu().long(), ref)
+
+
+def _fps_always_with_ws(xyz, M, ws):
+    """sn2_fps_status with the workspace handed over whatever the sizes (ops.fps withholds it where `fps_fills_ws` says no)."""
+    from stratanet2_vegetation_coverage_maps_amd import _lib
+    B, _, N = xyz.shape
+    assert ws.dtype == torch.int32 and ws.numel() == ops.fps_ws_words(B, N) and ws.data_ptr() % 16 == 0
+    idx = torch.empty(B, M, dtype=torch.int32, device=xyz.device)
+    cs, ca = torch.empty(B, 3, M, device=xyz.device), torch.empty(B * M, 4, device=xyz.device)
+    _lib.check(_lib.load().sn2_fps_status(xyz.data_ptr(), B, N, M, None, idx.data_ptr(), cs.data_ptr(), ca.data_ptr(), ws.data_ptr(), 0,
+                                          None, ops._stream()), "sn2_fps_status")
+    return idx
+
+
+def test_fps_route_predicate_is_what_the_kernels_do():
+    """sn2_fps_fills_ws against the device: a caller-owned workspace, pre-filled with a pattern and ALWAYS passed, is written
+    iff the predicate says so -- on each side of every boundary of the rule (2048 points, 16 samples, B*N % 4, many small
+    plots).  The same samples either way."""
+    from stratanet2_vegetation_coverage_maps_amd import _lib
+    lib = _lib.load()
+    for B, N, M in ((1, 2048, 64), (1, 2052, 64), (1, 2052, 16), (1, 2052, 17), (1, 2049, 64), (33, 4096, 64), (32, 4096, 64),
+                    (33, 4100, 64)):
+        xyz = torch.rand(B, 3, N, device=DEV) * 20.0
+        ws = torch.full((ops.fps_ws_words(B, N),), 0x5A5A5A5A, dtype=torch.int32, device=DEV)
+        idx = _fps_always_with_ws(xyz, M, ws)
+        written = bool((ws != 0x5A5A5A5A).any())
+        assert written == bool(lib.sn2_fps_fills_ws(B, N, M)), (B, N, M)
+        assert torch.equal(idx, ops.fps(xyz, M, None, bucketed=False)[0]), (B, N, M)
 
 
 @pytest.mark.parametrize("B,M", [(3, 1024), (2, 2500), (4, 256), (1, 10000), (2, 77), (40, 700)])      # 40 plots: 256 threads per plot
