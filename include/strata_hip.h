@@ -476,6 +476,22 @@ int sn2_debug_global_spin_limit(unsigned sweeps);
 
 /* ---- pointwise head: lin1+ReLU, lin2, softmax/sigmoid/product -- model/point_net2.py:141-151 ----------------
  * f (R,34) pre-BN with affine (fa,fc); coverages (R,4), proba (R,4). */
+/* The loss gradient that sn2_head_backward can compute itself (the fused route, sn2_head_loss_route): what
+ * sn2_projected_loss_backward takes, minus the two (R,4) buffers it writes.  The head backward then evaluates d loss / d proba and
+ * d loss / d coverages of a row where it consumes them (csrc/loss_grad.h: the same two device functions as
+ * sn2_projected_loss_backward's kernel, so the same bits) and the 32 B per point never travel through memory. */
+#define SN2_HEAD_LOSS_MAX_PLOTS 128  /* its per-plot table (gx, gz, gw, 1/nocc) lives in what the head backward's LDS leaves free */
+typedef struct sn2_loss_grad {
+    const float *pred;              /* (B,4) plot-wise coverages of sn2_projected_loss_forward                    */
+    const double *gt;               /* (B,4) fp64                                                                 */
+    const float *proba;             /* (R,4) the STORED probabilities of the forward pass, R = B*N                */
+    const double *pdf;              /* (R,3) fp64, or NULL when m = 0                                             */
+    const double *grad_total;       /* device fp64 scalar: d objective / d total                                  */
+    const int *arg, *nocc, *pix;    /* (B,D*D,3), (B), (R): sn2_projected_loss_forward's, sn2_plot_pixels'        */
+    int B, N, D;
+    double m, e;
+} sn2_loss_grad;
+
 typedef struct sn2_head {
     int R, cin, f_stride;           /* rows, 34, 36                                                              */
     const float *f, *fa, *fc;
@@ -492,6 +508,9 @@ typedef struct sn2_head {
     float *zero_fill; long zero_fill_words; /* sn2_head_forward only, or NULL / 0: a buffer (16-byte aligned, a multiple of 4 words)
                                        that the forward kernel also clears -- the backward pass's zero-filled arena (sn2_net_bwd),
                                        so that no launch of its own has to clear it in front of the backward pass */
+    const sn2_loss_grad *loss;      /* sn2_head_backward only; set by the caller, or NULL: gradients come in dcoverages / dproba as
+                                       before.  Set: both of those must be NULL, R = loss->B * loss->N and
+                                       sn2_head_loss_route(B, N, D) must say yes, else SN2_EINVAL */
 } sn2_head;
 int sn2_head_forward(const sn2_head *p, void *stream);
 /* EVAL only: the per-point layer (p: the 34 + 8 -> 34 block with its 3-NN table, source-side workspace p->src_ws required) and
@@ -500,6 +519,9 @@ int sn2_head_forward(const sn2_head *p, void *stream);
  * under model.eval(), predict.py:96-126).  Same operations in the same order as the two calls: the same bits. */
 int sn2_fp_head_eval(const sn2_fp *p, const sn2_head *hd, void *stream);
 int sn2_head_backward(const sn2_head *p, void *stream);
+/* tests only: the workgroups of sn2_head_backward's kernel (bf16: its bfloat16-row instantiation) that the runtime places on one
+ * CU, with the LDS of a launch with (with_loss != 0) or without a descriptor -- the kernel is built for 2; < 0: -hipError_t */
+int sn2_debug_head_backward_occupancy(int bf16, int with_loss);
 /* After sn2_head_backward: the gradients of the BatchNorm whose output the head reads (FP1's), obtained from lin1's weight
  * and bias gradients instead of a pass over all rows (derivation in head.hip).  gamma, beta, mean, invstd: that BatchNorm's
  * parameters and saved batch statistics; dgamma, dbeta: ACCUMULATED, complete on return.  *ok (device int) = 1 when the
@@ -771,6 +793,9 @@ typedef struct sn2_net_bwd {
                                             block's sn2_block.frozen_stats) */
     unsigned long long *gl_xchg; unsigned *gl_ctl;   /* set by the caller: sn2_global_level_backward's exchange area (its own, not
                                             sn2_net_io's), or NULL: the separate launches */
+    const sn2_loss_grad *loss;           /* set by the caller, or NULL: gradients come in dcov / dproba as before.  Set: both of
+                                            those must be NULL and sn2_head_loss_route must say yes (the caller asks first), else
+                                            SN2_EINVAL; handed to the head backward (sn2_head.loss) */
 } sn2_net_bwd;
 
 #define SN2_NET_FORK 1          /* geometry: level-2 chain on io.stream_b, per-point 3-NN chain on io.stream_c (needs io.ctx) */
@@ -844,6 +869,10 @@ int sn2_fp_source_side(long R, int cb, int force);
  * SN2_GLOBAL_MAX_PLOTS plots, fp32 operands; backward also batch statistics (frozen == 0) and M2 <= SN2_GLOBAL_BWD_MAX_ROWS */
 int sn2_global_level_forward_route(int B, int bf16);
 int sn2_global_level_backward_route(int B, int M2, int frozen, int bf16);
+/* sn2_head_backward takes a loss-gradient descriptor (sn2_head.loss, sn2_net_bwd.loss) for B plots of N points on a D x D grid:
+ * B <= SN2_HEAD_LOSS_MAX_PLOTS, B*N < 2^31 rows, D*D <= 2025 cells (what the projection covers).  Otherwise the caller runs
+ * sn2_projected_loss_backward and hands the two gradients over */
+int sn2_head_loss_route(int B, int N, int D);
 
 #ifdef __cplusplus
 }

@@ -60,13 +60,18 @@ class FP(Structure):  # sn2_fp
                 ("act_bf16", c_int), ("row_perm", c_void_p)]
 
 
+class LossGrad(Structure):  # sn2_loss_grad
+    _fields_ = [(n, c_void_p) for n in ("pred", "gt", "proba", "pdf", "grad_total", "arg", "nocc", "pix")] + [
+        ("B", c_int), ("N", c_int), ("D", c_int), ("m", c_double), ("e", c_double)]
+
+
 class Head(Structure):  # sn2_head
     _fields_ = [("R", c_int), ("cin", c_int), ("f_stride", c_int), ("f", c_void_p), ("fa", c_void_p),
                 ("fc", c_void_p), ("W1", c_void_p), ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
                 ("coverages", c_void_p), ("proba", c_void_p), ("dcoverages", c_void_p), ("dproba", c_void_p),
                 ("dy", c_void_p), ("dW1", c_void_p), ("db1", c_void_p), ("dW2", c_void_p), ("db2", c_void_p),
                 ("grad_replicas", c_int), ("grad_replica_stride", c_int), ("drop_mask", c_void_p), ("drop_scale", c_float),
-                ("act_bf16", c_int), ("zero_fill", c_void_p), ("zero_fill_words", c_long)]
+                ("act_bf16", c_int), ("zero_fill", c_void_p), ("zero_fill_words", c_long), ("loss", POINTER(LossGrad))]
 
 
 class NetLayer(Structure):  # sn2_net_layer
@@ -108,7 +113,7 @@ class NetBwd(Structure):  # sn2_net_bwd
                 ("image_stride", c_int)] + [(n, c_void_p) for n in (
                     "dy2", "dy3", "dx1", "dx2", "dx3", "dy_sa3", "sa1_ws", "dy1", "du1", "du2", "du3", "bn_ok", "src_ws1", "src_ws2")] + [
                         ("defer_grad_reduce", c_int), ("arena_is_zero", c_int), ("frozen_stats", c_int), ("gl_xchg", c_void_p),
-                        ("gl_ctl", c_void_p)]
+                        ("gl_ctl", c_void_p), ("loss", POINTER(LossGrad))]
 
 
 class NetIO(Structure):  # sn2_net_io
@@ -173,6 +178,7 @@ SIGNATURES = {
     "sn2_fp_bn_sums": [POINTER(FP), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_head_bn_sums": [POINTER(Head), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_head_backward": [POINTER(Head), c_void_p],
+    "sn2_debug_head_backward_occupancy": [c_int, c_int],
     "sn2_plot_project_forward": [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p],
     "sn2_plot_pixels": [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
@@ -215,6 +221,7 @@ SIGNATURES = {
     "sn2_fp_source_side": [c_long, c_int, c_int],
     "sn2_global_level_forward_route": [c_int, c_int],
     "sn2_global_level_backward_route": [c_int, c_int, c_int, c_int],
+    "sn2_head_loss_route": [c_int, c_int, c_int],
 }
 
 # workspace-size and layout helpers: name -> argtypes; they return size_t (32-bit words unless the header says otherwise; 0 =

@@ -4,6 +4,7 @@
 // sn2_fp_bn_sums, sn2_head_backward.  Replaces the head of PointNet2.forward.  The rows' accessors, WAVE_LDS_SYNC, the row side's
 // input stream and the source table come from fp_rows.h.
 #include "fp_rows.h"
+#include "loss_grad.h"
 
 namespace {
 
@@ -607,6 +608,8 @@ __device__ __forceinline__ hb_f32x2 lds_read_b64(const float* p) {
     asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(a) : "memory");
     return v;
 }
+typedef unsigned hb_u32x4 __attribute__((ext_vector_type(4)));
+typedef hb_u32x4 hb_u32x4_a8 __attribute__((aligned(8)));       // a 16-byte load from an 8-byte aligned address (a row's fp64 densities)
 constexpr int HB_ST = 64 * 36, HB_ZT = 64 * 20, HB_SC = 64 * 12;
 constexpr int HB_WAVE_FLOATS = HB_ST + HB_ZT + HB_SC + 64;      // + the rows' dropout words
 #ifndef SN2_HB_DIAG
@@ -624,10 +627,14 @@ __global__ __launch_bounds__(256, 2) void head_bwd_mfma_kernel(int R, const floa
                                                             const float* __restrict__ dproba, float* __restrict__ dy,
                                                             float* __restrict__ dW1, float* __restrict__ db1,
                                                             float* __restrict__ dW2, float* __restrict__ db2, int rep_k,
-                                                            int rep_stride, const int* __restrict__ drop_mask, float drop_scale) {
+                                                            int rep_stride, const int* __restrict__ drop_mask, float drop_scale,
+                                                            const sn2_loss_grad lg) {
     typedef hb_f32x2 f32x2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // the fused route (sn2_head.loss; wave-uniform, as dcov / dproba / drop_mask are): the incoming gradients of a row are
+    // computed in its one-row-per-lane phase from the loss's own inputs (loss_grad.h) instead of being read
+    const bool loss = lg.proba != nullptr;
     float* st = smem + wave * HB_WAVE_FLOATS;
     float4* st4 = reinterpret_cast<float4*>(st);
     float* zt = st + HB_ST;
@@ -635,6 +642,16 @@ __global__ __launch_bounds__(256, 2) void head_bwd_mfma_kernel(int R, const floa
     int* mk = reinterpret_cast<int*>(sc + HB_SC);
     const int n = lane & 15, kq = lane >> 4;
     float* tab = smem + 4 * HB_WAVE_FLOATS;
+    float4* ptab = reinterpret_cast<float4*>(tab + HB_TAB_FLOATS);          // fused route: (gx, gz, gw, 1 / nocc) per plot ...
+    double* pco = reinterpret_cast<double*>(ptab + PL_HEAD_MAX_PLOTS);      // ... and the two row coefficients (cn, ce)
+    if (loss && wave >= 2) {
+        // the fp64 square roots and divisions of d loss / d pred: once per plot and workgroup (waves 2, 3; wave 0 fills the
+        // weight table below) instead of once per point
+        const int pb = (int)threadIdx.x - 128;
+        const double g = lg.grad_total[0];
+        if (pb < lg.B) ptab[pb] = pl_plot_grad(lg.pred, lg.gt, lg.nocc, pb, lg.B, g);
+        if (pb == 0) pl_row_coeffs(g, lg.m, lg.e, (size_t)R, pco[0], pco[1]);
+    }
     // ---- the weight operands of lane (n, kq) -> the table
     if (wave == 0) {
         float c[4 * HB_CQ];
@@ -683,14 +700,24 @@ __global__ __launch_bounds__(256, 2) void head_bwd_mfma_kernel(int R, const floa
     float dsum[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     const long stride = (long)gridDim.x * 256;
     long r0 = ((long)blockIdx.x * 4 + wave) * 64;
-    float4 t[9], gc = make_float4(0.f, 0.f, 0.f, 0.f), gp = gc;
-    int keep = 0xFFFF;
+    float4 t[9], ga = make_float4(0.f, 0.f, 0.f, 0.f);
+    hb_u32x4 gb01 = {0u, 0u, 0u, 0u};           // (ONE 16-byte value, as gc / gp were: two 8-byte ones that the compiler merges into
+    uint2 gb2 = make_uint2(0u, 0u);             // one load afterwards are copied apart behind it, and the copy waits for the prefetch)
+    int keep = 0xFFFF, pixv = 0;
     // (a gradient or mask that is absent is loaded from the rows instead -- 16 valid bytes per row -- and dropped at its use:
     // a load under a branch, even a uniform one, is waited for where the branch joins, which would end the prefetch; for the
     // same reason the rows past the end are loaded from a clamped address: finite values whose d scores are zero)
-    const float4* gcp = reinterpret_cast<const float4*>(dcov ? dcov : f);
-    const float4* gpp = reinterpret_cast<const float4*>(dproba ? dproba : f);
+    // The same registers serve both routes, by address selection alone: `ga` = the row's dcoverages, or its stored probabilities;
+    // `gb01`, `gb2` = the 16 bytes of its dproba (and its first 8 again), or its three fp64 densities (24 B per row, 8-byte
+    // aligned; none when m = 0: the dummy again); `pixv` = its pixel id.
+    const float4* gap = reinterpret_cast<const float4*>(loss ? lg.proba : (dcov ? dcov : f));
+    const char* gbp = loss ? reinterpret_cast<const char*>(lg.pdf ? reinterpret_cast<const float*>(lg.pdf) : f)
+                           : reinterpret_cast<const char*>(dproba ? dproba : f);
+    const int gb_stride = loss ? 24 : 16, gb_third = loss ? 16 : 0;
     const int* kp = drop_mask ? drop_mask : reinterpret_cast<const int*>(f);
+    const int* pxp = loss ? lg.pix : reinterpret_cast<const int*>(f);
+    const int* argp = loss ? lg.arg : reinterpret_cast<const int*>(f);
+    const unsigned rows_per_plot = loss ? (unsigned)lg.N : 1u, ncell = loss ? (unsigned)(lg.D * lg.D) : 0u;
     auto request = [&](long q0) {               // the rows of a turn, one row's incoming gradients and dropout word per lane
         const long lim = (R - q0) * 9;
 #pragma unroll
@@ -700,9 +727,12 @@ __global__ __launch_bounds__(256, 2) void head_bwd_mfma_kernel(int R, const floa
         }
         const long r = q0 + lane;
         const size_t rr = r < R ? (size_t)r : 0;
-        gc = gcp[rr];
-        gp = gpp[rr];
+        ga = gap[rr];
+        const char* pb = gbp + rr * (size_t)gb_stride;
+        gb01 = *reinterpret_cast<const hb_u32x4_a8*>(pb);
+        gb2 = *reinterpret_cast<const uint2*>(pb + gb_third);
         keep = kp[rr];
+        pixv = pxp[rr];
     };
     if (r0 < R) request(r0);
     int turn_no = -1;
@@ -720,8 +750,15 @@ __global__ __launch_bounds__(256, 2) void head_bwd_mfma_kernel(int R, const floa
         }
         if (drop_mask) mk[lane] = keep;
         const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 gcv = dcov ? gc : zero4, gpv = dproba ? gp : zero4;
         const bool valid = r0 + lane < R;
+        // fused route: the row's plot (per LANE: a turn straddles two plots whenever N is no multiple of 64) and the arg-max
+        // points of its pixel -- a second round trip that depends on the prefetched pixel id, issued here and consumed in the
+        // d-scores phase, behind lin1 and lin2.  Without a descriptor: three words of the rows, dropped at their use.
+        const unsigned rowi = valid ? (unsigned)(r0 + lane) : 0u;
+        const unsigned plot = rowi / rows_per_plot;
+        const int row_in_plot = (int)(rowi - plot * rows_per_plot);
+        const int* ap = argp + (loss ? ((size_t)plot * ncell + (size_t)pixv) * 3 : (size_t)0);
+        const int a0 = ap[0], a1 = ap[1], a2 = ap[2];
         WAVE_LDS_SYNC();
         HSTAMP(1)
         if (!(HB_DIAG & 2)) {
@@ -817,6 +854,17 @@ __global__ __launch_bounds__(256, 2) void head_bwd_mfma_kernel(int R, const floa
 #pragma unroll
             for (int i = 0; i < 4; ++i) pr[i] = e[i] / den;
             const float dens = 1.0f / (1.0f + expf(-s4));
+            // the incoming gradients: from the STORED probabilities on the fused route (the bits of sn2_projected_loss_backward's
+            // dproba; the softmax backward below keeps the recomputed ones, as before), else what was loaded
+            float4 gcv, gpv;
+            if (loss) {
+                const float4 pg = ptab[plot];
+                pl_row_grad(lg.m != 0.0, lg.e != 0.0, ga, __hiloint2double((int)gb01.y, (int)gb01.x), __hiloint2double((int)gb01.w, (int)gb01.z),
+                            __hiloint2double((int)gb2.y, (int)gb2.x), pco[0], pco[1], pg, a0, a1, a2, row_in_plot, gpv, gcv);
+            } else {
+                gcv = dcov ? ga : zero4;
+                gpv = dproba ? make_float4(__uint_as_float(gb01.x), __uint_as_float(gb01.y), __uint_as_float(gb01.z), __uint_as_float(gb01.w)) : zero4;
+            }
             const float gcs[4] = {gcv.x, gcv.y, gcv.z, gcv.w}, gps[4] = {gpv.x, gpv.y, gpv.z, gpv.w};
             float dp[4], dot = 0.f, ddens = 0.f, ds[5];
 #pragma unroll
@@ -1164,17 +1212,44 @@ extern "C" int sn2_fp_bn_sums(const sn2_fp* p, const float* gamma, const float* 
     SN2_RETURN_LAUNCH();
 }
 
+// 79 136 bytes, and with a descriptor 2 064 more (the per-plot table and two coefficients).  Two workgroups per CU either way,
+// ASSUMING the hardware hands LDS out in blocks of at most 512 bytes: 81 200 rounds up to 81 408, twice that is 162 816 of
+// 163 840.  A coarser granularity (1 KB would still do: 81 920 x 2 = 163 840, no slack at all) or one more kilobyte of LDS ends
+// that: sn2_debug_head_backward_occupancy asks the runtime, and tests/test_gpu_head_loss_backward.py holds it to 2.
+constexpr size_t HB_LDS_TAB = ((size_t)HB_WAVE_FLOATS * 4 + HB_TAB_FLOATS) * 4, HB_LDS_LOSS = PL_HEAD_MAX_PLOTS * 16 + 16;
+constexpr size_t hb_lds_round(size_t b) { return (b + 511) / 512 * 512; }
+static_assert(2 * hb_lds_round(HB_LDS_TAB + HB_LDS_LOSS) <= 160 * 1024, "head backward: two workgroups per CU");
+
+extern "C" int sn2_debug_head_backward_occupancy(int bf16, int with_loss) {
+    auto km = bf16 ? &head_bwd_mfma_kernel<true> : &head_bwd_mfma_kernel<false>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(km), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(HB_LDS_TAB + HB_LDS_LOSS));
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, km, 256, HB_LDS_TAB + (with_loss ? HB_LDS_LOSS : 0));
+    return e == hipSuccess ? n : -(int)e;
+}
+
 extern "C" int sn2_head_backward(const sn2_head* p, void* stream) {
     SN2_TRY(check_head(p));
     if (!p->dy || !p->dW1 || !p->db1 || !p->dW2 || !p->db2) return SN2_EINVAL;
-    constexpr size_t lds_m = ((size_t)HB_WAVE_FLOATS * 4 + HB_TAB_FLOATS) * 4;      // 79 136 bytes: two workgroups per CU
+    sn2_loss_grad lg = {};
+    if (p->loss) {
+        lg = *p->loss;
+        if (p->dcoverages || p->dproba || !sn2_head_loss_route(lg.B, lg.N, lg.D) || (long)lg.B * lg.N != (long)p->R) return SN2_EINVAL;
+        if (!lg.pred || !lg.gt || !lg.proba || !lg.grad_total || !lg.arg || !lg.nocc || !lg.pix || (lg.m != 0.0 && !lg.pdf)) return SN2_EINVAL;
+        if (lg.m == 0.0) lg.pdf = nullptr;
+    }
+    const size_t lds_m = HB_LDS_TAB + (p->loss ? HB_LDS_LOSS : 0);
     auto km = p->act_bf16 ? &head_bwd_mfma_kernel<true> : &head_bwd_mfma_kernel<false>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(km), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(km), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(HB_LDS_TAB + HB_LDS_LOSS));
     int gm = sn2_cdiv(sn2_cdiv(p->R, 64), 4);
     const int cap = 2 * sn2_cu_count();
     if (gm > cap) gm = cap;
     hipLaunchKernelGGL(km, dim3(gm), dim3(256), lds_m, (hipStream_t)stream, p->R, p->f, p->fa, p->fc, p->W1, p->b1, p->W2,
                        p->b2, p->dcoverages, p->dproba, p->dy, p->dW1, p->db1, p->dW2, p->db2, p->grad_replicas,
-                       p->grad_replica_stride, p->drop_mask, p->drop_mask ? p->drop_scale : 1.f);
+                       p->grad_replica_stride, p->drop_mask, p->drop_mask ? p->drop_scale : 1.f, lg);
     SN2_RETURN_LAUNCH();
+}
+
+extern "C" int sn2_head_loss_route(int B, int N, int D) {
+    return B > 0 && N > 0 && D > 0 && B <= PL_HEAD_MAX_PLOTS && D <= 45 && D * D <= PL_MAX_CELLS && (long)B * N < (1L << 31);
 }

@@ -564,6 +564,11 @@ extern "C" int sn2_net_backward(const sn2_net_model* m, const sn2_net_dims* d, c
         !b->dy2 || !b->dy3 || !b->dx1 || !b->dx2 || !b->dx3 || !b->dy_sa3 || b->arena_words <= 0)
         return SN2_EINVAL;
     const int B = d->B, M2 = d->M2;
+    // a loss-gradient descriptor takes the place of both incoming gradients, for the sizes sn2_head_loss_route covers: the caller
+    // was supposed to ask it
+    if (b->loss && (b->dcov || b->dproba || b->loss->B != d->B || b->loss->N != d->N ||
+                    !sn2_head_loss_route(b->loss->B, b->loss->N, b->loss->D)))
+        return SN2_EINVAL;
     hipStream_t cur = (hipStream_t)stream;
     // one zero-filled arena: the images of the flat parameter gradient + every accumulate-into buffer of the chain
     if (!b->arena_is_zero) {
@@ -576,6 +581,7 @@ extern "C" int sn2_net_backward(const sn2_net_model* m, const sn2_net_dims* d, c
     head_desc(&hd, m, d, a, b->frozen_stats ? 0 : 1);       // (no dropout in an eval-mode forward)
     hd.coverages = hd.proba = nullptr;
     hd.dcoverages = b->dcov, hd.dproba = b->dproba, hd.dy = static_cast<float*>(b->dy1);
+    hd.loss = b->loss;                                      // the head backward computes the loss gradients itself
     hd.dW1 = b->arena + m->g_lin1_W, hd.db1 = b->arena + m->g_lin1_b, hd.dW2 = b->arena + m->g_lin2_W, hd.db2 = b->arena + m->g_lin2_b;
     hd.grad_replicas = GRAD_IMAGES, hd.grad_replica_stride = b->image_stride;
     SN2_TRY(sn2_head_backward(&hd, cur));

@@ -6,10 +6,11 @@
 // point on ties as torch_scatter's CPU loop -- LDS atomics per workgroup slice, then one global atomic per touched
 // pixel -- and a tiny per-plot finalisation.  HBM-bound: 8 B (xy) + 16 B (coverages) read per point.
 #include "common.h"
+#include "loss_grad.h"
 
 namespace {
 
-constexpr int MAX_CELLS = 2025;  // diam_pix <= 45: the D*D*3 keys of a workgroup fit the default 48 KiB dynamic LDS
+constexpr int MAX_CELLS = PL_MAX_CELLS;  // diam_pix <= 45: the D*D*3 keys of a workgroup fit the default 48 KiB dynamic LDS
 
 // project_to_2d.py:16-22   floor((xy - min) / (max - min + 0.0001) * diam_pix).int()
 __device__ __forceinline__ int p2_pix(float v, float mn, float mx, int D) {
@@ -328,9 +329,7 @@ extern "C" int sn2_plot_project_forward_pix(const float* pred_pointwise, const i
 // 1024 instead of 256 rows per workgroup (fp64: 1e-16).
 // ------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int PL_LOSS_BLOCKS = 512;
-constexpr float PL_EPS_F = 0.0001f;
-constexpr double PL_EPS_D = 0.0001;
+constexpr int PL_LOSS_BLOCKS = 512;          // (PL_EPS_F, PL_EPS_D: loss_grad.h)
 
 __device__ __forceinline__ double pl_wave_sum_f64(double v) {
 #pragma unroll
@@ -494,44 +493,22 @@ __global__ __launch_bounds__(256) void projected_loss_bwd_kernel(const float* __
                                                                  const int* __restrict__ arg, const int* __restrict__ nocc,
                                                                  const int* __restrict__ pix, float4* __restrict__ dcov,
                                                                  float4* __restrict__ dproba) {
+    // (the arithmetic lives in loss_grad.h: the head backward's fused route evaluates the same two functions)
     const size_t R = (size_t)B * N;
     const double g = gout[0];
-    const double cn = g * m / (double)R, ce = g * e / (2.0 * (double)R);
+    double cn, ce;
+    pl_row_coeffs(g, m, e, R, cn, ce);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < R; i += (size_t)gridDim.x * 256) {
         const float4 p = proba[i];
-        double d0 = 0.0, d2 = 0.0, d3 = 0.0;
-        if constexpr (NLL) {
-            const double f0 = pdf[3 * i], f1 = pdf[3 * i + 1], f2 = pdf[3 * i + 2];
-            const float pg = p.x + p.y;
-            const double lik = ((double)pg * f0 + (double)p.z * f1) + (double)p.w * f2;
-            const double il = -cn / lik;
-            d0 = il * f0, d2 = il * f1, d3 = il * f2;
-        }
-        if constexpr (ENT) {
-            const float h2 = -(logf(p.z + PL_EPS_F) + p.z / (p.z + PL_EPS_F) - logf(1.f - p.z + PL_EPS_F) - (1.f - p.z) / (1.f - p.z + PL_EPS_F));
-            const float h3 = -(logf(p.w + PL_EPS_F) + p.w / (p.w + PL_EPS_F) - logf(1.f - p.w + PL_EPS_F) - (1.f - p.w) / (1.f - p.w + PL_EPS_F));
-            d2 += ce * (double)h2, d3 += ce * (double)h3;
-        }
-        float4 d;
-        d.x = d.y = (float)d0;
-        d.z = (float)d2;
-        d.w = (float)d3;
-        dproba[i] = d;
-        // d loss / d coverages: the point receives its pixel's gradient iff it is the pixel's arg-max (p2_backward_kernel), with
-        // d loss / d pred of its plot recomputed here (loss_bwd_kernel's formula: column 1, bare soil, has no target)
+        double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+        if constexpr (NLL) f0 = pdf[3 * i], f1 = pdf[3 * i + 1], f2 = pdf[3 * i + 2];
+        // d loss / d pred of the row's plot is recomputed here by every thread
         const int b = (int)(i / N), n = (int)(i - (size_t)b * N);
-        const float4 pr = reinterpret_cast<const float4*>(pred)[b];
-        const double e0 = (double)pr.x - gt[4 * b + 0], e2 = (double)pr.z - gt[4 * b + 2], e3 = (double)pr.w - gt[4 * b + 3];
-        const float gx = (float)(g * e0 / sqrt(e0 * e0 + PL_EPS_D) / (3.0 * B));
-        const float gz = (float)(g * e2 / sqrt(e2 * e2 + PL_EPS_D) / (3.0 * B));
-        const float gw = (float)(g * e3 / sqrt(e3 * e3 + PL_EPS_D) / (3.0 * B));
+        const float4 pg = pl_plot_grad(pred, gt, nocc, b, B, g);
         const int* a = arg + ((size_t)b * D * D + pix[i]) * 3;
-        const float inv = 1.0f / fmaxf((float)nocc[b], 1.f);
-        float4 o;
-        o.x = a[0] == n ? (gx - 0.f) * inv : 0.f;      // (g.x - g.y) with g.y = 0: bare soil carries no gradient of its own
-        o.y = 0.f;
-        o.z = a[1] == n ? gz * inv : 0.f;
-        o.w = a[2] == n ? gw * inv : 0.f;
+        float4 d, o;
+        pl_row_grad(NLL, ENT, p, f0, f1, f2, cn, ce, pg, a[0], a[1], a[2], n, d, o);
+        dproba[i] = d;
         dcov[i] = o;
     }
 }

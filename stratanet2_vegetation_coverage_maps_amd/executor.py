@@ -435,8 +435,9 @@ def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None
     return cov, proba, s
 
 
-def backward(model, s, dcov, dproba):
-    """`PointNet2._backward_impl` as one call (sn2_net_backward) -> the parameter gradients (views of ONE flat buffer)."""
+def backward(model, s, dcov, dproba, loss=None):
+    """`PointNet2._backward_impl` as one call (sn2_net_backward) -> the parameter gradients (views of ONE flat buffer).
+    loss: a `hip_ops.loss_grad_desc` in place of both gradients (sn2_net_bwd.loss; the caller asked `ops.head_loss_route`)."""
     plan, ms = s.plan, s.ms
     dev = s.xyz.device
     R = plan.B * plan.N
@@ -457,6 +458,10 @@ def backward(model, s, dcov, dproba):
     if dproba is not None:
         dproba = ops._chk(dproba.contiguous(), F32, (R, 4), "dproba")
         cb.dproba = dproba.data_ptr()
+    if loss is not None:
+        if dcov is not None or dproba is not None:
+            raise ValueError("executor.backward: a loss-gradient descriptor takes the place of dcov and dproba")
+        cb.loss = ctypes.pointer(loss)
     defer = bool(getattr(model, "defer_grad_reduce", False))
     cb.defer_grad_reduce = int(defer)
     cb.arena_is_zero = int(pre_zeroed)

@@ -5,6 +5,7 @@ kernel is launched (a kernel that faults can take the whole node down) and raise
 Names follow the reference's third-party call sites (model/point_net2.py:9): fps, radius -> ball_query,
 knn_interpolate -> three_nn + the interpolation inside `fp_forward`, PointConv -> `sa_forward`.
 """
+import ctypes
 import math
 from typing import Optional
 
@@ -12,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FP, SA, Block, Head, StrataHipError, check
+from ._lib import FP, SA, Block, Head, LossGrad, StrataHipError, check
 
 I32, F32, F64, I64, BF16 = torch.int32, torch.float32, torch.float64, torch.int64, torch.bfloat16
 
@@ -1135,9 +1136,40 @@ def dropout_mask_words(keep: torch.Tensor) -> torch.Tensor:
     return ((keep != 0).to(torch.int32) * pow2).sum(1, dtype=torch.int32).contiguous()
 
 
+def head_loss_route(B: int, N: int, diam_pix: int) -> bool:
+    """include/strata_hip.h: sn2_head_loss_route -- the head backward takes a loss-gradient descriptor at these sizes."""
+    return bool(_host("sn2_head_loss_route", int(B), int(N), int(diam_pix)))
+
+
+def loss_grad_desc(pred, gt, proba, pdf, grad_total, arg, nocc, pix, B: int, N: int, diam_pix: int, m: float, e: float) -> LossGrad:
+    """include/strata_hip.h: sn2_loss_grad -- what `projected_loss_backward` takes, for `head_desc(loss=)` / the executor's
+    backward: the head backward computes d loss / d coverages and d loss / d proba itself.  pdf may be None when m == 0.  The
+    descriptor keeps its tensors alive (`.tensors`)."""
+    R, D = B * N, int(diam_pix)
+    _chk(pred, F32, (B, 4), "pred")
+    _chk(gt, F64, (B, 4), "gt")
+    _chk(proba, F32, (R, 4), "proba")
+    if pdf is not None:
+        _chk(pdf, F64, (R, 3), "pdf")
+    _chk(grad_total, F64, None, "grad_total")
+    _chk(arg, I32, (B * D * D * 3,), "arg")
+    _chk(nocc, I32, (B,), "nocc")
+    _chk(pix, I32, (R,), "pix")
+    if grad_total.numel() != 1:
+        raise ValueError("loss_grad_desc: grad_total is ONE fp64 scalar on the device")
+    g = LossGrad()
+    g.pred, g.gt, g.proba, g.pdf, g.grad_total = _ptr(pred), _ptr(gt), _ptr(proba), _ptr(pdf), _ptr(grad_total)
+    g.arg, g.nocc, g.pix = _ptr(arg), _ptr(nocc), _ptr(pix)
+    g.B, g.N, g.D, g.m, g.e = int(B), int(N), D, float(m), float(e)
+    g.tensors = (pred, gt, proba, pdf, grad_total, arg, nocc, pix)
+    return g
+
+
 def head_desc(f, fa, fc, lin1, lin2, coverages=None, proba=None, dcov=None, dproba=None, dy=None, grads=None,
-              grad_images=(1, 0), drop_mask=None, drop_p: float = 0.0, rows: Optional[int] = None) -> Head:
-    """f (R,36): the rows the head reads -- or None with `rows` = R for `fp_head_eval`, whose rows never reach memory."""
+              grad_images=(1, 0), drop_mask=None, drop_p: float = 0.0, rows: Optional[int] = None, loss: Optional[LossGrad] = None) -> Head:
+    """f (R,36): the rows the head reads -- or None with `rows` = R for `fp_head_eval`, whose rows never reach memory.
+    loss (`loss_grad_desc`, where `head_loss_route` says yes): `head_backward` computes the incoming gradients itself; dcov and
+    dproba must then be None."""
     if f is None:
         if rows is None or coverages is None:
             raise ValueError("head_desc: without f the row count and the outputs must be given")
@@ -1177,6 +1209,11 @@ def head_desc(f, fa, fc, lin1, lin2, coverages=None, proba=None, dcov=None, dpro
         d.drop_mask, d.drop_scale = _ptr(drop_mask), (1.0 / (1.0 - drop_p) if drop_p < 1.0 else 0.0)
     else:
         d.drop_mask, d.drop_scale = None, 1.0
+    if loss is not None:
+        if dcov is not None or dproba is not None:
+            raise ValueError("head_desc: a loss-gradient descriptor takes the place of dcov and dproba")
+        d.loss = ctypes.pointer(loss)
+        d._loss = loss                          # (the pointer does not keep the descriptor, nor that its tensors, alive)
     return d
 
 

@@ -14,6 +14,8 @@ instead of evaluating `args.kde_mixture` on the CPU each step (`loss_functions.p
 `KdeTables`, which `KdeTables.fit` / `from_plots` fit on the device (`learning/kde_mixture.py:16-100`) or `from_mixture` copies
 from a mixture the reference fitted.
 """
+import weakref
+
 import torch
 
 from . import hip_ops as ops
@@ -232,15 +234,75 @@ def total_loss(pred_coverages, proba_pointwise, gt, pdf_all, m=0.10, e=0.2 / 5):
     return total, (l_abs, l_log, l_e)
 
 
+_ZERO = {}      # device index -> a zero fp32 scalar that nothing ever writes (the fused route's placeholders are views of it)
+
+
+def _zero_scalar(dev):
+    """The cached zero of a device, made at the first fused backward pass.  If that pass runs under a stream capture (no eager
+    warm-up step in front of it, unlike bench.py and the training loops here) the scalar is memory of the capture's pool and is
+    NOT cached: that graph carries one fill node per replay and the next capture makes its own."""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    z = _ZERO.get(idx)
+    if z is None:
+        z = torch.zeros((), dtype=torch.float32, device=dev)
+        if torch.cuda.is_current_stream_capturing():
+            return z                    # memory of the capture's pool: not kept beyond it
+        _ZERO[idx] = z
+    return z
+
+
+class PendingLossGrad:
+    """What `_ProjectedLoss.backward` leaves on the network's autograd node on the fused route instead of two (R,4) gradients: the
+    inputs of `ops.projected_loss_backward` -- for the head backward, which computes both gradients itself (sn2_head.loss) -- and
+    the two placeholders it returned to autograd in their place: views of ONE zero scalar, expanded to (R,4), no memory of their
+    own.  If the network's node receives exactly those, nothing else consumed cov / proba and the descriptor is the whole
+    incoming gradient; if autograd summed something onto one of them, `materialize` gives the two gradients as tensors.
+    Who may see a placeholder instead of a gradient, and what is done about it:
+      * a second loss node on the same cov / proba: a network node is claimed by ONE fused loss node (`_fused_net_node`), every
+        further `projected_total_loss` over it returns real gradients, which autograd sums onto the placeholder: materialised;
+      * `cov.retain_grad()` / `cov.register_hook(...)` (or on proba), set at any time before the backward pass:
+        `_ProjectedLoss.backward` looks and returns real gradients;
+      * NOT covered: `torch.autograd.grad(total, cov)` (the network's node never runs: the caller receives the zero placeholder)
+        and hooks registered on the autograd NODE (`cov.grad_fn.register_prehook`).  Set `model.fuse_loss_backward = False` for
+        such uses."""
+
+    def __init__(self, saved, dims, g):
+        self.saved, self.dims, self.g = saved, dims, g
+        B, N = dims[0], dims[1]
+        z = _zero_scalar(g.device)
+        self.zero = z
+        self.placeholders = (z.expand(B * N, 4), z.expand(B * N, 4))
+
+    def is_placeholder(self, t):
+        return (t is not None and t.dtype == torch.float32 and t.dim() == 2 and t.stride() == (0, 0) and
+                t.shape == self.placeholders[0].shape and t.device == self.zero.device and t.data_ptr() == self.zero.data_ptr())
+
+    def materialize(self):
+        pred, proba, gt, pdf, arg, nocc, pix = self.saved
+        B, N, D, m, e = self.dims
+        return ops.projected_loss_backward(pred, gt, proba, pdf, B, N, D, m, e, self.g, arg, nocc, pix)
+
+    def desc(self):
+        """-> hip_ops.LossGrad (sn2_loss_grad) over the saved tensors"""
+        pred, proba, gt, pdf, arg, nocc, pix = self.saved
+        B, N, D, m, e = self.dims
+        return ops.loss_grad_desc(pred, gt, proba, pdf if m != 0.0 else None, self.g, arg, nocc, pix, B, N, D, m, e)
+
+
 class _ProjectedLoss(torch.autograd.Function):
     """`project_to_plotwise_coverages` + `total_loss` as ONE autograd node over three launches (csrc/project.hip:
-    sn2_projected_loss_forward / _backward) instead of two nodes over seven."""
+    sn2_projected_loss_forward / _backward) instead of two nodes over seven.  net_node: the `_PointNet2Fn` node that produced cov
+    and proba where the fused route applies (`projected_total_loss`), else None: the backward pass then launches nothing and
+    hands that node a `PendingLossGrad`."""
 
     @staticmethod
-    def forward(ctx, cov, proba, pix, gt, pdf, B, N, D, m, e):
+    def forward(ctx, cov, proba, pix, gt, pdf, B, N, D, m, e, net_node=None):
         out, pred, arg, nocc = ops.projected_loss_forward(cov, pix, proba, pdf, gt, B, N, D, m, e)
         ctx.save_for_backward(pred, proba, gt, pdf, arg, nocc, pix)
         ctx.dims = (B, N, D, m, e)
+        ctx.net_node = net_node
+        # (weak: the loss node must not keep the network's outputs alive; looked at in backward for hooks / retain_grad)
+        ctx.outs = (weakref.ref(cov), weakref.ref(proba)) if net_node is not None else None
         ctx.set_materialize_grads(False)
         total, l_abs, l_log, l_e = out[0], out[1], out[2], out[3]
         ctx.mark_non_differentiable(l_abs, l_log, l_e, pred)
@@ -249,11 +311,44 @@ class _ProjectedLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, *_):
         if g is None:
-            return (None,) * 10
+            return (None,) * 11
         pred, proba, gt, pdf, arg, nocc, pix = ctx.saved_tensors
         B, N, D, m, e = ctx.dims
-        dcov, dproba = ops.projected_loss_backward(pred, gt, proba, pdf, B, N, D, m, e, g.to(torch.float64).contiguous(), arg, nocc, pix)
-        return (dcov, dproba) + (None,) * 8
+        g = g.to(torch.float64).contiguous()
+        if ctx.net_node is not None and not any(_observed(r()) for r in ctx.outs):
+            # (one loss node per network node, `_fused_net_node`: a descriptor found here is this node's own from a backward pass
+            # that never reached the network, e.g. torch.autograd.grad w.r.t. cov alone -- replaced)
+            pending = PendingLossGrad((pred, proba, gt, pdf, arg, nocc, pix), ctx.dims, g)
+            ctx.net_node.loss_grad = pending
+            return pending.placeholders + (None,) * 9
+        dcov, dproba = ops.projected_loss_backward(pred, gt, proba, pdf, B, N, D, m, e, g, arg, nocc, pix)
+        return (dcov, dproba) + (None,) * 9
+
+
+def _observed(t):
+    """Does anything look at this tensor's gradient (retain_grad, a tensor hook)?  It must then be the real one."""
+    return t is not None and (bool(t.retains_grad) or bool(getattr(t, "_backward_hooks", None)))
+
+
+def _fused_net_node(cov, proba, cov32, proba32, B, N, D):
+    """The autograd node whose backward pass can take the loss gradient as a descriptor, or None: cov and proba are outputs 0 and
+    1 of ONE `_PointNet2Fn` node, untouched by the casts above (the very same tensors), that node's model has
+    `fuse_loss_backward` on, no other loss node has claimed it (two descriptors cannot both be the whole incoming gradient: the
+    second and later loss nodes over one forward return real gradients) and the library takes the sizes."""
+    from .point_net2 import _PointNet2Fn
+    node = cov.grad_fn
+    if node is None or node is not proba.grad_fn or not isinstance(node, _PointNet2Fn._backward_cls):
+        return None
+    if cov32 is not cov or proba32 is not proba or cov.output_nr != 0 or proba.output_nr != 1:
+        return None
+    if tuple(cov.shape) != (B * N, 4) or tuple(proba.shape) != (B * N, 4):
+        return None
+    if not getattr(getattr(node, "model", None), "fuse_loss_backward", False) or getattr(node, "saved", None) is None:
+        return None
+    if getattr(node, "loss_node_claimed", False) or not ops.head_loss_route(B, N, D):
+        return None
+    node.loss_node_claimed = True
+    return node
 
 
 def projected_total_loss(coverages_pointwise, proba_pointwise, clouds, gt, pdf_all, args, geometry=None, model=None):
@@ -262,7 +357,10 @@ def projected_total_loss(coverages_pointwise, proba_pointwise, clouds, gt, pdf_a
     geometry pass at hand (`geometry.p2_pix`: `model.p2_diam_pix = args.diam_pix`) the two are ONE autograd node over three
     launches -- the scatter of the coverages beside the pointwise loss sums, the per-plot finalisation whose last workgroup adds
     the loss up, and one backward pass that writes both gradients; same pred, same gradients (bits), the loss to fp64
-    re-association.  Without them: the two calls."""
+    re-association.  Without them: the two calls.
+    Where cov and proba are the two outputs of ONE network node whose model has `fuse_loss_backward` on, and the library takes the
+    sizes (`ops.head_loss_route`), that backward pass is no launch at all: the head backward computes both gradients from the
+    loss's inputs (`PendingLossGrad`; the same gradient bits, csrc/loss_grad.h)."""
     from .project_to_2d import project_to_plotwise_coverages
     pix = getattr(geometry, "p2_pix", None) if geometry is not None else None
     B = clouds.shape[0]
@@ -277,6 +375,8 @@ def projected_total_loss(coverages_pointwise, proba_pointwise, clouds, gt, pdf_a
     with torch.cuda.device(dev):
         gt = gt.to(device=dev, dtype=torch.float64).contiguous()
         pdf_all = pdf_all.to(device=dev, dtype=torch.float64).contiguous()
-        total, l_abs, l_log, l_e, pred = _ProjectedLoss.apply(coverages_pointwise.float().contiguous(), proba_pointwise.float().contiguous(),
-                                                              pix, gt, pdf_all, B, N, int(args.diam_pix), float(args.m), float(args.e))
+        cov32, proba32 = coverages_pointwise.float().contiguous(), proba_pointwise.float().contiguous()
+        total, l_abs, l_log, l_e, pred = _ProjectedLoss.apply(cov32, proba32, pix, gt, pdf_all, B, N, int(args.diam_pix), float(args.m),
+                                                              float(args.e), _fused_net_node(coverages_pointwise, proba_pointwise, cov32,
+                                                                                             proba32, B, N, int(args.diam_pix)))
     return total, (l_abs, l_log, l_e), pred

@@ -114,7 +114,19 @@ class _PointNet2Fn(torch.autograd.Function):
         # (after an eval-mode forward -- BatchNorm on its running statistics, model/point_net2.py:45-53 -- the gradient is the
         # running-statistics one, gamma * invstd * dy: the forward kept what a training forward keeps and marked its blocks
         # `frozen`, sn2_block.frozen_stats; round 5)
-        grads = ctx.model._backward_impl(ctx.saved, dcov, dproba)
+        # the loss node may have left its gradient as a descriptor (losses.PendingLossGrad) and two placeholders: if BOTH incoming
+        # gradients are exactly those, the head backward computes them itself; otherwise cov or proba had another consumer and
+        # autograd summed something onto a placeholder (a zero): the descriptor is materialised and added.  Cleared either way.
+        pending = ctx.__dict__.pop("loss_grad", None)
+        loss = None
+        if pending is not None:
+            if pending.is_placeholder(dcov) and pending.is_placeholder(dproba):
+                loss, dcov, dproba = pending.desc(), None, None
+            else:
+                gc, gp = pending.materialize()
+                dcov = gc if (dcov is None or pending.is_placeholder(dcov)) else dcov + gc
+                dproba = gp if (dproba is None or pending.is_placeholder(dproba)) else dproba + gp
+        grads = ctx.model._backward_impl(ctx.saved, dcov, dproba) if loss is None else ctx.model._backward_impl(ctx.saved, None, None, loss=loss)
         ctx.saved = None
         return (None, None, None, None, None, None) + tuple(grads)
 
@@ -186,6 +198,9 @@ class PointNet2(nn.Module):
     # training: SA3, its BatchNorm, the plot max, FP3 and its BatchNorm in one launch (sn2_global_level_forward) instead of five;
     # its workgroups exchange the batch statistics among themselves -- False where other processes share the device
     fuse_global_level = os.environ.get("SN2_FUSE_GLOBAL_LEVEL", "1") == "1"
+    # training: `losses.projected_total_loss` hands this model's backward pass the loss gradient as a descriptor and the head
+    # backward computes d loss / d coverages and d loss / d proba itself (sn2_head.loss) -- no sn2_projected_loss_backward launch
+    fuse_loss_backward = os.environ.get("SN2_FUSE_LOSS_BACKWARD", "1") == "1"
     # additive: a geometry pass that is handed the batch's `cloud` also does the two INPUT-only pieces of the feature pass --
     # the level-0 rows (`sn2_pack_rows`: 12 us of the step's critical path at C2) and, when `p2_diam_pix` is set (to
     # args.diam_pix), the pixel ids of `project_to_plotwise_coverages` (project_to_2d.py:16-22: a function of x, y only; 10 us) --
@@ -769,9 +784,10 @@ class PointNet2(nn.Module):
                            skip=s.rows0[:, 0:8], row_perm=getattr(s, "rank1", None), **kw)
 
     # ------------------------------------------------------------------------------------------ backward
-    def _backward_impl(self, s, dcov, dproba):
+    def _backward_impl(self, s, dcov, dproba, loss=None):
+        """loss: a `hip_ops.loss_grad_desc` in place of both gradients (the fused route of `losses.projected_total_loss`)"""
         if isinstance(s, X.NetSaved):
-            return X.backward(self, s, dcov, dproba)
+            return X.backward(self, s, dcov, dproba, loss=loss)
         dev = s.xyz.device
         B, N, M1, M2 = s.B, s.N, s.M1, s.M2
         params = self._params()
@@ -792,7 +808,7 @@ class PointNet2(nn.Module):
         dy1 = torch.empty(B * N, 36, dtype=s.h1.dtype, device=dev)
         hg = (views[id(self.lin1.weight)], views[id(self.lin1.bias)], views[id(self.lin2.weight)], views[id(self.lin2.bias)])
         hd = ops.head_desc(s.h1, s.b_fp1.a, s.b_fp1.c, self.lin1, self.lin2, dcov=dcov, dproba=dproba, dy=dy1, grads=hg,
-                           grad_images=images, drop_mask=getattr(s, "drop_keep", None), drop_p=self.drop)
+                           grad_images=images, drop_mask=getattr(s, "drop_keep", None), drop_p=self.drop, loss=loss)
         ops.head_backward(hd)
         # FP1's BatchNorm gradients fall out of lin1's (hip_ops.head_bn_sums): no extra pass over the B*N rows
         bn1 = self.fp1_module.nn[0][2]

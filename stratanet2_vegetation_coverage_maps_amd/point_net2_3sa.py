@@ -307,7 +307,7 @@ class PointNet2ThreeSA(PointNet2):
                            skip=s.x2, **kw)
 
     # ------------------------------------------------------------------------------------------ backward
-    def _backward_impl(self, s, dcov, dproba):
+    def _backward_impl(self, s, dcov, dproba, loss=None):
         dev = s.xyz.device
         B, N, M1, M2, M3 = s.B, s.N, s.M1, s.M2, s.M3
         params = list(self.parameters())
@@ -323,7 +323,7 @@ class PointNet2ThreeSA(PointNet2):
         dy1 = torch.empty(B * N, 36, dtype=s.h1.dtype, device=dev)
         hg = (views[id(self.lin1.weight)], views[id(self.lin1.bias)], views[id(self.lin2.weight)], views[id(self.lin2.bias)])
         hd = ops.head_desc(s.h1, s.b_fp1.a, s.b_fp1.c, self.lin1, self.lin2, dcov=dcov, dproba=dproba, dy=dy1, grads=hg,
-                           grad_images=images, drop_mask=getattr(s, "drop_keep", None), drop_p=self.drop)
+                           grad_images=images, drop_mask=getattr(s, "drop_keep", None), drop_p=self.drop, loss=loss)
         ops.head_backward(hd)
         bn_ok = torch.empty(4, dtype=I32, device=dev)
 
