@@ -685,10 +685,26 @@ int sn2_plot_losses(const float *coverages, const int *pix, const float *proba, 
                     int D, double m, double e, void *ws, float *pred, double *out, void *stream);
 
 /* ---- optimiser step of the timed training step -- torch.optim.Adam as configured in learning/train.py:180-185
- * (L2 weight decay added to the gradient), on flat buffers; grad_scale multiplies the gradient first (1/world). */
+ * (L2 weight decay added to the gradient), on flat buffers; grad_scale multiplies the gradient first (1/world).
+ * The learning rate is a by-value argument here: a launch captured into a hipGraph keeps the rate of its capture.  The ABI keeps
+ * this form (same kernel as sn2_adam_step_dev with no device word and no meter; same bits). */
 int sn2_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int *step_dev /* two device ints: {steps taken so far (incremented here), 0} */,
                   float grad_scale, void *stream);
+
+/* The same step with the learning rate read from ONE device word, *lr_dev (fp32), at launch time on the device: whoever writes
+ * that word in stream order between two launches -- or between two replays of a graph that holds this launch -- sets the rate of
+ * the next step (torch's StepLR, learning/train.py:152,185).  For the same rate value the results are sn2_adam_step's, bit for bit.
+ * Epoch meter (learning/train.py:68-79 reports the epoch means of the loss terms): n_terms > 0 adds this step's loss terms,
+ * terms[0 .. n_terms) (fp64, written by kernels earlier on the stream), to meter[0 .. n_terms) and 1 to meter[SN2_METER_TERMS];
+ * meter = SN2_METER_TERMS + 1 doubles = the sums, then the number of steps added.  The ONE thread of the launch that advances
+ * step_dev does it, with plain loads and stores: no atomics, no launch of its own.  n_terms == 0: terms and meter may be NULL and
+ * are not touched.  SN2_EINVAL before any device work: lr_dev NULL, n_terms outside 0 .. SN2_METER_TERMS, n_terms > 0 with terms
+ * or meter NULL, and everything sn2_adam_step refuses. */
+#define SN2_METER_TERMS 4
+int sn2_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int n, const float *lr_dev, float beta1,
+                      float beta2, float eps, float weight_decay, int *step_dev, float grad_scale, const double *terms, int n_terms,
+                      double *meter, void *stream);
 
 /* ==== the whole network behind ONE call per pass (round 5) ===================================================
  * PointNet2.forward of the reference (model/point_net2.py:106-153) is ~25 of the entry points above in a fixed order, and
@@ -842,10 +858,16 @@ int sn2_net_backward(const sn2_net_model *m, const sn2_net_dims *d, const sn2_ne
 
 /* sn2_grad_reduce + sn2_adam_step in one launch, for a step with no exchange between them: grad_images = the `replicas` images
  * of the flat gradient (image stride `stride` floats); image 0 holds the folded gradient afterwards (same additions, same order
- * as sn2_grad_reduce).  sn2_net_bwd.defer_grad_reduce makes sn2_net_backward leave the images unfolded for it. */
+ * as sn2_grad_reduce).  sn2_net_bwd.defer_grad_reduce makes sn2_net_backward leave the images unfolded for it.  The learning
+ * rate is by value, as in sn2_adam_step: fixed at capture time. */
 int sn2_adam_step_images(float *param, float *grad_images, int replicas, int stride, float *exp_avg, float *exp_avg_sq, int n,
                          float lr, float beta1, float beta2, float eps, float weight_decay, int *step_dev, float grad_scale,
                          void *stream);
+/* sn2_adam_step_images with the learning rate in a device word and the optional epoch meter, exactly as sn2_adam_step_dev is to
+ * sn2_adam_step (same bits for the same rate; the same additional SN2_EINVAL cases). */
+int sn2_adam_step_images_dev(float *param, float *grad_images, int replicas, int stride, float *exp_avg, float *exp_avg_sq, int n,
+                             const float *lr_dev, float beta1, float beta2, float eps, float weight_decay, int *step_dev,
+                             float grad_scale, const double *terms, int n_terms, double *meter, void *stream);
 
 /* ==== Routes =================================================================================================
  * Which kernel a size takes, and therefore which workspaces exist, stated ONCE: each predicate is host-only arithmetic (no HIP

@@ -20,7 +20,7 @@ CONSTANTS = {
     "SN2_GLOBAL_MAX_PLOTS": 28, "SN2_GLOBAL_CTL_WORDS": 8, "SN2_GLOBAL_BWD_MAX_ROWS": 256,
     "SN2_GLOBAL_BWD_XCHG_WORDS": 2 * 28 * 128, "SN2_GLOBAL_BWD_CTL_WORDS": 64,
     "SN2_MOSAIC_HIST_WORDS": 10004, "SN2_KDE_FIT_MAX_K": 65536, "SN2_LOSS_BLOCKS": 1024, "SN2_PROJECTED_LOSS_WS": 2 * 512 + 2,
-    "SN2_NET_GRAD_IMAGES": 32,
+    "SN2_NET_GRAD_IMAGES": 32, "SN2_METER_TERMS": 4,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
     "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256,
 }
@@ -197,6 +197,8 @@ SIGNATURES = {
                           c_void_p, c_void_p],
     "sn2_adam_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float,
                       c_void_p, c_float, c_void_p],
+    "sn2_adam_step_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_float,
+                          c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p],
     "sn2_projected_loss_forward": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_projected_loss_backward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
@@ -205,6 +207,8 @@ SIGNATURES = {
                         c_void_p, c_void_p],
     "sn2_adam_step_images": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float,
                              c_void_p, c_float, c_void_p],
+    "sn2_adam_step_images_dev": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float, c_float,
+                                 c_float, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p],
     "sn2_net_ctx_create": [POINTER(c_void_p)],
     "sn2_net_ctx_destroy": [c_void_p],
     "sn2_net_geo_carve": [POINTER(NetModel), POINTER(NetDims), c_void_p, POINTER(NetGeo), POINTER(ctypes.c_size_t)],

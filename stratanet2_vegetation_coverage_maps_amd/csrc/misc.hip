@@ -283,33 +283,57 @@ extern "C" int sn2_global_pool_backward(const float* du, int du_stride, const in
 // corrections.  step[0] = steps taken so far, step[1] = arrival ticket (zero between launches): every workgroup reads
 // step[0] before it takes a ticket, and the workgroup that takes the last one stores the incremented count -- one launch
 // (a one-thread "tick" kernel in front of this one was 4 us of every step).
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int n, float lr, float b1, float b2, float eps,
-                                                   float wd, int* __restrict__ step, float gscale) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int now = __hip_atomic_load(&step[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-    if (i < n) {
-        const float t = (float)now;
-        const float bc1 = 1.f - powf(b1, t);
-        const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
-        float grad = g[i] * gscale;
-        const float pi = p[i];
-        grad = fmaf(wd, pi, grad);
-        const float mi = m[i] + (1.f - b1) * (grad - m[i]);       // lerp, as torch
-        const float vi = b2 * v[i] + (1.f - b2) * grad * grad;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - (lr / bc1) * (mi / denom);
-    }
+// The learning rate lives there for the same reason: lr_dev (non-NULL: sn2_adam_step*_dev) is ONE device word every thread reads
+// in place of the by-value `lr` -- a uniform address, one scalar load per wave -- so a schedule is a stream-ordered write of that
+// word between replays and the arithmetic below never learns where its rate came from.
+namespace {
+// One element of the update, stated once for both kernels: `gsum` is the (folded) gradient, `now` the step number t >= 1.
+__device__ __forceinline__ void adam_update(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, int i, float gsum,
+                                            int now, float lr, float b1, float b2, float eps, float wd, float gscale) {
+    const float t = (float)now;
+    const float bc1 = 1.f - powf(b1, t);
+    const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
+    float grad = gsum * gscale;
+    const float pi = p[i];
+    grad = fmaf(wd, pi, grad);
+    const float mi = m[i] + (1.f - b1) * (grad - m[i]);       // lerp, as torch
+    const float vi = b2 * v[i] + (1.f - b2) * grad * grad;
+    m[i] = mi;
+    v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = pi - (lr / bc1) * (mi / denom);
+}
+
+// The end of a launch, also stated once: thread 0 of every workgroup takes a ticket; the one thread of the launch that takes
+// the LAST one (all workgroups have read step[0]) advances the count and -- n_terms > 0 -- adds this step's loss terms to the
+// epoch meter: meter[j] += terms[j], meter[SN2_METER_TERMS] += 1.  Exactly one thread per launch touches the meter, the kernels
+// that wrote `terms` precede this one in stream order and so does the previous step's launch: plain loads and stores, no atomics.
+__device__ __forceinline__ void adam_arrive(int* __restrict__ step, int now, const double* __restrict__ terms, int n_terms,
+                                            double* __restrict__ meter) {
     __syncthreads();                                               // every wave of this workgroup has its count
     if (threadIdx.x == 0) {
         const int ticket = atomicAdd(&step[1], 1);
-        if (ticket == (int)gridDim.x - 1) {                        // all workgroups have read step[0]
+        if (ticket == (int)gridDim.x - 1) {
             __hip_atomic_store(&step[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&step[0], now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (n_terms > 0) {
+                for (int j = 0; j < n_terms; ++j) meter[j] += terms[j];
+                meter[SN2_METER_TERMS] += 1.0;
+            }
         }
     }
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int n, float lr, const float* __restrict__ lr_dev,
+                                                   float b1, float b2, float eps, float wd, int* __restrict__ step, float gscale,
+                                                   const double* __restrict__ terms, int n_terms, double* __restrict__ meter) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int now = __hip_atomic_load(&step[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+    if (lr_dev) lr = lr_dev[0];
+    if (i < n) adam_update(p, m, v, i, g[i], now, lr, b1, b2, eps, wd, gscale);
+    adam_arrive(step, now, terms, n_terms, meter);
 }
 
 // The same step with the gradient still spread over `replicas` images (sn2_block.grad_replicas): folds them exactly as
@@ -317,10 +341,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // are right after the step -- and updates.  One launch instead of sn2_grad_reduce + sn2_adam_step where nothing (no exchange
 // between ranks) needs the folded gradient in between.
 __global__ __launch_bounds__(256) void adam_images_kernel(float* __restrict__ p, float* __restrict__ flat, int replicas, int stride,
-                                                          float* __restrict__ m, float* __restrict__ v, int n, float lr, float b1,
-                                                          float b2, float eps, float wd, int* __restrict__ step, float gscale) {
+                                                          float* __restrict__ m, float* __restrict__ v, int n, float lr,
+                                                          const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd,
+                                                          int* __restrict__ step, float gscale, const double* __restrict__ terms,
+                                                          int n_terms, double* __restrict__ meter) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int now = __hip_atomic_load(&step[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+    if (lr_dev) lr = lr_dev[0];
     if (i < n) {
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
         int r = 1;
@@ -333,28 +360,17 @@ __global__ __launch_bounds__(256) void adam_images_kernel(float* __restrict__ p,
         for (; r < replicas; ++r) s0 += flat[(size_t)r * stride + i];
         const float gsum = flat[i] + ((s0 + s1) + (s2 + s3));
         flat[i] = gsum;
-        const float t = (float)now;
-        const float bc1 = 1.f - powf(b1, t);
-        const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
-        float grad = gsum * gscale;
-        const float pi = p[i];
-        grad = fmaf(wd, pi, grad);
-        const float mi = m[i] + (1.f - b1) * (grad - m[i]);
-        const float vi = b2 * v[i] + (1.f - b2) * grad * grad;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - (lr / bc1) * (mi / denom);
+        adam_update(p, m, v, i, gsum, now, lr, b1, b2, eps, wd, gscale);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int ticket = atomicAdd(&step[1], 1);
-        if (ticket == (int)gridDim.x - 1) {
-            __hip_atomic_store(&step[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&step[0], now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    adam_arrive(step, now, terms, n_terms, meter);
 }
+
+namespace {
+// the checks the two _dev entry points add to their siblings'
+inline bool adam_dev_args_ok(const float* lr_dev, const double* terms, int n_terms, const double* meter) {
+    return lr_dev && n_terms >= 0 && n_terms <= SN2_METER_TERMS && (n_terms == 0 || (terms && meter));
+}
+}  // namespace
 
 extern "C" int sn2_adam_step_images(float* param, float* grad_images, int replicas, int stride, float* exp_avg, float* exp_avg_sq,
                                     int n, float lr, float beta1, float beta2, float eps, float weight_decay, int* step_dev,
@@ -362,7 +378,21 @@ extern "C" int sn2_adam_step_images(float* param, float* grad_images, int replic
     if (!param || !grad_images || !exp_avg || !exp_avg_sq || !step_dev || n <= 0 || replicas < 1 || (replicas > 1 && stride < n))
         return SN2_EINVAL;
     hipLaunchKernelGGL(adam_images_kernel, dim3(sn2_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad_images, replicas,
-                       stride, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, grad_scale);
+                       stride, exp_avg, exp_avg_sq, n, lr, (const float*)nullptr, beta1, beta2, eps, weight_decay, step_dev,
+                       grad_scale, (const double*)nullptr, 0, (double*)nullptr);
+    SN2_RETURN_LAUNCH();
+}
+
+extern "C" int sn2_adam_step_images_dev(float* param, float* grad_images, int replicas, int stride, float* exp_avg,
+                                        float* exp_avg_sq, int n, const float* lr_dev, float beta1, float beta2, float eps,
+                                        float weight_decay, int* step_dev, float grad_scale, const double* terms, int n_terms,
+                                        double* meter, void* stream) {
+    if (!param || !grad_images || !exp_avg || !exp_avg_sq || !step_dev || n <= 0 || replicas < 1 || (replicas > 1 && stride < n))
+        return SN2_EINVAL;
+    if (!adam_dev_args_ok(lr_dev, terms, n_terms, meter)) return SN2_EINVAL;
+    hipLaunchKernelGGL(adam_images_kernel, dim3(sn2_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad_images, replicas,
+                       stride, exp_avg, exp_avg_sq, n, 0.f, lr_dev, beta1, beta2, eps, weight_decay, step_dev, grad_scale, terms,
+                       n_terms, meter);
     SN2_RETURN_LAUNCH();
 }
 
@@ -371,7 +401,18 @@ extern "C" int sn2_adam_step(float* param, const float* grad, float* exp_avg, fl
                              void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !step_dev || n <= 0) return SN2_EINVAL;
     hipLaunchKernelGGL(adam_kernel, dim3(sn2_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                       exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, grad_scale);
+                       exp_avg_sq, n, lr, (const float*)nullptr, beta1, beta2, eps, weight_decay, step_dev, grad_scale,
+                       (const double*)nullptr, 0, (double*)nullptr);
+    SN2_RETURN_LAUNCH();
+}
+
+extern "C" int sn2_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int n, const float* lr_dev,
+                                 float beta1, float beta2, float eps, float weight_decay, int* step_dev, float grad_scale,
+                                 const double* terms, int n_terms, double* meter, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !step_dev || n <= 0) return SN2_EINVAL;
+    if (!adam_dev_args_ok(lr_dev, terms, n_terms, meter)) return SN2_EINVAL;
+    hipLaunchKernelGGL(adam_kernel, dim3(sn2_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                       exp_avg_sq, n, 0.f, lr_dev, beta1, beta2, eps, weight_decay, step_dev, grad_scale, terms, n_terms, meter);
     SN2_RETURN_LAUNCH();
 }
 

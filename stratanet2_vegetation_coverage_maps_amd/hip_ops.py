@@ -1537,6 +1537,39 @@ def adam_step_images(param, arena, replicas, stride, exp_avg, exp_avg_sq, lr, be
           beta2, eps, weight_decay, _ptr(step_dev), grad_scale, _stream())
 
 
+METER_TERMS = _lib.SN2_METER_TERMS           # sums of the optimiser's epoch meter (followed by the number of steps added)
+
+
+def _chk_lr_meter(lr_dev, terms, meter, who):
+    """The arguments sn2_adam_step_dev / sn2_adam_step_images_dev add: lr_dev fp32 (1,); terms None or fp64, contiguous, 1 to
+    METER_TERMS elements, then meter fp64 (METER_TERMS + 1,).  -> n_terms"""
+    _chk(lr_dev, F32, (1,), "lr_dev")
+    if terms is None:
+        return 0
+    _chk(terms, F64, None, "terms")
+    if not 1 <= terms.numel() <= METER_TERMS:
+        raise ValueError(f"{who}: terms holds {terms.numel()} values, the meter takes 1 to {METER_TERMS}")
+    _chk(meter, F64, (METER_TERMS + 1,), "meter")
+    return terms.numel()
+
+
+def adam_step_images_dev(param, arena, replicas, stride, exp_avg, exp_avg_sq, lr_dev, beta1, beta2, eps, weight_decay, step_dev,
+                         grad_scale=1.0, terms=None, meter=None):
+    """include/strata_hip.h: sn2_adam_step_images_dev -- adam_step_images with the learning rate read from the device word
+    `lr_dev` when the kernel runs, and `terms` (this step's loss terms) added to `meter` by the launch's last thread."""
+    n = param.numel()
+    for t, nme in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, F32, (n,), nme)
+    _chk(arena, F32, None, "arena")
+    if arena.numel() < replicas * stride or stride < n:
+        raise ValueError("adam_step_images_dev: arena smaller than its images")
+    _chk(step_dev, I32, (2,), "step_dev")
+    n_terms = _chk_lr_meter(lr_dev, terms, meter, "adam_step_images_dev")
+    _call("sn2_adam_step_images_dev", _ptr(param), _ptr(arena), int(replicas), int(stride), _ptr(exp_avg), _ptr(exp_avg_sq), n,
+          _ptr(lr_dev), beta1, beta2, eps, weight_decay, _ptr(step_dev), grad_scale, _ptr(terms), n_terms,
+          _ptr(meter) if n_terms else None, _stream())
+
+
 def loss_term_forward(kind: int, x: torch.Tensor, y: Optional[torch.Tensor]):
     """ONE term of the loss (the reference's loop calls them one by one, learning/train.py:58-60) -> out (4,) fp64 with
     out[kind] = the term: kind 1 = absolute (x = pred (B,4), y = gt (B,4) fp64), 2 = NLL (x = proba (R,4), y = pdf (R,3) fp64),
@@ -1582,3 +1615,17 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_de
     _chk(step_dev, I32, (2,), "step_dev")
     _call("sn2_adam_step", _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, lr, beta1, beta2, eps,
           weight_decay, _ptr(step_dev), grad_scale, _stream())
+
+
+def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, beta1, beta2, eps, weight_decay, step_dev, grad_scale=1.0, terms=None,
+                  meter=None):
+    """include/strata_hip.h: sn2_adam_step_dev -- adam_step with the learning rate read from the device word `lr_dev` (fp32 (1,))
+    when the kernel runs: a launch captured into a hipGraph follows whatever is written there between replays.  terms (fp64, 1 to
+    METER_TERMS values written earlier on the stream) are added to meter (fp64 (METER_TERMS + 1,): sums, then steps)."""
+    n = param.numel()
+    for t, nme in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, F32, (n,), nme)
+    _chk(step_dev, I32, (2,), "step_dev")
+    n_terms = _chk_lr_meter(lr_dev, terms, meter, "adam_step_dev")
+    _call("sn2_adam_step_dev", _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, _ptr(lr_dev), beta1, beta2, eps,
+          weight_decay, _ptr(step_dev), grad_scale, _ptr(terms), n_terms, _ptr(meter) if n_terms else None, _stream())

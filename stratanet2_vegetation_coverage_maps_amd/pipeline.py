@@ -255,9 +255,7 @@ class TrainPipeline:
             if self.split_exchange:
                 g2 = torch.cuda.CUDAGraph()
                 with ops.graph_capture(g2, self.dev, pool=pool):
-                    ops.adam_step(self.opt.flat, self.flat_grad[k], self.opt.exp_avg, self.opt.exp_avg_sq, self.opt.lr,
-                                  self.opt.betas[0], self.opt.betas[1], self.opt.eps, self.opt.weight_decay,
-                                  self.opt.step_words, 1.0 / world)
+                    self.opt.update(self.flat_grad[k], 1.0 / world)      # (the terms the feature pass tracked: into the meter)
                 self.graph_opt[k] = g2
         torch.cuda.synchronize(self.dev)
 
