@@ -236,6 +236,40 @@ size_t sn2_subsample_ws_words(int B, int n_max, int N, int form);
 int sn2_subsample(const int *offsets, int extra, int n_max, int B, int N, unsigned long long seed, const long long *plot_keys,
                   int form, int *ws, size_t ws_words, int *idx, void *stream);
 
+/* ---- a training batch from a plot set resident on the device (csrc/feed.hip): load_cloud(train=True) of the reference
+ * (data_loader/loader.py:73-87) for B plots picked by an id table ON THE DEVICE, written straight into the caller's buffers in
+ * stream order, no host read: centre, fake ground points, rotate, flip, clipped gaussian noise, rescale, subsample gather -- the
+ * arithmetic of sn2_prepare_plots, the draws from the generator of sn2_subsample.  No noise tensor exists anywhere.
+ * The set: raw (10,T) fp32 (channels as sn2_prepare_plots), offsets (P+1), centers (P,2) fp32, coverages (P,4) fp64; T < 2^31.
+ * plot_ids (B) int32 on the device, any order, need not be adjacent; EVERY id must be in [0, P): the caller checks that on the
+ * host copy the table was made from (the kernels do not).  n_max: the caller's bound on offsets[p+1] - offsets[p] + n_fake over
+ * the set (as sn2_subsample's).  cos_sin (360,2) fp64: cos and sin of 0 .. 359 degrees as the host computes them (numpy:
+ * cos(radians(a))), read, not recomputed, so the rotation is the host's bit for bit.  train = 0: no rotation, flip or noise
+ * (load_cloud(train=False)); noise = 0: train without the noise.
+ * Outputs: cloud (B,10,N), xyz (B,3,N), gt (B,4) fp64 = the plots' coverages rows, fps_start (2,B) int32.
+ *
+ * Draws: Philox4x32-10 exactly as under sn2_subsample, key (k0,k1) = seed, counter (i, c1, key.lo, key.hi) with the plot's
+ * key = epoch * P + plot id: a plot's rows depend on (seed, epoch, plot id, N) alone -- not on B, its place in the batch or the
+ * buffers.  c1 separates the domains, w0..w3 are the four output words:
+ *   c1 = 0         the subsample: sn2_subsample's row for (seed, key), candidates = the plot's raw points then the fake ones;
+ *   c1 = 1, i = 0  flip_x = w0 >> 31, flip_y = w1 >> 31, angle in whole degrees = (w2 * 360) >> 32 (numpy's choice(360));
+ *   c1 = 1, i = 1  fps_start[0,b] = (w0 * N) >> 32, fps_start[1,b] = (w1 * M1) >> 32  (drawn with train = 0 too);
+ *   c1 = 2, 3, i = the SOURCE index of the point (its candidate number before subsampling, fake points included: duplicates
+ *                  of a point share their noise, as in the reference): two Box-Muller pairs per call, all in fp64, from
+ *                  (wa, wb) = (w0, w1), then (w2, w3):  u1 = (wa + 1) 2^-32, u2 = wb 2^-32, r = sqrt(-2 ln u1),
+ *                  t = 6.283185307179586 u2, pair = (r cos t, r sin t).  c1 = 2 gives the deviates of x, y, red, green in that
+ *                  order, c1 = 3 those of blue and near_infrared (its second pair is unused).
+ *                  noise term = fp32(clamp(0.1 g, -c, c)), c = 0.3 for x, y and 0.03 * 65536 for the colours (the colours' sigma
+ *                  IS the xy sigma: loader.py:180,202), added in fp32 after rotation and flips.
+ * ws: 16-byte aligned, *words of sn2_train_batch_ws_words(B, n_max, N, &words) 32-bit words (8 B when n_max <= N: no plot of the
+ * set is subsampled without replacement, and no index row is written).  NULL buffers, B, N, P, M1, n_max <= 0, epoch < 0, a small
+ * or misaligned workspace: SN2_EINVAL; T >= 2^31 or B > 65535: SN2_ELIMIT -- all before any device work. */
+int sn2_train_batch_ws_words(int B, int n_max, int N, size_t *words);
+int sn2_train_batch(const float *raw, long T, const int *offsets, const float *centers, const double *coverages, int P,
+                    const int *plot_ids, int B, const float *fake_xy, int n_fake, int n_max, int N, int M1, float z_max,
+                    unsigned long long seed, long long epoch, const double *cos_sin, int train, int noise, int *ws,
+                    size_t ws_words, float *cloud, float *xyz, double *gt, int *fps_start, void *stream);
+
 /* z-normalisation of a raw plot (offline preparation): z_i - min{ z_j : |xy_i - xy_j| <= radius } --
  * normalize_z_with_minz_in_a_radius, utils/load_data.py:237-249 (sklearn kd-tree radius query in x,y + a python loop).
  * x, y, z (n) fp32; the test is sklearn's: fp64 reduced distance dx*dx + dy*dy <= radius*radius, inclusive.

@@ -156,6 +156,10 @@ SIGNATURES = {
     "sn2_subsample_form": [c_int, c_int],
     "sn2_subsample": [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_void_p, ctypes.c_size_t,
                       c_void_p, c_void_p],
+    "sn2_train_batch_ws_words": [c_int, c_int, c_int, POINTER(ctypes.c_size_t)],
+    "sn2_train_batch": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                        c_float, ctypes.c_ulonglong, c_longlong, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p,
+                        c_void_p, c_void_p, c_void_p],
     "sn2_sa_order": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "sn2_sa_order_group": [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_sa_forward": [POINTER(SA), c_int, c_void_p],

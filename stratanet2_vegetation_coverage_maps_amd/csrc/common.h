@@ -82,6 +82,11 @@ static inline int sn2_cu_count() {
     return n;
 }
 
+// sn2_subsample (sample.hip) for plots gathered from a resident set: plot b of the batch is entry ids[b] (device, B ints) of
+// `offsets`; ids == NULL is sn2_subsample itself.  Used by sn2_train_batch (feed.hip).
+int sn2_subsample_ids(const int* offsets, const int* ids, int extra, int n_max, int B, int N, unsigned long long seed,
+                      const long long* plot_keys, int form, int* ws, size_t ws_words, int* idx, hipStream_t stream);
+
 // ---- wave-uniform read-only tables (weights, BN constants) -------------------------------------------------------
 // `cfp` = the same global memory viewed through the CONSTANT address space: uniform loads from it always become
 // s_load (the memory is not written while the kernel runs).  `opaque()` hides a pointer's provenance from the

@@ -20,6 +20,7 @@
 //   form 2 (global): the same four steps as four launches over a workspace, any n; many workgroups per plot, no waiting
 //                    of one workgroup on another.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -40,20 +41,9 @@ inline int bucket_bits(int n_max, int lo, int hi) {
     return h < hl ? hl : (h > hh ? hh : h);
 }
 
-// Philox4x32-10 (Salmon et al., SC'11): counter (i, 0, key.lo, key.hi), key (seed.lo, seed.hi); u = word0 << 32 | word1
+// u(seed, key, i): philox.h (counter (i, 0, key.lo, key.hi), key (seed.lo, seed.hi); u = word0 << 32 | word1)
 __device__ __forceinline__ unsigned long long philox_u(unsigned long long seed, long long key, unsigned i) {
-    unsigned c0 = i, c1 = 0u, c2 = (unsigned)(unsigned long long)key, c3 = (unsigned)((unsigned long long)key >> 32);
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return ((unsigned long long)c0 << 32) | c1;
+    return sn2_philox_u(seed, key, i);
 }
 
 // first word of the pairs in form 2's workspace (8-byte aligned)
@@ -71,8 +61,11 @@ __device__ __forceinline__ bool pair_less(Pair a, Pair b, unsigned long long see
     return ua != ub ? ua < ub : a.i < b.i;
 }
 
-__device__ __forceinline__ int plot_candidates(const int* __restrict__ offs, int b, int extra, int n_max) {
-    const long n = (long)offs[b + 1] - offs[b] + extra;
+// ids (sn2_train_batch: the plots of a batch gathered from a resident set) or NULL: plot b is entry ids[b] / b of `offs`
+__device__ __forceinline__ int plot_candidates(const int* __restrict__ offs, const int* __restrict__ ids, int b, int extra,
+                                               int n_max) {
+    const int p = ids ? ids[b] : b;
+    const long n = (long)offs[p + 1] - offs[p] + extra;
     return n > n_max ? n_max : (n < 0 ? 0 : (int)n);
 }
 
@@ -124,15 +117,16 @@ __device__ __forceinline__ void scan_buckets(int* h, int nb, int N, int* s_wave,
 }
 
 // ---- form 1 -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void subsample_lds_kernel(const int* __restrict__ offs, int extra, int n_max, int N,
-                                                             unsigned long long seed, const long long* __restrict__ keys,
-                                                             int H, unsigned mid_mask, int* __restrict__ idx) {
+__global__ __launch_bounds__(1024) void subsample_lds_kernel(const int* __restrict__ offs, const int* __restrict__ ids, int extra,
+                                                             int n_max, int N, unsigned long long seed,
+                                                             const long long* __restrict__ keys, int H, unsigned mid_mask,
+                                                             int* __restrict__ idx) {
     extern __shared__ __attribute__((aligned(16))) int s_mem[];    // [NB] bucket starts / cursors | [n_max] pairs | scan scratch
     const int NB = 1 << H, b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     int* s_hist = s_mem;
     Pair* s_pairs = (Pair*)(s_mem + NB);
     int* s_wave = s_mem + NB + 2 * n_max;                          // 16 wave totals + the last bucket
-    const int n = plot_candidates(offs, b, extra, n_max);
+    const int n = plot_candidates(offs, ids, b, extra, n_max);
     const long long key = keys[b];
     int* row = idx + (size_t)b * N;
     if (n <= N) {
@@ -158,11 +152,12 @@ __global__ __launch_bounds__(1024) void subsample_lds_kernel(const int* __restri
 }
 
 // ---- form 2: workspace = [B][NB] bucket starts / cursors | [B] last bucket of a plot (-1: n <= N) | [B][n_max] pairs ----
-__global__ __launch_bounds__(256) void subsample_hist_kernel(const int* __restrict__ offs, int extra, int n_max, int N, int B,
+__global__ __launch_bounds__(256) void subsample_hist_kernel(const int* __restrict__ offs, const int* __restrict__ ids, int extra,
+                                                             int n_max, int N, int B,
                                                              unsigned long long seed, const long long* __restrict__ keys,
                                                              int H, int* __restrict__ ws) {
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        const int n = plot_candidates(offs, b, extra, n_max);
+        const int n = plot_candidates(offs, ids, b, extra, n_max);
         if (n <= N) continue;
         int* hist = ws + ((size_t)b << H);
         const long long key = keys[b];
@@ -171,12 +166,13 @@ __global__ __launch_bounds__(256) void subsample_hist_kernel(const int* __restri
     }
 }
 
-__global__ __launch_bounds__(1024) void subsample_scan_kernel(const int* __restrict__ offs, int extra, int n_max, int N, int B,
+__global__ __launch_bounds__(1024) void subsample_scan_kernel(const int* __restrict__ offs, const int* __restrict__ ids, int extra,
+                                                              int n_max, int N, int B,
                                                               int H, int* __restrict__ ws) {
     __shared__ int s_wave[17];
     const int b = blockIdx.x;
     int* last = ws + ((size_t)B << H) + b;
-    if (plot_candidates(offs, b, extra, n_max) <= N) {
+    if (plot_candidates(offs, ids, b, extra, n_max) <= N) {
         if (threadIdx.x == 0) *last = -1;
         return;
     }
@@ -184,13 +180,14 @@ __global__ __launch_bounds__(1024) void subsample_scan_kernel(const int* __restr
     if (threadIdx.x == 0) *last = s_wave[16];
 }
 
-__global__ __launch_bounds__(256) void subsample_scatter_kernel(const int* __restrict__ offs, int extra, int n_max, int B,
+__global__ __launch_bounds__(256) void subsample_scatter_kernel(const int* __restrict__ offs, const int* __restrict__ ids, int extra,
+                                                                int n_max, int B,
                                                                 unsigned long long seed, const long long* __restrict__ keys,
                                                                 int H, unsigned mid_mask, int* __restrict__ ws) {
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
         const int t = ws[((size_t)B << H) + b];
         if (t < 0) continue;
-        const int n = plot_candidates(offs, b, extra, n_max);
+        const int n = plot_candidates(offs, ids, b, extra, n_max);
         int* hist = ws + ((size_t)b << H);
         Pair* pairs = (Pair*)(ws + pairs_base(B, H)) + (size_t)b * n_max;
         const long long key = keys[b];
@@ -205,7 +202,8 @@ __global__ __launch_bounds__(256) void subsample_scatter_kernel(const int* __res
     }
 }
 
-__global__ __launch_bounds__(256) void subsample_rank_kernel(const int* __restrict__ offs, int extra, int n_max, int N, int B,
+__global__ __launch_bounds__(256) void subsample_rank_kernel(const int* __restrict__ offs, const int* __restrict__ ids, int extra,
+                                                             int n_max, int N, int B,
                                                              unsigned long long seed, const long long* __restrict__ keys,
                                                              int H, const int* __restrict__ ws, int* __restrict__ idx) {
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
@@ -214,7 +212,7 @@ __global__ __launch_bounds__(256) void subsample_rank_kernel(const int* __restri
         int* row = idx + (size_t)b * N;
         const int first = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
         if (t < 0) {
-            small_row(row, plot_candidates(offs, b, extra, n_max), N, seed, key, first, step);
+            small_row(row, plot_candidates(offs, ids, b, extra, n_max), N, seed, key, first, step);
             continue;
         }
         const int* hist = ws + ((size_t)b << H);
@@ -237,14 +235,15 @@ extern "C" size_t sn2_subsample_ws_words(int B, int n_max, int N, int form) {
     return pairs_base(B, bucket_bits(n_max, 1024, GLOBAL_MAX_BUCKETS)) + 2 * (size_t)B * (size_t)n_max;
 }
 
-extern "C" int sn2_subsample(const int* offsets, int extra, int n_max, int B, int N, unsigned long long seed,
-                             const long long* plot_keys, int form, int* ws, size_t ws_words, int* idx, void* stream) {
+// sn2_subsample with an optional id table on the device (common.h): plot b of the batch is plot ids[b] of `offsets`
+int sn2_subsample_ids(const int* offsets, const int* ids, int extra, int n_max, int B, int N, unsigned long long seed,
+                      const long long* plot_keys, int form, int* ws, size_t ws_words, int* idx, hipStream_t stream) {
     if (!offsets || !plot_keys || !idx || B <= 0 || N <= 0 || extra < 0 || n_max <= 0) return SN2_EINVAL;
     if (form < 0 || form > 7 || (form & 3) == 3) return SN2_EINVAL;
     const unsigned mid_mask = (form & SN2_SUBSAMPLE_COARSE) ? 0xC0000000u : 0xFFFFFFFFu;
     int f = form & 3;
     if (f == 0) f = sn2_subsample_form(n_max, N);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = stream;
     if (f == SN2_SUBSAMPLE_LDS) {
         if (n_max > LDS_MAX_N) return SN2_ELIMIT;
         const int H = bucket_bits(n_max, 256, LDS_MAX_BUCKETS);
@@ -254,7 +253,7 @@ extern "C" int sn2_subsample(const int* offsets, int extra, int n_max, int B, in
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         // few plots: sixteen waves per plot are the shortest pass; many: workgroups that find room beside other kernels
         const int threads = sn2_small_sort_wg(B) ? 512 : 1024;
-        hipLaunchKernelGGL(subsample_lds_kernel, dim3(B), dim3(threads), lds, st, offsets, extra, n_max, N, seed, plot_keys, H,
+        hipLaunchKernelGGL(subsample_lds_kernel, dim3(B), dim3(threads), lds, st, offsets, ids, extra, n_max, N, seed, plot_keys, H,
                            mid_mask, idx);
         SN2_RETURN_LAUNCH();
     }
@@ -266,14 +265,19 @@ extern "C" int sn2_subsample(const int* offsets, int extra, int n_max, int B, in
     const int gr = sn2_cdiv(nb > N ? nb : N, 256 * ITEMS) < 256 ? sn2_cdiv(nb > N ? nb : N, 256 * ITEMS) : 256;
     if (n_max > N) {
         sn2_fill_words(ws, 0u, (size_t)B << H, st);
-        hipLaunchKernelGGL(subsample_hist_kernel, dim3(gx, gy), dim3(256), 0, st, offsets, extra, n_max, N, B, seed, plot_keys, H,
-                           ws);
+        hipLaunchKernelGGL(subsample_hist_kernel, dim3(gx, gy), dim3(256), 0, st, offsets, ids, extra, n_max, N, B, seed, plot_keys,
+                           H, ws);
     }
-    hipLaunchKernelGGL(subsample_scan_kernel, dim3(B), dim3(1024), 0, st, offsets, extra, n_max, N, B, H, ws);
+    hipLaunchKernelGGL(subsample_scan_kernel, dim3(B), dim3(1024), 0, st, offsets, ids, extra, n_max, N, B, H, ws);
     if (n_max > N)
-        hipLaunchKernelGGL(subsample_scatter_kernel, dim3(gx, gy), dim3(256), 0, st, offsets, extra, n_max, B, seed, plot_keys, H,
-                           mid_mask, ws);
-    hipLaunchKernelGGL(subsample_rank_kernel, dim3(gr, gy), dim3(256), 0, st, offsets, extra, n_max, N, B, seed, plot_keys, H, ws,
-                       idx);
+        hipLaunchKernelGGL(subsample_scatter_kernel, dim3(gx, gy), dim3(256), 0, st, offsets, ids, extra, n_max, B, seed, plot_keys,
+                           H, mid_mask, ws);
+    hipLaunchKernelGGL(subsample_rank_kernel, dim3(gr, gy), dim3(256), 0, st, offsets, ids, extra, n_max, N, B, seed, plot_keys, H,
+                       ws, idx);
     SN2_RETURN_LAUNCH();
+}
+
+extern "C" int sn2_subsample(const int* offsets, int extra, int n_max, int B, int N, unsigned long long seed,
+                             const long long* plot_keys, int form, int* ws, size_t ws_words, int* idx, void* stream) {
+    return sn2_subsample_ids(offsets, nullptr, extra, n_max, B, N, seed, plot_keys, form, ws, ws_words, idx, (hipStream_t)stream);
 }

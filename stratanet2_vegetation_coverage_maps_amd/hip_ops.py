@@ -643,6 +643,48 @@ def subsample(offsets, extra: int, N: int, seed: int, plot_keys, n_max: Optional
     return idx
 
 
+def train_batch_ws_words(B: int, n_max: int, N: int) -> int:
+    """sn2_train_batch_ws_words of include/strata_hip.h: the 32-bit words of sn2_train_batch's workspace."""
+    words = ctypes.c_size_t()
+    check(_lib.load().sn2_train_batch_ws_words(int(B), int(n_max), int(N), ctypes.byref(words)), "sn2_train_batch_ws_words")
+    return int(words.value)
+
+
+def train_batch(raw, offsets, centers, coverages, plot_ids, fake_xy, n_max: int, M1: int, z_max: float, seed: int, epoch: int,
+                cos_sin, cloud, xyz, gt, fps_start, ws, train: bool = True, noise: bool = True):
+    """include/strata_hip.h: sn2_train_batch.  The resident set raw (10,T) f32, offsets (P+1) i32, centers (P,2) f32, coverages
+    (P,4) f64; plot_ids (B) i32 ON THE DEVICE -- the caller has checked 0 <= id < P on the host copy it uploaded (no kernel does);
+    cos_sin (360,2) f64; ws: i32, at least train_batch_ws_words(B, n_max, N) elements.  Writes cloud (B,10,N), xyz (B,3,N), gt (B,4)
+    f64 and fps_start (2,B) i32 in place, on the current stream, without a host read."""
+    _, T = raw.shape
+    P = offsets.numel() - 1
+    B, _, N = cloud.shape
+    _chk(raw, F32, (10, T), "raw")
+    _chk(offsets, I32, (P + 1,), "offsets")
+    _chk(centers, F32, (P, 2), "centers")
+    _chk(coverages, F64, (P, 4), "coverages")
+    _chk(plot_ids, I32, (B,), "plot_ids")
+    F = fake_xy.shape[0]
+    _chk(fake_xy, F32, (F, 2), "fake_xy")
+    _chk(cos_sin, F64, (360, 2), "cos_sin")
+    _chk(cloud, F32, (B, 10, N), "cloud")
+    _chk(xyz, F32, (B, 3, N), "xyz")
+    _chk(gt, F64, (B, 4), "gt")
+    _chk(fps_start, I32, (2, B), "fps_start")
+    _chk(ws, I32, None, "ws")
+    seed, epoch, n_max, M1 = int(seed), int(epoch), int(n_max), int(M1)
+    if not 0 <= seed < 2 ** 64 or not 0 <= epoch < 2 ** 31:
+        raise ValueError("train_batch: seed must fit 64 unsigned bits and epoch 31")
+    if P < 1 or B < 1 or N < 1 or not 0 < n_max < 2 ** 31 or not 0 < M1 <= N:
+        raise ValueError("train_batch: need P, B, N >= 1, 0 < n_max < 2^31 and 0 < M1 <= N")
+    need = train_batch_ws_words(B, n_max, N)
+    if ws.dim() != 1 or ws.numel() < need or ws.data_ptr() % 16:
+        raise ValueError(f"train_batch: ws must be a 16-byte aligned 1-D int32 tensor of at least {need} elements")
+    _call("sn2_train_batch", _ptr(raw), T, _ptr(offsets), _ptr(centers), _ptr(coverages), P, _ptr(plot_ids), B, _ptr(fake_xy), F,
+          n_max, N, M1, float(z_max), seed, epoch, _ptr(cos_sin), int(bool(train)), int(bool(noise)), _ptr(ws), ws.numel(),
+          _ptr(cloud), _ptr(xyz), _ptr(gt), _ptr(fps_start), _stream())
+
+
 def znorm(xyz: torch.Tensor, radius: float):
     """xyz (3,n) fp32 of ONE raw plot on the device -> (zmin (n), z - zmin (n)): the local-minimum z-normalisation of
     `normalize_z_with_minz_in_a_radius` (utils/load_data.py:237-249)."""
@@ -1389,8 +1431,10 @@ def mosaic_finalize(mean: torch.Tensor, wsum: torch.Tensor):
 LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS
 
 
-def kde_lookup(clouds_dev: torch.Tensor, z_max: float, X: torch.Tensor, Y: torch.Tensor, z_channel: int = 2) -> torch.Tensor:
-    """clouds (B,C,N) fp32 on the device, X (K) / Y (3,K) fp64 interpolation tables -> pdf_all (B*N,3) fp64."""
+def kde_lookup(clouds_dev: torch.Tensor, z_max: float, X: torch.Tensor, Y: torch.Tensor, z_channel: int = 2,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clouds (B,C,N) fp32 on the device, X (K) / Y (3,K) fp64 interpolation tables -> pdf_all (B*N,3) fp64 (into `out` when
+    one is given)."""
     B, C, N = clouds_dev.shape
     _chk(clouds_dev, F32, (B, C, N), "clouds")
     K = X.shape[0]
@@ -1398,7 +1442,7 @@ def kde_lookup(clouds_dev: torch.Tensor, z_max: float, X: torch.Tensor, Y: torch
     _chk(Y, F64, (3, K), "Y")
     if K < 2 or not (0 <= z_channel < C):
         raise ValueError("kde_lookup: need K >= 2 knots and a valid z channel")
-    pdf = torch.empty(B * N, 3, dtype=F64, device=clouds_dev.device)
+    pdf = torch.empty(B * N, 3, dtype=F64, device=clouds_dev.device) if out is None else _chk(out, F64, (B * N, 3), "out")
     _call("sn2_kde_lookup", _ptr(clouds_dev), B, C, N, int(z_channel), float(z_max), _ptr(X), _ptr(Y), K, _ptr(pdf), _stream())
     return pdf
 

@@ -160,8 +160,7 @@ class TrainPipeline:
             if self.feeder is not None:
                 # the next batch arrives from the host (pinned buffers): its copy into the slot rides on the side stream,
                 # in front of the geometry pass that reads it and behind the feature pass that last read the slot
-                for name, t in self.feeder(i).items():
-                    d[name].copy_(t, non_blocking=not self.feeder_blocking)
+                self._feed(i, d)
             self.model._geometry(d["xyz"], d["fps_start"], out=self.geo[k], **self._geo_kw, **self._cloud_kw(d))
             self.geo_ready[k].record(st)
         self.issued = max(self.issued, i + 1)
@@ -179,8 +178,7 @@ class TrainPipeline:
             for h, k in enumerate(ks):
                 d = self.inputs[k]
                 if self.feeder is not None:
-                    for name, t in self.feeder(i + h).items():
-                        d[name].copy_(t, non_blocking=not self.feeder_blocking)
+                    self._feed(i + h, d)
                 # (d["xyz"] / d["cloud"] ARE slices of the group's tensors: nothing to copy; the start indices -- 2 x B ints in a
                 # (2, G B) table -- are copied when a feeder may have changed them, and once otherwise)
                 if self.feeder is not None or not self._fs_synced[pb]:
@@ -194,6 +192,16 @@ class TrainPipeline:
             for k in ks:
                 self.geo_ready[k].record(st)
         self.issued = max(self.issued, i + G)
+
+    def _feed(self, i, d):
+        """Batch number i into slot `d`, on the current (side) stream.  A feeder with `fill_slot` (train_data.EpochFeeder) writes the
+        slot's tensors itself, on the device; a plain callable returns host tensors that are copied in."""
+        fill = getattr(self.feeder, "fill_slot", None)
+        if fill is not None:
+            fill(i, d)
+            return
+        for name, t in self.feeder(i).items():
+            d[name].copy_(t, non_blocking=not self.feeder_blocking)
 
     def _cloud_kw(self, d):
         return {"cloud": d["cloud"]} if self.input_only else {}
@@ -298,7 +306,8 @@ class TrainPipeline:
     def set_feeder(self, feeder):
         """feeder(i) -> {"cloud": ..., "xyz": ..., ...} HOST tensors (ideally pinned) for batch number i, same shapes and dtypes
         as the slot tensors of those names; they are copied into slot i % slots on the side stream before that batch's
-        geometry pass.  None = the slots already hold the data (the resident-input mode of bench.py)."""
+        geometry pass.  An object with `fill_slot(i, slot)` (train_data.EpochFeeder) is called in the same place instead and writes
+        the slot's tensors on the device.  None = the slots already hold the data (the resident-input mode of bench.py)."""
         self.feeder = feeder
 
     def drain(self, check: bool = False):

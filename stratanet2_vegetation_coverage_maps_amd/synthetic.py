@@ -45,6 +45,15 @@ def make_plot(n_points: int, seed: int):
     return cloud.contiguous(), xyz.contiguous()
 
 
+def make_raw_plot(n_points: int, seed: int, center=(0.0, 0.0)):
+    """`make_plot(n_points, seed)` as a RAW plot (10, n) fp32 in the units `load_cloud` starts from (`loader.py:73-87`, channel order
+    of `hip_ops.prepare_plots`): absolute metres around `center`, 16-bit colours, 15-bit intensity, return numbers from 1."""
+    cloud, xyz = make_plot(n_points, seed)
+    cx, cy = (float(c) for c in center)
+    return torch.cat([torch.stack([xyz[0] + cx, xyz[1] + cy, xyz[2]], 0), torch.floor(cloud[3:7] * 65535.0),
+                      torch.floor(cloud[7:8] * 32767.0), cloud[8:10] * 6.0 + 1.0], 0).contiguous()
+
+
 def make_batch(batch_size: int, n_points: int, first_plot: int = 0, base_seed: int = BASE_SEED):
     """Returns the `cloud_data` dict of the reference (CPU tensors) plus the harness-side extras of the
     training step: `coverages` (B,4) float64 ground truth and `pdf_all` (B*N,3) float64 (stand-in for the
