@@ -148,6 +148,24 @@ int sn2_fps_waves(const float *pos_soa, int B, int N, int M, const int *start, i
  * can tell that passes are being repeated (torch_cluster.fps has no such failure mode: model/point_net2.py:22). */
 int sn2_fps_status(const float *pos_soa, int B, int N, int M, const int *start, int *idx, float *cpos_soa,
                    float *cpos_aos, int *order_ws, int waves, unsigned *status, void *stream);
+/* The same over a plot's LIVE points.  n_live (B) int32 on the device, or NULL (= N for every plot); n_live[b] is clamped to
+ * [1, N] on the device, no host read.  The live set of plot b is {0 .. n_live[b]-1} together with its start point:
+ *   - only live points are ever arg-max candidates (lowest index on ties, as always); the start may lie behind the prefix and is
+ *     emitted as itself;
+ *   - once the largest running distance over the live points is 0, every remaining sample is index 0 (idx 0, point 0's position);
+ *   - n_live_out (B) int32 or NULL: the samples emitted before that happened, M if it never did.
+ * Precondition for this to BE farthest point sampling over all N points: every point of [n_live[b], N) is a bit-identical copy
+ * of a point of [0, n_live[b]) -- a copy's running distance always equals its original's, so it never wins a lowest-index tie,
+ * and a maximum of 0 over the live points is a maximum of 0 over all (torch's argmax of an all-zero row is 0).  That is how
+ * sn2_subsample, sn2_train_batch and numpy's sample_cloud lay a plot of fewer than N candidates out.  The prefix itself may hold
+ * duplicates.  Then idx / cpos are the bytes of sn2_fps_status, without the all-ties rounds coincident points cost it (a
+ * 51-point plot padded to thousands: ~n_live rounds instead of M), and n_live_out is a valid n_live for an FPS over cpos_soa
+ * (the next level): positions n_live_out.. are point 0's, which an earlier sample covers.  Without the precondition the answer is
+ * the definition above, the same from every kernel form.  The workspace describes all N points afterwards, as after sn2_fps.
+ * sn2_fps, sn2_fps_waves and sn2_fps_status are this call with n_live = n_live_out = NULL.  NULL pos_soa / idx / cpos_*, B, N,
+ * M <= 0, M > N, an unknown `waves`: SN2_EINVAL before any device work. */
+int sn2_fps_live(const float *pos_soa, int B, int N, int M, const int *start, const int *n_live, int *idx, float *cpos_soa,
+                 float *cpos_aos, int *order_ws, int waves, int *n_live_out, unsigned *status, void *stream);
 /* tests only: sweeps a wait of the multi-workgroup FPS makes before it gives up (0 = the default, 2^18 ~ 0.2 s) */
 int sn2_debug_fps_spin_limit(unsigned sweeps);
 
@@ -269,6 +287,13 @@ int sn2_train_batch(const float *raw, long T, const int *offsets, const float *c
                     const int *plot_ids, int B, const float *fake_xy, int n_fake, int n_max, int N, int M1, float z_max,
                     unsigned long long seed, long long epoch, const double *cos_sin, int train, int noise, int *ws,
                     size_t ws_words, float *cloud, float *xyz, double *gt, int *fps_start, void *stream);
+/* The same with n_live (B) int32 or NULL: n_live[b] = min(offsets[p+1] - offsets[p] + n_fake, N) for the plot p of slot b -- the
+ * distinct points at the front of the plot's rows (every later row repeats one of them, noise included: it is keyed by source
+ * index), i.e. sn2_fps_live's n_live for this batch.  sn2_train_batch is this call with NULL. */
+int sn2_train_batch_live(const float *raw, long T, const int *offsets, const float *centers, const double *coverages, int P,
+                         const int *plot_ids, int B, const float *fake_xy, int n_fake, int n_max, int N, int M1, float z_max,
+                         unsigned long long seed, long long epoch, const double *cos_sin, int train, int noise, int *ws,
+                         size_t ws_words, float *cloud, float *xyz, double *gt, int *fps_start, int *n_live, void *stream);
 
 /* z-normalisation of a raw plot (offline preparation): z_i - min{ z_j : |xy_i - xy_j| <= radius } --
  * normalize_z_with_minz_in_a_radius, utils/load_data.py:237-249 (sklearn kd-tree radius query in x,y + a python loop).
@@ -868,6 +893,8 @@ typedef struct sn2_net_io {
     void *ctx;                           /* sn2_net_ctx_create: the events that order them, or NULL (no fork) */
     int flags;                           /* SN2_NET_* */
     int training;                        /* model.training (0 / 1), or SN2_BN_FROZEN_KEEP: eval mode with a backward to come */
+    const int *fps_live;                 /* (B) sn2_fps_live's n_live of the level-1 FPS, or NULL (= N) */
+    int *fps_live1;                      /* (B) scratch: level 1's n_live_out = level 2's n_live; needed when fps_live is given */
 } sn2_net_io;
 
 /* events of a forked geometry pass: created once by the caller (one per model and device), used by one pass at a time */

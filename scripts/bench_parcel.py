@@ -5,10 +5,12 @@ prediction alone, the reference's CPU preparation (scipy discs + sklearn z-norm 
 EXTRAPOLATED to the parcel, the compulsory bytes of the count / fill passes against 8 TB/s, and the z-norm query's
 candidate tests per second.  Kernel times: run it under `rocprofv3 --kernel-trace --stats`.
 
-    python scripts/bench_parcel.py [--repeat 10] [--sample 6] [--batch 64] [--sampler numpy|device]
+    python scripts/bench_parcel.py [--repeat 10] [--sample 6] [--batch 64] [--sampler numpy|device] [--fps-live on|off]
 
 --sampler device draws the plots' subsamples with sn2_subsample instead of numpy on the host (`ParcelPlots.batches`); the
 prediction figures are then the median of --repeat runs as well, and sn2_subsample / sn2_prepare_plots are timed per parcel.
+--fps-live off drops the batches' "n_live" key (sn2_fps_live: the FPS kernels then sample over the repeated points of short plots
+as before): the same predictions, a cross-check inside one build.
 """
 import argparse
 import json
@@ -82,6 +84,7 @@ def main():
     ap.add_argument("--sample", type=int, default=6)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--sampler", choices=("numpy", "device"), default="numpy")
+    ap.add_argument("--fps-live", choices=("on", "off"), default="on")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_parcel: needs the GPU")
@@ -106,6 +109,7 @@ def main():
         P, SN = len(plots), int(plots.n_points.sum())
 
         skw = {"sampler": "device", "seed": 1} if a.sampler == "device" else {}
+        skw["n_live"] = a.fps_live == "on"
 
         def e2e():
             mos, pl = parcel.predict_parcel_cloud(model, cloud_dev, args, batch_size=a.batch, fps_start=0, **skw)
@@ -143,7 +147,8 @@ def main():
         prep_ms = statistics.median(times)
         cand = znorm_candidates(cloud, plots)
         out[name] = {
-            "points": T, "plots": P, "plot_points": SN, "sampler": a.sampler, "batch": a.batch,
+            "points": T, "plots": P, "plot_points": SN, "sampler": a.sampler, "batch": a.batch, "fps_live": a.fps_live,
+            "plots_below_subsample_size": int((plots.n_points + len(parcel.fake_ground_xy(args.diam_meters)) < args.subsample_size).sum()),
             "h2d_ms": round(h2d, 3),
             "prepare_ms_median": round(prep_ms, 3), "prepare_ms_min": round(min(times), 3),
             "entry_ms": entries,

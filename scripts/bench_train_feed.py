@@ -10,6 +10,11 @@ batches per geometry pass bench.py picks for the step count, hipGraph feature pa
 
     python scripts/bench_train_feed.py [--steps 200 --warmup 20 --repeats 3 --modes abcd --timeout 240]
     python scripts/bench_train_feed.py --mode c ...        (one mode in this process; what the driver starts)
+    python scripts/bench_train_feed.py --short-plots --fps-live on|off --modes c
+
+--short-plots: every second plot of the set has 2000 .. 6000 points instead (far fewer than the 32 768 a batch row holds: the row is
+mostly repeats, what a sparse real plot looks like); the default set stays as it is.  --fps-live on (default): the slots of (c) and
+(d) carry "n_live" (sn2_fps_live: the FPS kernels skip the repeats); off: they do not -- the same losses, a cross-check in one build.
 
 The driver starts one fresh process per mode, each under its own time limit, and stops at the first one that does not end
 normally.  Every mode prints one JSON line: ms per step of each of `--repeats` timed regions.  (c) and (d) draw their batches from
@@ -46,6 +51,10 @@ def run_mode(a):
     B, N, depth = bench.PLOTS_PER_GPU, bench.N_POINTS, 3
     G = bench.pipe_group_for(a.steps)
     w = bench.build_training(dev, 0, 0, 1, B, N, "ref", "f32", G * depth + G, exchange="none")
+    live = a.fps_live == "on" and a.mode in "cd"
+    if live:
+        for sl in w.slots:
+            sl["n_live"] = torch.full((B,), N, dtype=torch.int32, device=dev)
     pipe = TrainPipeline(w.model, w.opt, w.feature_step, w.slots, depth=depth, group=G, split_exchange=w.split,
                          phase=bench.pipe_phase_for(G, a.warmup, a.steps))
     pipe.capture()
@@ -56,6 +65,8 @@ def run_mode(a):
     elif a.mode in "cd":
         rng = np.random.RandomState(SET_SEED)
         sizes = rng.randint(16000, 36001, N_SET)
+        if a.short_plots:                               # (a generator of its own: the default set's draws stay as they are)
+            sizes[::2] = np.random.RandomState(SET_SEED + 1).randint(2000, 6001, len(sizes[::2]))
         centers = (rng.rand(N_SET, 2) * 1000).astype(np.float32)
         cov = rng.rand(N_SET, 4)
         raw = []
@@ -65,7 +76,7 @@ def run_mode(a):
                                   torch.floor(cloud[3:7] * 65535.0), torch.floor(cloud[7:8] * 32767.0), cloud[8:10] * 6.0 + 1.0], 0))
         tables = losses.KdeTables(np.linspace(-1.0, 30.0, 5000), *[np.linspace(0.1, 1.0, 5000) ** k for k in (1, 2, 3)], dev)
         note = {"plots": N_SET, "points_min": int(sizes.min()), "points_max": int(sizes.max()),
-                "plots_above_N": int((sizes + 316 > N).sum())}
+                "plots_above_N": int((sizes + 316 > N).sum()), "short_plots": bool(a.short_plots), "fps_live": a.fps_live}
         if a.mode == "c":
             plots = train_data.ResidentPlots.from_plots(raw, centers, cov, dev)
             pipe.set_feeder(train_data.EpochFeeder(plots, w.args, B, FEED_SEED, kde=tables,
@@ -83,8 +94,11 @@ def run_mode(a):
                 ids = orders[e][k * B:(k + 1) * B]
                 d = prepare_batch([dev_raw[p] for p in ids], centers[ids], w.args, train=True, rs=rs, device=dev, noise="device",
                                   sampler="device", seed=FEED_SEED, plot_keys=[e * N_SET + p for p in ids])
-                return {"cloud": d["cloud"], "xyz": d["xyz"], "gt": torch.from_numpy(cov[ids]),
-                        "pdf": losses.kde_densities(d["cloud"], w.args.z_max, tables)}
+                out = {"cloud": d["cloud"], "xyz": d["xyz"], "gt": torch.from_numpy(cov[ids]),
+                       "pdf": losses.kde_densities(d["cloud"], w.args.z_max, tables)}
+                if live:
+                    out["n_live"] = d["n_live"]
+                return out
             pipe.set_feeder(fresh)
     pipe.prime()
     for _ in range(a.warmup):
@@ -112,13 +126,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps per mode")
     ap.add_argument("--timeout", type=int, default=240, help="seconds each mode's process may take")
+    ap.add_argument("--short-plots", action="store_true", help="every second plot of the set of (c) and (d) has 2000 .. 6000 points")
+    ap.add_argument("--fps-live", choices=("on", "off"), default="on", help="whether the slots of (c) and (d) carry n_live")
     a = ap.parse_args()
     if a.mode is not None:
         run_mode(a)
         return 0
     for m in a.modes:                                   # this process never touches the GPU: one fresh child per mode
         cmd = [sys.executable, os.path.abspath(__file__), "--mode", m, "--steps", str(a.steps), "--warmup", str(a.warmup),
-               "--repeats", str(a.repeats)]
+               "--repeats", str(a.repeats), "--fps-live", a.fps_live] + (["--short-plots"] if a.short_plots else [])
         try:
             rc = subprocess.run(cmd, timeout=a.timeout).returncode
         except subprocess.TimeoutExpired:

@@ -119,7 +119,7 @@ class NetBwd(Structure):  # sn2_net_bwd
 class NetIO(Structure):  # sn2_net_io
     _fields_ = [("cloud", c_void_p), ("fps_start", c_void_p), ("fps_status", c_void_p), ("gl_xchg", c_void_p), ("gl_ctl", c_void_p),
                 ("stream_b", c_void_p), ("stream_c", c_void_p), ("stream_pack", c_void_p), ("ctx", c_void_p), ("flags", c_int),
-                ("training", c_int)]
+                ("training", c_int), ("fps_live", c_void_p), ("fps_live1", c_void_p)]
 
 
 # name -> argtypes; every entry point returns int (0 ok, >0 hipError_t, <0 argument error; the route predicates: 0 / 1)
@@ -136,6 +136,8 @@ SIGNATURES = {
     "sn2_fps": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_fps_waves": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "sn2_fps_status": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "sn2_fps_live": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                     c_void_p],
     "sn2_debug_fps_spin_limit": [ctypes.c_uint],
     "sn2_ball_query": [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p],
@@ -160,6 +162,9 @@ SIGNATURES = {
     "sn2_train_batch": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                         c_float, ctypes.c_ulonglong, c_longlong, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p,
                         c_void_p, c_void_p, c_void_p],
+    "sn2_train_batch_live": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                             c_float, ctypes.c_ulonglong, c_longlong, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_sa_order": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "sn2_sa_order_group": [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_sa_forward": [POINTER(SA), c_int, c_void_p],

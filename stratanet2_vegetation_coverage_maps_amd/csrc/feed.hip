@@ -28,10 +28,15 @@ __global__ __launch_bounds__(64) void train_plots_kernel(const int* __restrict__
                                                          const double* __restrict__ coverages, unsigned long long seed,
                                                          long long epoch, int N, int M1, int train,
                                                          const double* __restrict__ cos_sin, int* __restrict__ ws,
-                                                         double* __restrict__ gt, int* __restrict__ fps_start) {
+                                                         double* __restrict__ gt, int* __restrict__ fps_start,
+                                                         const int* __restrict__ offs, int n_fake, int* __restrict__ n_live) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     const int p = ids[b];
+    if (n_live) {                                                 // the distinct rows at the front of the plot (sn2_fps_live)
+        const long nc = (long)(offs[p + 1] - offs[p]) + n_fake;
+        n_live[b] = nc < N ? (int)nc : N;
+    }
     const long long key = epoch * (long long)P + p;
     reinterpret_cast<long long*>(ws)[b] = key;
     double* rot = reinterpret_cast<double*>(ws + 2 * (size_t)B);
@@ -160,6 +165,15 @@ extern "C" int sn2_train_batch(const float* raw, long T, const int* offsets, con
                                const int* plot_ids, int B, const float* fake_xy, int n_fake, int n_max, int N, int M1, float z_max,
                                unsigned long long seed, long long epoch, const double* cos_sin, int train, int noise, int* ws,
                                size_t ws_words, float* cloud, float* xyz, double* gt, int* fps_start, void* stream) {
+    return sn2_train_batch_live(raw, T, offsets, centers, coverages, P, plot_ids, B, fake_xy, n_fake, n_max, N, M1, z_max, seed, epoch,
+                                cos_sin, train, noise, ws, ws_words, cloud, xyz, gt, fps_start, nullptr, stream);
+}
+
+extern "C" int sn2_train_batch_live(const float* raw, long T, const int* offsets, const float* centers, const double* coverages, int P,
+                                    const int* plot_ids, int B, const float* fake_xy, int n_fake, int n_max, int N, int M1,
+                                    float z_max, unsigned long long seed, long long epoch, const double* cos_sin, int train,
+                                    int noise, int* ws, size_t ws_words, float* cloud, float* xyz, double* gt, int* fps_start,
+                                    int* n_live, void* stream) {
     if (!raw || !offsets || !centers || !coverages || !plot_ids || !cloud || !xyz || !gt || !fps_start) return SN2_EINVAL;
     if (B <= 0 || N <= 0 || P <= 0 || T <= 0 || M1 <= 0 || n_fake < 0 || n_max <= 0 || epoch < 0 || !(z_max > 0.f)) return SN2_EINVAL;
     if (n_fake > 0 && !fake_xy) return SN2_EINVAL;
@@ -170,7 +184,7 @@ extern "C" int sn2_train_batch(const float* raw, long T, const int* offsets, con
     if (!ws || ((uintptr_t)ws & 15) || ws_words < need) return SN2_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(train_plots_kernel, dim3(sn2_cdiv(B, 64)), dim3(64), 0, st, plot_ids, B, P, coverages, seed, epoch, N, M1,
-                       train, cos_sin, ws, gt, fps_start);
+                       train, cos_sin, ws, gt, fps_start, offsets, n_fake, n_live);
     int* idx = nullptr;
     if (n_max > N) {
         idx = ws + head_words(B);

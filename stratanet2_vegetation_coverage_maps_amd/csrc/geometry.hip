@@ -39,10 +39,34 @@ extern "C" int sn2_pack_rows(const float* cloud, const float* xyz, int B, int C,
 // waves and ONE barrier (LDS slots double-buffered by round parity).
 // Latency/VALU-bound by construction: M strictly sequential rounds; HBM traffic is 12 B/point once.
 // ------------------------------------------------------------------------------------------------------------
+// The live prefix of a plot (sn2_fps_live in include/strata_hip.h): n_live[b] clamped to [1, N] on the device, N without the array.
+// Points at and behind it are DEAD in every FPS kernel below: their running distance is +0.0f from the first round on (fminf keeps
+// it there), so none of them is ever a strict maximum, and a kernel that finds the plot's maximum at 0 ends through fps_fill_zero.
+__device__ __forceinline__ int fps_live_count(const int* __restrict__ n_live, int b, int N) {
+    int n = n_live ? n_live[b] : N;
+    n = n < 1 ? 1 : (n > N ? N : n);
+    return __builtin_amdgcn_readfirstlane(n);
+}
+// The plot's maximum reached 0 with `from` samples out: every point is at distance 0, the arg-max of an all-zero row is index 0,
+// and so is every later sample.  Called by all `nt` threads of the workgroup that writes the plot's samples.
+__device__ __forceinline__ void fps_fill_zero(const float* __restrict__ px, int N, int M, int b, int from, int tid, int nt,
+                                              int* __restrict__ idx_out, float* __restrict__ cpos_soa,
+                                              float* __restrict__ cpos_aos, int* __restrict__ n_live_out) {
+    const float x0 = px[0], y0 = px[N], z0 = px[2 * (size_t)N];
+    for (int i = from + tid; i < M; i += nt) {
+        idx_out[(size_t)b * M + i] = 0;
+        cpos_soa[((size_t)b * 3 + 0) * M + i] = x0;
+        cpos_soa[((size_t)b * 3 + 1) * M + i] = y0;
+        cpos_soa[((size_t)b * 3 + 2) * M + i] = z0;
+        reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M + i] = make_float4(x0, y0, z0, 0.f);
+    }
+    if (tid == 0 && n_live_out) n_live_out[b] = from;
+}
 template <int PPT, int T, bool ZLDS>
 __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ pos, int N, int M,
                                                 const int* __restrict__ start, int* __restrict__ idx_out,
-                                                float* __restrict__ cpos_soa, float* __restrict__ cpos_aos) {
+                                                float* __restrict__ cpos_soa, float* __restrict__ cpos_aos,
+                                                const int* __restrict__ n_live, int* __restrict__ n_live_out) {
     constexpr int NW = T / 64;
     // PLDS: a copy of the positions in LDS (16 B per point) where it is small: the winner's coordinates are then one LDS read
     // per round instead of three dependent global loads (~500 clocks of the ~1250 a round of the 1024 -> 256 level took)
@@ -57,6 +81,8 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ pos, i
     const float* py = px + N;
     const float* pz = py + N;
     float x[PPT], y[PPT], z[ZLDS ? 1 : PPT], d[PPT];
+    const int nlive = fps_live_count(n_live, b, N);
+    if (tid == 0 && n_live_out) n_live_out[b] = M;    // unless the maximum reaches 0 first (fps_fill_zero)
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
         const int j = k * T + tid;
@@ -65,7 +91,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ pos, i
         y[k] = v ? py[j] : 0.f;
         if constexpr (ZLDS) s_z[j] = v ? pz[j] : 0.f; else z[k] = v ? pz[j] : 0.f;
         if constexpr (PLDS) s_pos[j] = make_float4(x[k], y[k], z[k], 0.f);
-        d[k] = v ? INFINITY : 0.f;  // padding lanes: distance 0 and an index above every real point -> never win
+        d[k] = j < nlive ? INFINITY : 0.f;  // dead points and padding lanes: distance 0 -> never a strict maximum
     }
     int cur = start ? start[b] : 0;
     cur = cur < 0 ? 0 : (cur >= N ? N - 1 : cur);
@@ -113,13 +139,17 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ pos, i
         const float gv = wave_max_dpp(__uint_as_float((unsigned)(k2 >> 32)));
         const unsigned gi = wave_min_u32_dpp(__uint_as_float((unsigned)(k2 >> 32)) == gv ? (unsigned)(k2 & 0xFFFFFFFFull) : 0xFFFFFFFFu);
         cur = (int)gi;
+        if (gv == 0.f) {
+            fps_fill_zero(px, N, M, b, i + 1, tid, T, idx_out, cpos_soa, cpos_aos, n_live_out);
+            break;
+        }
     }
 }
 
 template <int PPT, int T, bool ZLDS = false>
 static int launch_fps(const float* pos, int B, int N, int M, const int* start, int* idx, float* cs, float* ca,
-                      hipStream_t st) {
-    hipLaunchKernelGGL((fps_kernel<PPT, T, ZLDS>), dim3(B), dim3(T), 0, st, pos, N, M, start, idx, cs, ca);
+                      const int* nl, int* nlo, hipStream_t st) {
+    hipLaunchKernelGGL((fps_kernel<PPT, T, ZLDS>), dim3(B), dim3(T), 0, st, pos, N, M, start, idx, cs, ca, nl, nlo);
     SN2_RETURN_LAUNCH();
 }
 
@@ -167,7 +197,7 @@ template <int U, int NT>
 __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __restrict__ pos, int N, int* __restrict__ order,
                                                                  float4* __restrict__ sorted, int* __restrict__ grid,
                                                                  unsigned* __restrict__ xchg, unsigned* __restrict__ ctl,
-                                                                 int* __restrict__ rank) {
+                                                                 int* __restrict__ rank, const int* __restrict__ n_live) {
     __shared__ int s_hist[ORDER_CELLS];
     __shared__ float s_mm[6][NT / 64];
     __shared__ int s_wsum[NT / 64];
@@ -269,24 +299,25 @@ __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __
     __syncthreads();
     int* ob = order + (size_t)b * N;
     float4* sb = sorted + (size_t)b * N;
+    const int nlive = fps_live_count(n_live, b, N);
     for_points([&](int i, float vx, float vy, float vz) {
         const int p = atomicAdd(&s_hist[cell_of(vx, vy, vz)], 1);
         ob[p] = i;
-        sb[p] = make_float4(vx, vy, vz, INFINITY);      // .w = running FPS distance
+        sb[p] = make_float4(vx, vy, vz, i < nlive ? INFINITY : 0.f);      // .w = running FPS distance (dead points: 0 throughout)
         if (rank) rank[(size_t)b * N + i] = p;
     });
 }
 
 // the plot's Morton order, sorted table and cell starts (+ the zeroed exchange area)
 static void launch_spatial_order(const float* pos, int B, int N, int* order, float4* sorted, int* grid, unsigned* xchg,
-                                 unsigned* ctl, hipStream_t st) {
+                                 unsigned* ctl, const int* nl, hipStream_t st) {
     int* rank = reinterpret_cast<int*>(ctl + FPS_CTL_WORDS);          // the last B*N words of the workspace
     if (sn2_small_sort_wg(B) && N <= 16 * 1024)          // many plots: 256 threads per plot (common.h)
-        hipLaunchKernelGGL((spatial_order_chunk_kernel<16, 256>), dim3(B), dim3(256), 0, st, pos, N, order, sorted, grid, xchg, ctl, rank);
+        hipLaunchKernelGGL((spatial_order_chunk_kernel<16, 256>), dim3(B), dim3(256), 0, st, pos, N, order, sorted, grid, xchg, ctl, rank, nl);
     else if (N <= 8 * 1024)
-        hipLaunchKernelGGL((spatial_order_chunk_kernel<8, 1024>), dim3(B), dim3(1024), 0, st, pos, N, order, sorted, grid, xchg, ctl, rank);
+        hipLaunchKernelGGL((spatial_order_chunk_kernel<8, 1024>), dim3(B), dim3(1024), 0, st, pos, N, order, sorted, grid, xchg, ctl, rank, nl);
     else
-        hipLaunchKernelGGL((spatial_order_chunk_kernel<16, 1024>), dim3(B), dim3(1024), 0, st, pos, N, order, sorted, grid, xchg, ctl, rank);
+        hipLaunchKernelGGL((spatial_order_chunk_kernel<16, 1024>), dim3(B), dim3(1024), 0, st, pos, N, order, sorted, grid, xchg, ctl, rank, nl);
 }
 
 // canonical, monotone lower bound of sn2_d2(p, c) over all p inside the box [lo, hi]
@@ -334,7 +365,8 @@ template <int SPW, int NW>
 __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __restrict__ pos, int N, int M,
                                                           const int* __restrict__ start, const int* __restrict__ order,
                                                           float4* sorted, int* __restrict__ idx_out,
-                                                          float* __restrict__ cpos_soa, float* __restrict__ cpos_aos) {
+                                                          float* __restrict__ cpos_soa, float* __restrict__ cpos_aos,
+                                                          int* __restrict__ n_live_out) {
     constexpr int NBK = SPW * NW;
     constexpr int SL = (SPW + 63) / 64;                // bucket slots per lane: slot s = 64 h + lane, h < SL
     static_assert(SPW <= 128 && NW <= 16, "at most two bucket slots per lane");
@@ -348,7 +380,8 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
     const float* py = px + N;
     const float* pz = py + N;
     const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_kernel)
+    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_kernel; dead: 0)
+    if (tid == 0 && n_live_out) n_live_out[b] = M;     // unless the maximum reaches 0 first (fps_fill_zero)
     float* my_box = s_box + wave * SPW;                // + component * NBK + slot
     for (int k = 0; k < SPW; ++k) {
         const int p = (k * NW + wave) * 64 + lane;     // position in the sorted order (bucket k*NW + wave)
@@ -493,6 +526,10 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
         const unsigned balv = (unsigned)__ballot(e.x == V) & ((1u << NW) - 1u);
         const int ww = __ffs(balv) - 1;
         const bool gtie = (__popc(balv) > 1) || (__builtin_amdgcn_readlane(__float_as_int(e.y), ww) != 0);
+        if (V == 0.f) {                                 // workgroup-uniform: every wave read the same records
+            fps_fill_zero(px, N, M, b, i + 1, tid, NW * 64, idx_out, cpos_soa, cpos_aos, n_live_out);
+            break;
+        }
         if (!gtie) {
             cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r.x), ww));
             cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r.y), ww));
@@ -586,7 +623,8 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
                                                         const int* __restrict__ start, const int* __restrict__ order,
                                                         float4* sorted, int* __restrict__ idx_out,
                                                         float* __restrict__ cpos_soa, float* __restrict__ cpos_aos,
-                                                        const unsigned* gate, unsigned* status) {
+                                                        const unsigned* gate, unsigned* status,
+                                                        const int* __restrict__ n_live, int* __restrict__ n_live_out) {
     constexpr int NBK = SPW * NW;
     constexpr int SL = (SPW + 63) / 64;                // bucket slots per lane of the owning wave
     constexpr int T = 4;                               // maxima every wave hands to the final selection
@@ -601,7 +639,7 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
     float2* s_top = reinterpret_cast<float2*>(s_q + NBK);          // [NW*T] per-wave maxima: (value, bucket | place << 16)
     float2* s_cand = s_top + NW * T;                               // [K + 2] the selection's candidates in order (+ the next one)
     int* s_keys = reinterpret_cast<int*>(s_cand + K + 2);          // [64] the selection's integer keys
-    int* s_ctl = s_keys + 64;           // [0] accepted (0: tie search), [1] done, [2] tie value, [3] queue length
+    int* s_ctl = s_keys + 64;           // [0] accepted (0: tie search), [1] done (2: the maximum is 0), [2] tie value, [3] queue length
     unsigned* s_win = reinterpret_cast<unsigned*>(s_ctl + 4);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -609,14 +647,15 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
     const float* py = px + N;
     const float* pz = py + N;
     const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_kernel)
+    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_kernel; dead: 0)
     if (gate) {
         // REPAIR launch behind fps_cluster_kernel (gate = that launch's control words): nothing to do unless one of its waits
         // gave up (gate[1] = the count); then every plot is sampled again by this kernel, which waits for nobody.  The running
-        // distances the abandoned pass left in the sorted table go back to +inf first.
+        // distances the abandoned pass left in the sorted table go back to +inf (dead points: 0) first.
         const unsigned gave_up = __builtin_amdgcn_readfirstlane(gate[1]);
         if (gave_up == 0u) return;
-        for (int p = tid; p < N; p += NW * 64) fps_st_dist(pts, p, INFINITY);
+        const int nlive = fps_live_count(n_live, b, N);
+        for (int p = tid; p < N; p += NW * 64) fps_st_dist(pts, p, ord[p] < nlive ? INFINITY : 0.f);
         if (b == 0 && tid == 0 && status) atomicAdd(status, gave_up);      // sticky: the host reads it where it synchronises anyway
         __threadfence_block();
         __syncthreads();
@@ -653,6 +692,7 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
         cpos_soa[((size_t)b * 3 + 2) * M] = az;
         reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M] = make_float4(ax, ay, az, 0.f);
         s_ctl[3] = 0;
+        if (n_live_out) n_live_out[b] = M;              // unless the maximum reaches 0 first (fps_fill_zero)
     }
     if (M <= 1) return;
     __syncthreads();
@@ -735,8 +775,9 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
                     g_fps_dbg2[29] += __popcll(__ballot(changed));                           // changed points
                 }
 #endif
-                // five of six queue entries change no point at all (the box test is necessary, not sufficient: fps_stamps.py)
-                if (__ballot(changed) == 0ull) continue;
+                // five of six queue entries change no point at all (the box test is necessary, not sufficient: fps_stamps.py);
+                // a bucket's FIRST visit always takes its maximum (a bucket of dead points only changes nothing and holds 0)
+                if (__ballot(changed) == 0ull && U[u] != INFINITY) continue;
                 // nothing of the bucket's maximum moved (no changed point held it): its (max, point) stand, and its
                 // second-max entry stays an UPPER bound of the true one, which is all the acceptance tests need
                 if (__ballot(changed && d0 == U[u]) == 0ull && U[u] != INFINITY) continue;
@@ -847,9 +888,10 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
             // (candidate 0 is only the first of the entries that share the top key)
             float vtop = 0.f;
             if (nj == 0) vtop = wave_max_fused(val);
+            const bool zero = nj == 0 && vtop <= 0.f;   // the plot's maximum is 0: no tie search, the rest is index 0
             if (lane == 0) {
                 s_ctl[0] = nj;
-                s_ctl[1] = (cnt + (nj > 0 ? nj : 1) >= M) ? 1 : 0;
+                s_ctl[1] = zero ? 2 : ((cnt + (nj > 0 ? nj : 1) >= M) ? 1 : 0);
                 s_ctl[2] = __float_as_int(vtop);
                 s_ctl[3] = 0;
                 *s_win = 0xFFFFFFFFu;
@@ -859,6 +901,10 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
         __syncthreads();
         j = s_ctl[0];
         const int done = s_ctl[1];
+        if (done == 2) {
+            fps_fill_zero(px, N, M, b, cnt, tid, NW * 64, idx_out, cpos_soa, cpos_aos, n_live_out);
+            break;
+        }
 #ifdef SN2_FPS_STAMPS
         STAMP(t6);
         if (b == 0 && tid == 0) {
@@ -929,7 +975,8 @@ static size_t fps_spec_lds_bytes() {
 #endif
 template <int SPW, int NW = 16>
 static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* start, int* ws, int* idx, float* cs,
-                             float* ca, hipStream_t st, bool speculate = true, bool repair = false, unsigned* status = nullptr) {
+                             float* ca, const int* nl, int* nlo, hipStream_t st, bool speculate = true, bool repair = false,
+                             unsigned* status = nullptr) {
     int* order = ws;                                               // B*N ints
     float4* sorted = reinterpret_cast<float4*>(ws + (size_t)B * N);   // B*N float4 (16-byte aligned: B*N*4 bytes offset
                                                                    // from a 16-byte aligned base with B*N % 4 == 0)
@@ -939,7 +986,7 @@ static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* s
     // repair = this launch follows fps_cluster_kernel on the same workspace: the tables are there, and the kernel returns at once
     // unless the control words say that the multi-workgroup pass gave up
     const unsigned* gate = repair ? ctl : nullptr;
-    if (!repair) launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, st);
+    if (!repair) launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, nl, st);
     if (speculate) {
         constexpr int K = SN2_FPS_K;
         const size_t lds = fps_spec_lds_bytes<SPW, NW, K>();
@@ -949,11 +996,11 @@ static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* s
         // three times as long as alone, and what the pass costs the step follows the time it is resident -- no effect, 0.7652
         // against 0.762 ms per step; round 3 had tried the opposite, the feature kernels raised: none either.)
         hipLaunchKernelGGL((fps_spec_kernel<SPW, NW, K>), dim3(B), dim3(NW * 64), lds, st, pos, N, M, start, (const int*)order,
-                           sorted, idx, cs, ca, gate, status);
+                           sorted, idx, cs, ca, gate, status, nl, nlo);
         SN2_RETURN_LAUNCH();
     }
     hipLaunchKernelGGL((fps_bucket_kernel<SPW, NW>), dim3(B), dim3(NW * 64), 0, st, pos, N, M, start, (const int*)order,
-                       sorted, idx, cs, ca);
+                       sorted, idx, cs, ca, nlo);
     SN2_RETURN_LAUNCH();
 }
 
@@ -976,7 +1023,8 @@ static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* s
 //     buckets are below) or its 8-th value (when more than 8 reach tau), a candidate is accepted only above every
 //     workgroup's bound, and a super-round that finds nothing above the bounds lowers tau and tries again (more than 64
 //     survivors: eight wave-max rounds instead of the ranking);
-//   * acceptance tests, exact-tie search (lowest ORIGINAL index, one more granule per workgroup) and emitted samples are
+//   * acceptance tests, exact-tie search (lowest ORIGINAL index at the plot's TRUE maximum: two more granules per workgroup, its
+//     winner and the maximum of its own buckets -- the published records are its top by 64-ulp keys only) and emitted samples are
 //     those of fps_spec_kernel, bit for bit (tests/test_gpu_geometry.py holds all kernels to each other and to the oracle).
 // Residency: a workgroup waits only for the P-1 peers of its plot.  Plots are handed out by a ticket counter in arrival
 // order (not by blockIdx), so the peers of every resident workgroup are resident too or are the very next workgroups to
@@ -989,7 +1037,7 @@ static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* s
 // ------------------------------------------------------------------------------------------------------------
 typedef unsigned long long fc_u64;
 constexpr int FC_TP = 8;                     // records a workgroup publishes per super-round
-constexpr int FC_PARITY_U64 = 512;           // granules per parity (6 * 8P record fields + P bounds + P tie words <= 400)
+constexpr int FC_PARITY_U64 = 512;           // granules per parity (6 * 8P record fields + P bounds + 2P tie words <= 408)
 constexpr unsigned FC_SPIN_LIMIT = 1u << 18; // sweeps (~1 us each) before a wait gives up (a resident peer answers within a few)
 #ifndef SN2_FC_FLAG_SLEEP
 #define SN2_FC_FLAG_SLEEP 3
@@ -1038,14 +1086,14 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
                                                            float4* sorted, int* __restrict__ idx_out,
                                                            float* __restrict__ cpos_soa, float* __restrict__ cpos_aos,
                                                            fc_u64* xchg_all, unsigned* ctl, int log_cap, int tau_keep,
-                                                           unsigned spin_limit) {
+                                                           unsigned spin_limit, int* __restrict__ n_live_out) {
     constexpr int NBL = SPW * NW;                      // buckets of this workgroup: local bucket lb = slot * NW + wave
     constexpr int SL = (SPW + 63) / 64;                // bucket slots per lane of the owning wave
     constexpr int VL = (NBL + 63) / 64;                // bucket values per lane of wave 0 in the selection
     constexpr int K = 8, TP = FC_TP, NE = TP * P;      // accepted per super-round, records per workgroup, merged records
     constexpr int SPWP = SPW < 64 ? SPW : 64;          // phase A: lane = (slot, sample): SPWP slots x KPL samples per pass
     constexpr int KPL = 64 / SPWP < 8 ? 64 / SPWP : 8;
-    static_assert(NE <= 64 && P <= 8 && SPW <= 128 && NBL <= 2048 && NW <= 16 && 6 * NE + 2 * P <= FC_PARITY_U64, "limits");
+    static_assert(NE <= 64 && P <= 8 && SPW <= 128 && NBL <= 2048 && NW <= 16 && 6 * NE + 3 * P <= FC_PARITY_U64, "limits");
     static_assert((SPWP & (SPWP - 1)) == 0 && TP <= 15, "slots per wave: a power of two; the record count rides in 4 bits");
     extern __shared__ __attribute__((aligned(16))) unsigned char fc_smem[];
     float4* s_pt = reinterpret_cast<float4*>(fc_smem);             // [NBL] arg-max point of the bucket: x, y, z, sorted position
@@ -1060,7 +1108,8 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
     unsigned* s_q = reinterpret_cast<unsigned*>(s_max2 + NBL);     // [NBL] work queue: local bucket | samples << 11
     int* s_keys = reinterpret_cast<int*>(s_q + NBL);               // [64 + 8] integer keys of a ranking (+ the pad of its last quad)
     int* s_ctl = s_keys + 72;                                      // [0] accepted, [1] done, [2] tie value, [3] queue length,
-                                                                   // [4] mode (0 accept, 1 tie search, 2 lower tau, 3 gave up),
+                                                                   // [4] mode (0 accept, 1 tie search, 2 lower tau, 3 gave up,
+                                                                   //     4 the plot's maximum is 0),
                                                                    // [5] tie winner, [7] ticket
     unsigned* s_win = reinterpret_cast<unsigned*>(s_ctl + 8);
     float4* s_log = reinterpret_cast<float4*>(s_win + 4);          // [log_cap] every sample of the plot (x, y, z, -1 - position | index):
@@ -1161,6 +1210,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
     };
     if (tid == 0) {
         if (part == 0) emit(0, ax, ay, az, cur);
+        if (part == 0 && n_live_out) n_live_out[b] = M;            // unless the maximum reaches 0 first (mode 4)
         s_acc[0] = make_float4(ax, ay, az, 0.f);
         s_ctl[3] = 0;
     }
@@ -1255,7 +1305,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
                 if (changed) {
                     if constexpr (LP) reinterpret_cast<float*>(s_pts + lb * 64 + lane)[3] = nd; else fps_st_dist(pts, p[u], nd);
                 }
-                if (__ballot(changed) == 0ull) continue;
+                if (__ballot(changed) == 0ull && U[u] != INFINITY) continue;       // (first visit: as in fps_spec_kernel)
                 if (__ballot(changed && d0 == U[u]) == 0ull && U[u] != INFINITY) continue;
                 if (!real) nd = -1.f;                               // padding lanes of the last bucket never win
                 const float m1 = wave_max_fused(nd);
@@ -1495,7 +1545,10 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
                 // maximum) or nothing reached the bounds (lower the threshold and select again)
                 if (nvalid > 0) {
                     vtop = wave_max_fused(valid ? val : -1.f);
-                    mode = 1;
+                    // the largest record at 0 = the plot's maximum is 0, the rest is index 0.  (A record of 0 is only published
+                    // with tau <= 0, i.e. every workgroup's top eight by key: a larger value left out of them would lie in the
+                    // 64-ulp key class of 0 -- a positive squared distance below 64 denormal ulps, which no coordinates give.)
+                    mode = vtop <= 0.f ? 4 : 1;
                 } else {
                     mode = 2;
                 }
@@ -1518,11 +1571,12 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
             if (lane == 0) {
                 if (failed) atomicAdd(&ctl[1], 1u);
                 s_ctl[0] = nj;
-                s_ctl[1] = (mode == 3 || cnt + (mode == 0 ? nj : (mode == 1 ? 1 : 0)) >= M) ? 1 : 0;
+                s_ctl[1] = (mode >= 3 || cnt + (mode == 0 ? nj : (mode == 1 ? 1 : 0)) >= M) ? 1 : 0;
                 s_ctl[2] = __float_as_int(vtop);
                 s_ctl[3] = 0;
                 s_ctl[4] = mode;
-                *s_win = 0xFFFFFFFFu;
+                s_win[0] = 0xFFFFFFFFu;                 // the tie search's winner (atomicMin) and this workgroup's maximum (atomicMax)
+                s_win[1] = 0u;
             }
 #ifdef SN2_FC_STAMPS
             FCSTAMP(t7);
@@ -1543,12 +1597,34 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
             gave_up = true;
             break;
         }
+        if (mode == 4) {
+            // every workgroup of the plot derived this from the same records: all leave, part 0 writes the rest (fps_fill_zero)
+            if (part == 0) {
+                const float x0 = px[0], y0 = py[0], z0 = pz[0];
+                for (int i = cnt + tid; i < M; i += NW * 64) emit(i, x0, y0, z0, 0);
+                if (tid == 0 && n_live_out) n_live_out[b] = cnt;
+            }
+            break;
+        }
         if (mode == 0) {
             const float4 a = s_acc[lane < j ? lane : 0];
             ax = a.x; ay = a.y; az = a.z;
         } else if (mode == 1) {
-            // exact tie of the maximal distance: lowest ORIGINAL index among all points of the plot attaining it
-            const float V = __int_as_float(s_ctl[2]);
+            // exact tie of the maximal distance: lowest ORIGINAL index among all points of the plot attaining it.  The maximum is
+            // NOT the largest published record: a workgroup publishes its top records by their 64-ulp keys, so a bucket it left out
+            // may hold a value above all of them inside the top key's class (distinct points at nearly equal distances: a rotated
+            // lattice of ground points gives hundreds).  Every workgroup therefore searches at its OWN true maximum and states it
+            // beside its winner; the plot's maximum is the largest of those.
+            float lmx = 0.f;
+#pragma unroll
+            for (int h = 0; h < SL; ++h) {
+                const int sl = 64 * h + lane;
+                if (sl < SPW) lmx = fmaxf(lmx, s_val[sl * NW + wave]);          // (empty buckets hold -1)
+            }
+            lmx = wave_max_fused(lmx);
+            if (lane == 0) atomicMax(s_win + 1, __float_as_uint(lmx));           // non-negative floats order as their bits
+            __syncthreads();
+            const float V = __uint_as_float(s_win[1]);
 #pragma unroll
             for (int h = 0; h < SL; ++h) {
                 const int sl = 64 * h + lane;
@@ -1569,15 +1645,19 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
             }
             __syncthreads();
             if (wave == 0) {
-                fc_u64* tg = xg + 6 * NE + P;           // one tie word per workgroup
-                if (lane == 0) fc_store(tg + part, epoch, *s_win);
-                fc_u64 tw = 0;
+                fc_u64* tg = xg + 6 * NE + P;           // two tie words per workgroup: its winner, its maximum
+                if (lane == 0) {
+                    fc_store(tg + part, epoch, s_win[0]);
+                    fc_store(tg + P + part, epoch, s_win[1]);
+                }
+                fc_u64 tw = 0, tv = 0;
                 bool failed = false;
                 for (unsigned spins = 0;;) {
                     bool ok = true;
                     if (lane < P) {
                         tw = fc_pick(FC_DUAL ? fc_load(tg + lane) : 0ull, fc_load(tg + FC_COPY_U64 + lane), epoch);
-                        ok = (unsigned)(tw >> 32) == epoch;
+                        tv = fc_pick(FC_DUAL ? fc_load(tg + P + lane) : 0ull, fc_load(tg + FC_COPY_U64 + P + lane), epoch);
+                        ok = (unsigned)(tw >> 32) == epoch && (unsigned)(tv >> 32) == epoch;
                     }
                     if (__ballot(!ok) == 0ull) break;
                     if (++spins > spin_limit) {
@@ -1586,7 +1666,9 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
                     }
                     __builtin_amdgcn_s_sleep(1);
                 }
-                const unsigned w = wave_min_u32_dpp(lane < P ? (unsigned)tw : 0xFFFFFFFFu);
+                // the plot's maximum = the largest of the workgroups' (as bits), the winner = the lowest index among those that hold it
+                const unsigned gmax = ~wave_min_u32_dpp(lane < P ? ~(unsigned)tv : 0xFFFFFFFFu);
+                const unsigned w = wave_min_u32_dpp(lane < P && (unsigned)tv == gmax ? (unsigned)tw : 0xFFFFFFFFu);
                 if (lane == 0) {
                     s_ctl[5] = (int)w;
                     if (failed || w == 0xFFFFFFFFu) {
@@ -1649,14 +1731,14 @@ extern "C" int sn2_debug_fps_spin_limit(unsigned sweeps) {
 }
 template <int SPW, int NW, int P>
 static int launch_fps_cluster(const float* pos, int B, int N, int M, const int* start, int* ws, int* idx, float* cs,
-                              float* ca, hipStream_t st) {
+                              float* ca, const int* nl, int* nlo, hipStream_t st) {
     constexpr int NBL = SPW * NW, NE = FC_TP * P;
     int* order = ws;
     float4* sorted = reinterpret_cast<float4*>(ws + (size_t)B * N);
     int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);
     unsigned* xchg = reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS);
     unsigned* ctl = reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N));
-    launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, st);
+    launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, nl, st);
     const int log_cap = M <= 4096 ? M : 0;           // the samples of a plot stay in LDS until the end (16 B each) when they fit
     const size_t lds0 = (size_t)NBL * 16 + 8 * 16 + 2 * (size_t)(NE + 16) * 16 + 2 * FC_TP * 16 + (size_t)NBL * 4 * 9 + 72 * 4 + 8 * 4 + 16 +
                         (size_t)log_cap * 16;
@@ -1668,43 +1750,44 @@ static int launch_fps_cluster(const float* pos, int B, int N, int M, const int* 
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((fps_cluster_kernel<SPW, NW, P, can_lp>), dim3(B * P), dim3(NW * 64), lds, st, pos, B, N, M, start,
                            (const int*)order, sorted, idx, cs, ca, reinterpret_cast<fc_u64*>(xchg), ctl, log_cap, fps_cluster_tau_keep,
-                           fps_cluster_spin_limit);
+                           fps_cluster_spin_limit, nlo);
         SN2_RETURN_LAUNCH();
     }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_cluster_kernel<SPW, NW, P, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0);
     hipLaunchKernelGGL((fps_cluster_kernel<SPW, NW, P, false>), dim3(B * P), dim3(NW * 64), lds0, st, pos, B, N, M, start,
                        (const int*)order, sorted, idx, cs, ca, reinterpret_cast<fc_u64*>(xchg), ctl, log_cap, fps_cluster_tau_keep,
-                       fps_cluster_spin_limit);
+                       fps_cluster_spin_limit, nlo);
     SN2_RETURN_LAUNCH();
 }
 
 // P workgroups of NW waves per plot; the slots per wave follow from the plot size
 template <int NW, int P>
 static int dispatch_fps_cluster(const float* pos, int B, int N, int M, const int* start, int* ws, int* idx, float* cs,
-                                float* ca, hipStream_t st) {
+                                float* ca, const int* nl, int* nlo, hipStream_t st) {
     const int nbl = sn2_cdiv(sn2_cdiv(N, 64), P);          // buckets per workgroup
     const int spw = sn2_cdiv(nbl, NW);
-    if (spw <= 2) return launch_fps_cluster<2, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, st);
-    if (spw <= 4) return launch_fps_cluster<4, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, st);
-    if (spw <= 8) return launch_fps_cluster<8, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, st);
-    if (spw <= 16) return launch_fps_cluster<16, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, st);
-    if (spw <= 32) return launch_fps_cluster<32, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, st);
+    if (spw <= 2) return launch_fps_cluster<2, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
+    if (spw <= 4) return launch_fps_cluster<4, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
+    if (spw <= 8) return launch_fps_cluster<8, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
+    if (spw <= 16) return launch_fps_cluster<16, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
+    if (spw <= 32) return launch_fps_cluster<32, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
     if constexpr (NW <= 8) {     // (64 slots x 16 waves = 16 bucket values per lane of the selecting wave: spills at 128 VGPRs)
-        if (spw <= 64) return launch_fps_cluster<64, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, st);
+        if (spw <= 64) return launch_fps_cluster<64, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
     }
     return SN2_ELIMIT;
 }
 
 // the single-workgroup kernel for a plot of N points, 16 waves (what `waves = 16` runs); repair = behind fps_cluster_kernel
 static int dispatch_fps_bucket16(const float* pos_soa, int B, int N, int M, const int* start, int* order_ws, int* idx,
-                                 float* cpos_soa, float* cpos_aos, hipStream_t st, bool spec, bool repair, unsigned* status) {
-    if (N <= 4096) return launch_fps_bucket<4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, spec, repair, status);
-    if (N <= 8192) return launch_fps_bucket<8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, spec, repair, status);
-    if (N <= 16384) return launch_fps_bucket<16>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, spec, repair, status);
-    if (N <= 32768) return launch_fps_bucket<32>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, spec, repair, status);
-    if (N <= 65536) return launch_fps_bucket<64>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, spec, repair, status);
-    if (N <= 131072) return launch_fps_bucket<128>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, spec, repair, status);
+                                 float* cpos_soa, float* cpos_aos, const int* nl, int* nlo, hipStream_t st, bool spec, bool repair,
+                                 unsigned* status) {
+    if (N <= 4096) return launch_fps_bucket<4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
+    if (N <= 8192) return launch_fps_bucket<8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
+    if (N <= 16384) return launch_fps_bucket<16>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
+    if (N <= 32768) return launch_fps_bucket<32>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
+    if (N <= 65536) return launch_fps_bucket<64>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
+    if (N <= 131072) return launch_fps_bucket<128>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
     return SN2_ELIMIT;
 }
 
@@ -1731,11 +1814,17 @@ extern "C" size_t sn2_znorm_ws_words(int n, long cells) { return SN2_ZNORM_WS_WO
 
 extern "C" int sn2_fps_waves(const float* pos_soa, int B, int N, int M, const int* start, int* idx, float* cpos_soa,
                              float* cpos_aos, int* order_ws, int waves, void* stream) {
-    return sn2_fps_status(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, order_ws, waves, nullptr, stream);
+    return sn2_fps_live(pos_soa, B, N, M, start, nullptr, idx, cpos_soa, cpos_aos, order_ws, waves, nullptr, nullptr, stream);
 }
 
 extern "C" int sn2_fps_status(const float* pos_soa, int B, int N, int M, const int* start, int* idx, float* cpos_soa,
                               float* cpos_aos, int* order_ws, int waves, unsigned* status, void* stream) {
+    return sn2_fps_live(pos_soa, B, N, M, start, nullptr, idx, cpos_soa, cpos_aos, order_ws, waves, nullptr, status, stream);
+}
+
+// nl = n_live, nlo = n_live_out (include/strata_hip.h): every kernel form below honours both
+extern "C" int sn2_fps_live(const float* pos_soa, int B, int N, int M, const int* start, const int* nl, int* idx, float* cpos_soa,
+                            float* cpos_aos, int* order_ws, int waves, int* nlo, unsigned* status, void* stream) {
     if (!pos_soa || !idx || !cpos_soa || !cpos_aos || B <= 0 || N <= 0 || M <= 0 || M > N) return SN2_EINVAL;
     bool cluster = waves == 34 || waves == 36 || waves == 40 || waves == 66 || waves == 68 || waves == 72;
     if (waves != 0 && waves != 16 && waves != 8 && waves != 4 && waves != 1 && !cluster) return SN2_EINVAL;
@@ -1760,16 +1849,16 @@ extern "C" int sn2_fps_status(const float* pos_soa, int B, int N, int M, const i
             const bool fits = (long)B * P <= sn2_cu_count() && sn2_cdiv(N, 64) >= 2 * P * NWc && sn2_cdiv(N, 64) <= 512 * P;
             if (fits) {
                 int rc;
-                if (waves == 34) rc = dispatch_fps_cluster<16, 2>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-                else if (waves == 36) rc = dispatch_fps_cluster<16, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-                else if (waves == 40) rc = dispatch_fps_cluster<16, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-                else if (waves == 66) rc = dispatch_fps_cluster<8, 2>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-                else if (waves == 68) rc = dispatch_fps_cluster<8, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-                else rc = dispatch_fps_cluster<8, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
+                if (waves == 34) rc = dispatch_fps_cluster<16, 2>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+                else if (waves == 36) rc = dispatch_fps_cluster<16, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+                else if (waves == 40) rc = dispatch_fps_cluster<16, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+                else if (waves == 66) rc = dispatch_fps_cluster<8, 2>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+                else if (waves == 68) rc = dispatch_fps_cluster<8, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+                else rc = dispatch_fps_cluster<8, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
                 if (rc != 0) return rc;
                 // the repair launch: B workgroups that read control word 1 and leave -- unless a wait of the pass above gave
                 // up (its workgroups are not guaranteed to be resident together), in which case they sample every plot again
-                return dispatch_fps_bucket16(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, true, true, status);
+                return dispatch_fps_bucket16(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, true, true, status);
             }
             waves = 16;
         }
@@ -1780,29 +1869,29 @@ extern "C" int sn2_fps_status(const float* pos_soa, int B, int N, int M, const i
         // waves = 4 (plots of at most 16 384 points): half the wave slots again, for passes that share the chip with MANY other
         // workgroups (the parcel loop: 512 plots per launch = two FPS workgroups per CU); larger plots take the 8-wave kernel
         if (waves == 4 && N <= 16384) {
-            if (N <= 8192) return launch_fps_bucket<32, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-            return launch_fps_bucket<64, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
+            if (N <= 8192) return launch_fps_bucket<32, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+            return launch_fps_bucket<64, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
         }
         // (four waves at 32 768 points -- launch_fps_bucket<128, 4> -- were measured in the training loop: 0.773 against 0.769 ms
         // per step with eight; not instantiated)
         if (waves == 4) waves = 8;
         if (waves == 8 && N <= 32768) {
-            if (N <= 4096) return launch_fps_bucket<8, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-            if (N <= 8192) return launch_fps_bucket<16, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-            if (N <= 16384) return launch_fps_bucket<32, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
-            return launch_fps_bucket<64, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st);
+            if (N <= 4096) return launch_fps_bucket<8, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+            if (N <= 8192) return launch_fps_bucket<16, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+            if (N <= 16384) return launch_fps_bucket<32, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
+            return launch_fps_bucket<64, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
         }
-        return dispatch_fps_bucket16(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, st, spec, false, nullptr);
+        return dispatch_fps_bucket16(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, false, nullptr);
     }
-    if (N <= 256) return launch_fps<1, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 512) return launch_fps<2, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 1024) return launch_fps<4, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 2048) return launch_fps<2, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (fps_many_small(B, N)) return launch_fps<16, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 4096) return launch_fps<4, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 8192) return launch_fps<8, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 16384) return launch_fps<16, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
-    if (N <= 32768) return launch_fps<32, 1024, true>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, st);
+    if (N <= 256) return launch_fps<1, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (N <= 512) return launch_fps<2, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (N <= 1024) return launch_fps<4, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (N <= 2048) return launch_fps<2, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (fps_many_small(B, N)) return launch_fps<16, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (N <= 4096) return launch_fps<4, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (N <= 8192) return launch_fps<8, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (N <= 16384) return launch_fps<16, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
+    if (N <= 32768) return launch_fps<32, 1024, true>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
     return SN2_ELIMIT;
 }
 

@@ -266,7 +266,10 @@ int geometry_impl(const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_g
     int* ws2 = sn2_fps_fills_ws(B, M1, M2) ? g->ws2 : nullptr;
     int waves = 0;
     if (flags & SN2_NET_SHARED) waves = B > 32 ? m->fps_waves_many : m->fps_waves_shared;
-    SN2_TRY(sn2_fps_status(g->xyz, B, N, M1, start0, g->idx1, g->pos1_soa, g->pos1_aos, ws1, waves, io->fps_status, cur));
+    // the live prefix (sn2_fps_live): level 1 counts its samples up to a maximum of 0, level 2 takes that count as its own prefix
+    if (io->fps_live && !io->fps_live1) return SN2_EINVAL;
+    int* live1 = io->fps_live ? io->fps_live1 : nullptr;
+    SN2_TRY(sn2_fps_live(g->xyz, B, N, M1, start0, io->fps_live, g->idx1, g->pos1_soa, g->pos1_aos, ws1, waves, live1, io->fps_status, cur));
     hipStream_t sb = cur, sc = cur;
     if (fork) {
         sb = (hipStream_t)io->stream_b, sc = (hipStream_t)io->stream_c;
@@ -275,7 +278,7 @@ int geometry_impl(const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_g
         NET_HIP(hipStreamWaitEvent(sc, ctx->fork, 0));
     }
     // (b) the level-2 chain
-    SN2_TRY(sn2_fps_status(g->pos1_soa, B, M1, M2, start1, g->idx2, g->pos2_soa, g->pos2_aos, ws2, 0, io->fps_status, sb));
+    SN2_TRY(sn2_fps_live(g->pos1_soa, B, M1, M2, start1, live1, g->idx2, g->pos2_soa, g->pos2_aos, ws2, 0, nullptr, io->fps_status, sb));
     // (the message totals are the counts of the batch-statistics BatchNorms: only a pass a backward may follow -- `inverted` --
     // needs them; an eval pass over hundreds of plots spent 0.2 ms per level in the one-workgroup sum.  A forward that finds
     // tables without them builds them with the inverted indices: inverted_tables)

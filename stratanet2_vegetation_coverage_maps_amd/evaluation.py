@@ -150,7 +150,8 @@ def evaluate(model, batches, args, kde=None, prefetch=3):
     """`learning/test.py:evaluate` for a fold given as batches -> (loss_dict, summaries).
 
     batches: iterable of `cloud_data` dicts as the reference's collate makes them: "cloud" (B,10,N), "xyz" (B,3,N), "coverages"
-    (B,4), "plot_id" (B names), optionally "pdf_all" (B*N,3) and "fps_start"; B and N may differ between batches.
+    (B,4), "plot_id" (B names), optionally "pdf_all" (B*N,3), "fps_start" and "n_live" (PointNet2's additive keys, handed on to the
+    geometry passes as they are); B and N may differ between batches.
     kde: a `losses.KdeTables`: a batch without "pdf_all" gets its densities from `kde_densities(cloud, args.z_max, kde)`; neither
     given while `args.m != 0` is an error, raised before the batch's first launch.
     prefetch: geometry passes in flight ahead of the feature pass (`PointNet2.prefetch_geometry`), 0 = none.

@@ -128,6 +128,7 @@ class ArenaGeometry:
         self.B, self.N, self.M1, self.M2 = plan.B, plan.N, plan.M1, plan.M2
         self.arena = torch.empty(plan.geo_bytes, dtype=U8, device=dev)
         self.pos3 = _pos3(dev, plan.B)
+        self.fps_live1 = torch.empty(plan.B, dtype=I32, device=dev)      # sn2_net_io.fps_live1, when a batch carries n_live
         self.xyz = None
         self.has_rows0, self.has_inverted = False, False
         self.ready, self._join = None, None
@@ -321,8 +322,10 @@ def _destroy_ctx(handle):
         pass
 
 
-def _io(model, dev, training, flags, cloud=None, fps_start=None, fork=False):
+def _io(model, dev, training, flags, cloud=None, fps_start=None, fork=False, n_live=None, geo=None):
     io = NetIO()
+    if n_live is not None:                # the plots' live prefixes (sn2_fps_live) and the handle's scratch for level 1's count
+        io.fps_live, io.fps_live1 = n_live.data_ptr(), geo.fps_live1.data_ptr()
     io.cloud = None if cloud is None else cloud.data_ptr()
     io.fps_start = None if fps_start is None else fps_start.data_ptr()
     io.fps_status = ops.fps_status_word(dev).data_ptr()
@@ -336,12 +339,14 @@ def _io(model, dev, training, flags, cloud=None, fps_start=None, fork=False):
     return io
 
 
-def geometry(model, ms, xyz, fps_start, out=None, fork=None, shared=False, defer_join=False, inverted=True, cloud=None):
+def geometry(model, ms, xyz, fps_start, out=None, fork=None, shared=False, defer_join=False, inverted=True, cloud=None, n_live=None):
     """`PointNet2._geometry` as one call (sn2_net_geometry)."""
     dev = xyz.device
     B, _, N = xyz.shape
     ops._chk(xyz, F32, (B, 3, N), "xyz")
     ops._chk(fps_start, I32, (2, B), "fps_start")
+    if n_live is not None:
+        ops._chk(n_live, I32, (B,), "n_live")
     plan = ms.plan(model, B, N)
     g = out if out is not None else ArenaGeometry(plan, dev, model)
     _check_handle(g, plan, "geometry buffers")
@@ -355,7 +360,7 @@ def geometry(model, ms, xyz, fps_start, out=None, fork=None, shared=False, defer
     if cloud is not None:
         ops._chk(cloud, F32, (B, 10, N), "cloud")
         flags |= _lib.NET_INPUT_ONLY
-    io = _io(model, dev, model.training, flags, cloud=cloud, fps_start=fps_start, fork=fork)
+    io = _io(model, dev, model.training, flags, cloud=cloud, fps_start=fps_start, fork=fork, n_live=n_live, geo=g)
     _lib.check(_lib.load().sn2_net_geometry(byref(ms.c), byref(plan.dims), byref(cg), byref(io), ops._stream()), "sn2_net_geometry")
     g.has_inverted = bool(inverted)
     g.has_rows0 = cloud is not None
@@ -365,7 +370,7 @@ def geometry(model, ms, xyz, fps_start, out=None, fork=None, shared=False, defer
     return g
 
 
-def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None, need_grad=True):
+def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None, need_grad=True, n_live=None):
     """`PointNet2._forward_impl` as one call (sn2_net_forward) -> (coverages_pointwise, proba_pointwise, NetSaved)."""
     dev = xyz.device
     B, _, N = xyz.shape
@@ -386,9 +391,11 @@ def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None
         flags = _lib.NET_WITH_GEOMETRY | (_lib.NET_FORK if fork else 0)
         geo.has_inverted = keep
         fs = fps_start
+        if n_live is not None:
+            ops._chk(n_live, I32, (B,), "n_live")
     else:
         _check_handle(geo, plan, "prefetched geometry tables")
-        flags, fs = 0, None
+        flags, fs, n_live = 0, None, None
         if getattr(geo, "has_rows0", False):
             flags |= _lib.NET_HAS_ROWS0
         if getattr(geo, "_join", None) is not None:
@@ -418,7 +425,7 @@ def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None
         # of its own in front of that pass
         bwd_arena = torch.empty(plan.bwd_arena_words, dtype=F32, device=dev)
         ca.bwd_arena, ca.bwd_arena_words = bwd_arena.data_ptr(), plan.bwd_arena_words
-    io = _io(model, dev, mode, flags, cloud=cloud, fps_start=fs, fork=fork)
+    io = _io(model, dev, mode, flags, cloud=cloud, fps_start=fs, fork=fork, n_live=n_live, geo=geo)
     if training and model.fuse_global_level and plan.gl_forward:
         ws = ops.global_level_ws(dev, owner=model)
         io.gl_xchg, io.gl_ctl = ws[0].data_ptr(), ws[1].data_ptr()

@@ -374,7 +374,8 @@ def fps_gave_up(dev, warn: bool = True) -> int:
 
 
 def fps(pos_soa: torch.Tensor, m: int, start: Optional[torch.Tensor] = None, bucketed: bool = True,
-        return_ws: bool = False, out=None, waves: int = 0):
+        return_ws: bool = False, out=None, waves: int = 0, n_live: Optional[torch.Tensor] = None,
+        n_live_out: Optional[torch.Tensor] = None):
     """pos_soa (B,3,N) -> idx (B,m) int32 local indices, cpos_soa (B,3,m), cpos_aos (B*m,4).
     waves: which bucketed kernel (include/strata_hip.h: sn2_fps_waves): 0 = the shortest pass (several workgroups per plot
     where the batch fits the chip), 16 / 8 / 4 = one workgroup of 16 / 8 / 4 waves per plot (8 = the pass that shares its CUs with
@@ -383,7 +384,11 @@ def fps(pos_soa: torch.Tensor, m: int, start: Optional[torch.Tensor] = None, buc
     1 = the one-sample-per-round kernel; same indices whichever runs.
     bucketed=False forces the brute-force kernel (same result; kept for cross-checks).  return_ws=True also returns
     the spatial-order workspace (or None), which `ball_query` over the same points can reuse.
-    out = (idx, cpos_soa, cpos_aos, workspace-or-None): caller-owned result buffers (persistent pipelines)."""
+    out = (idx, cpos_soa, cpos_aos, workspace-or-None): caller-owned result buffers (persistent pipelines).
+    n_live (B) int32 on the device: the plot's live prefix (include/strata_hip.h: sn2_fps_live) -- points [n_live[b], N) of plot b
+    are bit-identical copies of earlier ones, as every sampler of this package lays a short plot out; same bytes as without it,
+    minus the all-ties rounds.  n_live_out (B) int32: receives the samples emitted before the maximum reached 0 (m if never),
+    which is the n_live of an FPS over the returned positions."""
     B, three, N = pos_soa.shape
     _chk(pos_soa, F32, (B, 3, N), "pos_soa")
     if not (1 <= m <= N):
@@ -406,8 +411,16 @@ def fps(pos_soa: torch.Tensor, m: int, start: Optional[torch.Tensor] = None, buc
         cs = torch.empty(B, 3, m, dtype=F32, device=dev)
         ca = torch.empty(B * m, 4, dtype=F32, device=dev)
         order = torch.empty(fps_ws_words(B, N), dtype=I32, device=dev) if use_ws else None
-    _call("sn2_fps_status", _ptr(pos_soa), B, N, m, _ptr(start), _ptr(idx), _ptr(cs), _ptr(ca), _ptr(order), int(waves),
-          _ptr(fps_status_word(dev)), _stream(), tag=f"N={N}", key="sn2_fps")
+    if n_live is None and n_live_out is None:
+        _call("sn2_fps_status", _ptr(pos_soa), B, N, m, _ptr(start), _ptr(idx), _ptr(cs), _ptr(ca), _ptr(order), int(waves),
+              _ptr(fps_status_word(dev)), _stream(), tag=f"N={N}", key="sn2_fps")
+    else:
+        if n_live is not None:
+            _chk(n_live, I32, (B,), "n_live")
+        if n_live_out is not None:
+            _chk(n_live_out, I32, (B,), "n_live_out")
+        _call("sn2_fps_live", _ptr(pos_soa), B, N, m, _ptr(start), _ptr(n_live), _ptr(idx), _ptr(cs), _ptr(ca), _ptr(order),
+              int(waves), _ptr(n_live_out), _ptr(fps_status_word(dev)), _stream(), tag=f"N={N}", key="sn2_fps")
     if return_ws:
         return idx, cs, ca, order
     return idx, cs, ca
@@ -651,11 +664,12 @@ def train_batch_ws_words(B: int, n_max: int, N: int) -> int:
 
 
 def train_batch(raw, offsets, centers, coverages, plot_ids, fake_xy, n_max: int, M1: int, z_max: float, seed: int, epoch: int,
-                cos_sin, cloud, xyz, gt, fps_start, ws, train: bool = True, noise: bool = True):
+                cos_sin, cloud, xyz, gt, fps_start, ws, train: bool = True, noise: bool = True, n_live=None):
     """include/strata_hip.h: sn2_train_batch.  The resident set raw (10,T) f32, offsets (P+1) i32, centers (P,2) f32, coverages
     (P,4) f64; plot_ids (B) i32 ON THE DEVICE -- the caller has checked 0 <= id < P on the host copy it uploaded (no kernel does);
     cos_sin (360,2) f64; ws: i32, at least train_batch_ws_words(B, n_max, N) elements.  Writes cloud (B,10,N), xyz (B,3,N), gt (B,4)
-    f64 and fps_start (2,B) i32 in place, on the current stream, without a host read."""
+    f64 and fps_start (2,B) i32 in place, on the current stream, without a host read.  n_live (B) i32 or None: also the plots'
+    live prefixes min(points + fake points, N) (sn2_train_batch_live: what `fps(..., n_live=)` takes)."""
     _, T = raw.shape
     P = offsets.numel() - 1
     B, _, N = cloud.shape
@@ -680,9 +694,14 @@ def train_batch(raw, offsets, centers, coverages, plot_ids, fake_xy, n_max: int,
     need = train_batch_ws_words(B, n_max, N)
     if ws.dim() != 1 or ws.numel() < need or ws.data_ptr() % 16:
         raise ValueError(f"train_batch: ws must be a 16-byte aligned 1-D int32 tensor of at least {need} elements")
-    _call("sn2_train_batch", _ptr(raw), T, _ptr(offsets), _ptr(centers), _ptr(coverages), P, _ptr(plot_ids), B, _ptr(fake_xy), F,
-          n_max, N, M1, float(z_max), seed, epoch, _ptr(cos_sin), int(bool(train)), int(bool(noise)), _ptr(ws), ws.numel(),
-          _ptr(cloud), _ptr(xyz), _ptr(gt), _ptr(fps_start), _stream())
+    args = (_ptr(raw), T, _ptr(offsets), _ptr(centers), _ptr(coverages), P, _ptr(plot_ids), B, _ptr(fake_xy), F,
+            n_max, N, M1, float(z_max), seed, epoch, _ptr(cos_sin), int(bool(train)), int(bool(noise)), _ptr(ws), ws.numel(),
+            _ptr(cloud), _ptr(xyz), _ptr(gt), _ptr(fps_start))
+    if n_live is None:
+        _call("sn2_train_batch", *args, _stream())
+    else:
+        _chk(n_live, I32, (B,), "n_live")
+        _call("sn2_train_batch_live", *args, _ptr(n_live), _stream())
 
 
 def znorm(xyz: torch.Tensor, radius: float):

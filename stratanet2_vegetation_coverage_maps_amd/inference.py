@@ -78,7 +78,8 @@ class ParcelMosaic:
 @torch.no_grad()
 def predict_parcel(model, batches, mosaic: ParcelMosaic, args, prefetch: int = 3):
     """`batches`: iterable of dicts with "cloud" (B,10,N), "xyz" (B,3,N), "plot_center" (B,2) (the reference DataLoader's
-    collate of `inference/predict_utils.py:74-82`).  Returns the number of plots processed.
+    collate of `inference/predict_utils.py:74-82`), optionally PointNet2's additive keys "fps_start" and "n_live" (`ParcelPlots.batches`
+    sets "n_live"), which reach the geometry passes as they are.  Returns the number of plots processed.
     prefetch: how many batches ahead the position-only kernels (FPS, ball query, 3-NN) run, each on its own side stream
     (`PointNet2.prefetch_geometry`), while this batch's feature kernels, rasters and merge run.  FPS is M sequential rounds
     in one workgroup per plot -- 64 plots keep 64 of 256 CUs busy for most of an un-overlapped batch -- so several passes

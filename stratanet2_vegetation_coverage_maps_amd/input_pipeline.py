@@ -77,10 +77,19 @@ def draw_plot_randoms(n_points: int, subsample_size: int, train: bool, rs, noise
     return out
 
 
+def live_counts(n_raw, n_fake: int, subsample_size: int) -> np.ndarray:
+    """(B) int32: the distinct rows at the front of each plot's subsample, min(points + fake points, subsample_size).  Both
+    samplers (and `sample_cloud`, loader.py:233-247) lay a plot of at most subsample_size candidates out as its candidates in
+    order followed by repeats of them, so this is the `n_live` of `hip_ops.fps` / `cloud_data["n_live"]`."""
+    return np.minimum(np.asarray(n_raw, dtype=np.int64) + int(n_fake), int(subsample_size)).astype(np.int32)
+
+
 def prepare_batch(raw_plots, centers, args, train: bool, rs=np.random, device="cuda:0", noise="numpy", sampler="numpy",
-                  seed=None, plot_keys=None):
+                  seed=None, plot_keys=None, n_live: bool = True):
     """raw_plots: list of (10, n_i) float32 arrays/tensors (host or device); centers: (B,2).  Returns the `cloud_data`
-    dict the model takes: {"cloud": (B,10,N), "xyz": (B,3,N)} on the device.
+    dict the model takes: {"cloud": (B,10,N), "xyz": (B,3,N), "n_live": (B) int32} on the device (n_live: `live_counts`, the
+    additive key that spares the FPS kernels the repeated points of short plots; n_live=False leaves it out, as in
+    `ParcelPlots.batches`, and nothing else changes).
     sampler="device": the subsample of plot b is `hip_ops.subsample`'s row for (seed, plot_keys[b]); seed: None = one 64-bit
     seed drawn from `rs` per call (after the plots' augmentation draws); plot_keys: (B) integers, None = 0 .. B-1."""
     check_sampler(sampler)
@@ -122,4 +131,7 @@ def prepare_batch(raw_plots, centers, args, train: bool, rs=np.random, device="c
     with torch.cuda.device(dev):
         cloud, xyz = ops.prepare_plots(raw, offsets, torch.as_tensor(np.asarray(centers), dtype=torch.float32).to(dev).contiguous(),
                                        torch.from_numpy(fake).to(dev), idx, args.z_max, rot, flips, nz, noffs)
-    return {"cloud": cloud, "xyz": xyz}
+    out = {"cloud": cloud, "xyz": xyz}
+    if n_live:
+        out["n_live"] = torch.from_numpy(live_counts(n_raw, len(fake), N)).to(dev)
+    return out

@@ -26,7 +26,7 @@ import torch
 
 from . import hip_ops as ops
 from .inference import ParcelMosaic, predict_parcel
-from .input_pipeline import check_sampler, draw_plot_randoms, draw_seed, fake_ground_xy
+from .input_pipeline import check_sampler, draw_plot_randoms, draw_seed, fake_ground_xy, live_counts
 
 MIN_POINTS = 51              # prepare_utils.py:67-69 (< 50: None) and prepare.py:93 (> 50)
 LAS_PARCEL_BUFFER = 20       # prepare_utils.py:148
@@ -158,24 +158,29 @@ class ParcelPlots:
     def __len__(self):
         return len(self.n_points)
 
-    def batches(self, args, batch_size: int, rs=np.random, fps_start: Optional[int] = None, sampler="numpy", seed=None):
-        """The input dicts of `inference.predict_parcel` ("cloud", "xyz", "plot_center"), built on the device from raw /
+    def batches(self, args, batch_size: int, rs=np.random, fps_start: Optional[int] = None, sampler="numpy", seed=None,
+                n_live: bool = True):
+        """The input dicts of `inference.predict_parcel` ("cloud", "xyz", "plot_center", "n_live"), built on the device from raw /
         offsets by `sn2_prepare_plots` in eval mode.  Random draws: `draw_plot_randoms` per plot in plot order, so the
         batches equal `input_pipeline.prepare_batch(plots, centers, args, train=False, rs=rs)` on the same plots and seed.
         fps_start: None (the model draws the FPS starts) or one start index for every plot.
         sampler="device": the subsamples come from `hip_ops.subsample` instead (no host loop over plots, no index table
         copied per batch), keyed by `seed` (None: one 64-bit seed from `rs`, drawn when the first batch is asked for) and
-        the plot's position in this ParcelPlots, so a plot's points do not depend on `batch_size`."""
+        the plot's position in this ParcelPlots, so a plot's points do not depend on `batch_size`.
+        "n_live" (B) int32 = `input_pipeline.live_counts`: with either sampler a plot of fewer than subsample_size candidates is
+        its candidates in order, then repeats (a sparse parcel: half of its plots); the FPS kernels skip the repeats.  n_live=False
+        leaves the key out (same predictions; a cross-check and a timing comparison)."""
         check_sampler(sampler)                       # here, not in the generator: a bad argument fails at the call
         if sampler == "numpy" and seed is not None:
             raise ValueError("seed belongs to sampler='device'")
-        return self._batches(args, batch_size, rs, fps_start, sampler, seed)
+        return self._batches(args, batch_size, rs, fps_start, sampler, seed, n_live)
 
-    def _batches(self, args, batch_size, rs, fps_start, sampler, seed):
+    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True):
         dev = self.raw.device
         fake = fake_ground_xy(args.diam_meters)
         fake_dev = torch.from_numpy(fake).to(dev)
         N = args.subsample_size
+        n_live = torch.from_numpy(live_counts(self.n_points, len(fake), N)).to(dev)
         if sampler == "device":
             seed = draw_seed(rs) if seed is None else int(seed)
             keys = torch.arange(len(self), dtype=torch.int64, device=dev)
@@ -191,6 +196,8 @@ class ParcelPlots:
             with torch.cuda.device(dev):
                 cloud, xyz = ops.prepare_plots(self.raw, self.offsets[b0:b1 + 1], self.centers[b0:b1], fake_dev, idx, args.z_max)
             d = {"cloud": cloud, "xyz": xyz, "plot_center": self.centers_host[b0:b1]}
+            if with_live:
+                d["n_live"] = n_live[b0:b1]
             if fps_start is not None:
                 d["fps_start"] = torch.full((2, b1 - b0), int(fps_start), dtype=torch.int64)
             yield d
@@ -268,14 +275,14 @@ def parcel_mosaic(centers_host: np.ndarray, args, device) -> ParcelMosaic:
 
 
 def predict_parcel_cloud(model, parcel_cloud, args, batch_size: int = 20, rs=np.random, keep=None, prefetch: int = 3,
-                         centers=None, fps_start: Optional[int] = None, sampler="numpy", seed=None):
+                         centers=None, fps_start: Optional[int] = None, sampler="numpy", seed=None, n_live: bool = True):
     """prepare_parcel + a mosaic sized to the plots + `inference.predict_parcel` -> (ParcelMosaic, ParcelPlots).  The mosaic
-    is None when the parcel has no kept plot.  `mosaic.finalize()` gives the coverage bands.  sampler, seed: as
+    is None when the parcel has no kept plot.  `mosaic.finalize()` gives the coverage bands.  sampler, seed, n_live: as
     `ParcelPlots.batches`."""
     check_sampler(sampler)
     plots = prepare_parcel(parcel_cloud, args, centers=centers, keep=keep)
     if len(plots) == 0:
         return None, plots
     mosaic = parcel_mosaic(plots.centers_host, args, plots.raw.device)
-    predict_parcel(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed), mosaic, args, prefetch=prefetch)
+    predict_parcel(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live), mosaic, args, prefetch=prefetch)
     return mosaic, plots

@@ -34,7 +34,8 @@ class TrainPipeline:
     def __init__(self, model, opt, feature_step, slot_inputs, depth=2, use_graph=True, n_streams=None,
                  split_exchange=None, pair=None, group=None, phase=0):
         """model: PointNet2 (train mode); opt: FlatAdam; slot_inputs: list of depth+1 dicts with device tensors "cloud"
-        (B,10,N), "xyz" (B,3,N), "fps_start" (2,B) int32 + whatever `feature_step` needs;
+        (B,10,N), "xyz" (B,3,N), "fps_start" (2,B) int32 [, "n_live" (B) int32: the plots' live prefixes, PointNet2's additive
+        `cloud_data` key, in all slots or none; read on the device by every geometry pass] + whatever `feature_step` needs;
         feature_step(inputs, geometry) -> loss: zero_grad, forward (with cloud_data["geometry"] = geometry),
         projection, loss, backward -- everything of the step except the gradient exchange and the optimiser."""
         # pair mode: one geometry pass covers TWO consecutive batches (FPS is one workgroup per plot and M sequential
@@ -61,11 +62,12 @@ class TrainPipeline:
         self._geo_kw = {"fork": False, "shared": True} if hasattr(model, "geometry_fork") else {}
         self.inputs = slot_inputs
         self.depth, self.slots = depth, len(slot_inputs)
+        self.has_live = bool(getattr(model, "geometry_takes_n_live", False)) and all("n_live" in d for d in slot_inputs)
         dev = slot_inputs[0]["xyz"].device
         self.dev = dev
         B, _, N = slot_inputs[0]["xyz"].shape
         if self.pair:
-            self.geo, self.geo_pairs, self.xyz2, self.fs2 = [None] * self.slots, [], [], []
+            self.geo, self.geo_pairs, self.xyz2, self.fs2, self.nl2 = [None] * self.slots, [], [], [], []
             for pb in range(self.slots // G):
                 gp, parts = model.alloc_geometry_pair(B, N, dev, group=G) if G != 2 else model.alloc_geometry_pair(B, N, dev)
                 self.geo_pairs.append(gp)
@@ -73,6 +75,7 @@ class TrainPipeline:
                     self.geo[G * pb + h] = parts[h]
                 self.xyz2.append(torch.empty(G * B, 3, N, dtype=slot_inputs[0]["xyz"].dtype, device=dev))
                 self.fs2.append(torch.zeros(slot_inputs[0]["fps_start"].shape[0], G * B, dtype=torch.int32, device=dev))
+                self.nl2.append(torch.full((G * B,), N, dtype=torch.int32, device=dev) if self.has_live else None)
             # The positions (and, where the slots carry them, the clouds) of the G batches of a pass live in ONE tensor per pass
             # group, and the slots' entries are VIEWS of it (round 5): the pass reads the group's tensor directly -- no G + G
             # device-to-device copies in front of every pass -- and its input-only pieces run once over the whole group.
@@ -161,7 +164,8 @@ class TrainPipeline:
                 # the next batch arrives from the host (pinned buffers): its copy into the slot rides on the side stream,
                 # in front of the geometry pass that reads it and behind the feature pass that last read the slot
                 self._feed(i, d)
-            self.model._geometry(d["xyz"], d["fps_start"], out=self.geo[k], **self._geo_kw, **self._cloud_kw(d))
+            live = {"n_live": d["n_live"]} if self.has_live else {}
+            self.model._geometry(d["xyz"], d["fps_start"], out=self.geo[k], **self._geo_kw, **self._cloud_kw(d), **live)
             self.geo_ready[k].record(st)
         self.issued = max(self.issued, i + 1)
 
@@ -183,11 +187,15 @@ class TrainPipeline:
                 # (2, G B) table -- are copied when a feeder may have changed them, and once otherwise)
                 if self.feeder is not None or not self._fs_synced[pb]:
                     self.fs2[pb][:, h * B:(h + 1) * B].copy_(d["fps_start"], non_blocking=True)
+                    if self.has_live:
+                        self.nl2[pb][h * B:(h + 1) * B].copy_(d["n_live"], non_blocking=True)
             self._fs_synced[pb] = True
             kw = {}
             if self.input_only:
                 group_cloud = self.cloud2[pb] is not None and getattr(self.model, "geometry_pair_takes_group_cloud", False)
                 kw = {"cloud2": self.cloud2[pb]} if group_cloud else {"clouds": [self.inputs[k]["cloud"] for k in ks]}
+            if self.has_live:
+                kw["n_live2"] = self.nl2[pb]
             self.model._geometry_pair(self.xyz2[pb], self.fs2[pb], self.geo_pairs[pb], tuple(self.geo[k] for k in ks), **kw)
             for k in ks:
                 self.geo_ready[k].record(st)

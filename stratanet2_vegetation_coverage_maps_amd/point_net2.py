@@ -11,9 +11,12 @@ Underneath, `forward` is ONE autograd node whose forward and backward are sequen
 gather+MLP+BN+max (SA1, SA2) -> global SA -> 3-NN interpolation + MLP (FP3..FP1) -> head.  No torch_cluster /
 torch_scatter / torch_geometric, no per-edge tensors, no host synchronisation anywhere in a step.
 
-Additive extension: `cloud_data["fps_start"]` -- int tensor (2,B) of LOCAL start indices for the two FPS calls
+Additive extensions: `cloud_data["fps_start"]` -- int tensor (2,B) of LOCAL start indices for the two FPS calls
 (the reference's `fps` starts at a C `rand()` point and is unseeded).  Absent: random starts
 drawn with torch's generator in training mode... the reference draws them in eval mode too, so does this class.
+`cloud_data["n_live"]` -- int tensor (B): plot b's points [n_live[b], N) are bit-identical copies of earlier ones, which is how
+every sampler lays out a plot with fewer candidates than `subsample_size` (input_pipeline.live_counts).  The FPS kernels then skip
+the copies (include/strata_hip.h: sn2_fps_live); outputs and tables are the same bytes as without the key.  Absent: all N points.
 """
 import os
 from collections import OrderedDict
@@ -99,7 +102,10 @@ class _PointNet2Fn(torch.autograd.Function):
         # requires_grad flags WHATEVER the caller's grad mode (round 5: under torch.no_grad() it said yes, and an eval forward
         # took the everything-kept path of the eval-mode backward): the callers record torch.is_grad_enabled() in front of apply
         need_grad = bool(getattr(model, "_grad_mode_at_call", True)) and any(ctx.needs_input_grad[6:])
-        cov, proba, saved = model._forward_impl(xyz, cloud, fps_start, training, geo, drop_keep, need_grad=need_grad)
+        # (the batch's live prefixes, cloud_data["n_live"], ride the same way: only a forward that runs its own geometry pass reads them)
+        n_live = model.__dict__.pop("_n_live_at_call", None)
+        cov, proba, saved = model._forward_impl(xyz, cloud, fps_start, training, geo, drop_keep, need_grad=need_grad,
+                                                **({} if n_live is None else {"n_live": n_live}))
         ctx.model = model
         if not isinstance(saved, X.NetSaved):
             saved.training = training
@@ -248,6 +254,7 @@ class PointNet2(nn.Module):
                 xyz_d, fs = geo.xyz, None
             else:
                 xyz_d, fs = self._stage_positions(cloud_data, dev)
+                self._n_live_at_call = self._stage_live(cloud_data, dev, xyz_d.shape[0])
             self._last_cloud_dev = (cloud, cloud_d)  # lets project_to_plotwise_coverages skip a second H2D copy
             params = self._params()
             self._grad_mode_at_call = torch.is_grad_enabled()
@@ -269,7 +276,8 @@ class PointNet2(nn.Module):
         start.record(cur)
         xyz_d, fs = self._stage_positions(cloud_data, dev, ring=ring)
         # (the inverted tables: whenever a backward pass may follow -- training, or eval mode under autograd)
-        g = self._geometry(xyz_d, fs, defer_join=True, inverted=self.training or torch.is_grad_enabled())     # launched: the device is busy from here on
+        g = self._geometry(xyz_d, fs, defer_join=True, inverted=self.training or torch.is_grad_enabled(),     # launched: the device is busy from here on
+                           **self._live_kw(self._stage_live(cloud_data, dev, xyz_d.shape[0])))
         up = ops.shared_stream(dev, "upload")
         up.wait_event(start)                                                          # not for the geometry pass: only for the block's past
         ring.upload(cloud, stream=up, dtype=F32, out=cloud_d, consumer=cur)            # host memcpy + DMA beside the geometry pass
@@ -388,6 +396,7 @@ class PointNet2(nn.Module):
         g = _Saved()
         g.B, g.N, g.M1, g.M2 = B, N, M1, M2
         g.idx1, g.pos1_soa, g.pos1_aos = e(B, M1, dt=I32), e(B, 3, M1), e(B * M1, 4)
+        g.fps_live1 = e(B, dt=I32)              # level 1's count of live samples = level 2's n_live (hip_ops.fps), when a batch has one
         g.ws1 = e(ops.fps_ws_words(B, N), dt=I32) if ops.fps_fills_ws(B, N, M1) else None
         # every point's position along the plot's Morton curve (the level-1 FPS leaves it in its workspace): the order FP1's
         # backward keeps its d pre-activation rows in (hip_ops.fp_desc: row_perm)
@@ -427,7 +436,9 @@ class PointNet2(nn.Module):
             ops.plot_pixels(cloud, self.p2_diam_pix, out=(g.p2_mm, g.p2_pix))
             g.p2_diam_pix = int(self.p2_diam_pix)
 
-    def _geometry(self, xyz, fps_start, out=None, fork=None, shared=False, defer_join=False, inverted=True, cloud=None):
+    geometry_takes_n_live = True          # `_geometry(n_live=)` / `_geometry_pair(n_live2=)`: what TrainPipeline asks before passing it
+
+    def _geometry(self, xyz, fps_start, out=None, fork=None, shared=False, defer_join=False, inverted=True, cloud=None, n_live=None):
         """Everything that depends on the point POSITIONS only (no weights, no features): both FPS levels, both ball
         queries, the three 3-NN tables.  In the reference these are the torch_cluster calls inside SAModule / FPModule
         (point_net2.py:22-25, 63).  Because they need no parameters they can run ahead of the feature kernels: see
@@ -443,10 +454,13 @@ class PointNet2(nn.Module):
         does not need them -- a tenth of the geometry pass of the parcel loop); `g.has_inverted` records it.
         `shared`: the pass runs beside other batches' feature kernels (a pipelined loop, `prefetch_geometry`): the level-1
         FPS takes `fps_waves_shared` waves per plot (include/strata_hip.h: sn2_fps_waves).
-        `cloud` (B,10,N) on the device: also run the input-only pieces of the feature pass here (`_input_only`)."""
+        `cloud` (B,10,N) on the device: also run the input-only pieces of the feature pass here (`_input_only`).
+        `n_live` (B) int32 on the device or None: the plots' live prefixes (`cloud_data["n_live"]`; include/strata_hip.h:
+        sn2_fps_live) -- level 1 samples over them and counts its samples up to a maximum of 0, level 2 takes that count.  Same
+        tables with or without it."""
         if self._use_executor():
             return X.geometry(self, self._net_model(), xyz, fps_start, out=out, fork=fork, shared=shared, defer_join=defer_join,
-                              inverted=inverted, cloud=cloud)
+                              inverted=inverted, cloud=cloud, n_live=n_live)
         dev = xyz.device
         B, _, N = xyz.shape
         M1, M2 = self._sizes(N)
@@ -456,8 +470,9 @@ class PointNet2(nn.Module):
         g.xyz = xyz
         fork = self.geometry_fork if fork is None else fork
         cur = torch.cuda.current_stream(dev)
+        live1 = None if n_live is None else g.fps_live1
         ops.fps(xyz, M1, fps_start[0], out=(g.idx1, g.pos1_soa, g.pos1_aos, g.ws1),
-                waves=(self.fps_waves_many if B > 32 else self.fps_waves_shared) if shared else 0)
+                waves=(self.fps_waves_many if B > 32 else self.fps_waves_shared) if shared else 0, n_live=n_live, n_live_out=live1)
         if fork:
             sb, sc = ops.shared_stream(dev, "fork_b"), ops.shared_stream(dev, "fork_c")
             sb.wait_stream(cur)
@@ -465,7 +480,7 @@ class PointNet2(nn.Module):
         else:
             sb = sc = cur
         with torch.cuda.stream(sb):                                        # (b) the level-2 chain
-            ops.fps(g.pos1_soa, M2, fps_start[1], out=(g.idx2, g.pos2_soa, g.pos2_aos, g.ws2))
+            ops.fps(g.pos1_soa, M2, fps_start[1], out=(g.idx2, g.pos2_soa, g.pos2_aos, g.ws2), n_live=live1)
             # (the message totals: only where a backward may follow -- `inverted`; sn2_net_geometry)
             ops.ball_query(g.pos1_soa, g.pos2_soa, self.sa2_module.r, MAX_NEIGHBORS, g.tot2 if inverted else False, fps_ws=g.ws2,
                            out=(g.nbr2, g.cnt2))
@@ -544,22 +559,25 @@ class PointNet2(nn.Module):
             halves.append(g)
         return gp, tuple(halves)
 
-    def _geometry_pair(self, xyz2, fps_start2, gp, halves, clouds=None, cloud2=None):
+    def _geometry_pair(self, xyz2, fps_start2, gp, halves, clouds=None, cloud2=None, n_live2=None):
         """`_geometry` for len(halves) batches at once: xyz2 (G B,3,N), fps_start2 (2,G B); FPS, ball queries and 3-NN tables
         run on all plots in one launch each (into `gp`), the per-batch products (message totals, SA work items, inverted 3-NN
         indices) per batch.  Same tables as G `_geometry` calls.  clouds: the G batches' (B,10,N) device tensors -> also the
         input-only pieces of their feature passes (`_input_only`), batch by batch; cloud2 (G B,10,N): the same for the whole group
-        in one launch each (the batches' clouds live in one tensor: what TrainPipeline arranges)."""
+        in one launch each (the batches' clouds live in one tensor: what TrainPipeline arranges).  n_live2 (G B) int32 or None:
+        the plots' live prefixes, as `_geometry`'s n_live."""
         B2, _, N = xyz2.shape
         B = B2 // len(halves)
         M1, M2 = self._sizes(N)
         if (gp.B, gp.N) != (B2, N):
             raise ValueError("geometry buffers do not match this batch pair")
         # 8 waves per plot: this pass runs beside other batches' feature kernels (sn2_fps_waves)
-        ops.fps(xyz2, M1, fps_start2[0], out=(gp.idx1, gp.pos1_soa, gp.pos1_aos, gp.ws1), waves=self.fps_waves_shared)
+        live1 = None if n_live2 is None else gp.fps_live1
+        ops.fps(xyz2, M1, fps_start2[0], out=(gp.idx1, gp.pos1_soa, gp.pos1_aos, gp.ws1), waves=self.fps_waves_shared,
+                n_live=n_live2, n_live_out=live1)
         # (no message total of the GROUP: the batches' totals come from count_sum_group below)
         ops.ball_query(xyz2, gp.pos1_soa, self.sa1_module.r, MAX_NEIGHBORS, False, fps_ws=gp.ws1, out=(gp.nbr1, gp.cnt1))
-        ops.fps(gp.pos1_soa, M2, fps_start2[1], out=(gp.idx2, gp.pos2_soa, gp.pos2_aos, gp.ws2))
+        ops.fps(gp.pos1_soa, M2, fps_start2[1], out=(gp.idx2, gp.pos2_soa, gp.pos2_aos, gp.ws2), n_live=live1)
         ops.ball_query(gp.pos1_soa, gp.pos2_soa, self.sa2_module.r, MAX_NEIGHBORS, False, fps_ws=gp.ws2,
                        out=(gp.nbr2, gp.cnt2))
         ops.three_nn(gp.pos3, gp.pos2_soa, 1, out=gp.knn3)
@@ -605,12 +623,15 @@ class PointNet2(nn.Module):
             # has to read them
             xyz_d.record_stream(side)
             fs.record_stream(side)
+            nl = self._stage_live(cloud_data, dev, xyz_d.shape[0])
+            if nl is not None:
+                nl.record_stream(side)
             with torch.cuda.stream(side):
                 # one stream per pass: several passes are in flight on their own lanes already, and a fork inside each
                 # (three more streams + their events) cost the parcel loop 18 % (33 300 -> 27 100 plots/s)
                 cl = cloud_data.get("cloud", None) if isinstance(cloud_data, dict) else None
                 cl = cl if (isinstance(cl, torch.Tensor) and cl.is_cuda and cl.dtype == F32 and cl.is_contiguous()) else None
-                g = self._geometry(xyz_d, fs, shared=True, fork=False, inverted=self.training, cloud=cl)
+                g = self._geometry(xyz_d, fs, shared=True, fork=False, inverted=self.training, cloud=cl, **self._live_kw(nl))
                 g.fps_start = fs
                 g.ready = torch.cuda.Event()
                 g.ready.record(side)
@@ -634,9 +655,25 @@ class PointNet2(nn.Module):
             raise ValueError(f"fps_start must have shape (2,{B})")
         return xyz_d, fs
 
-    def _forward_impl(self, xyz, cloud, fps_start, training, geo=None, drop_keep=None, need_grad=True):
+    def _stage_live(self, cloud_data, dev, B):
+        """`cloud_data["n_live"]` (B) on the device as int32, or None: the additive key of the module docstring (a host tensor is
+        uploaded with the batch)."""
+        nl = cloud_data.get("n_live", None) if isinstance(cloud_data, dict) else None
+        if nl is None or not self.geometry_takes_n_live:         # (a subclass with its own geometry pass ignores the key)
+            return None
+        nl = torch.as_tensor(nl).to(device=dev, dtype=I32, non_blocking=True).contiguous()
+        if nl.shape != (B,):
+            raise ValueError(f"n_live must have shape ({B},)")
+        return nl
+
+    @staticmethod
+    def _live_kw(n_live):
+        return {} if n_live is None else {"n_live": n_live}
+
+    def _forward_impl(self, xyz, cloud, fps_start, training, geo=None, drop_keep=None, need_grad=True, n_live=None):
         if self._use_executor():
-            cov, proba, s = X.forward(self, self._net_model(), xyz, cloud, fps_start, training, geo, drop_keep, need_grad=need_grad)
+            cov, proba, s = X.forward(self, self._net_model(), xyz, cloud, fps_start, training, geo, drop_keep, need_grad=need_grad,
+                                      n_live=n_live)
             if self.log_embeddings:
                 self.last_G_tensor = s.x3
             return cov, proba, s
@@ -661,7 +698,7 @@ class PointNet2(nn.Module):
                     ops.pack_rows(cloud, xyz, out=rows0)
                     packed = torch.cuda.Event()
                     packed.record(pack_stream)
-            geo = self._geometry(xyz, fps_start, defer_join=True, inverted=keep)
+            geo = self._geometry(xyz, fps_start, defer_join=True, inverted=keep, n_live=n_live)
         elif (geo.B, geo.N, geo.M1, geo.M2) != (B, N, M1, M2):
             raise ValueError("prefetched geometry does not match this batch")
         join = getattr(geo, "_join", None)
@@ -684,7 +721,7 @@ class PointNet2(nn.Module):
             geo.has_inverted = True
         s = _Saved()
         s.__dict__.update({k: v for k, v in geo.__dict__.items()
-                           if k not in ("ready", "stream", "ws1", "ws2", "totals", "nn_ws", "fps_start", "_join", "has_rows0")})
+                           if k not in ("ready", "stream", "ws1", "ws2", "totals", "nn_ws", "fps_start", "_join", "has_rows0", "fps_live1")})
         s.xyz = xyz
         # per-forward arenas for the BN side buffers of the 7 blocks: a,c,mean,invstd and the per-workgroup statistics
         # slots (written before they are read: no zero fill)

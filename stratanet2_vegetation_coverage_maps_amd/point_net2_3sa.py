@@ -8,6 +8,9 @@ for throughput measurements next to the reference architecture; its parity partn
 
     SA1 [11,16,16] -> SA2 [19,32] -> SA3 [35,64] (ball query, ratio3, r3) -> SA4 global [67,64] -> max
     FP4 k=1 [64+64,64] -> FP3 k=3 [64+32,64] -> FP2 k=3 [64+16,34] -> FP1 k=3 [34+8,34] -> head (as the reference)
+
+`cloud_data["n_live"]` (PointNet2's additive key: the plots' live prefixes for the FPS kernels) is IGNORED here: the three FPS
+levels of this variant always sample over all points, and `TrainPipeline` does not hand the key on (`geometry_takes_n_live`).
 """
 from collections import OrderedDict
 
@@ -21,6 +24,8 @@ from .point_net2 import (F32, I32, I64, MLP, FPModule, GlobalSAModule, PointNet2
 
 
 class PointNet2ThreeSA(PointNet2):
+    geometry_takes_n_live = False         # cloud_data["n_live"] is ignored (module docstring)
+
     def __init__(self, args):
         nn.Module.__init__(self)
         self.cuda_device = args.cuda

@@ -93,7 +93,8 @@ class ResidentPlots:
         return ids.to(torch.int32)
 
     def fill(self, plot_ids, epoch: int, seed: int, args, out, train: bool = True, noise: bool = True, kde=None, ws=None):
-        """One batch into out = {"cloud" (B,10,N), "xyz" (B,3,N), "gt" (B,4) f64, "fps_start" (2,B) i32 [, "pdf" (B N,3) f64]} on the
+        """One batch into out = {"cloud" (B,10,N), "xyz" (B,3,N), "gt" (B,4) f64, "fps_start" (2,B) i32 [, "pdf" (B N,3) f64]
+        [, "n_live" (B) i32: the plots' live prefixes, `cloud_data["n_live"]` of PointNet2 -- written when `out` has it]} on the
         current stream.  plot_ids: a host sequence (checked and uploaded here), or an int32 DEVICE tensor whose host source the
         caller has put through `check_ids` (EpochFeeder).  kde: a `losses.KdeTables` -> out["pdf"] = the densities of the cloud
         just written, the bytes of `losses.kde_densities(cloud, z_max, kde)`."""
@@ -111,7 +112,8 @@ class ResidentPlots:
                     ws = self._ws[key] = self.workspace(B, N, args.diam_meters)
             M1 = ops.fps_num_samples(N, args.ratio1)
             ops.train_batch(self.raw, self.offsets, self.centers, self.coverages, plot_ids, fake, n_max, M1, args.z_max, seed, epoch,
-                            self._cos_sin, cloud, out["xyz"], out["gt"], out["fps_start"], ws, train=train, noise=noise)
+                            self._cos_sin, cloud, out["xyz"], out["gt"], out["fps_start"], ws, train=train, noise=noise,
+                            n_live=out.get("n_live"))
             if kde is not None:
                 ops.kde_lookup(cloud, args.z_max, kde.X, kde.Y, out=out["pdf"])
         return out
