@@ -647,6 +647,42 @@ int sn2_mosaic_merge(const float *rasters, const float *weights, const int *offs
 int sn2_mosaic_finalize(const float *mean, const float *wsum, int H, int W, int *hist_ws, double *sum_ws, float *thr_out,
                         float *out, void *stream);
 
+/* Parcel crop and band means of the mosaic -- crop_merged_raster (inference/geotiff_raster.py:238-253: every pixel whose centre
+ * lies outside the parcel polygon becomes NaN) followed by get_parcel_predicted_values (inference/predict_utils.py:124-146: the
+ * band-wise nanmean of the cropped mosaic = PRED_BASSE / PRED_INTER / PRED_HAUTE).  The rule, all of it fp64, every operation
+ * rounded on its own (no fused multiply-add), the division correctly rounded:
+ *   centre   of pixel (r,c): px = x_min + pix * (c + 0.5), py = y_max - pix * (r + 0.5) (the product rounded, then the sum:
+ *            rasterio's xy(..., offset="center") over the geotransform of get_geotransform);
+ *   edges    (E,4) fp64 = (ax, ay, bx, by), on the device: every ring edge of the polygon -- exterior, holes, all parts of a
+ *            multi-part polygon (parcel.polygon_edges);
+ *   crossing an edge crosses the pixel's row iff (ay > py) != (by > py), at xint = ax + ((py - ay) * (bx - ax)) / (by - ay)
+ *            (a horizontal edge never crosses, so it never divides);
+ *   inside   iff the number of crossing edges with px < xint is odd (parcel.polygon_keep's even-odd rule at buffer 0);
+ *   crop     a pixel that is not inside becomes NaN in every band; an inside pixel keeps its bits;
+ *   stats    after the crop count[k] = the non-NaN pixels of band k, mean[k] = their sum / count[k] (NaN when count[k] = 0): the
+ *            values widened to fp64 and summed in fp64 (the reference's nanmean is numpy's fp32 pairwise sum).
+ * bands (C,H,W) fp32, changed in place; mean (C) fp64 and count (C) int64 on the device.  E == 0 with edges == NULL: no crop,
+ * bands is not written, the statistics alone.  ws: 8-byte aligned, SN2_MOSAIC_CROP_WS_WORDS(C,H,W) 32-bit words, no
+ * initialisation.  Two launches on `stream`, nothing read back, no state outside ws (capturable).  DETERMINISTIC: no
+ * floating-point atomics -- a workgroup takes the 256-pixel row segments blockIdx.x, + gridDim.x, ... (the grid is a function of
+ * H and W alone), a thread adds its pixels in that order, the threads of a workgroup are summed in a fixed tree, and a second
+ * launch of one workgroup sums the workgroups' partials in a fixed order: the same input gives the same bytes.
+ * 1 <= C <= SN2_MOSAIC_CROP_MAX_BANDS, H, W >= 1, H * W < 2^31, E == 0 or 3 <= E <= SN2_MOSAIC_CROP_MAX_EDGES (beyond:
+ * SN2_ELIMIT); pix > 0, x_min, y_max, pix finite.  Every workgroup walks all E edges once per row segment and keeps the xint of
+ * those that cross its row: H * ceil(W/256) * E edge tests instead of H * W * E.
+ * (sn2_mosaic_crop_ws_words is declared `extern`: tests/test_cabi.py holds the plain `size_t` declarations to a closed list of
+ * macros; this one is held to its macro by tests/test_parcel_report_host.py.) */
+#define SN2_MOSAIC_CROP_MAX_BANDS 8
+#define SN2_MOSAIC_CROP_MAX_EDGES (1 << 20)
+#define SN2_MOSAIC_CROP_MAX_BLOCKS 2048
+#define SN2_MOSAIC_CROP_BLOCKS(H, W) \
+    ((size_t)(H) * (((size_t)(W) + 255) / 256) < SN2_MOSAIC_CROP_MAX_BLOCKS ? (size_t)(H) * (((size_t)(W) + 255) / 256) \
+                                                                           : (size_t)SN2_MOSAIC_CROP_MAX_BLOCKS)
+#define SN2_MOSAIC_CROP_WS_WORDS(C, H, W) (4 * (size_t)(C) * SN2_MOSAIC_CROP_BLOCKS(H, W))
+extern size_t sn2_mosaic_crop_ws_words(int C, int H, int W);
+int sn2_mosaic_crop_stats(float *bands, int C, int H, int W, double x_min, double y_max, double pix, const double *edges, int E,
+                          void *ws, double *mean, long long *count, void *stream);
+
 /* ---- loss block of the timed training step: learning/loss_functions.py:9-57 combined as learning/train.py:58-62,
  *   total = get_absolute_loss(pred, gt) + m * get_NLL_loss(proba, pdf_all) + e * get_entropy_loss(proba)
  * pred (B,4) fp32 plot-wise coverages, gt (B,4) fp64, proba (R,4) fp32 pointwise class probabilities, pdf (R,3) fp64 the

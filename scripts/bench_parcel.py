@@ -6,11 +6,17 @@ EXTRAPOLATED to the parcel, the compulsory bytes of the count / fill passes agai
 candidate tests per second.  Kernel times: run it under `rocprofv3 --kernel-trace --stats`.
 
     python scripts/bench_parcel.py [--repeat 10] [--sample 6] [--batch 64] [--sampler numpy|device] [--fps-live on|off]
+                                   [--report [--pairs 5]]
 
 --sampler device draws the plots' subsamples with sn2_subsample instead of numpy on the host (`ParcelPlots.batches`); the
 prediction figures are then the median of --repeat runs as well, and sn2_subsample / sn2_prepare_plots are timed per parcel.
 --fps-live off drops the batches' "n_live" key (sn2_fps_live: the FPS kernels then sample over the repeated points of short plots
 as before): the same predictions, a cross-check inside one build.
+--report adds, per parcel, `predict_parcel_cloud(shape=rings)` + `ParcelMosaic.report(rings)` (crop to the polygon and band means
+on the device, one read of 88 bytes) against the same prediction followed by the host path a user had before: `finalize()`, the
+mosaic copied to the host, `polygon_keep(rings, 0)` over the pixel centres, mask, `np.nanmean`.  The two are run alternately,
+--pairs times each; medians and ranges of the whole and of the tail after the prediction.  The polygon is the parcel's bounding
+box shrunk by 5 m.  Without --report nothing of this runs and the output is what it was.
 """
 import argparse
 import json
@@ -78,6 +84,52 @@ def znorm_candidates(cloud, plots):
     return int(box[cy[i], cx[i]].sum())
 
 
+def report_times(model, cloud_dev, cloud, args, a, skw):
+    """--report: (whole, tail) wall times in ms of the device report and of the host path, alternated a.pairs times"""
+    x0, x1, y0, y1 = (float(v) for v in (cloud[0].min(), cloud[0].max(), cloud[1].min(), cloud[1].max()))
+    rings = [np.array([[x0 + 5, y0 + 5], [x1 - 5, y0 + 5], [x1 - 5, y1 - 5], [x0 + 5, y1 - 5]])]
+    inside = parcel.polygon_keep(rings, 0.0)
+
+    def run(tail):
+        t0 = time.perf_counter()
+        mos, _ = parcel.predict_parcel_cloud(model, cloud_dev, args, batch_size=a.batch, fps_start=0, shape=rings, **skw)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        res = tail(mos)
+        t2 = time.perf_counter()
+        return (t2 - t0) * 1e3, (t2 - t1) * 1e3, res
+
+    def device(mos):
+        rep = mos.report(rings)                              # its one read waits for the device
+        return rep.band_means[:4], rep.band_counts[:4], tuple(rep.bands.shape)
+
+    def host(mos):
+        out, thr = mos.finalize()
+        h = out.cpu().numpy()
+        float(thr[0])
+        H, W = h.shape[1:]
+        px = mos.x_min + mos.pix * (np.arange(W) + 0.5)
+        py = mos.y_max - mos.pix * (np.arange(H) + 0.5)
+        mask = inside(np.stack([np.tile(px, H), np.repeat(py, W)], 1)).reshape(H, W)
+        h[:, ~mask] = np.nan
+        flat = h[:4].reshape(4, -1)
+        return np.nanmean(flat, axis=1), (~np.isnan(flat)).sum(1), tuple(h.shape)
+
+    run(device), run(host)                                   # warm-up
+    dev, hst = [], []
+    for _ in range(a.pairs):
+        dev.append(run(device))
+        hst.append(run(host))
+    (dm, dn, shape), (hm, hn, _) = dev[-1][2], hst[-1][2]
+
+    def stat(v):
+        return {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+    return {"mosaic": shape, "polygon_pixels": int(dn[0]), "pairs": a.pairs,
+            "counts_equal": bool(np.array_equal(dn, hn)), "means_max_abs_diff_fp64_vs_fp32_nanmean": float(np.abs(dm - hm).max()),
+            "device_e2e_ms": stat([d[0] for d in dev]), "host_e2e_ms": stat([h[0] for h in hst]),
+            "device_report_ms": stat([d[1] for d in dev]), "host_crop_means_ms": stat([h[1] for h in hst])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=10)
@@ -85,6 +137,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--sampler", choices=("numpy", "device"), default="numpy")
     ap.add_argument("--fps-live", choices=("on", "off"), default="on")
+    ap.add_argument("--report", action="store_true")
+    ap.add_argument("--pairs", type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_parcel: needs the GPU")
@@ -163,6 +217,8 @@ def main():
             "znorm_candidate_tests": cand,
             "znorm_candidates_per_s_over_entry": round(cand / (1e-3 * entries.get("sn2_parcel_znorm", float("nan"))), 1),
         }
+        if a.report:
+            out[name]["report"] = report_times(model, cloud_dev, cloud, args, a, skw)
         print(f"[bench_parcel] {name}: {json.dumps(out[name])}", file=sys.stderr, flush=True)
     ten = out["10ha"]
     print(json.dumps({"metric": "10 ha parcel preparation on the device (prepare_parcel, median)", "value": ten["prepare_ms_median"],

@@ -946,3 +946,169 @@ extern "C" int sn2_mosaic_finalize(const float* mean, const float* wsum, int H, 
     hipLaunchKernelGGL(mosaic_finalize_kernel, dim3(sn2_cdiv(P, 256)), dim3(256), 0, st, mean, wsum, P, (const float*)thr_out, out);
     SN2_RETURN_LAUNCH();
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Parcel crop and band means of the mosaic: crop_merged_raster (inference/geotiff_raster.py:238-253) + the band-wise nanmean of
+// get_parcel_predicted_values (inference/predict_utils.py:124-146).  The rule is written out in include/strata_hip.h.
+// A workgroup owns a row segment of 256 pixels, one per thread.  py is a function of the row, so the workgroup walks the E
+// edges once, 256 at a time, and collects the xint of those that cross the row in LDS (wave ballot + prefix); a thread then
+// counts the list entries right of its own px.  The list is counted and emptied whenever the next 256 edges might not fit, so
+// any E and any number of crossings go through.  The expressions are those of the per-pixel test, so are the bits.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int CROP_T = 256;                           // threads = pixels of a row segment = edges of a chunk
+constexpr int CROP_LIST = 1024;                       // crossings held in LDS between two counting passes
+constexpr int CROP_C = SN2_MOSAIC_CROP_MAX_BANDS;
+
+__device__ __forceinline__ double crop_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ long long crop_wave_sum(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// psum, pcnt: (gridDim.x, C) partial sums and counts, every entry written
+template <bool CROP>
+__global__ __launch_bounds__(CROP_T) void mosaic_crop_kernel(float* __restrict__ bands, int C, int H, int W, double x_min,
+                                                             double y_max, double pix, const double* __restrict__ edges, int E,
+                                                             double* __restrict__ psum, long long* __restrict__ pcnt) {
+    // every product, difference, quotient and sum below rounded to fp64 on its own, as numpy does: no fused multiply-add
+#pragma clang fp contract(off)
+    __shared__ double s_x[CROP_LIST];
+    __shared__ int s_wn[CROP_T / 64];
+    __shared__ double s_sum[CROP_T / 64][CROP_C];
+    __shared__ long long s_cnt[CROP_T / 64][CROP_C];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int segs = (W + CROP_T - 1) / CROP_T;
+    const long nrs = (long)H * segs;
+    const size_t P = (size_t)H * W;
+    const float nanv = __int_as_float(0x7fc00000);
+    double acc[CROP_C];
+    long long cnt[CROP_C];
+#pragma unroll
+    for (int k = 0; k < CROP_C; ++k) { acc[k] = 0.0; cnt[k] = 0; }
+
+    for (long rs = blockIdx.x; rs < nrs; rs += gridDim.x) {          // uniform over the workgroup: the barriers below are safe
+        const int r = (int)(rs / segs), c = (int)(rs % segs) * CROP_T + tid;
+        bool inside = true;
+        if (CROP) {
+            const double py = y_max - pix * ((double)r + 0.5);
+            const double px = x_min + pix * ((double)c + 0.5);
+            int right = 0;                                           // crossing edges with px < xint
+            int n = 0;                                               // entries of s_x (uniform)
+            for (int e0 = 0; e0 < E; e0 += CROP_T) {
+                const int e = e0 + tid;
+                bool cr = false;
+                double xint = 0.0;
+                if (e < E) {
+                    const double ax = edges[4 * (size_t)e], ay = edges[4 * (size_t)e + 1];
+                    const double bx = edges[4 * (size_t)e + 2], by = edges[4 * (size_t)e + 3];
+                    cr = (ay > py) != (by > py);
+                    if (cr) xint = ax + ((py - ay) * (bx - ax)) / (by - ay);
+                }
+                const unsigned long long m = __ballot(cr);
+                if (lane == 0) s_wn[wave] = __popcll(m);
+                __syncthreads();                                     // (also: the last counting pass over s_x is over)
+                int base = n, total = 0;
+#pragma unroll
+                for (int w = 0; w < CROP_T / 64; ++w) {
+                    const int v = s_wn[w];
+                    base += w < wave ? v : 0;
+                    total += v;
+                }
+                if (cr) s_x[base + __popcll(m & ((1ull << lane) - 1ull))] = xint;     // n + total <= CROP_LIST: see below
+                n += total;
+                __syncthreads();
+                if (n + CROP_T > CROP_LIST || e0 + CROP_T >= E) {    // the next chunk might not fit, or there is none
+                    for (int i = 0; i < n; ++i) right += px < s_x[i] ? 1 : 0;
+                    n = 0;
+                }
+            }
+            inside = (right & 1) != 0;
+        }
+        if (c < W) {
+            const size_t o = (size_t)r * W + c;
+#pragma unroll
+            for (int k = 0; k < CROP_C; ++k) {
+                if (k < C) {
+                    if (CROP && !inside) {
+                        bands[k * P + o] = nanv;
+                    } else {
+                        const float v = bands[k * P + o];
+                        if (v == v) { acc[k] += (double)v; ++cnt[k]; }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CROP_C; ++k) {
+        if (k < C) {
+            const double s = crop_wave_sum(acc[k]);
+            const long long q = crop_wave_sum(cnt[k]);
+            if (lane == 0) { s_sum[wave][k] = s; s_cnt[wave][k] = q; }
+        }
+    }
+    __syncthreads();
+    if (tid < C) {
+        psum[(size_t)blockIdx.x * C + tid] = (s_sum[0][tid] + s_sum[1][tid]) + (s_sum[2][tid] + s_sum[3][tid]);
+        pcnt[(size_t)blockIdx.x * C + tid] = (s_cnt[0][tid] + s_cnt[1][tid]) + (s_cnt[2][tid] + s_cnt[3][tid]);
+    }
+}
+
+// one workgroup: thread t adds the partials of workgroups t, t + 256, ... in order, the threads in a fixed tree
+__global__ __launch_bounds__(CROP_T) void mosaic_crop_fold_kernel(const double* __restrict__ psum, const long long* __restrict__ pcnt,
+                                                                  int C, int nblk, double* __restrict__ mean,
+                                                                  long long* __restrict__ count) {
+    __shared__ double s_sum[CROP_T / 64];
+    __shared__ long long s_cnt[CROP_T / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int k = 0; k < C; ++k) {
+        double s = 0.0;
+        long long q = 0;
+        for (int b = tid; b < nblk; b += CROP_T) { s += psum[(size_t)b * C + k]; q += pcnt[(size_t)b * C + k]; }
+        s = crop_wave_sum(s);
+        q = crop_wave_sum(q);
+        if (lane == 0) { s_sum[wave] = s; s_cnt[wave] = q; }
+        __syncthreads();
+        if (tid == 0) {
+            const double t = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+            const long long n = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+            mean[k] = n > 0 ? t / (double)n : __longlong_as_double(0x7ff8000000000000LL);
+            count[k] = n;
+        }
+        __syncthreads();
+    }
+}
+}  // namespace
+
+extern "C" size_t sn2_mosaic_crop_ws_words(int C, int H, int W) {
+    if (C < 1 || H < 1 || W < 1) return 0;
+    return SN2_MOSAIC_CROP_WS_WORDS(C, H, W);
+}
+
+extern "C" int sn2_mosaic_crop_stats(float* bands, int C, int H, int W, double x_min, double y_max, double pix, const double* edges,
+                                     int E, void* ws, double* mean, long long* count, void* stream) {
+    if (!bands || !ws || !mean || !count || C < 1 || H < 1 || W < 1 || E < 0) return SN2_EINVAL;
+    if ((E == 0) != (edges == nullptr) || (E > 0 && E < 3)) return SN2_EINVAL;        // a ring has three edges or more
+    if (!(pix > 0.0) || !std::isfinite(pix) || !std::isfinite(x_min) || !std::isfinite(y_max)) return SN2_EINVAL;
+    if (((uintptr_t)ws & 7) != 0) return SN2_EINVAL;
+    if (C > SN2_MOSAIC_CROP_MAX_BANDS || (long)H * W >= (1L << 31) || E > SN2_MOSAIC_CROP_MAX_EDGES) return SN2_ELIMIT;
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)SN2_MOSAIC_CROP_BLOCKS(H, W);
+    double* psum = (double*)ws;
+    long long* pcnt = (long long*)(psum + (size_t)nblk * C);
+    if (E > 0)
+        hipLaunchKernelGGL(mosaic_crop_kernel<true>, dim3(nblk), dim3(CROP_T), 0, st, bands, C, H, W, x_min, y_max, pix, edges, E, psum,
+                           pcnt);
+    else
+        hipLaunchKernelGGL(mosaic_crop_kernel<false>, dim3(nblk), dim3(CROP_T), 0, st, bands, C, H, W, x_min, y_max, pix, edges, E, psum,
+                           pcnt);
+    hipLaunchKernelGGL(mosaic_crop_fold_kernel, dim3(1), dim3(CROP_T), 0, st, (const double*)psum, (const long long*)pcnt, C, nblk, mean,
+                       count);
+    SN2_RETURN_LAUNCH();
+}

@@ -1433,18 +1433,59 @@ def mosaic_merge(rasters, weights, offsets, mean, wsum, window=None):
           y0, x0, wh, ww, _stream())
 
 
-def mosaic_finalize(mean: torch.Tensor, wsum: torch.Tensor):
-    """mean (3,H,W), wsum (H,W) -> out (5,H,W) = [Vb, Vm_soft, Vh, Vm_hard, weights], thr (2,) = threshold, its index."""
+def mosaic_finalize(mean: torch.Tensor, wsum: torch.Tensor, thr: Optional[torch.Tensor] = None):
+    """mean (3,H,W), wsum (H,W) -> out (5,H,W) = [Vb, Vm_soft, Vh, Vm_hard, weights], thr (2,) = threshold, its index (written
+    into `thr` when one is given)."""
     _, H, W = mean.shape
     _chk(mean, F32, (3, H, W), "mean")
     _chk(wsum, F32, (H, W), "wsum")
     dev = mean.device
     hist = torch.empty(_lib.SN2_MOSAIC_HIST_WORDS, dtype=I32, device=dev)
     acc = torch.empty(1, dtype=F64, device=dev)
-    thr = torch.empty(2, dtype=F32, device=dev)
+    thr = torch.empty(2, dtype=F32, device=dev) if thr is None else _chk(thr, F32, (2,), "thr")
     out = torch.empty(5, H, W, dtype=F32, device=dev)
     _call("sn2_mosaic_finalize", _ptr(mean), _ptr(wsum), H, W, _ptr(hist), _ptr(acc), _ptr(thr), _ptr(out), _stream())
     return out, thr
+
+
+MOSAIC_CROP_MAX_BANDS, MOSAIC_CROP_MAX_EDGES = _lib.SN2_MOSAIC_CROP_MAX_BANDS, _lib.SN2_MOSAIC_CROP_MAX_EDGES
+
+
+def mosaic_crop_ws_words(C: int, H: int, W: int) -> int:
+    """SN2_MOSAIC_CROP_WS_WORDS of include/strata_hip.h (32-bit words)."""
+    return _host("sn2_mosaic_crop_ws_words", int(C), int(H), int(W))
+
+
+def mosaic_crop_stats(bands: torch.Tensor, x_min: float, y_max: float, pix: float, edges=None, out=None):
+    """include/strata_hip.h: sn2_mosaic_crop_stats.  bands (C,H,W) fp32 on the device, CHANGED IN PLACE: every pixel whose centre
+    (x_min + pix (c + 0.5), y_max - pix (r + 0.5)) is not inside the polygon of `edges` ((E,4) fp64 = ax, ay, bx, by: numpy or a
+    device tensor, `parcel.polygon_edges`) becomes NaN in every band -> (mean (C) fp64, count (C) int64) on the device: the
+    band-wise mean and number of the pixels that are not NaN after the crop.  edges=None: no crop, `bands` is not written, the
+    statistics alone.  out: a (mean, count) pair of device tensors to write into.  Two launches on the current stream and no
+    read-back; the same input gives the same bytes.  The limits (C <= MOSAIC_CROP_MAX_BANDS, H W < 2^31, 3 <= E <=
+    MOSAIC_CROP_MAX_EDGES, pix > 0, finite geometry) are the library's: SN2_EINVAL / SN2_ELIMIT."""
+    _chk(bands, F32, None, "bands")
+    if bands.dim() != 3:
+        raise ValueError(f"bands: expected (C,H,W), got {tuple(bands.shape)}")
+    C, H, W = bands.shape
+    dev = bands.device
+    E = 0
+    if edges is not None:
+        if not isinstance(edges, torch.Tensor):
+            edges = torch.from_numpy(np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1, 4)))
+        edges = edges.to(dev)
+        E = edges.shape[0]
+        _chk(edges, F64, (E, 4), "edges")
+        if E == 0:
+            raise ValueError("edges: no edge (edges=None asks for the statistics alone)")
+    ws = torch.empty(max(mosaic_crop_ws_words(C, H, W), 2) // 2, dtype=F64, device=dev)
+    if out is None:
+        mean, count = torch.empty(C, dtype=F64, device=dev), torch.empty(C, dtype=I64, device=dev)
+    else:
+        mean, count = _chk(out[0], F64, (C,), "out[0]"), _chk(out[1], I64, (C,), "out[1]")
+    _call("sn2_mosaic_crop_stats", _ptr(bands), C, H, W, float(x_min), float(y_max), float(pix), _ptr(edges) if E else None, E,
+          _ptr(ws), _ptr(mean), _ptr(count), _stream())
+    return mean, count
 
 
 LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS

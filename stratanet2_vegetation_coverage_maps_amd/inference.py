@@ -10,6 +10,8 @@
 Pixel placement follows `get_geotransform` (geotiff_raster.py:46-61): a plot's top-left corner is
 (center_x - diam_meters//2, center_y + diam_meters//2) and a pixel is diam_meters/diam_pix metres wide.
 """
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 
@@ -73,6 +75,53 @@ class ParcelMosaic:
         threshold that `insert_hard_med_veg_raster_band` (:119-144) searches for."""
         out, thr = ops.mosaic_finalize(self.mean.contiguous(), self.wsum[0].contiguous())
         return out, thr
+
+    def report(self, rings=None) -> "ParcelReport":
+        """`finalize()`, then the crop of `crop_merged_raster` (geotiff_raster.py:238-253) on its (5,H,W) output in place --
+        every pixel whose centre is not inside the parcel polygon becomes NaN --, then the band-wise means of the cropped
+        mosaic that `get_parcel_predicted_values` (predict_utils.py:124-146) writes into the shapefile.  rings: every ring of
+        the polygon, each a (V,2) array, closed or not -- exterior, holes, all parts of a multi-part polygon
+        (`parcel.polygon_edges`; the inside test is `parcel.polygon_keep`'s even-odd rule, include/strata_hip.h:
+        sn2_mosaic_crop_stats); None: no crop, the means of the whole mosaic.  Everything stays on the device but ONE
+        device-to-host read of the threshold, the means and the counts together.
+
+        There is no PRED_ADM: the admissibility band (`insert_admissibility_raster`) is rasterio's `sieve` / `shapes`, a
+        shapely negative buffer and `geometry_mask`, whose rule turns on ties that cannot be pinned without those libraries.
+        Where it differs from the reference: the reference sends the fp32-cast coordinates of the outside pixels back through
+        `rowcol` (geotiff_raster.py:244-251), which at Lambert-93 magnitudes (an fp32 step of 0.5 m) masks a neighbouring
+        pixel now and then -- here the pixel that was tested is masked; and the means are fp64 sums, not numpy's fp32
+        pairwise `nanmean`."""
+        C = 5
+        pack = torch.empty(1 + 2 * C, dtype=torch.int64, device=self.mean.device)     # threshold + index | means | counts
+        thr, means, counts = pack[:1].view(torch.float32), pack[1:1 + C].view(torch.float64), pack[1 + C:]
+        bands, _ = ops.mosaic_finalize(self.mean.contiguous(), self.wsum[0].contiguous(), thr=thr)
+        edges = None
+        if rings is not None:
+            from .parcel import polygon_edges
+            edges = polygon_edges(rings)
+        ops.mosaic_crop_stats(bands, self.x_min, self.y_max, self.pix, edges, out=(means, counts))
+        host = pack.cpu().numpy()                                                      # the one read
+        m, n = host[1:1 + C].view(np.float64).copy(), host[1 + C:].copy()
+        return ParcelReport(bands, float(host[:1].view(np.float32)[0]),
+                            {k: float(m[i]) for i, k in enumerate(REPORT_BANDS)}, {k: int(n[i]) for i, k in enumerate(REPORT_BANDS)},
+                            m, n)
+
+
+REPORT_BANDS = ("PRED_BASSE", "PRED_INTER", "PRED_HAUTE", "hard_med")          # bands 0..3 of `finalize()`; band 4 = weights
+
+
+@dataclass
+class ParcelReport:
+    """`ParcelMosaic.report`: bands (5,H,W) on the device = [Vb, Vm_soft, Vh, Vm_hard, weights], NaN outside the parcel polygon
+    (and wherever no plot has data); threshold of the hard medium-vegetation band; means / counts: per name of REPORT_BANDS the
+    mean over, and the number of, the band's pixels that are not NaN; band_means (5) fp64 / band_counts (5) int64: the same for
+    all five bands in order."""
+    bands: torch.Tensor
+    threshold: float
+    means: dict
+    counts: dict
+    band_means: np.ndarray
+    band_counts: np.ndarray
 
 
 @torch.no_grad()

@@ -4,7 +4,8 @@ by `predict.py`, without the GIS file I/O.
 
     plots = prepare_parcel(cloud, args, keep=polygon_keep([exterior, *holes], shape_buffer(args)))
     for batch in plots.batches(args, 20): ...           # the dicts `inference.predict_parcel` takes
-    mosaic, plots = predict_parcel_cloud(model, cloud, args)
+    mosaic, plots = predict_parcel_cloud(model, cloud, args, shape=[exterior, *holes])
+    report = mosaic.report([exterior, *holes])          # bands cropped to the polygon, PRED_BASSE / PRED_INTER / PRED_HAUTE
 
 Rules kept from the reference (the centres in `parcel_plot_centers`, the discs and the z-normalisation in
 csrc/parcel.hip):
@@ -73,13 +74,10 @@ def parcel_plot_centers(x_min, x_max, y_min, y_max, args, keep=None) -> np.ndarr
     return lattice.astype(np.float32)
 
 
-def polygon_keep(rings, buffer_m: float):
-    """Host restatement of `shape.buffer(buffer_m).contains(Point(x, y))` for a polygon: rings = [exterior, *holes], each
-    a (V,2) array (closed or not).  A point is kept iff it is inside by the even-odd rule or its distance to the boundary
-    is < buffer_m (`contains` excludes the buffer's own boundary).
-
-    Deviation: shapely draws the round joins of a buffer with 16 segments per quarter circle, inside the true circle, so a
-    point within about 4 cm of the offset curve near a convex vertex (at a 30 m buffer) may be classed differently here."""
+def polygon_edges(rings) -> np.ndarray:
+    """The rings of a polygon -- [exterior, *holes], and those of every further part of a multi-part polygon --, each a (V,2)
+    array, closed (last vertex = first) or not -> (E,4) float64 = (ax, ay, bx, by): every ring edge, the closing one included, in
+    ring order.  What `polygon_keep` tests and `hip_ops.mosaic_crop_stats` takes."""
     segs = []
     for r in rings:
         r = np.asarray(r, dtype=np.float64).reshape(-1, 2)
@@ -88,7 +86,17 @@ def polygon_keep(rings, buffer_m: float):
         if len(r) < 2:
             raise ValueError("a ring needs at least two vertices")
         segs.append(np.concatenate([r, np.roll(r, -1, axis=0)], 1))
-    seg = np.concatenate(segs, 0)
+    return np.ascontiguousarray(np.concatenate(segs, 0))
+
+
+def polygon_keep(rings, buffer_m: float):
+    """Host restatement of `shape.buffer(buffer_m).contains(Point(x, y))` for a polygon: rings = [exterior, *holes], each
+    a (V,2) array (closed or not).  A point is kept iff it is inside by the even-odd rule or its distance to the boundary
+    is < buffer_m (`contains` excludes the buffer's own boundary).
+
+    Deviation: shapely draws the round joins of a buffer with 16 segments per quarter circle, inside the true circle, so a
+    point within about 4 cm of the offset curve near a convex vertex (at a 30 m buffer) may be classed differently here."""
+    seg = polygon_edges(rings)
     ax, ay, bx, by = (seg[:, k][None, :] for k in range(4))
     dx, dy = bx - ax, by - ay
     l2 = dx * dx + dy * dy
@@ -275,11 +283,16 @@ def parcel_mosaic(centers_host: np.ndarray, args, device) -> ParcelMosaic:
 
 
 def predict_parcel_cloud(model, parcel_cloud, args, batch_size: int = 20, rs=np.random, keep=None, prefetch: int = 3,
-                         centers=None, fps_start: Optional[int] = None, sampler="numpy", seed=None, n_live: bool = True):
+                         centers=None, fps_start: Optional[int] = None, sampler="numpy", seed=None, n_live: bool = True,
+                         shape=None):
     """prepare_parcel + a mosaic sized to the plots + `inference.predict_parcel` -> (ParcelMosaic, ParcelPlots).  The mosaic
     is None when the parcel has no kept plot.  `mosaic.finalize()` gives the coverage bands.  sampler, seed, n_live: as
-    `ParcelPlots.batches`."""
+    `ParcelPlots.batches`.  shape: the rings of the parcel polygon (`polygon_edges`); with keep=None the lattice is then
+    filtered by `polygon_keep(shape, shape_buffer(args))` as the reference filters it, and `mosaic.report(shape)` gives the
+    bands cropped to the polygon and the parcel's band means."""
     check_sampler(sampler)
+    if shape is not None and keep is None:
+        keep = polygon_keep(shape, shape_buffer(args))
     plots = prepare_parcel(parcel_cloud, args, centers=centers, keep=keep)
     if len(plots) == 0:
         return None, plots
