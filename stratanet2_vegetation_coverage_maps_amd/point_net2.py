@@ -11,7 +11,7 @@ Underneath, `forward` is ONE autograd node whose forward and backward are sequen
 gather+MLP+BN+max (SA1, SA2) -> global SA -> 3-NN interpolation + MLP (FP3..FP1) -> head.  No torch_cluster /
 torch_scatter / torch_geometric, no per-edge tensors, no host synchronisation anywhere in a step.
 
-Additive extensions: `cloud_data["fps_start"]` -- int tensor (2,B) of LOCAL start indices for the two FPS calls
+Additive extensions: `cloud_data["fps_start"]` -- int tensor (2,B) of LOCAL start indices for the two FPS calls ((L,B) for L levels)
 (the reference's `fps` starts at a C `rand()` point and is unseeded).  Absent: random starts
 drawn with torch's generator in training mode... the reference draws them in eval mode too, so does this class.
 `cloud_data["n_live"]` -- int tensor (B): plot b's points [n_live[b], N) are bit-identical copies of earlier ones, which is how
@@ -69,6 +69,19 @@ class FPModule(nn.Module):
         super().__init__()
         self.k = k
         self.nn = nn_
+
+
+def _at(o, stem, l, tail=""):
+    """The level-numbered attribute `<stem><l><tail>` of a geometry handle or a saved set: idx1, pos2_soa, knn3, ..."""
+    return getattr(o, f"{stem}{l}{tail}")
+
+
+def _put(o, stem, l, value, tail=""):
+    setattr(o, f"{stem}{l}{tail}", value)
+
+
+def _pad4(c):
+    return (c + 3) // 4 * 4
 
 
 class _Saved:
@@ -140,21 +153,7 @@ class _PointNet2Fn(torch.autograd.Function):
 class PointNet2(nn.Module):
     def __init__(self, args):
         super().__init__()
-        self.cuda_device = args.cuda
-        self.subsample_size = args.subsample_size
-        self.n_class = args.n_class
-        self.drop = args.drop
-        self.n_input_feats = args.n_input_feats - 2  # x and y are not fed to the network (point_net2.py:77)
-        self.set_patience_attributes(args)
-        self.log_embeddings = args.log_embeddings
-        self.last_G_tensor = None
-        self._last_flat_grad = None
-        self._last_cloud_dev = None
-        # additive extension (not a reference flag): "bf16" = bfloat16 operands on the matrix cores (BASELINE.json
-        # configs[4]); default "fp32" = the reference's precision
-        self.set_mma_dtype(getattr(args, "mma_dtype", "fp32"))
-        if self.n_class != 4 or self.n_input_feats != 8:
-            raise ValueError("the HIP kernels cover the reference architecture: n_class=4, 10 input features")
+        self._init_fields(args)
         ndim = 3
         mlp1 = [self.n_input_feats + ndim, 16, 16]
         mlp2 = [mlp1[-1] + ndim, 32]
@@ -176,6 +175,25 @@ class PointNet2(nn.Module):
         self.sigmoid = nn.Sigmoid()
         if self.cuda_device is not None:
             self.cuda(self.cuda_device)
+
+    def _init_fields(self, args):
+        """Everything of the constructor that is not the architecture (shared with point_net2_3sa.PointNet2ThreeSA); draws nothing
+        from the RNG."""
+        self.cuda_device = args.cuda
+        self.subsample_size = args.subsample_size
+        self.n_class = args.n_class
+        self.drop = args.drop
+        self.n_input_feats = args.n_input_feats - 2  # x and y are not fed to the network (point_net2.py:77)
+        self.set_patience_attributes(args)
+        self.log_embeddings = args.log_embeddings
+        self.last_G_tensor = None
+        self._last_flat_grad = None
+        self._last_cloud_dev = None
+        # additive extension (not a reference flag): "bf16" = bfloat16 operands on the matrix cores (BASELINE.json
+        # configs[4]); default "fp32" = the reference's precision
+        self.set_mma_dtype(getattr(args, "mma_dtype", "fp32"))
+        if self.n_class != 4 or self.n_input_feats != 8:
+            raise ValueError("the HIP kernels cover the reference architecture: n_class=4, 10 input features")
 
     # the blocks `mma_dtype = "bf16"` applies to: everything that runs on the matrix cores -- the set-abstraction levels and
     # the dense layers over centroids (SA3, FP3, FP2).  The two per-point layers (FP1 in its source-side form, the head)
@@ -378,10 +396,53 @@ class PointNet2(nn.Module):
         (`_fp1_source_side`), else fp32.  These 75 MB buffers are what the per-point kernels stream."""
         return torch.bfloat16 if (self.mma_dtype == "bf16" and self._fp1_source_side(rows)) else F32
 
+    # ------------------------------------------------------------------------------------------ the architecture as data
+    # The per-call path below is written ONCE over these, for L = len(sa_levels) ball-query levels (2 in the reference
+    # architecture, 3 in point_net2_3sa.PointNet2ThreeSA).  They read the registered submodules in construction order -- the SA
+    # levels bottom up, the FP levels top down, as the reference constructs them -- and register nothing.  Handles and saved sets
+    # number their attributes by level: idx/pos/ws/nbr/cnt/tot/ord/ext/arg/x/M 1..L, knn/inv/h 1..L+1; the global level is L+1.
+    @property
+    def sa_levels(self):
+        """The ball-query set-abstraction modules in order: (sa1_module, sa2_module, ...)."""
+        return tuple(m for m in self._modules.values() if isinstance(m, SAModule))
+
+    @property
+    def global_sa(self):
+        """The global set-abstraction module: level L+1 (`sa3_module` of the reference architecture)."""
+        return next(m for m in self._modules.values() if isinstance(m, GlobalSAModule))
+
+    @property
+    def fp_levels(self):
+        """The feature-propagation modules from the top (k = 1, out of the global feature) down to `fp1_module`."""
+        return tuple(m for m in self._modules.values() if isinstance(m, FPModule))
+
+    def _fp_by_level(self):
+        """{j: the FP module that writes level j-1's rows}: j = L+1 (top) .. 1."""
+        fps = self.fp_levels
+        return dict(zip(range(len(fps), 0, -1), fps))
+
+    def _block_seqs(self):
+        """(state-dict prefix, Sequential of blocks) in the order of the BatchNorm side-buffer arena: the SA levels, the global
+        level, FP top down to FP1."""
+        sa = [(f"sa{l}_module.conv.local_nn", m.conv.local_nn) for l, m in enumerate(self.sa_levels, 1)]
+        fp = self._fp_by_level()
+        return sa + [(f"sa{len(sa) + 1}_module.nn", self.global_sa.nn)] + [(f"fp{j}_module.nn", m.nn) for j, m in fp.items()]
+
     def _sizes(self, N):
-        M1 = ops.fps_num_samples(N, self.sa1_module.ratio)
-        M2 = ops.fps_num_samples(M1, self.sa2_module.ratio)
-        return M1, M2
+        """(M1, ..., ML): the sample count of every ball-query level for plots of N points."""
+        out = []
+        for m in self.sa_levels:
+            N = ops.fps_num_samples(N, m.ratio)
+            out.append(N)
+        return tuple(out)
+
+    def _level_sizes(self, N):
+        """[N, M1, ..., ML]: points per plot at level 0 (the input) .. L."""
+        return [N, *self._sizes(N)]
+
+    @staticmethod
+    def _dims(g, L):
+        return (g.B, g.N) + tuple(_at(g, "M", l) for l in range(1, L + 1))
 
     # ------------------------------------------------------------------------------------------ geometry
     def alloc_geometry(self, B, N, device=None):
@@ -391,30 +452,36 @@ class PointNet2(nn.Module):
         if self._use_executor():
             with torch.cuda.device(dev):
                 return X.ArenaGeometry(self._net_model().plan(self, B, N), dev, self)      # one allocation, views on demand
-        M1, M2 = self._sizes(N)
+        Ms = self._level_sizes(N)
+        L = len(Ms) - 1
         e = lambda *shape, dt=F32: torch.empty(*shape, dtype=dt, device=dev)          # noqa: E731
         g = _Saved()
-        g.B, g.N, g.M1, g.M2 = B, N, M1, M2
-        g.idx1, g.pos1_soa, g.pos1_aos = e(B, M1, dt=I32), e(B, 3, M1), e(B * M1, 4)
-        g.fps_live1 = e(B, dt=I32)              # level 1's count of live samples = level 2's n_live (hip_ops.fps), when a batch has one
-        g.ws1 = e(ops.fps_ws_words(B, N), dt=I32) if ops.fps_fills_ws(B, N, M1) else None
+        g.B, g.N = B, N
+        g.totals = torch.zeros(L, dtype=I64, device=dev)
+        for l in range(1, L + 1):
+            S, M = Ms[l - 1], Ms[l]
+            _put(g, "M", l, M)
+            _put(g, "idx", l, e(B, M, dt=I32))
+            _put(g, "pos", l, e(B, 3, M), "_soa")
+            _put(g, "pos", l, e(B * M, 4), "_aos")
+            _put(g, "ws", l, e(ops.fps_ws_words(B, S), dt=I32) if ops.fps_fills_ws(B, S, M) else None)
+            _put(g, "nbr", l, e(B * M, min(MAX_NEIGHBORS, S), dt=I32))
+            _put(g, "cnt", l, e(B * M, dt=I32))
+            _put(g, "tot", l, g.totals[l - 1:l])
+            _put(g, "ord", l, e(ops.sa_order_len(B, M), dt=I32))
+            if l < L:       # level l's count of live samples = level l+1's n_live (hip_ops.fps), when a batch has one
+                _put(g, "fps_live", l, e(B, dt=I32))
         # every point's position along the plot's Morton curve (the level-1 FPS leaves it in its workspace): the order FP1's
         # backward keeps its d pre-activation rows in (hip_ops.fp_desc: row_perm)
         g.rank1 = ops.fps_ws_rank(g.ws1, B, N) if (self.fp1_morton_rows and g.ws1 is not None and self._fp1_source_side(B * N)) else None
-        g.nbr1, g.cnt1 = e(B * M1, min(MAX_NEIGHBORS, N), dt=I32), e(B * M1, dt=I32)
-        g.idx2, g.pos2_soa, g.pos2_aos = e(B, M2, dt=I32), e(B, 3, M2), e(B * M2, 4)
-        g.ws2 = e(ops.fps_ws_words(B, M1), dt=I32) if ops.fps_fills_ws(B, M1, M2) else None
-        g.nbr2, g.cnt2 = e(B * M2, min(MAX_NEIGHBORS, M1), dt=I32), e(B * M2, dt=I32)
-        g.totals = torch.zeros(2, dtype=I64, device=dev)
-        g.pos3 = torch.zeros(B, 3, 1, dtype=F32, device=dev)
-        g.knn3 = (e(B * M2, 3, dt=I32), e(B * M2, 3))
-        g.knn2 = (e(B * M1, 3, dt=I32), e(B * M1, 3))
-        g.knn1 = (e(B * N, 3, dt=I32), e(B * N, 3))
-        g.tot1, g.tot2 = g.totals[0:1], g.totals[1:2]
-        g.ord1, g.ord2 = e(ops.sa_order_len(B, M1), dt=I32), e(ops.sa_order_len(B, M2), dt=I32)
-        g.inv3, g.inv2, g.inv1 = (e(ops.interp_ws_words(B, R, S)) for R, S in ((M2, 1), (M1, M2), (N, M1)))
-        g.nn_ws = tuple(e(ops.three_nn_ws_words(B, S, T), dt=I32) if ops.three_nn_uses_grid(S, T) else None
-                        for S, T in ((M2, M1), (M1, N)))
+        _put(g, "pos", L + 1, torch.zeros(B, 3, 1, dtype=F32, device=dev))        # the plots' global feature sits at the origin
+        for j in range(L + 1, 0, -1):
+            R = B * Ms[j - 1]
+            _put(g, "knn", j, (e(R, 3, dt=I32), e(R, 3)))
+            _put(g, "inv", j, e(ops.interp_ws_words(B, Ms[j - 1], Ms[j] if j <= L else 1)))
+        # nn_ws[k]: the grid workspace of knn{L-k}
+        g.nn_ws = tuple(e(ops.three_nn_ws_words(B, Ms[j], Ms[j - 1]), dt=I32) if ops.three_nn_uses_grid(Ms[j], Ms[j - 1]) else None
+                        for j in range(L, 0, -1))
         self._alloc_input_only(g, B, N, dev)
         g.ready = None
         return g
@@ -438,70 +505,104 @@ class PointNet2(nn.Module):
 
     geometry_takes_n_live = True          # `_geometry(n_live=)` / `_geometry_pair(n_live2=)`: what TrainPipeline asks before passing it
 
+    # ---- the position-only launches of one level / one 3-NN table, as `_geometry`, `_geometry_pair` and `_forward_impl` issue them
+    @staticmethod
+    def _positions(g, xyz, L):
+        """[xyz, pos1_soa, ..., posL_soa, pos{L+1}]: the positions of level 0 .. L+1 (the last: the origin, one per plot)."""
+        return [xyz] + [_at(g, "pos", l, "_soa") for l in range(1, L + 1)] + [_at(g, "pos", L + 1)]
+
+    @staticmethod
+    def _fps_level(g, pos, l, m, start, n_live=None, waves=0):
+        """Level l's m samples of level l-1's points.  -> the live count of its samples (the next level's n_live), or None."""
+        live_out = getattr(g, f"fps_live{l}", None) if n_live is not None else None
+        ops.fps(pos[l - 1], m, start, out=(_at(g, "idx", l), pos[l], _at(g, "pos", l, "_aos"), _at(g, "ws", l)), waves=waves,
+                n_live=n_live, n_live_out=live_out)
+        return live_out
+
+    @staticmethod
+    def _ball_level(g, pos, l, r, total):
+        ops.ball_query(pos[l - 1], pos[l], r, MAX_NEIGHBORS, total, fps_ws=_at(g, "ws", l), out=(_at(g, "nbr", l), _at(g, "cnt", l)))
+
+    @staticmethod
+    def _nn_table(g, pos, j, k):
+        """knn{j}: for every point of level j-1 its k nearest of level j (FP module j's k: 1 from the plot's global feature)."""
+        L = len(pos) - 2
+        ops.three_nn(pos[j], pos[j - 1], k, out=_at(g, "knn", j), **({"ws": g.nn_ws[L - j]} if j <= L else {}))
+
+    @staticmethod
+    def _inverted_table(g, Ms, j):
+        """inv{j}: the inverted index of knn{j} that the backward pass gathers through."""
+        B, L = g.B, len(Ms) - 1
+        kw = {"src_pos": g.pos1_aos, "row_perm": getattr(g, "rank1", None)} if j == 1 else {}
+        ops.interp_index(_at(g, "knn", j), B, Ms[j - 1], Ms[j] if j <= L else 1, out=_at(g, "inv", j), **kw)
+
     def _geometry(self, xyz, fps_start, out=None, fork=None, shared=False, defer_join=False, inverted=True, cloud=None, n_live=None):
-        """Everything that depends on the point POSITIONS only (no weights, no features): both FPS levels, both ball
-        queries, the three 3-NN tables.  In the reference these are the torch_cluster calls inside SAModule / FPModule
+        """Everything that depends on the point POSITIONS only (no weights, no features): the FPS levels, their ball
+        queries, the 3-NN tables.  In the reference these are the torch_cluster calls inside SAModule / FPModule
         (point_net2.py:22-25, 63).  Because they need no parameters they can run ahead of the feature kernels: see
         `prefetch_geometry`.  `out`: buffers from `alloc_geometry` to write into (no allocation, same addresses every
         time: what a hipGraph-replayed feature pass needs).
         `fork` (default `self.geometry_fork`): after the level-1 FPS the three independent chains -- (a) ball query 1 +
-        its work items, (b) level-2 FPS, ball query 2, the two small 3-NN tables, (c) the per-point 3-NN table + its
-        inverted index -- run on three streams and join before returning (captured into a hipGraph they become parallel
-        branches): the level-2 FPS is 16 workgroups for 0.15 ms, chains (a) and (c) fill the chip beside it.
+        its work items, (b) the levels above (FPS, ball query, work items), every 3-NN table but the per-point one and their
+        inverted indices, (c) the per-point 3-NN table + its inverted index -- run on three streams and join before returning
+        (captured into a hipGraph they become parallel branches): the level-2 FPS is 16 workgroups for 0.15 ms, chains (a) and
+        (c) fill the chip beside it.
         `defer_join` (with `fork`): return without joining; `g._join = (stream of chain b, stream of chain c)` for the caller
         to wait on where it first needs them (`_forward_impl`: the first set-abstraction level starts beside chain b).
-        `inverted=False`: skip the inverted 3-NN tables (only the backward pass gathers through them: an eval-mode forward
-        does not need them -- a tenth of the geometry pass of the parcel loop); `g.has_inverted` records it.
+        `inverted=False`: skip the inverted 3-NN tables and the message totals (only the backward pass reads them: an eval-mode
+        forward does not need them -- a tenth of the geometry pass of the parcel loop); `g.has_inverted` records it.
         `shared`: the pass runs beside other batches' feature kernels (a pipelined loop, `prefetch_geometry`): the level-1
         FPS takes `fps_waves_shared` waves per plot (include/strata_hip.h: sn2_fps_waves).
         `cloud` (B,10,N) on the device: also run the input-only pieces of the feature pass here (`_input_only`).
         `n_live` (B) int32 on the device or None: the plots' live prefixes (`cloud_data["n_live"]`; include/strata_hip.h:
-        sn2_fps_live) -- level 1 samples over them and counts its samples up to a maximum of 0, level 2 takes that count.  Same
-        tables with or without it."""
+        sn2_fps_live) -- level 1 samples over them and counts its samples up to a maximum of 0, the next level takes that count.
+        Same tables with or without it."""
         if self._use_executor():
             return X.geometry(self, self._net_model(), xyz, fps_start, out=out, fork=fork, shared=shared, defer_join=defer_join,
                               inverted=inverted, cloud=cloud, n_live=n_live)
         dev = xyz.device
         B, _, N = xyz.shape
-        M1, M2 = self._sizes(N)
+        Ms = self._level_sizes(N)
+        L = len(Ms) - 1
         g = out if out is not None else self.alloc_geometry(B, N, dev)
-        if (g.B, g.N, g.M1, g.M2) != (B, N, M1, M2):
+        if self._dims(g, L) != (B, *Ms):
             raise ValueError("geometry buffers do not match this batch")
         g.xyz = xyz
         fork = self.geometry_fork if fork is None else fork
         cur = torch.cuda.current_stream(dev)
-        live1 = None if n_live is None else g.fps_live1
-        ops.fps(xyz, M1, fps_start[0], out=(g.idx1, g.pos1_soa, g.pos1_aos, g.ws1),
-                waves=(self.fps_waves_many if B > 32 else self.fps_waves_shared) if shared else 0, n_live=n_live, n_live_out=live1)
+        pos, sa, fp = self._positions(g, xyz, L), self.sa_levels, self._fp_by_level()
+        # (the message totals: only where a backward may follow -- `inverted`; sn2_net_geometry)
+        total = (lambda l: _at(g, "tot", l)) if inverted else (lambda l: False)
+        live = self._fps_level(g, pos, 1, Ms[1], fps_start[0], n_live,
+                               waves=(self.fps_waves_many if B > 32 else self.fps_waves_shared) if shared else 0)
         if fork:
             sb, sc = ops.shared_stream(dev, "fork_b"), ops.shared_stream(dev, "fork_c")
             sb.wait_stream(cur)
             sc.wait_stream(cur)
         else:
             sb = sc = cur
-        with torch.cuda.stream(sb):                                        # (b) the level-2 chain
-            ops.fps(g.pos1_soa, M2, fps_start[1], out=(g.idx2, g.pos2_soa, g.pos2_aos, g.ws2), n_live=live1)
-            # (the message totals: only where a backward may follow -- `inverted`; sn2_net_geometry)
-            ops.ball_query(g.pos1_soa, g.pos2_soa, self.sa2_module.r, MAX_NEIGHBORS, g.tot2 if inverted else False, fps_ws=g.ws2,
-                           out=(g.nbr2, g.cnt2))
-            ops.sa_order(g.cnt2, B, M2, out=g.ord2)
-            ops.three_nn(g.pos3, g.pos2_soa, 1, out=g.knn3)
-            ops.three_nn(g.pos2_soa, g.pos1_soa, 3, out=g.knn2, ws=g.nn_ws[0])
+        with torch.cuda.stream(sb):                                        # (b) the chain of the levels above
+            for l in range(2, L + 1):
+                live = self._fps_level(g, pos, l, Ms[l], fps_start[l - 1], live)
+                self._ball_level(g, pos, l, sa[l - 1].r, total(l))
+                ops.sa_order(_at(g, "cnt", l), B, Ms[l], out=_at(g, "ord", l))
+            for j in range(L + 1, 1, -1):
+                self._nn_table(g, pos, j, fp[j].k)
             # the inverted 3-NN tables the backward pass gathers through: positions only, so they belong here
             if inverted:
-                ops.interp_index(g.knn3, B, M2, 1, out=g.inv3)
-                ops.interp_index(g.knn2, B, M1, M2, out=g.inv2)
+                for j in range(L + 1, 1, -1):
+                    self._inverted_table(g, Ms, j)
         with torch.cuda.stream(sc):                                        # (c) the per-point table
-            ops.three_nn(g.pos1_soa, xyz, 3, out=g.knn1, ws=g.nn_ws[1])
+            self._nn_table(g, pos, 1, fp[1].k)
             if inverted:
-                ops.interp_index(g.knn1, B, N, M1, out=g.inv1, src_pos=g.pos1_aos, row_perm=g.rank1)
+                self._inverted_table(g, Ms, 1)
         g.has_inverted = bool(inverted)
         g.has_rows0 = False
         if cloud is not None:
             self._input_only(g, cloud, xyz)
         # (a)
-        ops.ball_query(xyz, g.pos1_soa, self.sa1_module.r, MAX_NEIGHBORS, g.tot1 if inverted else False, fps_ws=g.ws1, out=(g.nbr1, g.cnt1))
-        ops.sa_order(g.cnt1, B, M1, out=g.ord1)
+        self._ball_level(g, pos, 1, sa[0].r, total(1))
+        ops.sa_order(g.cnt1, B, Ms[1], out=g.ord1)
         g._join = None
         if fork and defer_join:
             g._join = (sb, sc)
@@ -515,7 +616,8 @@ class PointNet2(nn.Module):
         (FPS is one workgroup per plot and M sequential rounds: several batches take as long as one), plus the per-batch views
         the feature passes read.  -> (combined buffers, (geometry of the first batch, of the second, ...))."""
         dev = torch.device(device if device is not None else self.lin1.weight.device)
-        M1, M2 = self._sizes(N)
+        Ms = self._level_sizes(N)
+        L = len(Ms) - 1
         gp = self.alloc_geometry(group * B, N, dev)
         e = lambda *shape, dt=F32: torch.empty(*shape, dtype=dt, device=dev)          # noqa: E731
         # the per-batch products -- message totals, SA work items, inverted 3-NN indices -- of all `group` batches live in ONE
@@ -523,36 +625,41 @@ class PointNet2(nn.Module):
         # (hip_ops.*_group; round 5: 18 small launches per pass of eight batches instead of 144); a batch's slice is an ordinary
         # per-batch table
         up4 = lambda n: (n + 3) // 4 * 4          # noqa: E731
-        so1, so2 = ops.sa_order_len(B, M1), ops.sa_order_len(B, M2)
-        si = [up4(ops.interp_ws_words(B, R, S)) for R, S in ((M2, 1), (M1, M2), (N, M1))]
+        inv_words = {j: ops.interp_ws_words(B, Ms[j - 1], Ms[j] if j <= L else 1) for j in range(L + 1, 0, -1)}
         grp = _Saved()
-        grp.G, grp.so1, grp.so2, grp.si = group, so1, so2, si
-        grp.ord1, grp.ord2 = e(group * so1, dt=I32), e(group * so2, dt=I32)
-        grp.inv = [e(group * w) for w in si]
-        grp.totals = torch.zeros(group, 2, dtype=I64, device=dev)
+        grp.G = group
+        grp.so = {l: ops.sa_order_len(B, Ms[l]) for l in range(1, L + 1)}          # strides of the batches' tables in ord / inv
+        grp.si = {j: up4(w) for j, w in inv_words.items()}
+        grp.ord = {l: e(group * n, dt=I32) for l, n in grp.so.items()}
+        grp.inv = {j: e(group * n) for j, n in grp.si.items()}
+        grp.totals = torch.zeros(group, L, dtype=I64, device=dev)
         gp._grp = grp
         halves = []
         for h in range(group):
             g = _Saved()
-            g.B, g.N, g.M1, g.M2 = B, N, M1, M2
-            pl, r1, r2, rn = slice(h * B, (h + 1) * B), slice(h * B * M1, (h + 1) * B * M1), \
-                slice(h * B * M2, (h + 1) * B * M2), slice(h * B * N, (h + 1) * B * N)
-            g.idx1, g.pos1_soa, g.pos1_aos, g.nbr1, g.cnt1 = gp.idx1[pl], gp.pos1_soa[pl], gp.pos1_aos[r1], gp.nbr1[r1], gp.cnt1[r1]
-            g.idx2, g.pos2_soa, g.pos2_aos, g.nbr2, g.cnt2 = gp.idx2[pl], gp.pos2_soa[pl], gp.pos2_aos[r2], gp.nbr2[r2], gp.cnt2[r2]
-            g.knn3 = (gp.knn3[0][r2], gp.knn3[1][r2])
-            g.knn2 = (gp.knn2[0][r1], gp.knn2[1][r1])
-            g.knn1 = (gp.knn1[0][rn], gp.knn1[1][rn])
+            g.B, g.N = B, N
+            pl = slice(h * B, (h + 1) * B)
+            rows = [slice(h * B * M, (h + 1) * B * M) for M in Ms]          # batch h's rows at level 0 .. L
             g.totals = grp.totals[h]
-            g.tot1, g.tot2 = grp.totals[h, 0:1], grp.totals[h, 1:2]
-            g.ord1, g.ord2 = grp.ord1[h * so1:(h + 1) * so1], grp.ord2[h * so2:(h + 1) * so2]
-            g.inv3, g.inv2, g.inv1 = (grp.inv[k][h * si[k]:h * si[k] + ops.interp_ws_words(B, R, S)]
-                                      for k, (R, S) in enumerate(((M2, 1), (M1, M2), (N, M1))))
-            g.ws1 = g.ws2 = g.nn_ws = None
-            g.rank1 = gp.rank1[rn] if (gp.rank1 is not None and self._fp1_source_side(B * N)) else None
+            for l in range(1, L + 1):
+                _put(g, "M", l, Ms[l])
+                _put(g, "idx", l, _at(gp, "idx", l)[pl])
+                _put(g, "pos", l, _at(gp, "pos", l, "_soa")[pl], "_soa")
+                for stem, tail in (("pos", "_aos"), ("nbr", ""), ("cnt", "")):
+                    _put(g, stem, l, _at(gp, stem, l, tail)[rows[l]], tail)
+                _put(g, "tot", l, grp.totals[h, l - 1:l])
+                _put(g, "ord", l, grp.ord[l][h * grp.so[l]:(h + 1) * grp.so[l]])
+                _put(g, "ws", l, None)
+            for j in range(L + 1, 0, -1):
+                idx, w = _at(gp, "knn", j)
+                _put(g, "knn", j, (idx[rows[j - 1]], w[rows[j - 1]]))
+                _put(g, "inv", j, grp.inv[j][h * grp.si[j]:h * grp.si[j] + inv_words[j]])
+            g.nn_ws = None
+            g.rank1 = gp.rank1[rows[0]] if (gp.rank1 is not None and self._fp1_source_side(B * N)) else None
             # the input-only pieces of the feature pass: the batch's slices of the GROUP's buffers (one launch each for the whole
             # group when the pass is handed the group's clouds in one tensor: `_geometry_pair(..., cloud2=)`)
-            g.rows0, g.has_rows0 = gp.rows0[rn], False
-            g.p2_pix = gp.p2_pix[rn] if gp.p2_pix is not None else None
+            g.rows0, g.has_rows0 = gp.rows0[rows[0]], False
+            g.p2_pix = gp.p2_pix[rows[0]] if gp.p2_pix is not None else None
             g.p2_mm = gp.p2_mm[pl] if gp.p2_mm is not None else None
             g.p2_diam_pix = None
             g.ready = None
@@ -560,41 +667,40 @@ class PointNet2(nn.Module):
         return gp, tuple(halves)
 
     def _geometry_pair(self, xyz2, fps_start2, gp, halves, clouds=None, cloud2=None, n_live2=None):
-        """`_geometry` for len(halves) batches at once: xyz2 (G B,3,N), fps_start2 (2,G B); FPS, ball queries and 3-NN tables
+        """`_geometry` for len(halves) batches at once: xyz2 (G B,3,N), fps_start2 (L,G B); FPS, ball queries and 3-NN tables
         run on all plots in one launch each (into `gp`), the per-batch products (message totals, SA work items, inverted 3-NN
         indices) per batch.  Same tables as G `_geometry` calls.  clouds: the G batches' (B,10,N) device tensors -> also the
         input-only pieces of their feature passes (`_input_only`), batch by batch; cloud2 (G B,10,N): the same for the whole group
         in one launch each (the batches' clouds live in one tensor: what TrainPipeline arranges).  n_live2 (G B) int32 or None:
         the plots' live prefixes, as `_geometry`'s n_live."""
         B2, _, N = xyz2.shape
-        B = B2 // len(halves)
-        M1, M2 = self._sizes(N)
+        G = len(halves)
+        B = B2 // G
+        Ms = self._level_sizes(N)
+        L = len(Ms) - 1
         if (gp.B, gp.N) != (B2, N):
             raise ValueError("geometry buffers do not match this batch pair")
-        # 8 waves per plot: this pass runs beside other batches' feature kernels (sn2_fps_waves)
-        live1 = None if n_live2 is None else gp.fps_live1
-        ops.fps(xyz2, M1, fps_start2[0], out=(gp.idx1, gp.pos1_soa, gp.pos1_aos, gp.ws1), waves=self.fps_waves_shared,
-                n_live=n_live2, n_live_out=live1)
-        # (no message total of the GROUP: the batches' totals come from count_sum_group below)
-        ops.ball_query(xyz2, gp.pos1_soa, self.sa1_module.r, MAX_NEIGHBORS, False, fps_ws=gp.ws1, out=(gp.nbr1, gp.cnt1))
-        ops.fps(gp.pos1_soa, M2, fps_start2[1], out=(gp.idx2, gp.pos2_soa, gp.pos2_aos, gp.ws2), n_live=live1)
-        ops.ball_query(gp.pos1_soa, gp.pos2_soa, self.sa2_module.r, MAX_NEIGHBORS, False, fps_ws=gp.ws2,
-                       out=(gp.nbr2, gp.cnt2))
-        ops.three_nn(gp.pos3, gp.pos2_soa, 1, out=gp.knn3)
-        ops.three_nn(gp.pos2_soa, gp.pos1_soa, 3, out=gp.knn2, ws=gp.nn_ws[0])
-        # (the targets in the FPS pass's existing Morton order -- `dst_fps_ws=gp.ws1`, no target sort -- made the pipelined step
-        # SLOWER, 0.739 against 0.718 ms: the search's query boxes grow more than the sort costs; round 5)
-        ops.three_nn(gp.pos1_soa, xyz2, 3, out=gp.knn1, ws=gp.nn_ws[1])
-        grp, G = gp._grp, len(halves)
-        tot_flat = grp.totals.view(-1)                       # (G,2): [h][0] = level-1 messages of batch h, [h][1] = level-2
-        ops.count_sum_group(gp.cnt1, G, B * M1, tot_flat, 2)
-        ops.count_sum_group(gp.cnt2, G, B * M2, tot_flat[1:], 2)
-        ops.sa_order_group(gp.cnt1, G, B, M1, grp.ord1, grp.so1)
-        ops.sa_order_group(gp.cnt2, G, B, M2, grp.ord2, grp.so2)
-        ops.interp_index_group(gp.knn3, G, B, M2, 1, grp.inv[0], grp.si[0])
-        ops.interp_index_group(gp.knn2, G, B, M1, M2, grp.inv[1], grp.si[1])
+        pos, sa, fp = self._positions(gp, xyz2, L), self.sa_levels, self._fp_by_level()
+        live = n_live2
+        for l in range(1, L + 1):
+            # 8 waves per plot at level 1: this pass runs beside other batches' feature kernels (sn2_fps_waves)
+            live = self._fps_level(gp, pos, l, Ms[l], fps_start2[l - 1], live, waves=self.fps_waves_shared if l == 1 else 0)
+            # (no message total of the GROUP: the batches' totals come from count_sum_group below)
+            self._ball_level(gp, pos, l, sa[l - 1].r, False)
+        # (the per-point table's targets in the FPS pass's existing Morton order -- `dst_fps_ws=gp.ws1`, no target sort -- made the
+        # pipelined step SLOWER, 0.739 against 0.718 ms: the search's query boxes grow more than the sort costs; round 5)
+        for j in range(L + 1, 0, -1):
+            self._nn_table(gp, pos, j, fp[j].k)
+        grp = gp._grp
+        tot_flat = grp.totals.view(-1)                       # (G,L): [h][l-1] = level-l messages of batch h
+        for l in range(1, L + 1):
+            ops.count_sum_group(_at(gp, "cnt", l), G, B * Ms[l], tot_flat[l - 1:], L)
+        for l in range(1, L + 1):
+            ops.sa_order_group(_at(gp, "cnt", l), G, B, Ms[l], grp.ord[l], grp.so[l])
         rank = gp.rank1 if halves[0].rank1 is not None else None
-        ops.interp_index_group(gp.knn1, G, B, N, M1, grp.inv[2], grp.si[2], src_pos=gp.pos1_aos, row_perm=rank)
+        for j in range(L + 1, 0, -1):
+            kw = {"src_pos": gp.pos1_aos, "row_perm": rank} if j == 1 else {}
+            ops.interp_index_group(_at(gp, "knn", j), G, B, Ms[j - 1], Ms[j] if j <= L else 1, grp.inv[j], grp.si[j], **kw)
         if cloud2 is not None:
             self._input_only(gp, cloud2, xyz2)                    # one launch each over the whole group
         for h, g in enumerate(halves):
@@ -645,14 +751,15 @@ class PointNet2(nn.Module):
         else:
             xyz_d = xyz.to(device=dev, dtype=F32, non_blocking=True).contiguous()
         B, _, N = xyz_d.shape
+        Ms = self._level_sizes(N)
+        L = len(Ms) - 1
         fs = cloud_data.get("fps_start", None) if isinstance(cloud_data, dict) else None
         if fs is None:
             # reference behaviour: an independent random start per plot and per FPS call
-            m1 = ops.fps_num_samples(N, self.sa1_module.ratio)
-            fs = torch.stack([torch.randint(0, N, (B,)), torch.randint(0, m1, (B,))])
+            fs = torch.stack([torch.randint(0, S, (B,)) for S in Ms[:L]])
         fs = torch.as_tensor(fs).to(device=dev, dtype=I32, non_blocking=True).contiguous()
-        if fs.shape != (2, B):
-            raise ValueError(f"fps_start must have shape (2,{B})")
+        if fs.shape != (L, B):
+            raise ValueError(f"fps_start must have shape ({L},{B})")
         return xyz_d, fs
 
     def _stage_live(self, cloud_data, dev, B):
@@ -679,7 +786,9 @@ class PointNet2(nn.Module):
             return cov, proba, s
         dev = xyz.device
         B, _, N = xyz.shape
-        M1, M2 = self._sizes(N)
+        Ms = self._level_sizes(N)
+        L = len(Ms) - 1
+        G = L + 1                                # the global level
         cur_stream = torch.cuda.current_stream(dev)
         # eval mode with gradients wanted: everything a training forward keeps, on the running statistics (SN2_BN_FROZEN_KEEP)
         frozen = (not training) and bool(need_grad)
@@ -699,7 +808,7 @@ class PointNet2(nn.Module):
                     packed = torch.cuda.Event()
                     packed.record(pack_stream)
             geo = self._geometry(xyz, fps_start, defer_join=True, inverted=keep, n_live=n_live)
-        elif (geo.B, geo.N, geo.M1, geo.M2) != (B, N, M1, M2):
+        elif self._dims(geo, L) != (B, *Ms):
             raise ValueError("prefetched geometry does not match this batch")
         join = getattr(geo, "_join", None)
         geo._join = None
@@ -713,32 +822,33 @@ class PointNet2(nn.Module):
                 cur_stream.wait_stream(join[0])
                 cur_stream.wait_stream(join[1])
                 join = None
-            ops.count_sum(geo.cnt1, geo.tot1)          # (the message totals an eval-mode geometry pass did not make)
-            ops.count_sum(geo.cnt2, geo.tot2)
-            ops.interp_index(geo.knn3, B, M2, 1, out=geo.inv3)
-            ops.interp_index(geo.knn2, B, M1, M2, out=geo.inv2)
-            ops.interp_index(geo.knn1, B, N, M1, out=geo.inv1, src_pos=geo.pos1_aos, row_perm=getattr(geo, "rank1", None))
+            for l in range(1, L + 1):          # (the message totals an eval-mode geometry pass did not make)
+                ops.count_sum(_at(geo, "cnt", l), _at(geo, "tot", l))
+            for j in range(G, 0, -1):
+                self._inverted_table(geo, Ms, j)
             geo.has_inverted = True
         s = _Saved()
         s.__dict__.update({k: v for k, v in geo.__dict__.items()
-                           if k not in ("ready", "stream", "ws1", "ws2", "totals", "nn_ws", "fps_start", "_join", "has_rows0", "fps_live1")})
+                           if k not in ("ready", "stream", "totals", "nn_ws", "fps_start", "_join", "has_rows0")
+                           and not k.startswith(("ws", "fps_live"))})
         s.xyz = xyz
-        # per-forward arenas for the BN side buffers of the 7 blocks: a,c,mean,invstd and the per-workgroup statistics
+        # per-forward arenas for the BN side buffers of all blocks: a,c,mean,invstd and the per-workgroup statistics
         # slots (written before they are read: no zero fill)
-        widths = [16, 16, 32, 64, 64, 34, 34]
-        aux = torch.empty(4 * sum(widths), dtype=F32, device=dev)
-        stats = torch.empty(STAT_SLOTS * 2 * sum(widths), dtype=F32, device=dev)
+        seqs = self._block_seqs()
+        width = sum(blk[0].out_features for _, seq in seqs for blk in seq)
+        aux = torch.empty(4 * width, dtype=F32, device=dev)
+        stats = torch.empty(STAT_SLOTS * 2 * width, dtype=F32, device=dev)
         cur = [0, 0]
-        bf = lambda prefix: self.mma_dtype == "bf16" and prefix in self.BF16_BLOCKS      # noqa: E731
-        s.b_sa1 = _blocks_of(self.sa1_module.conv.local_nn, aux, stats, cur, bf("sa1_module.conv.local_nn"))
-        s.b_sa2 = _blocks_of(self.sa2_module.conv.local_nn, aux, stats, cur, bf("sa2_module.conv.local_nn"))
-        s.b_sa3 = _blocks_of(self.sa3_module.nn, aux, stats, cur, bf("sa3_module.nn"))[0]
-        s.b_fp3 = _blocks_of(self.fp3_module.nn, aux, stats, cur, bf("fp3_module.nn"))[0]
-        s.b_fp2 = _blocks_of(self.fp2_module.nn, aux, stats, cur, bf("fp2_module.nn"))[0]
-        s.b_fp1 = _blocks_of(self.fp1_module.nn, aux, stats, cur)[0]
+        blocks = [_blocks_of(seq, aux, stats, cur, self.mma_dtype == "bf16" and prefix in self.BF16_BLOCKS) for prefix, seq in seqs]
+        # b_sa[l]: the blocks of ball-query level l; b_glob: the global level's block; b_fp[j]: FP level j's, j = L+1 .. 1
+        s.b_sa = dict(enumerate(blocks[:L], 1))
+        s.b_glob = blocks[L][0]
+        s.b_fp = dict(zip(range(G, 0, -1), (b[0] for b in blocks[G:])))
+        s.blocks = [bb for b in blocks for bb in b]
         s.aux, s.stats = aux, stats
-        for bb in s.b_sa1 + s.b_sa2 + [s.b_sa3, s.b_fp3, s.b_fp2, s.b_fp1]:
+        for bb in s.blocks:
             bb.frozen = frozen
+        e = lambda *shape, dt=F32: torch.empty(*shape, dtype=dt, device=dev)          # noqa: E731
 
         # ---- level 0 rows: [8 features | x y z 0]
         if packed is not None:
@@ -748,77 +858,88 @@ class PointNet2(nn.Module):
             s.rows0 = rows0
         else:
             s.rows0 = ops.pack_rows(cloud, xyz)
-        # ---- SA1: gather + MLP[11,16,16] + BN + max over the ball-query lists     (point_net2.py:131, 21-29)
-        s.ext1 = torch.empty(B * M1, 16, dtype=F32, device=dev)
-        s.arg1 = torch.empty(B * M1, 16, dtype=I32, device=dev)
-        s.x1 = torch.empty(B * M1, 16, dtype=F32, device=dev)
-        ops.sa_forward(self._sa1_desc(s), mode)
-        if join is not None:
-            cur_stream.wait_stream(join[0])      # chain b of the forked geometry pass: level-2 tables, small 3-NN tables
-        # ---- SA2: MLP[19,32]                                                     (:132)
-        s.ext2 = torch.empty(B * M2, 32, dtype=F32, device=dev)
-        s.arg2 = torch.empty(B * M2, 32, dtype=I32, device=dev)
-        s.x2 = torch.empty(B * M2, 32, dtype=F32, device=dev)
-        ops.sa_forward(self._sa2_desc(s), mode)
-        # ---- SA3: MLP[35,64] on cat[x2, pos2] -> per-plot max                    (:133, 37-42)
-        s.h_sa3 = torch.empty(B * M2, 64, dtype=F32, device=dev)
-        s.h3 = torch.empty(B * M2, 64, dtype=F32, device=dev)
-        if training and self.fuse_global_level and ops.global_level_forward_fused(B, s.b_sa3, s.b_fp3):
-            # ... and its max, FP3 (k=1 from the plot's global feature) and both BatchNorms: one launch  (:133-137)
-            s.x3 = torch.empty(B, 64, dtype=F32, device=dev)
-            s.arg3 = torch.empty(B, 64, dtype=I32, device=dev)
-            ops.global_level_forward(self._sa3_desc(s), self._fp3_desc(s), s.x3, s.arg3, owner=self)
+        # ---- SA1 .. SAL: gather + MLP + BN + max over the ball-query lists        (point_net2.py:131-132, 21-29)
+        for l in range(1, L + 1):
+            R, C = B * Ms[l], s.b_sa[l][-1].cout
+            _put(s, "ext", l, e(R, C))
+            _put(s, "arg", l, e(R, C, dt=I32))
+            _put(s, "x", l, e(R, C))
+            ops.sa_forward(self._sa_desc(s, l), mode)
+            if l == 1 and join is not None:
+                cur_stream.wait_stream(join[0])      # chain b of the forked geometry pass: the tables of the levels above, small 3-NN tables
+        # ---- the global level: MLP on cat[x_L, pos_L] -> per-plot max             (:133, 37-42)
+        R, C = B * Ms[L], s.b_glob.cout
+        _put(s, "h_sa", G, e(R, _pad4(C)))
+        _put(s, "h", G, e(R, _pad4(s.b_fp[G].cout)))
+        if training and self.fuse_global_level and ops.global_level_forward_fused(B, s.b_glob, s.b_fp[G]):
+            # ... and its max, the top FP level (k=1 from the plot's global feature) and both BatchNorms: one launch  (:133-137)
+            _put(s, "x", G, e(B, C))
+            _put(s, "arg", G, e(B, C, dt=I32))
+            ops.global_level_forward(self._global_sa_desc(s), self._fp_desc(s, G), _at(s, "x", G), _at(s, "arg", G), owner=self)
         else:
-            ops.fp_forward(self._sa3_desc(s), mode)
-            s.x3, s.arg3 = ops.plot_max_forward(s.h_sa3, s.b_sa3.a, s.b_sa3.c, B, M2, 64)
-            # ---- FP3 (k=1 from the plot's global feature at the origin), FP2, FP1 (k=3)   (:137-139, 62-67)
-            ops.fp_forward(self._fp3_desc(s), mode)
+            ops.fp_forward(self._global_sa_desc(s), mode)
+            x, arg = ops.plot_max_forward(_at(s, "h_sa", G), s.b_glob.a, s.b_glob.c, B, Ms[L], C)
+            _put(s, "x", G, x)
+            _put(s, "arg", G, arg)
+            # ---- FP from the top (k=1 from the plot's global feature at the origin) down (k=3)   (:137-139, 62-67)
+            ops.fp_forward(self._fp_desc(s, G), mode)
         if self.log_embeddings:
-            self.last_G_tensor = s.x3
-        s.h2 = torch.empty(B * M1, 36, dtype=F32, device=dev)
-        ops.fp_forward(self._fp2_desc(s), mode)
+            self.last_G_tensor = _at(s, "x", G)
+        for j in range(L, 1, -1):
+            _put(s, "h", j, e(B * Ms[j - 1], _pad4(s.b_fp[j].cout)))
+            ops.fp_forward(self._fp_desc(s, j), mode)
         if join is not None:
             cur_stream.wait_stream(join[1])      # chain c: the per-point 3-NN table and its inverted index
-        cov = torch.empty(B * N, 4, dtype=F32, device=dev)
-        proba = torch.empty(B * N, 4, dtype=F32, device=dev)
+        cov, proba = e(B * N, 4), e(B * N, 4)
         s.drop_keep = drop_keep
+        b1 = s.b_fp[1]
         if not keep and self.fuse_eval_head and self._act_dtype(B * N) == F32 and ops.SOURCE_SIDE:
             # EVAL: FP1 and the head (:139-151) in one pass, the (B*N,36) rows of h1 never reach memory (nothing is kept for a backward)
             s.h1 = None
-            d1 = ops.fp_desc(s.b_fp1, B, N, M1, 34, 8, s.h2, None, src_affine=(s.b_fp2.a, s.b_fp2.c), knn=s.knn1,
-                             skip=s.rows0[:, 0:8], force_src_ws=True)
-            ops.fp_head_eval(d1, ops.head_desc(None, s.b_fp1.a, s.b_fp1.c, self.lin1, self.lin2, cov, proba, rows=B * N))
+            ops.fp_head_eval(self._fp_desc(s, 1, force_src_ws=True),
+                             ops.head_desc(None, b1.a, b1.c, self.lin1, self.lin2, cov, proba, rows=B * N))
             return cov, proba, s
-        s.h1 = torch.empty(B * N, 36, dtype=self._act_dtype(B * N), device=dev)
-        ops.fp_forward(self._fp1_desc(s), mode)
+        s.h1 = torch.empty(B * N, _pad4(b1.cout), dtype=self._act_dtype(B * N), device=dev)
+        ops.fp_forward(self._fp_desc(s, 1), mode)
         # ---- head                                                                  (:141-151)
-        ops.head_forward(ops.head_desc(s.h1, s.b_fp1.a, s.b_fp1.c, self.lin1, self.lin2, cov, proba, drop_mask=drop_keep,
-                                       drop_p=self.drop))
+        ops.head_forward(ops.head_desc(s.h1, b1.a, b1.c, self.lin1, self.lin2, cov, proba, drop_mask=drop_keep, drop_p=self.drop))
         return cov, proba, s
 
-    # ---- descriptors (shared by forward and backward; gradient views are attached for the backward call)
-    def _sa1_desc(self, s, dout=None, g=False, bwd_ws=None):
-        return ops.sa_desc(s.b_sa1, s.rows0[:, 0:8], 8, s.rows0[:, 8:12], s.pos1_aos, s.nbr1, s.cnt1, s.tot1, s.B, s.N,
-                           s.M1, s.ext1, s.arg1, s.x1, dout=dout, dfeat=None, with_grads=g, order=getattr(s, "ord1", None),
-                           bwd_ws=bwd_ws)
+    # ---- descriptors (shared by forward and backward; gradient views are attached for the backward call); channel widths are the
+    # blocks' own (Linear.in_features / out_features)
+    def _sa_desc(self, s, l, dout=None, dfeat=None, g=False, bwd_ws=None):
+        """Ball-query level l (1..L): its sources are the level-0 rows (l = 1) or level l-1's features and positions."""
+        blocks = s.b_sa[l]
+        cf = blocks[0].cin - 3
+        if l == 1:
+            feat, spos, S = s.rows0[:, 0:cf], s.rows0[:, cf:cf + 4], s.N
+        else:
+            feat, spos, S = _at(s, "x", l - 1), _at(s, "pos", l - 1, "_aos"), _at(s, "M", l - 1)
+        return ops.sa_desc(blocks, feat, cf, spos, _at(s, "pos", l, "_aos"), _at(s, "nbr", l), _at(s, "cnt", l), _at(s, "tot", l), s.B, S,
+                           _at(s, "M", l), _at(s, "ext", l), _at(s, "arg", l), _at(s, "x", l), dout=dout, dfeat=dfeat, with_grads=g,
+                           order=getattr(s, f"ord{l}", None), bwd_ws=bwd_ws)
 
-    def _sa2_desc(self, s, dout=None, dfeat=None, g=False):
-        return ops.sa_desc(s.b_sa2, s.x1, 16, s.pos1_aos, s.pos2_aos, s.nbr2, s.cnt2, s.tot2, s.B, s.M1, s.M2, s.ext2,
-                           s.arg2, s.x2, dout=dout, dfeat=dfeat, with_grads=g, order=getattr(s, "ord2", None))
+    def _global_sa_desc(self, s, **kw):
+        """The global level (L+1): a dense block over cat[x_L, pos_L]; its per-plot max is a launch of its own."""
+        L = len(s.b_sa)
+        M = _at(s, "M", L)
+        return ops.fp_desc(s.b_glob, s.B, M, M, s.b_glob.cin - 3, 3, _at(s, "x", L), _at(s, "h_sa", L + 1), skip=_at(s, "pos", L, "_aos"), **kw)
 
-    def _sa3_desc(self, s, **kw):
-        return ops.fp_desc(s.b_sa3, s.B, s.M2, s.M2, 32, 3, s.x2, s.h_sa3, skip=s.pos2_aos, **kw)
-
-    def _fp3_desc(self, s, **kw):
-        return ops.fp_desc(s.b_fp3, s.B, s.M2, 1, 64, 32, s.x3, s.h3, knn=s.knn3, skip=s.x2, **kw)
-
-    def _fp2_desc(self, s, **kw):
-        return ops.fp_desc(s.b_fp2, s.B, s.M1, s.M2, 64, 16, s.h3, s.h2, src_affine=(s.b_fp3.a, s.b_fp3.c), knn=s.knn2,
-                           skip=s.x1, **kw)
-
-    def _fp1_desc(self, s, **kw):
-        return ops.fp_desc(s.b_fp1, s.B, s.N, s.M1, 34, 8, s.h2, s.h1, src_affine=(s.b_fp2.a, s.b_fp2.c), knn=s.knn1,
-                           skip=s.rows0[:, 0:8], row_perm=getattr(s, "rank1", None), **kw)
+    def _fp_desc(self, s, j, **kw):
+        """FP level j (L+1 = the top .. 1): level j's features (the plot's global feature at the top, else FP level j+1's output
+        behind its BatchNorm affine) interpolated through knn{j} onto level j-1's rows, beside that level's own features."""
+        L, blk = len(s.b_sa), s.b_fp[j]
+        if j == L + 1:
+            src, S, ca, affine = _at(s, "x", j), 1, s.b_glob.cout, None
+        else:
+            up = s.b_fp[j + 1]
+            src, S, ca, affine = _at(s, "h", j + 1), _at(s, "M", j), up.cout, (up.a, up.c)
+        if j == 1:
+            R, skip = s.N, s.rows0[:, 0:blk.cin - ca]
+            kw["row_perm"] = getattr(s, "rank1", None)
+        else:
+            R, skip = _at(s, "M", j - 1), _at(s, "x", j - 1)
+        return ops.fp_desc(blk, s.B, R, S, ca, blk.cin - ca, src, _at(s, "h", j), src_affine=affine, knn=_at(s, "knn", j), skip=skip, **kw)
 
     # ------------------------------------------------------------------------------------------ backward
     def _backward_impl(self, s, dcov, dproba, loss=None):
@@ -826,68 +947,75 @@ class PointNet2(nn.Module):
         if isinstance(s, X.NetSaved):
             return X.backward(self, s, dcov, dproba, loss=loss)
         dev = s.xyz.device
-        B, N, M1, M2 = s.B, s.N, s.M1, s.M2
+        B, N, L = s.B, s.N, len(s.b_sa)
+        G = L + 1
+        Ms = [N] + [_at(s, "M", l) for l in range(1, G)]
         params = self._params()
-        # one zero-filled arena: flat parameter gradient + every accumulate-into buffer of the backward chain
-        sizes = OrderedDict(dy2=B * M1 * 36, dy3=B * M2 * 64, dx1=B * M1 * 16, dx2=B * M2 * 32, dx3=B * 64,
-                            dy_sa3=B * M2 * 64, sa1_ws=ops.SA_BWD_WS_WORDS)
+        # one zero-filled arena: flat parameter gradient + every accumulate-into buffer of the backward chain --
+        # dy{j}: d (FP level j's output), dx{l}: d x{l}, dy_sa{L+1}: d (the global level's rows)
+        shapes = OrderedDict((f"dy{j}", (B * Ms[j - 1], _pad4(s.b_fp[j].cout))) for j in range(2, G + 1))
+        shapes.update((f"dx{l}", (B * Ms[l], s.b_sa[l][-1].cout)) for l in range(1, G))
+        shapes[f"dx{G}"] = (B, s.b_glob.cout)
+        shapes[f"dy_sa{G}"] = (B * Ms[L], _pad4(s.b_glob.cout))
+        sizes = OrderedDict((k, r * c) for k, (r, c) in shapes.items())
+        sizes["sa1_ws"] = ops.SA_BWD_WS_WORDS
         flat, buf, views, images, arena = self._grad_arena(params, sizes, dev)
-
-        def attach(bb):
+        dy = {j: buf[f"dy{j}"].view(shapes[f"dy{j}"]) for j in range(2, G + 1)}
+        dx = {l: buf[f"dx{l}"].view(shapes[f"dx{l}"]) for l in range(1, G + 1)}
+        for bb in s.blocks:
             bb.grads = (views[id(bb.lin.weight)], views[id(bb.lin.bias)], views[id(bb.bn.weight)], views[id(bb.bn.bias)])
             bb.grad_images = images
-
-        for bb in s.b_sa1 + s.b_sa2 + [s.b_sa3, s.b_fp3, s.b_fp2, s.b_fp1]:
-            attach(bb)
         dcov = None if dcov is None else dcov.contiguous()
         dproba = None if dproba is None else dproba.contiguous()
+        e = lambda *shape, dt=F32: torch.empty(*shape, dtype=dt, device=dev)          # noqa: E731
+        bn_ok = e(L + 2, dt=I32)      # per BatchNorm: did the shortcut apply (else the same kernel's row pass)
+
+        def bn_sums(fn, d, blk, k):
+            """The gradients of `blk`'s BatchNorm from the weight gradients of the layer `d` that consumes its output."""
+            fn(d, blk.bn.weight.detach(), blk.bn.bias.detach(), blk.aux[2], blk.aux[3], views[id(blk.bn.weight)], views[id(blk.bn.bias)],
+               bn_ok[k:k + 1])
+
         # head
-        dy1 = torch.empty(B * N, 36, dtype=s.h1.dtype, device=dev)
+        b1 = s.b_fp[1]
+        dy[1] = e(B * N, _pad4(b1.cout), dt=s.h1.dtype)
         hg = (views[id(self.lin1.weight)], views[id(self.lin1.bias)], views[id(self.lin2.weight)], views[id(self.lin2.bias)])
-        hd = ops.head_desc(s.h1, s.b_fp1.a, s.b_fp1.c, self.lin1, self.lin2, dcov=dcov, dproba=dproba, dy=dy1, grads=hg,
+        hd = ops.head_desc(s.h1, b1.a, b1.c, self.lin1, self.lin2, dcov=dcov, dproba=dproba, dy=dy[1], grads=hg,
                            grad_images=images, drop_mask=getattr(s, "drop_keep", None), drop_p=self.drop, loss=loss)
         ops.head_backward(hd)
         # FP1's BatchNorm gradients fall out of lin1's (hip_ops.head_bn_sums): no extra pass over the B*N rows
-        bn1 = self.fp1_module.nn[0][2]
-        bn_ok = torch.empty(4, dtype=I32, device=dev)      # per BatchNorm: did the shortcut apply (else the same kernel's row pass)
-        ops.head_bn_sums(hd, bn1.weight.detach(), bn1.bias.detach(), s.b_fp1.aux[2], s.b_fp1.aux[3], views[id(bn1.weight)],
-                         views[id(bn1.bias)], bn_ok[0:1])
-        # FP1 -> d(fp2 output)
-        dy2 = buf["dy2"].view(B * M1, 36)
-        d1 = self._fp1_desc(s, dy=dy1, dsrc=dy2, du_scratch=torch.empty(B * N, 36, dtype=s.h1.dtype, device=dev), with_grads=True,
-                            interp_index=s.inv1, bn_sums_done=bn_ok[0:1])
-        ops.fp_backward(d1)
-        bn2 = self.fp2_module.nn[0][2]      # FP2's BatchNorm feeds FP1's interpolation: its gradients from FP1's dW, db
-        ops.fp_bn_sums(d1, bn2.weight.detach(), bn2.bias.detach(), s.b_fp2.aux[2], s.b_fp2.aux[3], views[id(bn2.weight)],
-                       views[id(bn2.bias)], bn_ok[1:2])
-        # FP2 -> d(fp3 output), d x1
-        dy3, dx1 = buf["dy3"].view(B * M2, 64), buf["dx1"].view(B * M1, 16)
-        d2 = self._fp2_desc(s, dy=dy2, dsrc=dy3, dskip=dx1, du_scratch=torch.empty(B * M1, 64, dtype=F32, device=dev),
-                            with_grads=True, interp_index=s.inv2, bn_sums_done=bn_ok[1:2])
-        ops.fp_backward(d2)
-        dx3, dx2 = buf["dx3"].view(B, 64), buf["dx2"].view(B * M2, 32)
-        if self.fuse_global_level and ops.global_level_backward_fused(B, M2, getattr(s.b_fp3, "frozen", False), s.b_sa3, s.b_fp3):
-            # FP3's BatchNorm sums, FP3, the pool between FP3 and SA3, SA3's BatchNorm sums and SA3 in one launch
-            ops.global_level_backward(self._sa3_desc(s, dsrc=dx2, with_grads=True),
-                                      self._fp3_desc(s, dy=dy3, dsrc=dx3, dskip=dx2, with_grads=True), s.arg3, owner=self)
+        bn_sums(ops.head_bn_sums, hd, b1, 0)
+        # FP1 .. FPL: FP level j -> d (FP level j+1's output) and d x{j-1}; FP level j+1's BatchNorm feeds level j's
+        # interpolation: its gradients from level j's dW, db
+        for j in range(1, G):
+            blk, ca = s.b_fp[j], s.b_fp[j + 1].cout
+            du = e(B * Ms[j - 1], max(ca, _pad4(blk.cout)), dt=dy[j].dtype)
+            d = self._fp_desc(s, j, dy=dy[j], dsrc=dy[j + 1], du_scratch=du, with_grads=True, interp_index=_at(s, "inv", j),
+                              bn_sums_done=bn_ok[j - 1:j], **({"dskip": dx[j - 1]} if j > 1 else {}))
+            ops.fp_backward(d)
+            if j < L:
+                bn_sums(ops.fp_bn_sums, d, s.b_fp[j + 1], j)
+        top, gb = s.b_fp[G], s.b_glob
+        if self.fuse_global_level and ops.global_level_backward_fused(B, Ms[L], getattr(top, "frozen", False), gb, top):
+            # the top FP level's BatchNorm sums, that level, the pool under it, the global level's BatchNorm sums and the global
+            # level in one launch
+            ops.global_level_backward(self._global_sa_desc(s, dsrc=dx[L], with_grads=True),
+                                      self._fp_desc(s, G, dy=dy[G], dsrc=dx[G], dskip=dx[L], with_grads=True), _at(s, "arg", G), owner=self)
         else:
-            bn3 = self.fp3_module.nn[0][2]      # and FP3's from FP2's
-            ops.fp_bn_sums(d2, bn3.weight.detach(), bn3.bias.detach(), s.b_fp3.aux[2], s.b_fp3.aux[3], views[id(bn3.weight)],
-                           views[id(bn3.bias)], bn_ok[2:3])
-            # FP3 -> d x2 and the per-row gradients of its interpolated part (left in du3: scatter_ready = -1); then the pool
-            # between FP3 and SA3 in one launch (hip_ops.global_pool_backward): d x3, its routing to the SA3 rows that attained
-            # the maximum, and SA3's BatchNorm sums over those B x 64 entries
-            du3 = torch.empty(B * M2, 64, dtype=F32, device=dev)
-            ops.fp_backward(self._fp3_desc(s, dy=dy3, dsrc=dx3, dskip=dx2, du_scratch=du3, with_grads=True,
-                                           interp_index=s.inv3, bn_sums_done=bn_ok[2:3], gather=False))
-            dy_sa3 = buf["dy_sa3"].view(B * M2, 64)
-            bn_sa3 = self.sa3_module.nn[0][2]
-            ops.global_pool_backward(du3, s.arg3, s.h_sa3, s.b_sa3.aux[2], s.b_sa3.aux[3], B, M2, dx3, dy_sa3,
-                                     views[id(bn_sa3.weight)], views[id(bn_sa3.bias)])
-            ops.fp_backward(self._sa3_desc(s, dy=dy_sa3, dsrc=dx2, with_grads=True, bn_sums_done=bn_ok[3:4]))
-        # SA2 -> d x1 ; SA1
-        ops.sa_backward(self._sa2_desc(s, dout=dx2, dfeat=dx1, g=True))
-        ops.sa_backward(self._sa1_desc(s, dout=dx1, g=True, bwd_ws=buf["sa1_ws"]))      # (both blocks in one message pass)
+            bn_sums(ops.fp_bn_sums, d, top, L)
+            # top FP level -> d x_L and the per-row gradients of its interpolated part (left in du: scatter_ready = -1); then the
+            # pool under it in one launch (hip_ops.global_pool_backward): d x{L+1}, its routing to the global level's rows that
+            # attained the maximum, and that level's BatchNorm sums over those B x C entries
+            du = e(B * Ms[L], max(gb.cout, _pad4(top.cout)))
+            ops.fp_backward(self._fp_desc(s, G, dy=dy[G], dsrc=dx[G], dskip=dx[L], du_scratch=du, with_grads=True,
+                                          interp_index=_at(s, "inv", G), bn_sums_done=bn_ok[L:L + 1], gather=False))
+            dy_sa = buf[f"dy_sa{G}"].view(shapes[f"dy_sa{G}"])
+            ops.global_pool_backward(du, _at(s, "arg", G), _at(s, "h_sa", G), gb.aux[2], gb.aux[3], B, Ms[L], dx[G], dy_sa,
+                                     views[id(gb.bn.weight)], views[id(gb.bn.bias)])
+            ops.fp_backward(self._global_sa_desc(s, dy=dy_sa, dsrc=dx[L], with_grads=True, bn_sums_done=bn_ok[L + 1:L + 2]))
+        # SAL -> d x{L-1} ; ... ; SA1
+        for l in range(L, 1, -1):
+            ops.sa_backward(self._sa_desc(s, l, dout=dx[l], dfeat=dx[l - 1], g=True))
+        ops.sa_backward(self._sa_desc(s, 1, dout=dx[1], g=True, bwd_ws=buf["sa1_ws"]))      # (both blocks in one message pass)
         if getattr(self, "defer_grad_reduce", False):
             self._grad_images_pending = (arena,) + tuple(images)       # FlatAdam folds the images inside its own kernel
         else:

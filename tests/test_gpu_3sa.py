@@ -163,3 +163,66 @@ def test_3sa_prefetched_geometry_and_parcel_loop():
     mos0 = inference.ParcelMosaic(0.0, float(H), H, W, args, torch.device("cuda:0"))
     assert inference.predict_parcel(model, batches, mos0, args, prefetch=0) == 3 * B
     assert torch.equal(torch.nan_to_num(mos0.result()), torch.nan_to_num(mos.result()))
+
+
+def test_3sa_grouped_geometry_pass_matches_the_per_batch_passes():
+    """`_geometry_pair` of the variant (the base class's grouped pass: `*_group` launches into strided buffers, the group's cloud
+    in one tensor) against one `_geometry(..., cloud=)` call per batch: the same bits in every table, and a training step through a
+    grouped handle gives the outputs of a step through the per-batch handle.  M = 512 / 128 / 32 on 4096 points: the level-1 FPS
+    fills its workspace and the per-point 3-NN table takes its grid form."""
+    from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
+    B, N, L = 2, 4096, 3
+    dev = torch.device("cuda:0")
+    args = make_args(cuda=0, subsample_size=N, ratio1=0.125, r1=1.0, ratio2=0.25, r2=2.0, ratio3=0.25, r3=4.0)
+    model = PointNet2ThreeSA(args)
+    model.load_state_dict(network.init_state_dict_3sa(2))
+    model.train()
+    model.p2_diam_pix = int(args.diam_pix)
+    Ms = (N,) + tuple(model._sizes(N))
+    assert Ms == (4096, 512, 128, 32)
+    assert ops.fps_fills_ws(B, N, Ms[1]) and ops.three_nn_uses_grid(Ms[1], N)
+
+    def tables(g, with_cloud):
+        t = {}
+        for l in range(1, L + 1):
+            cnt = getattr(g, f"cnt{l}")
+            nbr = getattr(g, f"nbr{l}")
+            live = torch.arange(nbr.shape[1], device=dev)[None, :] < cnt[:, None]         # the first cnt entries of a list are defined
+            t[f"nbr{l}"] = torch.where(live, nbr, -1)
+            for name in (f"idx{l}", f"pos{l}_aos", f"pos{l}_soa", f"cnt{l}", f"tot{l}", f"ord{l}"):
+                t[name] = getattr(g, name)
+        for j in range(1, L + 2):
+            t[f"knn{j}_idx"], t[f"knn{j}_w"] = getattr(g, f"knn{j}")
+        if with_cloud:
+            assert g.has_rows0 and g.p2_diam_pix == int(args.diam_pix)
+            t["rows0"], t["p2_pix"], t["p2_mm"] = g.rows0, g.p2_pix, g.p2_mm
+        return t
+
+    step = None
+    for G, group_cloud in ((2, True), (3, False)):
+        hosts = [make_batch(B, N, first_plot=700 + 10 * G + h * B) for h in range(G)]
+        xyz2 = torch.cat([h["xyz"] for h in hosts]).to(dev, torch.float32).contiguous()
+        cloud2 = torch.cat([h["cloud"] for h in hosts]).to(dev, torch.float32).contiguous()
+        fs2 = (torch.arange(L * G * B, dtype=torch.int32).view(L, G * B) * 3 % 32).to(dev)
+        gp, halves = model.alloc_geometry_pair(B, N, dev, group=G)
+        model._geometry_pair(xyz2, fs2, gp, halves, **({"cloud2": cloud2} if group_cloud else {}))
+        for h, g in enumerate(halves):
+            sl = slice(h * B, (h + 1) * B)
+            ref = model._geometry(xyz2[sl], fs2[:, sl].contiguous(), cloud=cloud2[sl])
+            got, want = tables(g, group_cloud), tables(ref, group_cloud)
+            for name in want:
+                assert torch.equal(got[name], want[name]), f"G={G}, batch {h}: {name}"
+            if step is None and h == 1:
+                step = (hosts[h], fs2[:, sl].contiguous(), g, ref)
+    # a training forward and backward through the grouped handle and through the per-batch handle
+    d, fs, g_grp, g_one = step
+    out = []
+    for geo in (g_grp, g_one):
+        model.zero_grad(set_to_none=True)
+        cov, proba = model({"cloud": d["cloud"], "xyz": d["xyz"], "fps_start": fs, "geometry": geo})
+        (cov.sum() + proba.sum()).backward()
+        out.append((cov, proba, [p.grad.clone() for p in model.parameters()]))
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
+    for a, b in zip(out[0][2], out[1][2]):
+        # the backward adds its weight gradients with float atomics: two runs agree to ~1e-6 of a tensor's magnitude
+        assert float((a - b).abs().max()) <= 1e-5 * float(b.abs().max()) + 1e-12
