@@ -295,6 +295,29 @@ int sn2_train_batch_live(const float *raw, long T, const int *offsets, const flo
                          unsigned long long seed, long long epoch, const double *cos_sin, int train, int noise, int *ws,
                          size_t ws_words, float *cloud, float *xyz, double *gt, int *fps_start, int *n_live, void *stream);
 
+/* ---- growing such a set on the device (csrc/plotset.hip): K plots of a source plot list -- a parcel's prepared plots
+ * (sn2_parcel_fill / sn2_parcel_znorm) with the plot-wise predictions of an eval forward as their coverages, or another set --
+ * appended to a destination set that has spare capacity, in stream order, no host read, one launch.
+ * Source: src_raw (10,src_T) fp32 with row stride src_T, src_offsets (Ps+1) int32, src_centers (Ps,2) fp32, src_cov (Ps,4) fp32 in
+ * the projection's order (low, soil, medium, high).  sel (K) int32 on the device: source plot numbers, any order, need not be
+ * adjacent, a plot may be named twice, plots without points are allowed; EVERY entry must be in [0, Ps): the caller checks that on
+ * the host copy the table was made from (the kernel does not), as for plot_ids under sn2_train_batch.
+ * Destination: dst_raw (10,cap_T) fp32 with row stride cap_T, dst_offsets (cap_P+1) int32, dst_centers (cap_P,2) fp32, dst_cov
+ * (cap_P,4) fp64; P0 plots and T0 points are already there.  dst_start (K+1) int32 on the device: the destination column of each
+ * appended plot's first point, made by the host from the point counts it knows: dst_start[0] = T0, dst_start[k+1] = dst_start[k]
+ * + the points of plot sel[k], dst_start[K] = new_T (the host argument must equal it).
+ * Writes, and nothing else:
+ *   dst_raw[c, dst_start[k] + i] = src_raw[c, src_offsets[sel[k]] + i]      c = 0..9, i = 0 .. points of sel[k] - 1
+ *   dst_offsets[P0 + k] = dst_start[k]                                      k = 0..K   (P0 + K included)
+ *   dst_centers[P0 + k] = src_centers[sel[k]],  dst_cov[P0 + k] = (double) src_cov[sel[k]]   k = 0..K-1   (the widening is exact)
+ * Columns at or beyond new_T, columns below T0 and table rows outside [P0, P0 + K) (offsets: outside [P0, P0 + K]) keep their
+ * bytes.  A plain copy: no atomics, no workspace, every word has one writer -- the bytes do not depend on the order of the waves.
+ * NULL buffers, K <= 0, P0 < 0, T0 < 0, P0 + K > cap_P, new_T > cap_T or new_T < T0: SN2_EINVAL; cap_T >= 2^31 or src_T >= 2^31:
+ * SN2_ELIMIT -- all before any device work. */
+int sn2_plots_append(const float *src_raw, long src_T, const int *src_offsets, const float *src_centers, const float *src_cov,
+                     const int *sel, int K, float *dst_raw, long cap_T, int *dst_offsets, float *dst_centers, double *dst_cov,
+                     int cap_P, int P0, long T0, const int *dst_start, long new_T, void *stream);
+
 /* z-normalisation of a raw plot (offline preparation): z_i - min{ z_j : |xy_i - xy_j| <= radius } --
  * normalize_z_with_minz_in_a_radius, utils/load_data.py:237-249 (sklearn kd-tree radius query in x,y + a python loop).
  * x, y, z (n) fp32; the test is sklearn's: fp64 reduced distance dx*dx + dy*dy <= radius*radius, inclusive.

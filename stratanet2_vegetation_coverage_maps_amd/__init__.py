@@ -12,7 +12,9 @@ from .point_net2 import PointNet2  # noqa: F401
 from .project_to_2d import (project_batch_to_2d_rasters, project_to_2d_rasters,  # noqa: F401
                             project_to_plotwise_coverages)
 from .train_data import EpochFeeder, ResidentPlots  # noqa: F401
+from .pseudo_label import label_plots, pretrain_split, pseudo_label_parcel  # noqa: F401
 
 __all__ = ["PointNet2", "project_to_plotwise_coverages", "project_to_2d_rasters", "project_batch_to_2d_rasters", "ParcelPlots",
            "parcel_plot_centers", "polygon_keep", "prepare_parcel", "predict_parcel_cloud", "subsample", "subsample_form",
-           "evaluate", "plot_losses", "plot_losses_torch", "ResidentPlots", "EpochFeeder"]
+           "evaluate", "plot_losses", "plot_losses_torch", "ResidentPlots", "EpochFeeder", "label_plots",
+           "pseudo_label_parcel", "pretrain_split"]

@@ -166,6 +166,8 @@ SIGNATURES = {
     "sn2_train_batch_live": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                              c_float, ctypes.c_ulonglong, c_longlong, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_plots_append": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_void_p,
+                         c_void_p, c_int, c_int, c_long, c_void_p, c_long, c_void_p],
     "sn2_sa_order": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "sn2_sa_order_group": [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_sa_forward": [POINTER(SA), c_int, c_void_p],

@@ -704,6 +704,36 @@ def train_batch(raw, offsets, centers, coverages, plot_ids, fake_xy, n_max: int,
         _call("sn2_train_batch_live", *args, _ptr(n_live), _stream())
 
 
+def plots_append(src_raw, src_offsets, src_centers, src_cov, sel, dst_raw, dst_offsets, dst_centers, dst_cov, P0: int, T0: int,
+                 dst_start, new_T: int):
+    """include/strata_hip.h: sn2_plots_append.  Source plot list src_raw (10,src_T) f32, src_offsets (Ps+1) i32, src_centers (Ps,2)
+    f32, src_cov (Ps,4) f32; sel (K) i32 ON THE DEVICE -- the caller has checked 0 <= sel < Ps on the host copy it uploaded (no
+    kernel does); the destination arena dst_raw (10,cap_T) f32, dst_offsets (cap_P+1) i32, dst_centers (cap_P,2) f32, dst_cov
+    (cap_P,4) f64 holds P0 plots / T0 points; dst_start (K+1) i32 on the device, dst_start[0] = T0 and dst_start[K] = new_T.
+    Appends in place, on the current stream, without a host read."""
+    _, src_T = src_raw.shape
+    Ps = src_offsets.numel() - 1
+    K = sel.numel()
+    _, cap_T = dst_raw.shape
+    cap_P = dst_offsets.numel() - 1
+    _chk(src_raw, F32, (10, src_T), "src_raw")
+    _chk(src_offsets, I32, (Ps + 1,), "src_offsets")
+    _chk(src_centers, F32, (Ps, 2), "src_centers")
+    _chk(src_cov, F32, (Ps, 4), "src_cov")
+    _chk(sel, I32, (K,), "sel")
+    _chk(dst_raw, F32, (10, cap_T), "dst_raw")
+    _chk(dst_offsets, I32, (cap_P + 1,), "dst_offsets")
+    _chk(dst_centers, F32, (cap_P, 2), "dst_centers")
+    _chk(dst_cov, F64, (cap_P, 4), "dst_cov")
+    _chk(dst_start, I32, (K + 1,), "dst_start")
+    P0, T0, new_T = int(P0), int(T0), int(new_T)
+    if K < 1 or Ps < 1 or P0 < 0 or P0 + K > cap_P or not 0 <= T0 <= new_T <= cap_T:
+        raise ValueError("plots_append: need K, Ps >= 1, 0 <= P0, P0 + K <= the plot capacity and 0 <= T0 <= new_T <= the point "
+                         "capacity")
+    _call("sn2_plots_append", _ptr(src_raw), src_T, _ptr(src_offsets), _ptr(src_centers), _ptr(src_cov), _ptr(sel), K, _ptr(dst_raw),
+          cap_T, _ptr(dst_offsets), _ptr(dst_centers), _ptr(dst_cov), cap_P, P0, T0, _ptr(dst_start), new_T, _stream())
+
+
 def znorm(xyz: torch.Tensor, radius: float):
     """xyz (3,n) fp32 of ONE raw plot on the device -> (zmin (n), z - zmin (n)): the local-minimum z-normalisation of
     `normalize_z_with_minz_in_a_radius` (utils/load_data.py:237-249)."""

@@ -217,11 +217,15 @@ def _empty(dev) -> ParcelPlots:
                        np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), [], np.zeros((0, 2), dtype=np.float32))
 
 
-def prepare_parcel(parcel_cloud, args, centers=None, keep=None, device=None) -> ParcelPlots:
+def prepare_parcel(parcel_cloud, args, centers=None, keep=None, device=None, min_points: int = MIN_POINTS) -> ParcelPlots:
     """parcel_cloud: (10,T) float32, numpy or a device tensor, in the reference's channel order and absolute metres ->
-    the kept plots (>= 51 points) of the parcel, prepared on the device.  centers: None (the reference's lattice over the
-    parcel's bounding box, `parcel_plot_centers` with `keep`) or a (P,2) set of plot centres (any: duplicates and centres
-    without points included)."""
+    the kept plots (>= min_points points: 51) of the parcel, prepared on the device.  centers: None (the reference's lattice over
+    the parcel's bounding box, `parcel_plot_centers` with `keep`) or a (P,2) set of plot centres (any: duplicates and centres
+    without points included).  min_points: a plot is kept iff it has at least that many points (pseudo-labelling keeps the
+    plots above 2000: the others are then never extracted); the kept plots' bytes do not depend on it."""
+    min_points = int(min_points)
+    if min_points < 1:
+        raise ValueError("prepare_parcel: min_points must be at least 1")
     dev = torch.device(device) if device is not None else (
         parcel_cloud.device if isinstance(parcel_cloud, torch.Tensor) and parcel_cloud.is_cuda else torch.device("cuda"))
     cloud = torch.as_tensor(parcel_cloud).to(device=dev, dtype=torch.float32).contiguous()
@@ -251,7 +255,7 @@ def prepare_parcel(parcel_cloud, args, centers=None, keep=None, device=None) -> 
             raise ValueError(f"prepare_parcel: {starts[-1]} plot points in all discs, at most 2^31 - 1")
         starts = starts[:-1]
         counts = np.diff(starts)
-        kept = counts >= MIN_POINTS
+        kept = counts >= min_points
         if not kept.any():
             return _empty(dev)
         n_points = counts[kept]
