@@ -706,6 +706,76 @@ extern size_t sn2_mosaic_crop_ws_words(int C, int H, int W);
 int sn2_mosaic_crop_stats(float *bands, int C, int H, int W, double x_min, double y_max, double pix, const double *edges, int E,
                           void *ws, double *mean, long long *count, void *stream);
 
+/* ---- Mosaic atlas: the mosaics of K parcels in one arena, merged, finalised and cropped K canvases per launch (csrc/atlas.hip).
+ * A shapefile of 1 ha parcels gives canvases of a few thousand pixels; the single-canvas calls above then pay their launches, and
+ * ParcelMosaic.report its device-to-host read, once per parcel.  The atlas kernels execute the per-pixel rules of the single-canvas
+ * kernels (csrc/mosaic_rules.h: the same functions), so every contract below reads "the bytes the single-canvas call gives".
+ *
+ * LAYOUT.  Canvas k has H_k x W_k pixels and the geotransform (x_min_k, y_max_k); base_k = the exclusive prefix of H_k W_k (int64).
+ * It owns a contiguous, canvas-major slice of each arena: mean (3,H_k,W_k) at word 3 base_k, wsum the same, bands (C,H_k,W_k) at
+ * C base_k (C = 5 from sn2_atlas_finalize) -- a zero-copy (C,H,W) view that the single-canvas entry points accept.
+ * CANVAS TABLE.  (K+1) rows of SN2_ATLAS_CANVAS_COLS int64, written by sn2_atlas_canvas_table (host arithmetic, no device):
+ *   [0] base_k  [1] H_k  [2] W_k  [3] exclusive prefix of SN2_ATLAS_FINALIZE_BLOCKS(H,W)  [4] the same of SN2_MOSAIC_CROP_BLOCKS(H,W)
+ *   [5] x_min_k and [6] y_max_k as the bits of an fp64 (0.0 when x_min, y_max are NULL)  [7] 0;  row K: the three totals, 0 elsewhere.
+ * Every entry point takes the table twice: `canvas_host` (checked against the rule above before any launch, it also gives the grid
+ * sizes) and `canvas_dev`, the same bytes on the device (the kernels find their canvas in it by a wave-uniform binary search).
+ * ERRORS, before any launch: SN2_EINVAL on a NULL pointer, K <= 0, a canvas with H or W <= 0, a non-finite geotransform or a table
+ * that is not sn2_atlas_canvas_table's; SN2_ELIMIT on a canvas of H W >= 2^31 pixels or more than 2^31 - 1 workgroups in all.
+ * wave64; vector stores only; no cross-workgroup spin; no floating-point atomics. */
+#define SN2_ATLAS_CANVAS_COLS 8
+#define SN2_ATLAS_SEG_COLS 8
+#define SN2_ATLAS_FINALIZE_MAX_BLOCKS 1024
+#define SN2_ATLAS_FINALIZE_BLOCKS(H, W) \
+    (((size_t)(H) * (size_t)(W) + 255) / 256 < SN2_ATLAS_FINALIZE_MAX_BLOCKS ? ((size_t)(H) * (size_t)(W) + 255) / 256 \
+                                                                            : (size_t)SN2_ATLAS_FINALIZE_MAX_BLOCKS)
+int sn2_atlas_canvas_table(int K, const int *H, const int *W, const double *x_min, const double *y_max, long long *table);
+
+/* Merge of one batch of plots into the atlas: ONE launch.  rasters (B,3,D,D), weights (D,D) as sn2_mosaic_merge takes them;
+ * place (B,3) int32 on the device = each plot's (canvas, row, col), the plots in NON-DECREASING canvas order.  Each run of equal
+ * canvas is one segment; the segment table -- `seg_host`, and `seg_dev` the same bytes on the device -- has (S+1) rows of
+ * SN2_ATLAS_SEG_COLS int32:  [0] canvas (ascending)  [1] first plot  [2] last plot + 1  [3..6] y0, x0, h, w: the run's bounding
+ * window (rows min row .. max row + D, columns alike) clipped to the canvas, h or w = 0 when nothing is left
+ * [7] the exclusive prefix of the runs' workgroups, ceil(w/64) ceil(h/4) each;  row S: [7] = their total, 0 elsewhere.
+ * A workgroup finds its run from [7] by a wave-uniform search and folds that run's plots only, in order, into its 4 x 64 tile:
+ * the work is proportional to the runs' windows, not to the atlas.
+ * CONTRACT: canvas by canvas, the arenas hold exactly the words sn2_mosaic_merge leaves when it is called on that canvas's view
+ * with that run's plots and window; a canvas without a plot in the batch keeps its bytes.  A plot window that sticks out of its
+ * canvas is clipped.  The host table is checked (runs ascending, plots [0,B) cut in order, windows inside their canvases, the
+ * prefix as stated: else SN2_EINVAL), so whatever `place` holds on the device, nothing is written outside a run's canvas. */
+int sn2_atlas_merge(const float *rasters, const float *weights, const int *place, int B, int D, int K, const long long *canvas_host,
+                    const long long *canvas_dev, const int *seg_host, const int *seg_dev, int S, float *mean, float *wsum,
+                    void *stream);
+
+/* Finalisation of all K canvases: sn2_mosaic_finalize's four launches once instead of K times.  mean, wsum: the arenas;
+ * bands: the (5,H_k,W_k) arena; thr (K,2) = threshold, its index per canvas.  ws: 8-byte aligned, SN2_ATLAS_FINALIZE_WS_WORDS(K)
+ * 32-bit words, no initialisation: per canvas the histogram of k(v) over the medium band (int atomics) with the valid count, then
+ * one fp64 partial sum per workgroup of the canvas.  Canvas k is cut into SN2_ATLAS_FINALIZE_BLOCKS(H_k,W_k) workgroups, workgroup
+ * j takes the pixels 256 j + t, + 256 blocks, ...; its sum is a fixed tree, and the ONE threshold workgroup of the canvas (about
+ * 100 KB of LDS) adds the partials in workgroup order: DETERMINISTIC, no floating-point atomics.
+ * CONTRACT: histogram, count and index rule (first minimum, all-NaN -> 0) are sn2_mosaic_finalize's; bands and threshold equal
+ * its bytes whenever both fp64 sums round to the same fp32 target (the single-canvas call adds its partials with an fp64 atomic,
+ * in any order: the last fp64 bit of its sum may differ; sums of multiples of 2^-16 are exact in every order).
+ * (The size helper returns its value through a pointer, as the carve functions do: tests/test_cabi.py and
+ * tests/test_parcel_report_host.py hold the `size_t` and `extern size_t` declarations of this header to closed lists.) */
+#define SN2_ATLAS_FINALIZE_CANVAS_WORDS (SN2_MOSAIC_HIST_WORDS + 2 * SN2_ATLAS_FINALIZE_MAX_BLOCKS)
+#define SN2_ATLAS_FINALIZE_WS_WORDS(K) ((size_t)(K) * SN2_ATLAS_FINALIZE_CANVAS_WORDS)
+int sn2_atlas_finalize_ws_words(int K, size_t *words);
+int sn2_atlas_finalize(const float *mean, const float *wsum, int K, const long long *canvas_host, const long long *canvas_dev,
+                       void *ws, float *thr, float *bands, void *stream);
+
+/* Crop and band statistics of all K canvases: TWO launches.  bands: the (C,H_k,W_k) arena, changed in place; the geotransforms
+ * are the table's; edges (sum E,4) fp64 on the device, ragged: canvas k owns rows edge_start[k] .. edge_start[k+1] (int32, K+1
+ * entries, `edge_start_host` and the same bytes on the device).  E_k = 0: no crop for that canvas, its bands are not written, the
+ * statistics alone (edges == NULL iff every E_k = 0).  mean (K,C) fp64, count (K,C) int64 on the device.
+ * ws: 8-byte aligned, 4 C table[K][4] 32-bit words (= the sum of SN2_MOSAIC_CROP_WS_WORDS over the canvases), no initialisation.
+ * Canvas k is cut into SN2_MOSAIC_CROP_BLOCKS(H_k,W_k) workgroups that take the row segments j, j + blocks, ... as the
+ * single-canvas call's do; the second launch runs one workgroup per canvas.
+ * CONTRACT: bands, means and counts of canvas k are the bytes sn2_mosaic_crop_stats gives on that canvas's view with that
+ * canvas's edges -- the fp64 means too: the partition and the trees are the same.  Limits per canvas as there (C, E_k, pix). */
+int sn2_atlas_crop_stats(float *bands, int C, int K, const long long *canvas_host, const long long *canvas_dev, double pix,
+                         const double *edges, const int *edge_start_host, const int *edge_start_dev, void *ws, double *mean,
+                         long long *count, void *stream);
+
 /* ---- loss block of the timed training step: learning/loss_functions.py:9-57 combined as learning/train.py:58-62,
  *   total = get_absolute_loss(pred, gt) + m * get_NLL_loss(proba, pdf_all) + e * get_entropy_loss(proba)
  * pred (B,4) fp32 plot-wise coverages, gt (B,4) fp64, proba (R,4) fp32 pointwise class probabilities, pdf (R,3) fp64 the

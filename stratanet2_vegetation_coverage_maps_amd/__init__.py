@@ -6,8 +6,9 @@ The HIP library (csrc/libstrata_hip.so) is loaded on first use and is mandatory:
 """
 from .evaluation import evaluate, plot_losses, plot_losses_torch  # noqa: F401
 from .hip_ops import subsample, subsample_form  # noqa: F401
-from .parcel import (ParcelPlots, parcel_plot_centers, polygon_keep, predict_parcel_cloud,  # noqa: F401
-                     prepare_parcel)
+from .inference import AtlasReport, MosaicAtlas  # noqa: F401
+from .parcel import (ParcelPlots, ParcelSet, parcel_plot_centers, polygon_keep, predict_parcel_cloud,  # noqa: F401
+                     predict_parcels, prepare_parcel, prepare_parcels)
 from .point_net2 import PointNet2  # noqa: F401
 from .project_to_2d import (project_batch_to_2d_rasters, project_to_2d_rasters,  # noqa: F401
                             project_to_plotwise_coverages)
@@ -17,4 +18,4 @@ from .pseudo_label import label_plots, pretrain_split, pseudo_label_parcel  # no
 __all__ = ["PointNet2", "project_to_plotwise_coverages", "project_to_2d_rasters", "project_batch_to_2d_rasters", "ParcelPlots",
            "parcel_plot_centers", "polygon_keep", "prepare_parcel", "predict_parcel_cloud", "subsample", "subsample_form",
            "evaluate", "plot_losses", "plot_losses_torch", "ResidentPlots", "EpochFeeder", "label_plots",
-           "pseudo_label_parcel", "pretrain_split"]
+           "pseudo_label_parcel", "pretrain_split", "ParcelSet", "prepare_parcels", "predict_parcels", "MosaicAtlas", "AtlasReport"]

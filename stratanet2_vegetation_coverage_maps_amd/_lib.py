@@ -20,7 +20,8 @@ CONSTANTS = {
     "SN2_GLOBAL_MAX_PLOTS": 28, "SN2_GLOBAL_CTL_WORDS": 8, "SN2_GLOBAL_BWD_MAX_ROWS": 256,
     "SN2_GLOBAL_BWD_XCHG_WORDS": 2 * 28 * 128, "SN2_GLOBAL_BWD_CTL_WORDS": 64,
     "SN2_MOSAIC_HIST_WORDS": 10004, "SN2_MOSAIC_CROP_MAX_BANDS": 8, "SN2_MOSAIC_CROP_MAX_EDGES": 1 << 20,
-    "SN2_MOSAIC_CROP_MAX_BLOCKS": 2048, "SN2_KDE_FIT_MAX_K": 65536, "SN2_LOSS_BLOCKS": 1024, "SN2_PROJECTED_LOSS_WS": 2 * 512 + 2,
+    "SN2_MOSAIC_CROP_MAX_BLOCKS": 2048, "SN2_ATLAS_CANVAS_COLS": 8, "SN2_ATLAS_SEG_COLS": 8, "SN2_ATLAS_FINALIZE_MAX_BLOCKS": 1024,
+    "SN2_ATLAS_FINALIZE_CANVAS_WORDS": 10004 + 2 * 1024, "SN2_KDE_FIT_MAX_K": 65536, "SN2_LOSS_BLOCKS": 1024, "SN2_PROJECTED_LOSS_WS": 2 * 512 + 2,
     "SN2_NET_GRAD_IMAGES": 32, "SN2_METER_TERMS": 4,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
     "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256,
@@ -203,6 +204,14 @@ SIGNATURES = {
     "sn2_mosaic_finalize": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_mosaic_crop_stats": [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_int, c_void_p, c_void_p,
                               c_void_p, c_void_p],
+    # the mosaic atlas (csrc/atlas.hip); canvas_host, seg_host, edge_start_host are host pointers
+    "sn2_atlas_canvas_table": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_atlas_finalize_ws_words": [c_int, POINTER(ctypes.c_size_t)],
+    "sn2_atlas_merge": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                        c_void_p, c_void_p],
+    "sn2_atlas_finalize": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_atlas_crop_stats": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p],
     "sn2_kde_lookup": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "sn2_kde_fit": [c_void_p, c_long, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_loss_forward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,

@@ -7,6 +7,7 @@
 // pixel -- and a tiny per-plot finalisation.  HBM-bound: 8 B (xy) + 16 B (coverages) read per point.
 #include "common.h"
 #include "loss_grad.h"
+#include "mosaic_rules.h"
 
 namespace {
 
@@ -762,38 +763,14 @@ namespace {
 __global__ void mosaic_merge_kernel(const float* __restrict__ rasters, const float* __restrict__ weights,
                                     const int* __restrict__ offsets, int B, int D, int H, int W,
                                     float* __restrict__ mean, float* __restrict__ wsum, int y0, int x0, int wh, int ww) {
-    // each product, sum and quotient rounded to fp32 on its own, as numpy does on the reference's float32 canvas (bit-exact
-    // against tests/golden/f_mosaic.npz): no fused multiply-add
-#pragma clang fp contract(off)
+    // (the fold itself: mosaic_rules.h, shared with the atlas kernels)
     const int wx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int wy = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int band = blockIdx.z;
     if (wx >= ww || wy >= wh) return;
     const int gy = y0 + wy, gx = x0 + wx;
     if (gy < 0 || gy >= H || gx < 0 || gx >= W) return;
-    const size_t o = ((size_t)band * H + gy) * W + gx;
-    float V = mean[o], Wt = wsum[o];
-    const float nan = __int_as_float(0x7fc00000);
-    for (int b = 0; b < B; ++b) {
-        const int y = gy - offsets[2 * b], x = gx - offsets[2 * b + 1];
-        if (y < 0 || y >= D || x < 0 || x >= D) continue;     // pixel outside this plot's raster: the callback is not
-                                                              // called on it
-        const float v = rasters[(((size_t)b * 3 + band) * D + y) * D + x];
-        const float w = weights[y * D + x];
-        const bool on = V != V, nn = v != v, own = Wt != Wt, nwn = w != w;
-        if (on && nn) {
-            V = nan;
-        } else {
-            float a_old = V * Wt, a_new = v * w;               // NaN (no data) contributes nothing: np.nansum
-            a_old = (on || a_old != a_old) ? 0.f : a_old;
-            a_new = (nn || a_new != a_new) ? 0.f : a_new;
-            const float w_old = (on || own) ? 0.f : Wt, w_new = (nn || nwn) ? 0.f : w;
-            V = (a_old + a_new) / (w_old + w_new);
-        }
-        Wt = (own && nwn) ? nan : (own ? 0.f : Wt) + (nwn ? 0.f : w);
-    }
-    mean[o] = V;
-    wsum[o] = Wt;
+    mosaic_fold_pixel(rasters, weights, offsets, 2, 0, B, D, band, H, W, gy, gx, mean, wsum);
 }
 }  // namespace
 
@@ -815,101 +792,23 @@ extern "C" int sn2_mosaic_merge(const float* rasters, const float* weights, cons
 // the comparison v > lin[i] is made in fp64.
 // ------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int HARD_STEPS = 10001;
-
-__device__ __forceinline__ double hard_lin(int i) { return i >= HARD_STEPS - 1 ? 1.0 : (double)i * (1.0 / 10000.0); }
-
+// (HARD_STEPS, hard_lin, the bin rule, the threshold search and the NaN rule: mosaic_rules.h, shared with the atlas kernels)
 // ws: [0..HARD_STEPS] histogram of k, [HARD_STEPS+1] number of valid pixels; sum_ws: fp64 sum of the valid values
 __global__ __launch_bounds__(256) void hard_hist_kernel(const float* __restrict__ med, long P, int* __restrict__ ws,
                                                         double* __restrict__ sum_ws) {
-    __shared__ double s_sum[4];
-    __shared__ int s_cnt[4];
-    double acc = 0.0;
-    int nv = 0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long)gridDim.x * 256) {
-        const float vf = med[i];
-        if (vf != vf) continue;
-        const double v = (double)vf;
-        int k = (int)floor(v * 10000.0);
-        k = k < 0 ? 0 : (k > HARD_STEPS - 1 ? HARD_STEPS - 1 : k);
-        while (k <= HARD_STEPS - 1 && hard_lin(k) < v) ++k;            // k = #{ i : lin[i] < v }
-        while (k > 0 && !(hard_lin(k - 1) < v)) --k;
-        atomicAdd(&ws[k], 1);
-        acc += v;
-        ++nv;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc += __shfl_xor(acc, o);
-        nv += __shfl_xor(nv, o);
-    }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = acc; s_cnt[threadIdx.x >> 6] = nv; }
-    __syncthreads();
+    double sum;
+    int cnt;
+    hard_hist_block(med, P, (long)blockIdx.x * 256, (long)gridDim.x * 256, ws, sum, cnt);
     if (threadIdx.x == 0) {
-        atomicAdd(sum_ws, (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
-        atomicAdd(&ws[HARD_STEPS + 1], (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]));
+        atomicAdd(sum_ws, sum);
+        atomicAdd(&ws[HARD_STEPS + 1], cnt);
     }
 }
 
 // one workgroup: suffix sums, deltas, first minimum -> thr_out[0] = threshold (fp64 value as float), thr_out[1] = index
 __global__ __launch_bounds__(1024) void hard_threshold_kernel(const int* __restrict__ ws, const double* __restrict__ sum_ws,
                                                               float* __restrict__ thr_out) {
-    __shared__ long long s_above[HARD_STEPS + 1];     // s_above[i] = #{pixels with k > i}
-    __shared__ double s_best[1024];
-    __shared__ int s_idx[1024];
-    const int tid = threadIdx.x;
-    // chunked suffix sum over k = HARD_STEPS .. 0: 1024 threads x 10 bins
-    constexpr int PER = (HARD_STEPS + 1 + 1023) / 1024;
-    long long loc = 0;
-    const int hi = HARD_STEPS - tid * PER;            // this thread's bins: hi, hi-1, ... (descending)
-    for (int j = 0; j < PER; ++j) {
-        const int k = hi - j;
-        if (k >= 0) loc += ws[k];
-    }
-    __shared__ long long s_chunk[1024];
-    s_chunk[tid] = loc;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int t = 0; t < 1024; ++t) { const long long c = s_chunk[t]; s_chunk[t] = run; run += c; }
-    }
-    __syncthreads();
-    long long run = s_chunk[tid];                     // pixels with k above this thread's highest bin
-    for (int j = 0; j < PER; ++j) {
-        const int k = hi - j;
-        if (k >= 0) {
-            if (k <= HARD_STEPS) s_above[k] = run;    // #{k' > k}
-            run += ws[k];
-        }
-    }
-    __syncthreads();
-    const int nvalid = ws[HARD_STEPS + 1];
-    // np.nanmean of a float32 image is a float32; the hard images are fp64 (1.0 * bool)
-    const double target = nvalid > 0 ? (double)(float)(sum_ws[0] / (double)nvalid) : __longlong_as_double(0x7ff8000000000000LL);
-    double best = INFINITY;
-    int bidx = 0x7FFFFFFF;
-    for (int i = tid; i < HARD_STEPS; i += 1024) {
-        // pixels with v > lin[i]  <=>  k(v) > i
-        const double hard_mean = nvalid > 0 ? (double)s_above[i] / (double)nvalid : __longlong_as_double(0x7ff8000000000000LL);
-        const double d = fabs(target - hard_mean);
-        if (d < best) { best = d; bidx = i; }         // ascending i per thread: first minimum kept
-    }
-    s_best[tid] = best;
-    s_idx[tid] = bidx;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double ob = s_best[tid + o];
-            const int oi = s_idx[tid + o];
-            if (ob < s_best[tid] || (ob == s_best[tid] && oi < s_idx[tid])) { s_best[tid] = ob; s_idx[tid] = oi; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int i = s_idx[0] == 0x7FFFFFFF ? 0 : s_idx[0];   // all-NaN deltas: np.argmin returns 0
-        thr_out[0] = (float)hard_lin(i);
-        thr_out[1] = (float)i;
-    }
+    hard_threshold_search(ws, ws[HARD_STEPS + 1], sum_ws[0], thr_out);
 }
 
 // out (5,H,W) = [Vb, Vm_soft, Vh, Vm_hard, weights] with the reference's NaN rule: NaN -> 0 wherever at least one of the
@@ -918,17 +817,7 @@ __global__ __launch_bounds__(256) void mosaic_finalize_kernel(const float* __res
                                                               long P, const float* __restrict__ thr, float* __restrict__ out) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
-    const float nanv = __int_as_float(0x7fc00000);
-    const float b0 = mean[i], b1 = mean[P + i], b2 = mean[2 * P + i], w = wsum[i];
-    const bool none = (b0 != b0) && (b1 != b1) && (b2 != b2);
-    const double t = hard_lin((int)thr[1]);
-    float hard = (b1 != b1) ? nanv : (((double)b1 > t) ? 1.f : 0.f);
-    auto fix = [&](float v) { return none ? nanv : (v != v ? 0.f : v); };
-    out[i] = fix(b0);
-    out[P + i] = fix(b1);
-    out[2 * P + i] = fix(b2);
-    out[3 * P + i] = fix(hard);
-    out[4 * P + i] = fix(w);
+    mosaic_finalize_pixel(mean, wsum, P, i, hard_lin((int)thr[1]), out);
 }
 }  // namespace
 
@@ -950,139 +839,25 @@ extern "C" int sn2_mosaic_finalize(const float* mean, const float* wsum, int H, 
 // ------------------------------------------------------------------------------------------------------------
 // Parcel crop and band means of the mosaic: crop_merged_raster (inference/geotiff_raster.py:238-253) + the band-wise nanmean of
 // get_parcel_predicted_values (inference/predict_utils.py:124-146).  The rule is written out in include/strata_hip.h.
-// A workgroup owns a row segment of 256 pixels, one per thread.  py is a function of the row, so the workgroup walks the E
-// edges once, 256 at a time, and collects the xint of those that cross the row in LDS (wave ballot + prefix); a thread then
-// counts the list entries right of its own px.  The list is counted and emptied whenever the next 256 edges might not fit, so
-// any E and any number of crossings go through.  The expressions are those of the per-pixel test, so are the bits.
+// A workgroup owns row segments of 256 pixels, one pixel per thread; the walk over the edges and the summation trees are
+// mosaic_crop_block / mosaic_crop_fold of mosaic_rules.h, which the atlas kernels (atlas.hip) execute as well.
 // ------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int CROP_T = 256;                           // threads = pixels of a row segment = edges of a chunk
-constexpr int CROP_LIST = 1024;                       // crossings held in LDS between two counting passes
-constexpr int CROP_C = SN2_MOSAIC_CROP_MAX_BANDS;
-
-__device__ __forceinline__ double crop_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ long long crop_wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // psum, pcnt: (gridDim.x, C) partial sums and counts, every entry written
 template <bool CROP>
 __global__ __launch_bounds__(CROP_T) void mosaic_crop_kernel(float* __restrict__ bands, int C, int H, int W, double x_min,
                                                              double y_max, double pix, const double* __restrict__ edges, int E,
                                                              double* __restrict__ psum, long long* __restrict__ pcnt) {
-    // every product, difference, quotient and sum below rounded to fp64 on its own, as numpy does: no fused multiply-add
-#pragma clang fp contract(off)
-    __shared__ double s_x[CROP_LIST];
-    __shared__ int s_wn[CROP_T / 64];
-    __shared__ double s_sum[CROP_T / 64][CROP_C];
-    __shared__ long long s_cnt[CROP_T / 64][CROP_C];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int segs = (W + CROP_T - 1) / CROP_T;
-    const long nrs = (long)H * segs;
-    const size_t P = (size_t)H * W;
-    const float nanv = __int_as_float(0x7fc00000);
-    double acc[CROP_C];
-    long long cnt[CROP_C];
-#pragma unroll
-    for (int k = 0; k < CROP_C; ++k) { acc[k] = 0.0; cnt[k] = 0; }
-
-    for (long rs = blockIdx.x; rs < nrs; rs += gridDim.x) {          // uniform over the workgroup: the barriers below are safe
-        const int r = (int)(rs / segs), c = (int)(rs % segs) * CROP_T + tid;
-        bool inside = true;
-        if (CROP) {
-            const double py = y_max - pix * ((double)r + 0.5);
-            const double px = x_min + pix * ((double)c + 0.5);
-            int right = 0;                                           // crossing edges with px < xint
-            int n = 0;                                               // entries of s_x (uniform)
-            for (int e0 = 0; e0 < E; e0 += CROP_T) {
-                const int e = e0 + tid;
-                bool cr = false;
-                double xint = 0.0;
-                if (e < E) {
-                    const double ax = edges[4 * (size_t)e], ay = edges[4 * (size_t)e + 1];
-                    const double bx = edges[4 * (size_t)e + 2], by = edges[4 * (size_t)e + 3];
-                    cr = (ay > py) != (by > py);
-                    if (cr) xint = ax + ((py - ay) * (bx - ax)) / (by - ay);
-                }
-                const unsigned long long m = __ballot(cr);
-                if (lane == 0) s_wn[wave] = __popcll(m);
-                __syncthreads();                                     // (also: the last counting pass over s_x is over)
-                int base = n, total = 0;
-#pragma unroll
-                for (int w = 0; w < CROP_T / 64; ++w) {
-                    const int v = s_wn[w];
-                    base += w < wave ? v : 0;
-                    total += v;
-                }
-                if (cr) s_x[base + __popcll(m & ((1ull << lane) - 1ull))] = xint;     // n + total <= CROP_LIST: see below
-                n += total;
-                __syncthreads();
-                if (n + CROP_T > CROP_LIST || e0 + CROP_T >= E) {    // the next chunk might not fit, or there is none
-                    for (int i = 0; i < n; ++i) right += px < s_x[i] ? 1 : 0;
-                    n = 0;
-                }
-            }
-            inside = (right & 1) != 0;
-        }
-        if (c < W) {
-            const size_t o = (size_t)r * W + c;
-#pragma unroll
-            for (int k = 0; k < CROP_C; ++k) {
-                if (k < C) {
-                    if (CROP && !inside) {
-                        bands[k * P + o] = nanv;
-                    } else {
-                        const float v = bands[k * P + o];
-                        if (v == v) { acc[k] += (double)v; ++cnt[k]; }
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < CROP_C; ++k) {
-        if (k < C) {
-            const double s = crop_wave_sum(acc[k]);
-            const long long q = crop_wave_sum(cnt[k]);
-            if (lane == 0) { s_sum[wave][k] = s; s_cnt[wave][k] = q; }
-        }
-    }
-    __syncthreads();
-    if (tid < C) {
-        psum[(size_t)blockIdx.x * C + tid] = (s_sum[0][tid] + s_sum[1][tid]) + (s_sum[2][tid] + s_sum[3][tid]);
-        pcnt[(size_t)blockIdx.x * C + tid] = (s_cnt[0][tid] + s_cnt[1][tid]) + (s_cnt[2][tid] + s_cnt[3][tid]);
-    }
+    __shared__ CropLds s;
+    mosaic_crop_block<CROP>(s, bands, C, H, W, x_min, y_max, pix, edges, E, (int)blockIdx.x, (int)gridDim.x,
+                            psum + (size_t)blockIdx.x * C, pcnt + (size_t)blockIdx.x * C);
 }
 
 // one workgroup: thread t adds the partials of workgroups t, t + 256, ... in order, the threads in a fixed tree
 __global__ __launch_bounds__(CROP_T) void mosaic_crop_fold_kernel(const double* __restrict__ psum, const long long* __restrict__ pcnt,
                                                                   int C, int nblk, double* __restrict__ mean,
                                                                   long long* __restrict__ count) {
-    __shared__ double s_sum[CROP_T / 64];
-    __shared__ long long s_cnt[CROP_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int k = 0; k < C; ++k) {
-        double s = 0.0;
-        long long q = 0;
-        for (int b = tid; b < nblk; b += CROP_T) { s += psum[(size_t)b * C + k]; q += pcnt[(size_t)b * C + k]; }
-        s = crop_wave_sum(s);
-        q = crop_wave_sum(q);
-        if (lane == 0) { s_sum[wave] = s; s_cnt[wave] = q; }
-        __syncthreads();
-        if (tid == 0) {
-            const double t = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-            const long long n = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-            mean[k] = n > 0 ? t / (double)n : __longlong_as_double(0x7ff8000000000000LL);
-            count[k] = n;
-        }
-        __syncthreads();
-    }
+    mosaic_crop_fold(psum, pcnt, C, nblk, mean, count);
 }
 }  // namespace
 

@@ -1518,6 +1518,181 @@ def mosaic_crop_stats(bands: torch.Tensor, x_min: float, y_max: float, pix: floa
     return mean, count
 
 
+# ---- the mosaic atlas (include/strata_hip.h, "Mosaic atlas"; csrc/atlas.hip): the canvases of K parcels in one arena ----------
+def atlas_canvas_table(H, W, x_min=None, y_max=None) -> np.ndarray:
+    """sn2_atlas_canvas_table: the (K+1, SN2_ATLAS_CANVAS_COLS) int64 canvas table of K canvases of H[k] x W[k] pixels with the
+    geotransforms (x_min[k], y_max[k]) (None: zeros).  Host arithmetic, no device.  SN2_EINVAL / SN2_ELIMIT raise."""
+    H = np.ascontiguousarray(np.asarray(H, dtype=np.int64).reshape(-1))
+    W = np.ascontiguousarray(np.asarray(W, dtype=np.int64).reshape(-1))
+    K = len(H)
+    if len(W) != K or (x_min is None) != (y_max is None):
+        raise ValueError("atlas_canvas_table: H, W (and x_min, y_max) need one entry per canvas")
+    if K and (np.abs(H).max() >= 2 ** 31 or np.abs(W).max() >= 2 ** 31):
+        raise ValueError("atlas_canvas_table: H, W must fit an int32")
+    h32, w32 = H.astype(np.int32), W.astype(np.int32)
+    geo = [None, None]
+    if x_min is not None:
+        geo = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (x_min, y_max)]
+        if len(geo[0]) != K or len(geo[1]) != K:
+            raise ValueError("atlas_canvas_table: x_min, y_max need one entry per canvas")
+    table = np.zeros((K + 1, _lib.SN2_ATLAS_CANVAS_COLS), dtype=np.int64)
+    check(_lib.load().sn2_atlas_canvas_table(K, h32.ctypes.data, w32.ctypes.data, *(None if g is None else g.ctypes.data for g in geo),
+                                             table.ctypes.data), "sn2_atlas_canvas_table")
+    return table
+
+
+class AtlasTable:
+    """The canvas table of a mosaic atlas on the host (`host`, numpy) and, with a device, on the device (`dev`): what the atlas
+    entry points take.  K canvases; `pixels` = the sum of H W; base(k), shape(k) = (H, W), geo(k) = (x_min, y_max);
+    view(arena, C, k): canvas k's zero-copy (C,H,W) view of a C-band arena."""
+
+    def __init__(self, H, W, x_min=None, y_max=None, device=None):
+        self.host = atlas_canvas_table(H, W, x_min, y_max)
+        self.K = len(self.host) - 1
+        self.pixels = int(self.host[self.K, 0])
+        self.dev = None if device is None else torch.from_numpy(self.host).to(device)
+
+    def base(self, k: int) -> int:
+        return int(self.host[k, 0])
+
+    def shape(self, k: int):
+        return int(self.host[k, 1]), int(self.host[k, 2])
+
+    def geo(self, k: int):
+        g = self.host[k, 5:7].view(np.float64)
+        return float(g[0]), float(g[1])
+
+    def view(self, arena: torch.Tensor, C: int, k: int) -> torch.Tensor:
+        (H, W), b = self.shape(k), self.base(k)
+        return arena[C * b:C * (b + H * W)].view(C, H, W)
+
+
+def atlas_segments(place, D: int, table: np.ndarray) -> np.ndarray:
+    """The segment table of sn2_atlas_merge for one batch: place (B,3) = (canvas, row, col) per plot on the host, the canvases
+    NON-DECREASING (else ValueError) -> (S+1, SN2_ATLAS_SEG_COLS) int32: per run of equal canvas [canvas, first plot, last plot + 1,
+    y0, x0, h, w, first workgroup]; the window is the run's bounding window clipped to the canvas (h = w = 0 when nothing is left);
+    row S holds the number of workgroups."""
+    place = np.asarray(place).reshape(-1, 3).astype(np.int64)
+    B, K = len(place), len(table) - 1
+    if B == 0:
+        raise ValueError("atlas_segments: no plot")
+    c = place[:, 0]
+    if (np.diff(c) < 0).any():
+        raise ValueError("atlas_segments: the plots of a batch must come in non-decreasing canvas order")
+    if c[0] < 0 or c[-1] >= K:
+        raise ValueError(f"atlas_segments: canvas index outside [0, {K})")
+    first = np.flatnonzero(np.concatenate([[True], c[1:] != c[:-1]]))
+    canvas = c[first]
+    H, W = table[canvas, 1], table[canvas, 2]
+    y0 = np.clip(np.minimum.reduceat(place[:, 1], first), 0, H)
+    y1 = np.clip(np.maximum.reduceat(place[:, 1], first) + D, 0, H)
+    x0 = np.clip(np.minimum.reduceat(place[:, 2], first), 0, W)
+    x1 = np.clip(np.maximum.reduceat(place[:, 2], first) + D, 0, W)
+    some = (y1 > y0) & (x1 > x0)
+    h, w = np.where(some, y1 - y0, 0), np.where(some, x1 - x0, 0)
+    wg = -(-w // 64) * -(-h // 4)
+    S = len(first)
+    seg = np.zeros((S + 1, _lib.SN2_ATLAS_SEG_COLS), dtype=np.int64)
+    seg[:S, 0], seg[:S, 1], seg[:S, 2] = canvas, first, np.concatenate([first[1:], [B]])
+    seg[:S, 3], seg[:S, 4], seg[:S, 5], seg[:S, 6] = np.where(some, y0, 0), np.where(some, x0, 0), h, w
+    seg[1:, 7] = np.cumsum(wg)
+    if seg[S, 7] >= 2 ** 31:
+        raise StrataHipError("atlas_segments: more than 2^31 - 1 workgroups (SN2_ELIMIT)")
+    return seg.astype(np.int32)
+
+
+def _arena(t, bands, table, name):
+    return _chk(t, F32, (bands * table.pixels,), name)
+
+
+def atlas_merge(rasters, weights, place, table: AtlasTable, mean, wsum):
+    """include/strata_hip.h: sn2_atlas_merge.  Fold the plots of a batch, in order, each into ITS canvas of the atlas, in one
+    launch.  rasters (B,3,D,D), weights (D,D) on the device; place (B,3) int = (canvas, row, col) on the HOST, canvases
+    non-decreasing (ValueError otherwise); mean, wsum: the (3 pixels,) arenas, changed in place.  place and the segment table go
+    to the device in one copy."""
+    B, _, D, _ = rasters.shape
+    _chk(rasters, F32, (B, 3, D, D), "rasters")
+    _chk(weights, F32, (D, D), "weights")
+    _arena(mean, 3, table, "mean")
+    _arena(wsum, 3, table, "wsum")
+    place = np.ascontiguousarray(np.asarray(place).reshape(-1, 3).astype(np.int32))
+    if len(place) != B:
+        raise ValueError(f"place: expected ({B},3), got {place.shape}")
+    seg = np.ascontiguousarray(atlas_segments(place, D, table.host))
+    S = len(seg) - 1
+    both = torch.from_numpy(np.concatenate([place.reshape(-1), seg.reshape(-1)])).to(rasters.device)
+    _call("sn2_atlas_merge", _ptr(rasters), _ptr(weights), _ptr(both), B, D, table.K, table.host.ctypes.data, _ptr(table.dev),
+          seg.ctypes.data, both.data_ptr() + 4 * 3 * B, S, _ptr(mean), _ptr(wsum), _stream())
+
+
+def atlas_finalize_ws_words(K: int) -> int:
+    """SN2_ATLAS_FINALIZE_WS_WORDS of include/strata_hip.h (32-bit words)."""
+    words = ctypes.c_size_t()
+    check(_lib.load().sn2_atlas_finalize_ws_words(int(K), ctypes.byref(words)), "sn2_atlas_finalize_ws_words")
+    return int(words.value)
+
+
+def atlas_finalize(mean, wsum, table: AtlasTable, thr: Optional[torch.Tensor] = None):
+    """include/strata_hip.h: sn2_atlas_finalize.  The arenas mean, wsum (3 pixels,) -> bands (5 pixels,): canvas k's (5,H,W) =
+    [Vb, Vm_soft, Vh, Vm_hard, weights]; thr (K,2) = threshold, its index (written into `thr` when one is given)."""
+    _arena(mean, 3, table, "mean")
+    _arena(wsum, 3, table, "wsum")
+    dev, K = mean.device, table.K
+    ws = torch.empty(atlas_finalize_ws_words(K) // 2, dtype=F64, device=dev)
+    thr = torch.empty(K, 2, dtype=F32, device=dev) if thr is None else _chk(thr, F32, (K, 2), "thr")
+    bands = torch.empty(5 * table.pixels, dtype=F32, device=dev)
+    _call("sn2_atlas_finalize", _ptr(mean), _ptr(wsum), K, table.host.ctypes.data, _ptr(table.dev), _ptr(ws), _ptr(thr), _ptr(bands),
+          _stream())
+    return bands, thr
+
+
+def atlas_edges(edges, K: int):
+    """edges: None, or K entries, each None or the (E,4) fp64 edges of that canvas's polygon (`parcel.polygon_edges`) ->
+    (all edges (sum E,4) fp64 or None, edge_start (K+1) int32), on the host."""
+    start = np.zeros(K + 1, dtype=np.int64)
+    parts = []
+    if edges is not None:
+        if len(edges) != K:
+            raise ValueError(f"edges: expected one entry per canvas ({K}), got {len(edges)}")
+        for k, e in enumerate(edges):
+            n = 0
+            if e is not None:
+                e = np.asarray(e, dtype=np.float64).reshape(-1, 4)
+                n = len(e)
+                if n == 0:
+                    raise ValueError("edges: a canvas without a crop is given as None, not as an empty array")
+                parts.append(e)
+            start[k + 1] = start[k] + n
+    if start[K] >= 2 ** 31:
+        raise StrataHipError("atlas_edges: more than 2^31 - 1 edges (SN2_ELIMIT)")
+    return (np.ascontiguousarray(np.concatenate(parts, 0)) if parts else None), start.astype(np.int32)
+
+
+def atlas_crop_stats(bands, C: int, table: AtlasTable, pix: float, edges=None, out=None):
+    """include/strata_hip.h: sn2_atlas_crop_stats.  bands: the (C pixels,) arena, CHANGED IN PLACE canvas by canvas as
+    `mosaic_crop_stats` changes a single one, with the table's geotransforms; edges: as `atlas_edges` takes them (None, or None
+    for a canvas: no crop, the statistics alone) -> (mean (K,C) fp64, count (K,C) int64) on the device.  Two launches, one
+    host-to-device copy (the edges and their starts), no read-back."""
+    _arena(bands, C, table, "bands")
+    dev, K = bands.device, table.K
+    e, start = atlas_edges(edges, K)
+    n0 = (K + 2) // 2                                             # the int32 starts in front, padded to fp64 words
+    buf = np.zeros(n0 + (0 if e is None else e.size), dtype=np.float64)
+    buf[:n0].view(np.int32)[:K + 1] = start
+    if e is not None:
+        buf[n0:] = e.reshape(-1)
+    both = torch.from_numpy(buf).to(dev)
+    ws = torch.empty(max(2 * C * int(table.host[K, 4]), 1), dtype=F64, device=dev)
+    if out is None:
+        mean, count = torch.empty(K, C, dtype=F64, device=dev), torch.empty(K, C, dtype=I64, device=dev)
+    else:
+        mean, count = _chk(out[0], F64, (K, C), "out[0]"), _chk(out[1], I64, (K, C), "out[1]")
+    _call("sn2_atlas_crop_stats", _ptr(bands), int(C), K, table.host.ctypes.data, _ptr(table.dev), float(pix),
+          None if e is None else both.data_ptr() + 8 * n0, start.ctypes.data, both.data_ptr(), _ptr(ws), _ptr(mean), _ptr(count),
+          _stream())
+    return mean, count
+
+
 LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS
 
 

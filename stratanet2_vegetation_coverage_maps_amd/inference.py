@@ -133,6 +133,13 @@ def predict_parcel(model, batches, mosaic: ParcelMosaic, args, prefetch: int = 3
     (`PointNet2.prefetch_geometry`), while this batch's feature kernels, rasters and merge run.  FPS is M sequential rounds
     in one workgroup per plot -- 64 plots keep 64 of 256 CUs busy for most of an un-overlapped batch -- so several passes
     in flight is what fills the chip; 0 = no overlap."""
+    return predict_batches(model, batches, args, lambda rasters, cur: mosaic.add(rasters, cur["plot_center"]), prefetch=prefetch)
+
+
+@torch.no_grad()
+def predict_batches(model, batches, args, sink, prefetch: int = 3):
+    """The prefetching loop of `predict_parcel`: every batch's rasters (B,3,D,D) go to `sink(rasters, batch)` -- a
+    `ParcelMosaic.add`, or a `MosaicAtlas.add` for batches that cut across parcels.  Returns the number of plots processed."""
     from collections import deque
     model.eval()
     n = 0
@@ -161,8 +168,109 @@ def predict_parcel(model, batches, mosaic: ParcelMosaic, args, prefetch: int = 3
         clouds_dev = model._last_cloud_dev[1]
         model._last_cloud_dev = None
         rasters, _ = project_batch_to_2d_rasters(clouds_dev, cov, args)
-        mosaic.add(rasters, cur["plot_center"])
+        sink(rasters, cur)
         n += clouds_dev.shape[0]
     # (no check of hip_ops.fps_gave_up here: it reads a device word, i.e. synchronises; callers that synchronise anyway --
     # reading the mosaic back -- may ask for it)
     return n
+
+
+class MosaicAtlas:
+    """The running mosaics of K parcels in one arena on the device (include/strata_hip.h, "Mosaic atlas"): what K `ParcelMosaic`s
+    hold, canvas k the bytes of parcel k's own mosaic, but merged, finalised, cropped and read back K canvases at a time.
+    canvases: per parcel (x_min, y_max, height_pix, width_pix), or None for a parcel without plots (it owns a one-pixel canvas
+    that nothing is merged into; `mosaic(k)` and its report's bands are None)."""
+
+    def __init__(self, canvases, args, device):
+        self.args = args
+        self.pix = args.diam_meters / args.diam_pix
+        self.empty = [c is None for c in canvases]
+        full = [(0.0, 0.0, 1, 1) if c is None else c for c in canvases]
+        self.table = ops.AtlasTable([c[2] for c in full], [c[3] for c in full], [float(c[0]) for c in full], [float(c[1]) for c in full],
+                                    device=device)
+        self.K = self.table.K
+        self._x_min = torch.tensor([float(c[0]) for c in full], dtype=torch.float64)
+        self._y_max = torch.tensor([float(c[1]) for c in full], dtype=torch.float64)
+        nan = float("nan")
+        self.mean = torch.full((3 * self.table.pixels,), nan, dtype=torch.float32, device=device)
+        self.wsum = torch.full((3 * self.table.pixels,), nan, dtype=torch.float32, device=device)
+        self.w = torch.from_numpy(weights_band(args.diam_pix).astype(np.float32)).to(device)
+
+    @classmethod
+    def for_plots(cls, parcel_set, args, device=None):
+        """One canvas per parcel of a `parcel.ParcelSet`, each sized as `parcel.parcel_mosaic` sizes a parcel's own."""
+        from .parcel import mosaic_extent
+        start = parcel_set.parcel_start
+        canvases = [mosaic_extent(parcel_set.centers_host[start[k]:start[k + 1]], args) if start[k + 1] > start[k] else None
+                    for k in range(len(start) - 1)]
+        return cls(canvases, args, parcel_set.raw.device if device is None else device)
+
+    def offsets(self, plot_centers, parcel) -> np.ndarray:
+        """(B,2) plot centres in metres and (B,) parcel indices -> (B,3) int32 (canvas, row, col) of the plots' top-left pixels
+        (`ParcelMosaic.offsets`' arithmetic with the geotransform of each plot's own canvas), on the host."""
+        c = torch.as_tensor(plot_centers, dtype=torch.float64).reshape(-1, 2)
+        k = torch.as_tensor(np.asarray(parcel), dtype=torch.int64).reshape(-1)
+        half = self.args.diam_meters // 2
+        col = torch.round(((c[:, 0] - half) - self._x_min[k]) / self.pix)
+        row = torch.round((self._y_max[k] - (c[:, 1] + half)) / self.pix)
+        return torch.stack([k.to(torch.float64), row, col], 1).to(torch.int32).numpy()
+
+    def add(self, rasters: torch.Tensor, plot_centers, parcel):
+        """Fold a batch's rasters, in order, each into the canvas of its parcel: ONE launch.  parcel: (B,) non-decreasing."""
+        ops.atlas_merge(rasters.contiguous(), self.w, self.offsets(plot_centers, parcel), self.table, self.mean, self.wsum)
+
+    def mosaic(self, k: int):
+        """(mean, wsum): parcel k's (3,H,W) views of the arenas -- what its `ParcelMosaic` holds --, None without plots."""
+        if self.empty[k]:
+            return None
+        return self.table.view(self.mean, 3, k), self.table.view(self.wsum, 3, k)
+
+    def finalize(self):
+        """`ParcelMosaic.finalize` of every canvas at once: (the (5,H_k,W_k) band arena, thr (K,2))."""
+        return ops.atlas_finalize(self.mean, self.wsum, self.table)
+
+    def report(self, shapes=None) -> "AtlasReport":
+        """`ParcelMosaic.report` of all K parcels: one finalisation, one crop and one statistics pass over the atlas, and ONE
+        device-to-host read of the K thresholds, means and counts together.  shapes: None (no crop), or per parcel the rings of
+        its polygon or None."""
+        C, K = 5, self.K
+        pack = torch.empty(K + 2 * K * C, dtype=torch.int64, device=self.mean.device)     # thresholds + indices | means | counts
+        thr = pack[:K].view(torch.float32).view(K, 2)
+        means, counts = pack[K:K + K * C].view(torch.float64).view(K, C), pack[K + K * C:].view(K, C)
+        bands, _ = ops.atlas_finalize(self.mean, self.wsum, self.table, thr=thr)
+        edges = None
+        if shapes is not None:
+            from .parcel import polygon_edges
+            if len(shapes) != K:
+                raise ValueError(f"shapes: expected one entry per parcel ({K}), got {len(shapes)}")
+            edges = [None if (r is None or self.empty[k]) else polygon_edges(r) for k, r in enumerate(shapes)]
+        ops.atlas_crop_stats(bands, C, self.table, self.pix, edges, out=(means, counts))
+        host = pack.cpu().numpy()                                                          # the one read
+        thresholds = host[:K].view(np.float32).reshape(K, 2)[:, 0].astype(np.float64)
+        thresholds[np.asarray(self.empty, dtype=bool)] = np.nan
+        return AtlasReport(thresholds, host[K:K + K * C].view(np.float64).reshape(K, C).copy(), host[K + K * C:].reshape(K, C).copy(),
+                           bands, self.table, list(self.empty))
+
+
+@dataclass
+class AtlasReport:
+    """`MosaicAtlas.report`: thresholds (K) fp64, band_means (K,5) fp64 and band_counts (K,5) int64 on the host, the cropped band
+    arena on the device.  bands(k): parcel k's (5,H,W) view; parcel(k): its `ParcelReport`.  A parcel without plots has None
+    bands, a NaN threshold, NaN means and zero counts."""
+    thresholds: np.ndarray
+    band_means: np.ndarray
+    band_counts: np.ndarray
+    band_arena: torch.Tensor
+    table: object
+    empty: list
+
+    def __len__(self):
+        return len(self.thresholds)
+
+    def bands(self, k: int):
+        return None if self.empty[k] else self.table.view(self.band_arena, 5, k)
+
+    def parcel(self, k: int) -> ParcelReport:
+        m, n = self.band_means[k], self.band_counts[k]
+        return ParcelReport(self.bands(k), float(self.thresholds[k]), {b: float(m[i]) for i, b in enumerate(REPORT_BANDS)},
+                            {b: int(n[i]) for i, b in enumerate(REPORT_BANDS)}, m, n)

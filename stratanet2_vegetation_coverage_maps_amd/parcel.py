@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import hip_ops as ops
-from .inference import ParcelMosaic, predict_parcel
+from .inference import MosaicAtlas, ParcelMosaic, predict_batches, predict_parcel
 from .input_pipeline import check_sampler, draw_plot_randoms, draw_seed, fake_ground_xy, live_counts
 
 MIN_POINTS = 51              # prepare_utils.py:67-69 (< 50: None) and prepare.py:93 (> 50)
@@ -167,7 +167,7 @@ class ParcelPlots:
         return len(self.n_points)
 
     def batches(self, args, batch_size: int, rs=np.random, fps_start: Optional[int] = None, sampler="numpy", seed=None,
-                n_live: bool = True):
+                n_live: bool = True, key_base: int = 0):
         """The input dicts of `inference.predict_parcel` ("cloud", "xyz", "plot_center", "n_live"), built on the device from raw /
         offsets by `sn2_prepare_plots` in eval mode.  Random draws: `draw_plot_randoms` per plot in plot order, so the
         batches equal `input_pipeline.prepare_batch(plots, centers, args, train=False, rs=rs)` on the same plots and seed.
@@ -177,13 +177,19 @@ class ParcelPlots:
         the plot's position in this ParcelPlots, so a plot's points do not depend on `batch_size`.
         "n_live" (B) int32 = `input_pipeline.live_counts`: with either sampler a plot of fewer than subsample_size candidates is
         its candidates in order, then repeats (a sparse parcel: half of its plots); the FPS kernels skip the repeats.  n_live=False
-        leaves the key out (same predictions; a cross-check and a timing comparison)."""
+        leaves the key out (same predictions; a cross-check and a timing comparison).
+        key_base: the device sampler's key of plot i is key_base + i (`plot_keys`); a parcel run with key_base = k << 32 draws
+        the points it draws as parcel k of a `ParcelSet`."""
         check_sampler(sampler)                       # here, not in the generator: a bad argument fails at the call
         if sampler == "numpy" and seed is not None:
             raise ValueError("seed belongs to sampler='device'")
-        return self._batches(args, batch_size, rs, fps_start, sampler, seed, n_live)
+        return self._batches(args, batch_size, rs, fps_start, sampler, seed, n_live, int(key_base))
 
-    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True):
+    def plot_keys(self, key_base: int = 0) -> np.ndarray:
+        """(P) int64: the Philox key of every plot for `hip_ops.subsample` = key_base + the plot's position."""
+        return int(key_base) + np.arange(len(self), dtype=np.int64)
+
+    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True, key_base=0):
         dev = self.raw.device
         fake = fake_ground_xy(args.diam_meters)
         fake_dev = torch.from_numpy(fake).to(dev)
@@ -191,7 +197,7 @@ class ParcelPlots:
         n_live = torch.from_numpy(live_counts(self.n_points, len(fake), N)).to(dev)
         if sampler == "device":
             seed = draw_seed(rs) if seed is None else int(seed)
-            keys = torch.arange(len(self), dtype=torch.int64, device=dev)
+            keys = torch.from_numpy(self.plot_keys(key_base)).to(dev)
         for b0 in range(0, len(self), batch_size):
             b1 = min(len(self), b0 + batch_size)
             if sampler == "device":
@@ -274,26 +280,32 @@ def prepare_parcel(parcel_cloud, args, centers=None, keep=None, device=None, min
                        [plot_id(k, centers[k]) for k in plot_index], centers_kept)
 
 
-def parcel_mosaic(centers_host: np.ndarray, args, device) -> ParcelMosaic:
-    """The mosaic that holds every plot raster of the given centres: left = min cx - diam_meters//2, top = max cy +
-    diam_meters//2, pixels of diam_meters/diam_pix metres, plot windows placed as `ParcelMosaic.offsets` places them."""
+def mosaic_extent(centers_host: np.ndarray, args):
+    """(x_min, y_max, height_pix, width_pix) of the mosaic that holds every plot raster of the given centres: left = min cx -
+    diam_meters//2, top = max cy + diam_meters//2, pixels of diam_meters/diam_pix metres, plot windows placed as
+    `ParcelMosaic.offsets` places them."""
     half = args.diam_meters // 2
     c = torch.as_tensor(np.asarray(centers_host), dtype=torch.float64).reshape(-1, 2)
     left, top = float(c[:, 0].min()) - half, float(c[:, 1].max()) + half
     pix = args.diam_meters / args.diam_pix
     rows = torch.round((top - (c[:, 1] + half)) / pix)                # as ParcelMosaic.offsets
     cols = torch.round(((c[:, 0] - half) - left) / pix)
-    return ParcelMosaic(left, top, int(rows.max()) + args.diam_pix, int(cols.max()) + args.diam_pix, args, device)
+    return left, top, int(rows.max()) + args.diam_pix, int(cols.max()) + args.diam_pix
+
+
+def parcel_mosaic(centers_host: np.ndarray, args, device) -> ParcelMosaic:
+    """The `ParcelMosaic` of `mosaic_extent`."""
+    return ParcelMosaic(*mosaic_extent(centers_host, args), args, device)
 
 
 def predict_parcel_cloud(model, parcel_cloud, args, batch_size: int = 20, rs=np.random, keep=None, prefetch: int = 3,
                          centers=None, fps_start: Optional[int] = None, sampler="numpy", seed=None, n_live: bool = True,
-                         shape=None):
+                         shape=None, key_base: int = 0):
     """prepare_parcel + a mosaic sized to the plots + `inference.predict_parcel` -> (ParcelMosaic, ParcelPlots).  The mosaic
     is None when the parcel has no kept plot.  `mosaic.finalize()` gives the coverage bands.  sampler, seed, n_live: as
     `ParcelPlots.batches`.  shape: the rings of the parcel polygon (`polygon_edges`); with keep=None the lattice is then
     filtered by `polygon_keep(shape, shape_buffer(args))` as the reference filters it, and `mosaic.report(shape)` gives the
-    bands cropped to the polygon and the parcel's band means."""
+    bands cropped to the polygon and the parcel's band means.  key_base: as `ParcelPlots.batches`."""
     check_sampler(sampler)
     if shape is not None and keep is None:
         keep = polygon_keep(shape, shape_buffer(args))
@@ -301,5 +313,81 @@ def predict_parcel_cloud(model, parcel_cloud, args, batch_size: int = 20, rs=np.
     if len(plots) == 0:
         return None, plots
     mosaic = parcel_mosaic(plots.centers_host, args, plots.raw.device)
-    predict_parcel(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live), mosaic, args, prefetch=prefetch)
+    predict_parcel(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live, key_base), mosaic, args,
+                   prefetch=prefetch)
     return mosaic, plots
+
+
+@dataclass
+class ParcelSet(ParcelPlots):
+    """The kept plots of K parcels as ONE `ParcelPlots` (raw concatenated, offsets shifted; plot ids, centres, n_points and
+    plot_index as they are per parcel; point_index relative to the plot's own parcel cloud) plus parcel_of (P): the parcel of
+    every plot, and parcel_start (K+1): parcel k owns the plots parcel_start[k] .. parcel_start[k+1] (none is legal).  Both on
+    the host."""
+    parcel_of: np.ndarray = None
+    parcel_start: np.ndarray = None
+
+    @property
+    def n_parcels(self) -> int:
+        return len(self.parcel_start) - 1
+
+    def plot_keys(self, key_base: int = 0) -> np.ndarray:
+        """key_base + (parcel index << 32) + the plot's position inside its parcel: what the parcel's own `ParcelPlots` gives
+        with key_base = k << 32, so a plot draws the same points in a set and alone."""
+        k = self.parcel_of.astype(np.int64)
+        return int(key_base) + (k << 32) + (np.arange(len(self), dtype=np.int64) - self.parcel_start[k])
+
+    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True, key_base=0):
+        """`ParcelPlots.batches` over the whole set -- a batch may cut across parcels -- with one more key, "parcel": (B,) the
+        parcel of every plot, on the host (non-decreasing)."""
+        b0 = 0
+        for d in super()._batches(args, batch_size, rs, fps_start, sampler, seed, with_live, key_base):
+            b1 = b0 + len(d["plot_center"])
+            d["parcel"] = self.parcel_of[b0:b1]
+            b0 = b1
+            yield d
+
+
+def prepare_parcels(clouds, args, shapes=None, keeps=None, device=None, min_points: int = MIN_POINTS) -> ParcelSet:
+    """`prepare_parcel` of every cloud, unchanged, concatenated into a `ParcelSet`.  shapes: per parcel the rings of its
+    polygon or None -- the lattice is filtered by `polygon_keep(shape, shape_buffer(args))` --; keeps: per parcel a `keep`
+    callable or None, which goes before the shape."""
+    K = len(clouds)
+    if K == 0:
+        raise ValueError("prepare_parcels: no parcel")
+    for name, v in (("shapes", shapes), ("keeps", keeps)):
+        if v is not None and len(v) != K:
+            raise ValueError(f"prepare_parcels: {name} needs one entry per parcel")
+    parts = []
+    for k, cloud in enumerate(clouds):
+        keep = keeps[k] if keeps is not None else None
+        if keep is None and shapes is not None and shapes[k] is not None:
+            keep = polygon_keep(shapes[k], shape_buffer(args))
+        parts.append(prepare_parcel(cloud, args, keep=keep, device=device, min_points=min_points))
+    dev = parts[0].raw.device
+    counts = np.array([len(p) for p in parts], dtype=np.int64)
+    n_points = np.concatenate([p.n_points for p in parts]).astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(n_points)])
+    if offsets[-1] >= 2 ** 31:
+        raise ValueError(f"prepare_parcels: {offsets[-1]} plot points in all parcels, at most 2^31 - 1")
+    return ParcelSet(torch.cat([p.raw for p in parts], 1), torch.from_numpy(offsets.astype(np.int32)).to(dev),
+                     torch.cat([p.point_index for p in parts]), torch.cat([p.centers for p in parts]), n_points,
+                     np.concatenate([p.plot_index for p in parts]), [i for p in parts for i in p.plot_ids],
+                     np.concatenate([p.centers_host for p in parts]).astype(np.float32).reshape(-1, 2),
+                     np.repeat(np.arange(K, dtype=np.int64), counts), np.concatenate([[0], np.cumsum(counts)]))
+
+
+def predict_parcels(model, clouds, args, shapes=None, batch_size: int = 512, sampler="device", seed=None,
+                    fps_start: Optional[int] = None, prefetch: int = 3, n_live: bool = True, rs=np.random):
+    """K parcels predicted in shared batches: `prepare_parcels`, a `MosaicAtlas` with one canvas per parcel, and
+    `inference.predict_parcel`'s prefetching loop over the set's batches, which cut across parcels -- each batch ends in ONE
+    `atlas.add` -> (MosaicAtlas, ParcelSet).  `atlas.report(shapes)` gives every parcel's cropped bands and band means with one
+    device-to-host read.  Canvas k holds the bytes of `predict_parcel_cloud(model, clouds[k], ..., key_base=k << 32)`'s mosaic
+    (an eval forward of a plot does not depend on the batch it is in)."""
+    check_sampler(sampler)
+    plots = prepare_parcels(clouds, args, shapes=shapes)
+    atlas = MosaicAtlas.for_plots(plots, args)
+    if len(plots):
+        predict_batches(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live), args,
+                        lambda rasters, cur: atlas.add(rasters, cur["plot_center"], cur["parcel"]), prefetch=prefetch)
+    return atlas, plots
