@@ -1077,6 +1077,21 @@ int sn2_fp_rows_small(long R);
 /* sn2_fp.src_ws is used (the source-side form): 0 < cb <= 16, cb a multiple of 4, and more rows than sn2_fp_rows_small takes --
  * or force != 0 (sn2_fp_head_eval, which has no other form).  Only this form keeps bfloat16 rows (sn2_fp.act_bf16). */
 int sn2_fp_source_side(long R, int cb, int force);
+/* Which of its three kernel forms sn2_fp_forward (pass = its `training` argument, 0 / 1 / 2) or sn2_fp_backward (pass = 3)
+ * takes for a descriptor: the plan those entry points themselves run before their first launch, so SN2_FP_FORM_*, or the
+ * negative code the entry point would return (no pointer is dereferenced).
+ *   SPLIT        the 64-row matrix-core kernels; the only form with bfloat16 operands (sn2_block.mma_bf16)
+ *   SOURCE_SIDE  everything linear in the interpolation once per source row, in sn2_fp.src_ws; the only form with bfloat16
+ *                rows (sn2_fp.act_bf16) and permuted gradient rows (sn2_fp.row_perm)
+ *   DENSE        the grid-stride row kernels
+ * Forward: SPLIT where sn2_fp_rows_small(B*R); else SOURCE_SIDE where sn2_fp_source_side(B*R, cb, 0) holds on a k-NN block that
+ * has src_ws, 4-float aligned skip rows, src rows padded to 4 floats, h_stride = cout rounded up to 4 and B*R*3 < 2^31; else
+ * DENSE -- but SPLIT in an eval pass (0), which writes no statistic slots.  Backward: the same rule without the eval case, and
+ * SOURCE_SIDE also needs dsrc, du_scratch and scatter_ws given and dskip NULL: without them the block falls back to DENSE. */
+#define SN2_FP_FORM_SPLIT 0
+#define SN2_FP_FORM_SOURCE_SIDE 1
+#define SN2_FP_FORM_DENSE 2
+int sn2_fp_form(const sn2_fp *p, int pass);
 /* sn2_net_forward / sn2_net_backward take the one-launch global level (bf16: either block has sn2_block.mma_bf16): at most
  * SN2_GLOBAL_MAX_PLOTS plots, fp32 operands; backward also batch statistics (frozen == 0) and M2 <= SN2_GLOBAL_BWD_MAX_ROWS */
 int sn2_global_level_forward_route(int B, int bf16);

@@ -23,6 +23,7 @@ CONSTANTS = {
     "SN2_MOSAIC_CROP_MAX_BLOCKS": 2048, "SN2_ATLAS_CANVAS_COLS": 8, "SN2_ATLAS_SEG_COLS": 8, "SN2_ATLAS_FINALIZE_MAX_BLOCKS": 1024,
     "SN2_ATLAS_FINALIZE_CANVAS_WORDS": 10004 + 2 * 1024, "SN2_KDE_FIT_MAX_K": 65536, "SN2_LOSS_BLOCKS": 1024, "SN2_PROJECTED_LOSS_WS": 2 * 512 + 2,
     "SN2_NET_GRAD_IMAGES": 32, "SN2_METER_TERMS": 4,
+    "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
     "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256,
 }
@@ -246,6 +247,7 @@ SIGNATURES = {
     "sn2_three_nn_uses_grid": [c_int, c_int],
     "sn2_fp_rows_small": [c_long],
     "sn2_fp_source_side": [c_long, c_int, c_int],
+    "sn2_fp_form": [POINTER(FP), c_int],         # SN2_FP_FORM_*, or the negative code of the entry point
     "sn2_global_level_forward_route": [c_int, c_int],
     "sn2_global_level_backward_route": [c_int, c_int, c_int, c_int],
     "sn2_head_loss_route": [c_int, c_int, c_int],

@@ -1453,76 +1453,129 @@ __global__ __launch_bounds__(256) void fp_bwd_split_kernel(
     FSTAMP(8);
 }
 
-// the source-side form applies: workspace given, quads aligned, 32-bit row offsets
-template <int CA, int CO>
-bool fp_source_side_ok(const sn2_fp* p) {
+// ---- the dispatch: one plan per direction says which of the three kernel forms a descriptor takes, or refuses it, in host
+// arithmetic alone; one launcher per form launches it.  sn2_fp_form (include/strata_hip.h, "Routes") is the plans, exported.
+enum class FpForm { Split = SN2_FP_FORM_SPLIT, SourceSide = SN2_FP_FORM_SOURCE_SIDE, Dense = SN2_FP_FORM_DENSE };
+
+// the blocks whose source-side kernels are instantiated: the same test as sn2_fp_source_side's, at compile time
+template <int CB, bool KNN>
+constexpr bool FP_SRC_SIDE_CB = KNN && CB > 0 && CB % 4 == 0 && CB <= 16;
+
+// The forward's rule.  Split: the matrix-core kernel (64 rows x 4 channel groups per workgroup): its per-workgroup statistic
+// slots bound the rows of a TRAINING pass.  SourceSide: more rows than that on a block with the workspace (the per-point layer
+// keeps this form in every mode).  What is left: Dense -- but an eval pass (mode 0) writes no statistics, so any row count takes
+// Split (parcel inference: FP3 on 80 000 rows ran the dense kernel at 0.31 ms, 15 x what the contraction needs).
+// mode == SN2_BN_FROZEN_KEEP: the form a TRAINING pass of this shape takes (the backward pass that follows must find the rows
+// of that form), without statistic sums; BatchNorm finalised from the running statistics, nothing updated.
+template <int CA, int CB, int CO, bool KNN>
+int fp_forward_plan(const sn2_fp* p, int mode, FpForm* form) {
+    if (mode < 0 || mode > SN2_BN_FROZEN_KEEP) return SN2_EINVAL;
     const long R = (long)p->B * p->R_per_plot;
-    return p->src_ws && p->knn_idx && (p->skip_stride & 3) == 0 && p->src_stride >= 4 * ((CA + 3) / 4) &&
-           p->h_stride == 4 * ((CO + 3) / 4) && R * 3 < (1L << 31);
+    const bool src_side = FP_SRC_SIDE_CB<CB, KNN> && sn2_fp_source_side(R, CB, 0) && fp_source_side_ok<CA, CO>(p);
+    *form = sn2_fp_rows_small(R) ? FpForm::Split : src_side ? FpForm::SourceSide : mode == 0 ? FpForm::Split : FpForm::Dense;
+    // bfloat16 rows: the source-side form of the per-point layer only; bfloat16 operands: the matrix-core kernel only
+    if ((p->act_bf16 && *form != FpForm::SourceSide) || (p->blk.mma_bf16 && *form != FpForm::Split)) return SN2_ELIMIT;
+    return 0;
+}
+
+// Split and Dense hand the rows' input gradients to the transpose of the interpolation (bwd_gather) unless the caller does
+// that itself (scatter_ready < 0)
+template <bool KNN>
+bool fp_backward_gathers(const sn2_fp* p) { return KNN && p->dsrc && p->scatter_ready >= 0; }
+
+// The backward's rule: the forward's in a training pass, with two differences.  There is no eval case; and the source-side
+// form also needs the backward's own buffers -- dsrc, du_scratch and the inverted index in scatter_ws, and no dskip (its
+// kernels write none) -- so a block that ran SourceSide forward falls back to Dense when they are not all there.
+template <int CA, int CB, int CO, bool KNN>
+int fp_backward_plan(const sn2_fp* p, FpForm* form) {
+    if (!p->dy || !p->blk.dW || !p->blk.db || !p->blk.dgamma || !p->blk.dbeta) return SN2_EINVAL;
+    const long R = (long)p->B * p->R_per_plot;
+    const bool src_side = FP_SRC_SIDE_CB<CB, KNN> && sn2_fp_source_side(R, CB, 0) && fp_source_side_ok<CA, CO>(p) && p->dsrc &&
+                          !p->dskip && p->du_scratch && p->scatter_ws;
+    *form = sn2_fp_rows_small(R) ? FpForm::Split : src_side ? FpForm::SourceSide : FpForm::Dense;
+    // bfloat16 rows: the source-side form only, and its BatchNorm sums come from the consumer (no row pass reads bfloat16 dy)
+    if (p->act_bf16 && !(*form == FpForm::SourceSide && p->bn_sums_done)) return SN2_ELIMIT;
+    if (KNN && p->dsrc && !p->du_scratch) return SN2_EINVAL;
+    // bfloat16 operands: the matrix-core kernel only; permuted du rows: the source-side kernels only
+    if ((p->blk.mma_bf16 && *form != FpForm::Split) || (p->row_perm && *form != FpForm::SourceSide)) return SN2_ELIMIT;
+    if (*form == FpForm::SourceSide || fp_backward_gathers<KNN>(p)) {       // what reads the inverted index
+        if (!p->scatter_ws) return SN2_EINVAL;
+        if (p->S_per_plot > 8192) return SN2_ELIMIT;
+    }
+    // the chunk table of the source-side form: B * CM slots within what its kernels index
+    if (*form == FpForm::SourceSide && (long)p->B * inv_chunks_per_plot(p->R_per_plot, p->S_per_plot) >= (1L << 31) / 64)
+        return SN2_ELIMIT;
+    return 0;
+}
+
+// ---- forward launchers: each ends in its sn2_bn_finalize
+// (fp_fwd_split_kernel and fp_fwd_kernel take the same arguments)
+template <class K>
+int launch_fwd_rows(K kern, int grid, size_t lds, const sn2_fp* p, int training, hipStream_t st) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, p->B * p->R_per_plot, p->R_per_plot,
+                       p->S_per_plot, p->src_stride, p->skip_stride, p->h_stride, p->src, p->src_a, p->src_c, p->knn_idx,
+                       p->knn_w, p->skip, p->blk.W, p->blk.b, p->h, training ? p->blk.stat_slots : (float*)nullptr);
+    SN2_RETURN_LAUNCH();
+}
+
+template <int CA, int CB, int CO, bool KNN>
+int fwd_split(const sn2_fp* p, int training, hipStream_t st) {
+    const int R = p->B * p->R_per_plot, grid = sn2_cdiv(R, 64);
+    constexpr size_t lf = (size_t)(64 * OuterAcc<16, CA + CB + 1>::QS + 2 * 16 * ((CO + 15) / 16)) * sizeof(float);
+    static_assert(lf <= 48 * 1024, "fp_fwd_split_kernel staging");
+    auto kf = p->blk.mma_bf16 ? &fp_fwd_split_kernel<CA, CB, CO, KNN, true> : &fp_fwd_split_kernel<CA, CB, CO, KNN, false>;
+    SN2_TRY(launch_fwd_rows(kf, grid, lf, p, training, st));
+    return sn2_bn_finalize(&p->blk, training ? grid : 0, nullptr, R, training, st);
+}
+
+template <int CA, int CB, int CO>
+int fwd_source_side(const sn2_fp* p, int training, hipStream_t st) {
+    const int R = p->B * p->R_per_plot, n_src = p->B * p->S_per_plot;
+    SN2_TRY((launch_src_table<CA, CB, CO>(n_src, p->src_stride, p->src, p->src_a, p->src_c, p->blk.W, p->src_ws, st)));
+    const long n_grp = sn2_cdiv(R, 64 / ((CO + 3) / 4));
+    int grid = sn2_cdiv(n_grp, 8);
+    // two workgroups per CU: at 143 VGPRs three waves fit a SIMD, so 1024 workgroups ran as one full round and a
+    // third of a second one (0.057 ms; 768: 0.056; 512: 0.052; 384: 0.058)
+    const int cap_fwd_rows = 2 * sn2_cu_count() < SN2_STAT_SLOTS ? 2 * sn2_cu_count() : SN2_STAT_SLOTS;
+    if (grid > cap_fwd_rows) grid = cap_fwd_rows;
+    // (round 4: a variant with the plot's whole table in LDS -- 144 KB, one 16-wave workgroup per CU, the 226 MB of L2
+    // gathers replaced by ds_read_b128 -- ran in 38.1 us against this kernel's 36.5: the gathers are not its bound; at
+    // ~14 instructions per row and wave-instruction it is instruction issue, like the head kernels; the skip part's FMA
+    // chains as v_pk_fma_f32 pairs -- 32 instructions fewer per two rows -- ran in 38.0 us as well)
+    // (round 5: the row pass with its input stream fetched one element per lane, four iterations ahead;
+    // sn2_debug_fp_rows_form(0): the first form, kept for cross-checks -- same bits)
+    const bool rows2 = g_fp_rows_form != 0;
+    auto kr = rows2 ? (p->act_bf16 ? &fp_fwd_rows2_kernel<CA, CB, CO, true> : &fp_fwd_rows2_kernel<CA, CB, CO, false>)
+                    : (p->act_bf16 ? &fp_fwd_rows_kernel<CA, CB, CO, true> : &fp_fwd_rows_kernel<CA, CB, CO, false>);
+    hipLaunchKernelGGL(kr, dim3(grid), dim3(256), 0, st, R, p->R_per_plot, p->S_per_plot,
+                       p->skip_stride, (const float*)p->src_ws, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.b, p->h,
+                       training ? p->blk.stat_slots : (float*)nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return sn2_bn_finalize(&p->blk, grid, nullptr, R, training, st);
+}
+
+template <int CA, int CB, int CO, bool KNN>
+int fwd_dense(const sn2_fp* p, int training, hipStream_t st) {
+    const int R = p->B * p->R_per_plot;
+    int grid = pick_grid(R, 256, 4);
+    if (grid > SN2_STAT_SLOTS) grid = SN2_STAT_SLOTS;
+    SN2_TRY(launch_fwd_rows(&fp_fwd_kernel<CA, CB, CO, KNN>, grid, 0, p, training, st));
+    return sn2_bn_finalize(&p->blk, grid, nullptr, R, training, st);
 }
 
 template <int CA, int CB, int CO, bool KNN>
 int fp_forward_t(const sn2_fp* p, int mode, hipStream_t st) {
-    // mode == SN2_BN_FROZEN_KEEP: the kernel a TRAINING pass of this shape takes (the backward pass that follows chooses its
-    // kernels by the same rules), without statistic sums; BatchNorm finalised from the running statistics, nothing updated
-    const int training = mode == 1, keep = mode != 0;
-    const int R = p->B * p->R_per_plot;
-    // the matrix-core kernel (64 rows x 4 channel groups per workgroup): its per-workgroup statistic slots bound the rows of a
-    // TRAINING pass; an eval pass writes no statistics, so any row count takes it (parcel inference: FP3 on 80 000 rows ran
-    // the scalar-weight fallback below at 0.31 ms, 15 x what the contraction needs)
-    const bool small = sn2_fp_rows_small(R);
-    bool src_side = false;                      // (the per-point layer keeps its source-side form in both modes)
-    if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16) src_side = sn2_fp_source_side(R, CB, 0) && fp_source_side_ok<CA, CO>(p);
-    if (small || (!keep && !src_side)) {
-        if (p->act_bf16) return SN2_ELIMIT;
-        const int grid = sn2_cdiv(R, 64);
-        constexpr size_t lf = (size_t)(64 * OuterAcc<16, CA + CB + 1>::QS + 2 * 16 * ((CO + 15) / 16)) * sizeof(float);
-        static_assert(lf <= 48 * 1024, "fp_fwd_split_kernel staging");
-        auto kf = p->blk.mma_bf16 ? &fp_fwd_split_kernel<CA, CB, CO, KNN, true> : &fp_fwd_split_kernel<CA, CB, CO, KNN, false>;
-        hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lf, st, R, p->R_per_plot,
-                           p->S_per_plot, p->src_stride, p->skip_stride, p->h_stride, p->src, p->src_a, p->src_c, p->knn_idx,
-                           p->knn_w, p->skip, p->blk.W, p->blk.b, p->h, training ? p->blk.stat_slots : (float*)nullptr);
-        hipError_t e0 = hipGetLastError();
-        if (e0 != hipSuccess) return (int)e0;
-        return sn2_bn_finalize(&p->blk, training ? grid : 0, nullptr, R, training, st);
+    FpForm form;
+    SN2_TRY((fp_forward_plan<CA, CB, CO, KNN>(p, mode, &form)));
+    const int training = mode == 1;
+    switch (form) {
+    case FpForm::Split: return fwd_split<CA, CB, CO, KNN>(p, training, st);
+    case FpForm::Dense: return fwd_dense<CA, CB, CO, KNN>(p, training, st);
+    case FpForm::SourceSide:
+        if constexpr (FP_SRC_SIDE_CB<CB, KNN>) return fwd_source_side<CA, CB, CO>(p, training, st);
     }
-    if (p->blk.mma_bf16) return SN2_ELIMIT;   // bf16 operands exist on the matrix-core kernel of the small layers only
-    if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16) {
-        if (fp_source_side_ok<CA, CO>(p)) {               // the per-point layer: source-side form
-            const int n_src = p->B * p->S_per_plot;
-            SN2_TRY((launch_src_table<CA, CB, CO>(n_src, p->src_stride, p->src, p->src_a, p->src_c, p->blk.W, p->src_ws, st)));
-            const long n_grp = sn2_cdiv(R, 64 / ((CO + 3) / 4));
-            int grid = sn2_cdiv(n_grp, 8);
-            // two workgroups per CU: at 143 VGPRs three waves fit a SIMD, so 1024 workgroups ran as one full round and a
-            // third of a second one (0.057 ms; 768: 0.056; 512: 0.052; 384: 0.058)
-            const int cap_fwd_rows = 2 * sn2_cu_count() < SN2_STAT_SLOTS ? 2 * sn2_cu_count() : SN2_STAT_SLOTS;
-            if (grid > cap_fwd_rows) grid = cap_fwd_rows;
-            // (round 4: a variant with the plot's whole table in LDS -- 144 KB, one 16-wave workgroup per CU, the 226 MB of L2
-            // gathers replaced by ds_read_b128 -- ran in 38.1 us against this kernel's 36.5: the gathers are not its bound; at
-            // ~14 instructions per row and wave-instruction it is instruction issue, like the head kernels; the skip part's FMA
-            // chains as v_pk_fma_f32 pairs -- 32 instructions fewer per two rows -- ran in 38.0 us as well)
-            // (round 5: the row pass with its input stream fetched one element per lane, four iterations ahead;
-            // sn2_debug_fp_rows_form(0): the first form, kept for cross-checks -- same bits)
-            const bool rows2 = g_fp_rows_form != 0;
-            auto kr = rows2 ? (p->act_bf16 ? &fp_fwd_rows2_kernel<CA, CB, CO, true> : &fp_fwd_rows2_kernel<CA, CB, CO, false>)
-                            : (p->act_bf16 ? &fp_fwd_rows_kernel<CA, CB, CO, true> : &fp_fwd_rows_kernel<CA, CB, CO, false>);
-            hipLaunchKernelGGL(kr, dim3(grid), dim3(256), 0, st, R, p->R_per_plot, p->S_per_plot,
-                               p->skip_stride, (const float*)p->src_ws, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.b, p->h,
-                               training ? p->blk.stat_slots : (float*)nullptr);
-            hipError_t e1 = hipGetLastError();
-            if (e1 != hipSuccess) return (int)e1;
-            return sn2_bn_finalize(&p->blk, grid, nullptr, R, training, st);
-        }
-    }
-    if (p->act_bf16) return SN2_ELIMIT;       // bfloat16 rows: the source-side form of the per-point layer only
-    int grid = pick_grid(R, 256, 4);
-    if (grid > SN2_STAT_SLOTS) grid = SN2_STAT_SLOTS;
-    hipLaunchKernelGGL((fp_fwd_kernel<CA, CB, CO, KNN>), dim3(grid), dim3(256), 0, st, R, p->R_per_plot,
-                       p->S_per_plot, p->src_stride, p->skip_stride, p->h_stride, p->src, p->src_a, p->src_c, p->knn_idx,
-                       p->knn_w, p->skip, p->blk.W, p->blk.b, p->h, training ? p->blk.stat_slots : (float*)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    return sn2_bn_finalize(&p->blk, grid, nullptr, R, training, st);
+    return SN2_EINVAL;
 }
 
 extern "C" int sn2_debug_fp_table_form(int form) {
@@ -1541,24 +1594,32 @@ extern "C" int sn2_debug_fp1_backward_parts(int mask) {
     return 0;
 }
 
-template <int CA, int CB, int CO, bool KNN>
-int fp_backward_t(const sn2_fp* p, hipStream_t st) {
-    constexpr int CI = CA + CB;
-    using Acc = OuterAcc<CO, CI + 1, 32>;
-    // waves per workgroup (one workgroup per CU): as many as the staging regions and 256 VGPRs per lane allow
-    constexpr int WAVES = (Acc::LDS_FLOATS * 4 * 8 <= 150 * 1024) ? 8 : ((Acc::LDS_FLOATS * 4 * 4 <= 150 * 1024) ? 4 : 2);
+// ---- backward launchers
+// 1 / (rows of the batch statistics); frozen_stats: the forward's statistics were constants (running statistics) -- the
+// batch-mean and batch-variance terms of the BatchNorm backward vanish
+inline float fp_inv_rows(const sn2_fp* p) { return p->blk.frozen_stats ? 0.f : 1.0f / (float)(p->B * p->R_per_plot); }
+// fp_bwd_split_kernel and fp_bwd_main_kernel take the same arguments; du: where they leave the rows' input gradients
+template <int CA, bool KNN, class K>
+int launch_bwd_rows(K kern, int grid, int threads, size_t lds, const sn2_fp* p, hipStream_t st) {
+    float* du = !KNN ? p->dsrc : p->dsrc ? p->du_scratch : nullptr;
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, p->B * p->R_per_plot, p->R_per_plot, p->S_per_plot, p->src_stride,
+                       p->skip_stride, p->h_stride, p->dskip_stride, KNN ? CA : p->dsrc_stride, fp_inv_rows(p), p->src,
+                       p->src_a, p->src_c, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.gamma,
+                       (const float*)p->blk.mean, (const float*)p->blk.invstd, (const float*)p->blk.dgamma,
+                       (const float*)p->blk.dbeta, (const float*)p->h, p->dy, p->blk.dW, p->blk.db, du, p->dskip,
+                       p->blk.grad_replicas, p->blk.grad_replica_stride);
+    SN2_RETURN_LAUNCH();
+}
+
+// dgamma / dbeta of the block's BatchNorm from a pass over the rows.  bn_sums_done (non-NULL): sn2_head_bn_sums /
+// sn2_fp_bn_sums already completed them (by the identity or by their own pass over the rows)
+template <int CO>
+int bwd_bn_sums(const sn2_fp* p, hipStream_t st) {
+    if (p->bn_sums_done) return 0;
     const int R = p->B * p->R_per_plot;
-    // 1 / (rows of the batch statistics); frozen_stats: the forward's statistics were constants (running statistics) -- the
-    // batch-mean and batch-variance terms of the BatchNorm backward vanish
-    const float invR = p->blk.frozen_stats ? 0.f : 1.0f / (float)R;
-    if (p->act_bf16 && !(p->bn_sums_done && p->src_ws && p->du_scratch && p->scatter_ws && p->dsrc && !p->dskip &&
-                         !sn2_fp_rows_small(R)))
-        return SN2_ELIMIT;                    // bfloat16 rows: the source-side form of the per-point layer only
-    // bn_sums_done (non-NULL): dgamma / dbeta of this block's BatchNorm already came from sn2_head_bn_sums / sn2_fp_bn_sums
-    if (p->bn_sums_done) {
-        // sn2_head_bn_sums / sn2_fp_bn_sums already completed dgamma / dbeta of this block (by the identity or by their
-        // own pass over the rows)
-    } else if (R <= (1 << 16)) {
+    if (R <= (1 << 16)) {
         hipLaunchKernelGGL((fp_bwd_bn_small_kernel<CO>), dim3(sn2_cdiv(R, 64)), dim3(256), 0, st, R, p->h_stride, p->h, p->dy,
                            p->blk.mean, p->blk.invstd, p->blk.dgamma, p->blk.dbeta, p->bn_sums_done);
     } else {
@@ -1567,109 +1628,106 @@ int fp_backward_t(const sn2_fp* p, hipStream_t st) {
         hipLaunchKernelGGL((fp_bwd_bn_kernel<CO>), dim3(g1), dim3(256), 0, st, R, p->h_stride, p->h, p->dy,
                            p->blk.mean, p->blk.invstd, p->blk.dgamma, p->blk.dbeta, p->bn_sums_done);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    float* du_out0 = KNN ? p->du_scratch : p->dsrc;
-    if (KNN && p->dsrc && !p->du_scratch) return SN2_EINVAL;
-    if (KNN && !p->dsrc) du_out0 = nullptr;
+    SN2_RETURN_LAUNCH();
+}
+
+// the 64-row x 4-channel-group kernel for small layers
+template <int CA, int CB, int CO, bool KNN>
+int bwd_split(const sn2_fp* p, hipStream_t st) {
+    constexpr int CI = CA + CB;
     constexpr size_t lb = fp_split_lds_bytes<CI>(fp_split_du_seq<CI>() ? 1 : 4);
     static_assert(lb <= 150 * 1024, "fp_bwd_split_kernel staging must fit LDS");
-    const bool small = sn2_fp_rows_small(R);                // the 64-row x 4-channel-group kernel for small layers
-    if (!small && p->blk.mma_bf16) return SN2_ELIMIT;       // bf16 operands: that kernel only
-    if (small) {
-        auto ks = p->blk.mma_bf16 ? &fp_bwd_split_kernel<CA, CB, CO, KNN, true> : &fp_bwd_split_kernel<CA, CB, CO, KNN, false>;
-        if (lb > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-        hipLaunchKernelGGL(ks, dim3(sn2_cdiv(R, 64)), dim3(256), lb, st, R, p->R_per_plot, p->S_per_plot, p->src_stride,
-                           p->skip_stride, p->h_stride, p->dskip_stride, KNN ? CA : p->dsrc_stride, invR, p->src,
-                           p->src_a, p->src_c, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.gamma,
-                           (const float*)p->blk.mean, (const float*)p->blk.invstd, (const float*)p->blk.dgamma,
-                           (const float*)p->blk.dbeta, (const float*)p->h, p->dy, p->blk.dW, p->blk.db, du_out0, p->dskip,
-                           p->blk.grad_replicas, p->blk.grad_replica_stride);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16) {
-        if (sn2_fp_source_side(R, CB, 0) && fp_source_side_ok<CA, CO>(p) && p->dsrc && !p->dskip && p->du_scratch && p->scatter_ws) {
-            const int S = p->S_per_plot, Rp = p->R_per_plot, B = p->B, n_src = B * S;
-            if (S > 8192) return SN2_ELIMIT;
-            constexpr int NT = 512;                       // 2 workgroups x 8 waves per CU
-            constexpr size_t lb1 = (size_t)(NT / 64) * (4 * ((CO + 3) / 4)) * (CB + 1) * sizeof(float);
-            auto k1 = p->act_bf16 ? &fp_bwd_rows_kernel<CA, CB, CO, NT, true> : &fp_bwd_rows_kernel<CA, CB, CO, NT, false>;
-            if (lb1 > 48 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb1);
-            const int parts = g_fp1_bwd_parts;
-            if (parts & 1)
-            hipLaunchKernelGGL(k1, dim3(2 * sn2_cu_count()), dim3(NT), lb1, st, R, p->skip_stride, invR, p->skip,
-                               p->blk.gamma, (const float*)p->blk.mean, (const float*)p->blk.invstd,
-                               (const float*)p->blk.dgamma, (const float*)p->blk.dbeta, (const float*)p->h, p->dy,
-                               p->du_scratch, p->blk.dW, p->blk.db, p->blk.grad_replicas, p->blk.grad_replica_stride,
-                               p->row_perm, Rp);
-            if (!p->scatter_ready) SN2_TRY(build_interp_index(p->knn_idx, p->knn_w, nullptr, B, Rp, S, p->scatter_ws, st, p->row_perm));
-            const InterpIndex x = carve_interp_index(p->scatter_ws, B, Rp, S);
-            // waves over the chunk table (as many as the chip holds at once, L <= 64 slots each), then a lane per source for
-            // what G[s] is for
-            if ((long)B * x.CM >= (1L << 31) / 64) return SN2_ELIMIT;
-            const int n_chunks = B * x.CM;
-            const int waves_resident = sn2_cu_count() * 32;
-            int L = sn2_cdiv(n_chunks, waves_resident);
-            if (L < 4) L = 4;
-            if (L > 64) L = 64;
-            const int gc = (sn2_cdiv(sn2_cdiv(n_chunks, L), 4) + 7) & ~7;
-            auto kc = p->act_bf16 ? &fp_bwd_src_chunk_kernel<CA, CB, CO, true> : &fp_bwd_src_chunk_kernel<CA, CB, CO, false>;
-            if (parts & 2)
-            hipLaunchKernelGGL(kc, dim3(gc), dim3(256), 0, st, n_chunks, L, R, Rp, S, (const int4*)x.chunks, (const int*)x.inv_row,
-                               (const float*)x.inv_w, (const float*)p->du_scratch, p->src_ws);
-            if (parts & 4)
-            hipLaunchKernelGGL((fp_bwd_src_merge_dw_kernel<CA, CB, CO>), dim3(sn2_cdiv(n_src, 64)), dim3(256), 0, st, n_src, S, x.CM,
-                               p->src_stride, p->dsrc_stride, (const int4*)x.items, p->src, p->src_a, p->src_c,
-                               (const float*)p->src_ws, p->blk.W, p->dsrc,
-                               p->blk.dW, p->blk.grad_replicas, p->blk.grad_replica_stride, L);
-            SN2_RETURN_LAUNCH();
-        }
-    }
-    if (p->act_bf16 || p->row_perm) return SN2_ELIMIT;    // (both belong to the source-side form above)
+    auto ks = p->blk.mma_bf16 ? &fp_bwd_split_kernel<CA, CB, CO, KNN, true> : &fp_bwd_split_kernel<CA, CB, CO, KNN, false>;
+    return launch_bwd_rows<CA, KNN>(ks, sn2_cdiv(p->B * p->R_per_plot, 64), 256, lb, p, st);
+}
+
+template <int CA, int CB, int CO>
+int bwd_source_side(const sn2_fp* p, hipStream_t st) {
+    const int S = p->S_per_plot, Rp = p->R_per_plot, B = p->B, R = B * Rp, n_src = B * S;
+    constexpr int NT = 512;                       // 2 workgroups x 8 waves per CU
+    constexpr size_t lb1 = (size_t)(NT / 64) * (4 * ((CO + 3) / 4)) * (CB + 1) * sizeof(float);
+    auto k1 = p->act_bf16 ? &fp_bwd_rows_kernel<CA, CB, CO, NT, true> : &fp_bwd_rows_kernel<CA, CB, CO, NT, false>;
+    if (lb1 > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb1);
+    const int parts = g_fp1_bwd_parts;
+    if (parts & 1)
+        hipLaunchKernelGGL(k1, dim3(2 * sn2_cu_count()), dim3(NT), lb1, st, R, p->skip_stride, fp_inv_rows(p), p->skip,
+                           p->blk.gamma, (const float*)p->blk.mean, (const float*)p->blk.invstd,
+                           (const float*)p->blk.dgamma, (const float*)p->blk.dbeta, (const float*)p->h, p->dy,
+                           p->du_scratch, p->blk.dW, p->blk.db, p->blk.grad_replicas, p->blk.grad_replica_stride,
+                           p->row_perm, Rp);
+    if (!p->scatter_ready) SN2_TRY(build_interp_index(p->knn_idx, p->knn_w, nullptr, B, Rp, S, p->scatter_ws, st, p->row_perm));
+    const InterpIndex x = carve_interp_index(p->scatter_ws, B, Rp, S);
+    // waves over the chunk table (as many as the chip holds at once, L <= 64 slots each), then a lane per source for
+    // what G[s] is for
+    const int n_chunks = B * x.CM;
+    const int waves_resident = sn2_cu_count() * 32;
+    int L = sn2_cdiv(n_chunks, waves_resident);
+    if (L < 4) L = 4;
+    if (L > 64) L = 64;
+    const int gc = (sn2_cdiv(sn2_cdiv(n_chunks, L), 4) + 7) & ~7;
+    auto kc = p->act_bf16 ? &fp_bwd_src_chunk_kernel<CA, CB, CO, true> : &fp_bwd_src_chunk_kernel<CA, CB, CO, false>;
+    if (parts & 2)
+        hipLaunchKernelGGL(kc, dim3(gc), dim3(256), 0, st, n_chunks, L, R, Rp, S, (const int4*)x.chunks, (const int*)x.inv_row,
+                           (const float*)x.inv_w, (const float*)p->du_scratch, p->src_ws);
+    if (parts & 4)
+        hipLaunchKernelGGL((fp_bwd_src_merge_dw_kernel<CA, CB, CO>), dim3(sn2_cdiv(n_src, 64)), dim3(256), 0, st, n_src, S, x.CM,
+                           p->src_stride, p->dsrc_stride, (const int4*)x.items, p->src, p->src_a, p->src_c,
+                           (const float*)p->src_ws, p->blk.W, p->dsrc,
+                           p->blk.dW, p->blk.grad_replicas, p->blk.grad_replica_stride, L);
+    SN2_RETURN_LAUNCH();
+}
+
+template <int CA, int CB, int CO, bool KNN>
+int bwd_dense(const sn2_fp* p, hipStream_t st) {
+    using Acc = OuterAcc<CO, CA + CB + 1, 32>;
+    // waves per workgroup (one workgroup per CU): as many as the staging regions and 256 VGPRs per lane allow
+    constexpr int WAVES = (Acc::LDS_FLOATS * 4 * 8 <= 150 * 1024) ? 8 : ((Acc::LDS_FLOATS * 4 * 4 <= 150 * 1024) ? 4 : 2);
     constexpr size_t lds_bytes = (size_t)Acc::LDS_FLOATS * 4 * WAVES;
-    auto kern = &fp_bwd_main_kernel<CA, CB, CO, KNN, WAVES>;
-    if (lds_bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_bytes);
-    float* du_out = KNN ? p->du_scratch : p->dsrc;
-    if (KNN && p->dsrc && !p->du_scratch) return SN2_EINVAL;
-    if (KNN && !p->dsrc) du_out = nullptr;
-    int grid = pick_grid(R, WAVES * 64, 4);
+    int grid = pick_grid(p->B * p->R_per_plot, WAVES * 64, 4);
     if (grid > 256) grid = 256;
-    if (!small) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds_bytes, st, R, p->R_per_plot, p->S_per_plot, p->src_stride,
-                       p->skip_stride, p->h_stride, p->dskip_stride, KNN ? CA : p->dsrc_stride, invR, p->src, p->src_a, p->src_c,
-                       p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.gamma, (const float*)p->blk.mean,
-                       (const float*)p->blk.invstd, (const float*)p->blk.dgamma, (const float*)p->blk.dbeta,
-                       (const float*)p->h, p->dy, p->blk.dW, p->blk.db, du_out, p->dskip, p->blk.grad_replicas,
-                       p->blk.grad_replica_stride);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (KNN && p->dsrc && p->scatter_ready >= 0) {       // (scatter_ready < 0: the caller transposes the interpolation itself)
-        if (!p->scatter_ws) return SN2_EINVAL;
-        const int S = p->S_per_plot, Rp = p->R_per_plot, B = p->B;
-        if (S > 8192) return SN2_ELIMIT;
-        if (!p->scatter_ready) SN2_TRY(build_interp_index(p->knn_idx, p->knn_w, nullptr, B, Rp, S, p->scatter_ws, st));
-        const InterpIndex x = carve_interp_index(p->scatter_ws, B, Rp, S);
-        const int* off = x.off;
-        const int* cnt = x.cnt;
-        const int* inv_row = x.inv_row;
-        const float* inv_w = x.inv_w;
-        const int n_src = B * S;
-        if ((long)Rp >= 128L * S && CA <= 64)     // >= 128 entries per list on average: a workgroup per source
-            hipLaunchKernelGGL((interp_gather_long_kernel<CA, 16>), dim3(n_src), dim3(1024), 0, st, n_src, Rp, S,
-                               p->dsrc_stride, (const int*)off, (const int*)cnt, (const int*)inv_row, (const float*)inv_w,
-                               (const float*)p->du_scratch, p->dsrc);
-        else
-            hipLaunchKernelGGL((interp_gather_kernel<CA>), dim3(sn2_cdiv(n_src, 4)), dim3(256), 0, st, n_src, Rp, S,
-                               p->dsrc_stride, (const int*)off, (const int*)cnt, (const int*)inv_row, (const float*)inv_w,
-                               (const float*)p->du_scratch, p->dsrc);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+    return launch_bwd_rows<CA, KNN>(&fp_bwd_main_kernel<CA, CB, CO, KNN, WAVES>, grid, WAVES * 64, lds_bytes, p, st);
+}
+
+// the transpose of the interpolation for Split and Dense: dsrc += the rows of du_scratch, gathered through the inverted index
+template <int CA>
+int bwd_gather(const sn2_fp* p, hipStream_t st) {
+    const int S = p->S_per_plot, Rp = p->R_per_plot, B = p->B, n_src = B * S;
+    if (!p->scatter_ready) SN2_TRY(build_interp_index(p->knn_idx, p->knn_w, nullptr, B, Rp, S, p->scatter_ws, st));
+    const InterpIndex x = carve_interp_index(p->scatter_ws, B, Rp, S);
+    if ((long)Rp >= 128L * S && CA <= 64)     // >= 128 entries per list on average: a workgroup per source
+        hipLaunchKernelGGL((interp_gather_long_kernel<CA, 16>), dim3(n_src), dim3(1024), 0, st, n_src, Rp, S,
+                           p->dsrc_stride, (const int*)x.off, (const int*)x.cnt, (const int*)x.inv_row, (const float*)x.inv_w,
+                           (const float*)p->du_scratch, p->dsrc);
+    else
+        hipLaunchKernelGGL((interp_gather_kernel<CA>), dim3(sn2_cdiv(n_src, 4)), dim3(256), 0, st, n_src, Rp, S,
+                           p->dsrc_stride, (const int*)x.off, (const int*)x.cnt, (const int*)x.inv_row, (const float*)x.inv_w,
+                           (const float*)p->du_scratch, p->dsrc);
+    SN2_RETURN_LAUNCH();
+}
+
+template <int CA, int CB, int CO, bool KNN>
+int fp_backward_t(const sn2_fp* p, hipStream_t st) {
+    FpForm form;
+    SN2_TRY((fp_backward_plan<CA, CB, CO, KNN>(p, &form)));
+    SN2_TRY(bwd_bn_sums<CO>(p, st));
+    switch (form) {
+    case FpForm::Split: SN2_TRY((bwd_split<CA, CB, CO, KNN>(p, st))); break;
+    case FpForm::Dense: SN2_TRY((bwd_dense<CA, CB, CO, KNN>(p, st))); break;
+    case FpForm::SourceSide:
+        if constexpr (FP_SRC_SIDE_CB<CB, KNN>) return bwd_source_side<CA, CB, CO>(p, st);
+        return SN2_EINVAL;
     }
-    return 0;
+    return fp_backward_gathers<KNN>(p) ? bwd_gather<CA>(p, st) : 0;
+}
+
+// sn2_fp_form: pass 0 / 1 / 2 = the forward in that mode, 3 = the backward
+template <int CA, int CB, int CO, bool KNN>
+int fp_form_t(const sn2_fp* p, int pass) {
+    FpForm form;
+    if (pass == 3) SN2_TRY((fp_backward_plan<CA, CB, CO, KNN>(p, &form)));
+    else SN2_TRY((fp_forward_plan<CA, CB, CO, KNN>(p, pass, &form)));
+    return (int)form;
 }
 
 // the four dense-row blocks of the reference architecture (model/point_net2.py:83,88-93)
@@ -1689,7 +1747,7 @@ int fp_backward_t(const sn2_fp* p, hipStream_t st) {
 }  // namespace
 
 // Routes (include/strata_hip.h).  The templates above instantiate the source-side kernels for the blocks whose cb passes the
-// same test at compile time (`if constexpr (KNN && CB > 0 && CB % 4 == 0 && CB <= 16)`).
+// same test at compile time (FP_SRC_SIDE_CB).
 extern "C" int sn2_fp_rows_small(long R) { return sn2_cdiv(R, 64) <= SN2_STAT_SLOTS; }
 extern "C" int sn2_fp_source_side(long R, int cb, int force) {
     return cb > 0 && cb <= 16 && cb % 4 == 0 && (!sn2_fp_rows_small(R) || force);
@@ -1697,15 +1755,18 @@ extern "C" int sn2_fp_source_side(long R, int cb, int force) {
 extern "C" size_t sn2_fp_src_ws_words(int B, int R_per_plot, int S_per_plot, int cout) {
     return SN2_FP_SRC_WS_WORDS(B, R_per_plot, S_per_plot, cout);
 }
+extern "C" int sn2_fp_form(const sn2_fp* p, int pass) {
+    SN2_TRY(check_fp(p));
+    if (pass < 0 || pass > 3) return SN2_EINVAL;
+    FP_DISPATCH(fp_form_t, p, pass);
+}
 
 extern "C" int sn2_fp_forward(const sn2_fp* p, int training, void* stream) {
     SN2_TRY(check_fp(p));
-    if (training < 0 || training > SN2_BN_FROZEN_KEEP) return SN2_EINVAL;
     FP_DISPATCH(fp_forward_t, p, training, (hipStream_t)stream);
 }
 
 extern "C" int sn2_fp_backward(const sn2_fp* p, void* stream) {
     SN2_TRY(check_fp(p));
-    if (!p->dy || !p->blk.dW || !p->blk.db || !p->blk.dgamma || !p->blk.dbeta) return SN2_EINVAL;
     FP_DISPATCH(fp_backward_t, p, (hipStream_t)stream);
 }

@@ -399,4 +399,13 @@ inline int check_fp(const sn2_fp* p) {
     return 0;
 }
 
+// the source-side form applies: workspace given, quads aligned, 32-bit row offsets; with_h: the rows of h are written
+// (sn2_fp_head_eval keeps them in LDS and reads no h_stride)
+template <int CA, int CO>
+bool fp_source_side_ok(const sn2_fp* p, bool with_h = true) {
+    const long R = (long)p->B * p->R_per_plot;
+    return p->src_ws && p->knn_idx && (p->skip_stride & 3) == 0 && p->src_stride >= 4 * ((CA + 3) / 4) &&
+           (!with_h || p->h_stride == 4 * ((CO + 3) / 4)) && R * 3 < (1L << 31);
+}
+
 }  // namespace

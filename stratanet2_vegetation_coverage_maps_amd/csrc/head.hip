@@ -1162,7 +1162,7 @@ extern "C" int sn2_fp_head_eval(const sn2_fp* p, const sn2_head* hd, void* strea
     if (hd->R <= 0 || hd->cin != 34 || !hd->fa || !hd->fc || !hd->W1 || !hd->b1 || !hd->W2 || !hd->b2) return SN2_EINVAL;
     if (!hd->coverages || !hd->proba || hd->drop_mask || hd->act_bf16 || p->act_bf16) return SN2_EINVAL;
     if (!(p->knn_idx && p->ca == 34 && p->cb == 8 && p->blk.cout == 34 && hd->R == p->B * p->R_per_plot)) return SN2_ELIMIT;
-    if (!(p->src_ws && (p->skip_stride & 3) == 0 && p->src_stride >= 36 && (long)hd->R * 3 < (1L << 31))) return SN2_ELIMIT;
+    if (!fp_source_side_ok<34, 34>(p, /*with_h=*/false)) return SN2_ELIMIT;       // (hd->R == B * R_per_plot: the line above)
     hipStream_t st = (hipStream_t)stream;
     const int R = hd->R, n_src = p->B * p->S_per_plot;
     // the layer's BatchNorm on its running statistics -> (a, c) = what the head applies to the rows (hd->fa, hd->fc name the

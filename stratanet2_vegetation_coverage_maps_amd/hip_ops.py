@@ -1081,6 +1081,15 @@ def fp_backward(d: FP):
     _call("sn2_fp_backward", d, _stream(), tag=f"{d.ca}+{d.cb}->{d.blk.cout}")
 
 
+FP_FORM_SPLIT, FP_FORM_SOURCE_SIDE, FP_FORM_DENSE = _lib.SN2_FP_FORM_SPLIT, _lib.SN2_FP_FORM_SOURCE_SIDE, _lib.SN2_FP_FORM_DENSE
+
+
+def fp_form(d: FP, fp_pass: int) -> int:
+    """sn2_fp_form: the kernel form (FP_FORM_*) that fp_forward(d, training = fp_pass) takes for fp_pass 0 / 1 / 2 and
+    fp_backward(d) for fp_pass 3, or the negative code the call would return.  Host arithmetic: nothing is launched."""
+    return _lib.load().sn2_fp_form(d, int(fp_pass))
+
+
 def plot_max_forward(h, a, c, B, R_per_plot, C):
     hs = (C + 3) // 4 * 4
     _chk(h, F32, (B * R_per_plot, hs), "h")

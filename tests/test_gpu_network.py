@@ -426,6 +426,66 @@ def test_per_point_layer_source_side_form(N):
         assert err <= 1e-3, f"{k}: {err:.2e}"
 
 
+def _fp1_form(B, N, M1, fp_pass):
+    """The kernel form (ops.FP_FORM_*) the per-point layer's forward takes at this shape, asked of the library for the
+    descriptor the host would hand it (uninitialised buffers: nothing is launched)."""
+    dev = torch.device("cuda:0")
+
+    def e(*shape):
+        return torch.empty(*shape, device=dev)
+    blk = ops.BlockBuffers(torch.nn.Linear(42, 34).to(dev), torch.nn.BatchNorm1d(34).to(dev))
+    knn = (torch.empty(B * N, 3, dtype=torch.int32, device=dev), e(B * N, 3))
+    return ops.fp_form(ops.fp_desc(blk, B, N, M1, 34, 8, e(B * M1, 36), e(B * N, 36), src_affine=(e(34), e(34)), knn=knn,
+                                   skip=e(B * N, 12)[:, 0:8]), fp_pass)
+
+
+@pytest.mark.parametrize("defect,want", [("row_perm", -2), ("no_scatter_ws", -1), (None, 0)])
+def test_fp_backward_refuses_a_descriptor_before_its_first_launch(defect, want):
+    """sn2_fp_backward validates first (include/strata_hip.h: SN2_EINVAL / SN2_ELIMIT come back with the device untouched).  The
+    64 + 16 -> 34 k-NN block on 2 x 64 rows over 2 x 16 sources (the Split form), every buffer really allocated:
+    row_perm -- an identity permutation -- belongs to the source-side form only (SN2_ELIMIT), and dsrc with du_scratch but no
+    scatter_ws has nothing to gather through (SN2_EINVAL).  The dispatch once returned both codes after the BatchNorm-sum kernel
+    and fp_bwd_split_kernel had run -- the latter adds into dW / db with atomics.  The gradient arena, du_scratch and dsrc must
+    hold the same int32 words as before the call; the same descriptor without a defect returns 0 and changes dW."""
+    from stratanet2_vegetation_coverage_maps_amd import _lib
+    dev = torch.device("cuda:0")
+    B, Rp, Sp, ca, cb, co = 2, 64, 16, 64, 16, 34
+    g = torch.Generator(device="cpu").manual_seed(11)
+
+    def r(*shape):
+        return torch.randn(*shape, generator=g).to(dev)
+    knn = ops.three_nn(r(B, 3, Sp), r(B, 3, Rp), 3)
+    blk = ops.BlockBuffers(torch.nn.Linear(ca + cb, co).to(dev), torch.nn.BatchNorm1d(co).to(dev))
+    n_w = co * (ca + cb)
+    arena, flat, images, _ = ops.grad_images_alloc(n_w + 3 * co, dev)
+    blk.grads = (flat[:n_w].view(co, ca + cb),) + tuple(flat[n_w + i * co:n_w + (i + 1) * co] for i in range(3))
+    blk.grad_images = images
+    src, skip, h, dy = r(B * Sp, ca), r(B * Rp, cb), torch.empty(B * Rp, 36, device=dev), r(B * Rp, 36)
+    dsrc, du = torch.empty(B * Sp, ca, device=dev), torch.empty(B * Rp, ca, device=dev)
+    ops.fp_forward(ops.fp_desc(blk, B, Rp, Sp, ca, cb, src, h, knn=knn, skip=skip), 1)
+    before = []
+    for t in (arena, du, dsrc):
+        t.view(-1).copy_((torch.arange(t.numel(), device=dev) % 251) * 0.25 + 1.0)           # the sentinel pattern
+        before.append(t.view(torch.int32).clone())
+    d = ops.fp_desc(blk, B, Rp, Sp, ca, cb, src, h, knn=knn, skip=skip, dy=dy, dsrc=dsrc, du_scratch=du, with_grads=True)
+    perm = torch.arange(Rp, dtype=torch.int32, device=dev).repeat(B)
+    if defect == "row_perm":
+        d.row_perm = perm.data_ptr()
+    elif defect == "no_scatter_ws":
+        d.scatter_ws = None
+    assert ops.fp_form(d, 3) == (want if want < 0 else ops.FP_FORM_SPLIT)
+    rc = _lib.load().sn2_fp_backward(d, ops._stream())
+    torch.cuda.synchronize()
+    assert rc == want
+    same = [torch.equal(t.view(torch.int32), b) for t, b in zip((arena, du, dsrc), before)]
+    if want < 0:
+        assert same == [True, True, True], dict(zip(("gradient arena", "du_scratch", "dsrc"), same))
+    else:
+        dW = sum(arena[i * images[1]:i * images[1] + n_w] - before[0].view(torch.float32)[i * images[1]:i * images[1] + n_w]
+                 for i in range(images[0]))
+        assert not same[0] and bool(torch.isfinite(dW).all()) and float(dW.abs().max()) > 0
+
+
 @pytest.mark.parametrize("B,N,M1", [(3, 24001, 1024), (16, 32768, 1024), (72, 1024, 8), (5, 14001, 3500), (20, 10000, 3300)])
 def test_the_two_row_passes_of_the_source_side_forward_give_the_same_bits(B, N, M1):
     """fp_fwd_rows2_kernel (round 5: a wave fetches an iteration's indices, weights and skip quads one element per lane, four
@@ -457,7 +517,9 @@ def test_the_two_row_passes_of_the_source_side_forward_give_the_same_bits(B, N, 
                 lin.bias.copy_(torch.randn(34, generator=g) * 0.1)
             blk = ops.BlockBuffers(lin, bn)
             h1 = torch.full((B * N, 36), 7.0, device=dev)
-            ops.fp_forward(ops.fp_desc(blk, B, N, M1, 34, 8, h2, h1, src_affine=(a2, c2), knn=knn, skip=rows0[:, 0:8]), 1)
+            desc = ops.fp_desc(blk, B, N, M1, 34, 8, h2, h1, src_affine=(a2, c2), knn=knn, skip=rows0[:, 0:8])
+            assert ops.fp_form(desc, 1) == ops.FP_FORM_SOURCE_SIDE
+            ops.fp_forward(desc, 1)
             torch.cuda.synchronize()
             out[(form, table)] = (h1.clone(), blk.aux.clone(), bn.running_mean.clone(), bn.running_var.clone())
     finally:
@@ -480,6 +542,7 @@ def test_source_side_form_with_many_tiny_plots():
     B, N = 72, 1024
     args = make_args(subsample_size=N, ratio1=8 / N, r1=6.0, ratio2=0.5, r2=12.0)
     assert ops.interp_chunks(N, 8) < 64 and B * N > 65536
+    assert _fp1_form(B, N, 8, 1) == ops.FP_FORM_SOURCE_SIDE
     d = make_batch(B, N, first_plot=400)
     sd = network.init_state_dict(6)
     fs = torch.stack([torch.arange(B) * 11 % N, torch.arange(B) % 8])
@@ -551,8 +614,10 @@ def test_eval_fused_per_point_layer_and_head(B, N):
             _lib.load().sn2_debug_fp_rows_form(1)
         assert torch.equal(cov0, out[True][0]) and torch.equal(proba0, out[True][1])
     if B * N > 65536:
+        assert _fp1_form(B, N, ops.fps_num_samples(N, 0.03), 0) == ops.FP_FORM_SOURCE_SIDE
         assert torch.equal(out[True][0], out[False][0]) and torch.equal(out[True][1], out[False][1])
     else:
+        assert _fp1_form(B, N, ops.fps_num_samples(N, 0.03), 0) == ops.FP_FORM_SPLIT
         assert float((out[True][0] - out[False][0]).abs().max()) < 2e-6 and float((out[True][1] - out[False][1]).abs().max()) < 2e-6
     with torch.no_grad():
         cov_r, proba_r, _ = network.forward(sd_now, d["cloud"], d["xyz"], args, training=False, use_kdtree=True)
