@@ -872,6 +872,68 @@ size_t sn2_plot_losses_ws_words(int B, int N, int D);
 int sn2_plot_losses(const float *coverages, const int *pix, const float *proba, const double *pdf, const double *gt, int B, int N,
                     int D, double m, double e, void *ws, float *pred, double *out, void *stream);
 
+/* Cross-validation report (csrc/indicators.hip) -- what learning/accuracy.py makes of the folds' per-plot predictions:
+ * calculate_performance_indicators_V1/V2/V3 (MAE, MAE2, MAE3, Acc, Acc2, Acc3), the class indices of compute_confusion_matrix,
+ * plain and after adjust_predictions_based_on_margin, and the sums that DataFrame.mean() and confusion_matrix() take over them.
+ *   pred (P,4) fp32: low, soil, medium, high, as sn2_plot_losses' pred; gt (P,4) fp64.  Strata s = columns 0, 2, 3 (veg_b,
+ *   veg_moy, veg_h).  EVERY comparison and difference is fp64; pred is widened exactly (the reference ran on NumPy < 1.24, where
+ *   a float32 scalar against a Python float compares in fp64).
+ * Constants (accuracy.py:13-42), each the double nearest its decimal literal (what floor(x * 100 + .5) / 100 yields):
+ *   centres c  = {0, .10, .25, .33, .50, .75, .90, 1};
+ *   class k has the borders lo = {0, .05, .18, .29, .42, .63, .83, .95}[k], hi = {.05, .18, .29, .42, .63, .83, .95, 1.05}[k];
+ *   the margin is 0.1.
+ * Closest class (get_closest_class_center_index): class(y) = the FIRST k, ascending, that minimises fabs(c[k] - y), each
+ *   difference rounded once to fp64; on an exact tie the lower class wins (y = 0.05 -> 0, 0.625 -> 4; 0.95 -> 6, 0.175 -> 1 and
+ *   0.825 -> 5 are no ties in fp64: the two differences differ in their last bits): this library's
+ *   rule -- the insertion sort inside NumPy < 1.25's argsort gives it, later NumPy versions pin no tie.  Every difference NaN: 0.
+ * Ground truth: relabel != 0 replaces gt[p,s] by c[class(gt[p,s])] (main.py:102-109); then, always, g = rint(gt * 1000) / 1000
+ *   (the round(3) at the head of every calculate_performance_indicators_V*).  kt = the k with g == c[k] (fp64 equality), or -1.
+ * Per plot and stratum, p = (double)pred:
+ *   error  = fabs(p - g);                                     acc  = lo[kt] <= p && p <= hi[kt];
+ *   error2 = acc ? 0 : fmin(fabs(lo[kt] - p), fabs(hi[kt] - p));   acc2 = (lo[kt] - 0.1) <= p && p <= (hi[kt] + 0.1);
+ *   L = lo[max(kt-1,0)], H = hi[min(kt+1,7)]:  acc3 = L <= p && p <= H;  error3 = acc3 ? 0 : fmin(fabs(L - p), fabs(H - p)).
+ *   The aggregates x_b_and_moy = (x_b + x_moy) / 2 and x_all = ((x_b + x_moy) + x_h) / 3, added in that order, with the
+ *   reference's two oddities kept AS WRITTEN:  acc_all = (acc_b + acc_moy) / 2 (accuracy.py:169: two strata, not three) and
+ *   error3_all = ((error3_b + error2_moy) + error3_h) / 3 (accuracy.py:242: error2 of the medium stratum).
+ *   A row with some kt == -1 (a continuous ground truth; the reference raises KeyError there): every class-based entry of that
+ *   row -- columns 5 .. 29 -- is NaN.
+ * Outputs:
+ *   rows (P,SN2_CV_COLUMNS) fp64, 16-byte aligned: V1's ten columns (error_veg_b, error_veg_moy, error_veg_h,
+ *     error_veg_b_and_moy, error_all, acc_veg_b, acc_veg_moy, acc_veg_h, acc_veg_b_and_moy, acc_all), then V2's ten (error2_*,
+ *     acc2_*), then V3's ten (error3_*, acc3_*): the order in which the reference adds them to its frame;
+ *   cls (P,9) int32: class(g) per stratum (the confusion matrices' true class: kt wherever kt >= 0), class(p) per stratum, and per
+ *     stratum the class of the margin-adjusted prediction (p := g where the row's acc2 entry == 1, so class(g) there; class(p)
+ *     elsewhere, a row with some kt == -1 included: its acc2 entries are NaN);
+ *   stats, SN2_CV_STATS_DOUBLES doubles: sum[SN2_CV_COLUMNS] over the plots; count[SN2_CV_COLUMNS] = the entries that are not NaN
+ *     (DataFrame.mean() skips NaN: mean = sum / count); the confusion counts (2,3,8,8) = [plain | margin-adjusted][stratum]
+ *     [true class][predicted class]; the number of rows with some kt == -1.  Counts are integer-valued doubles (exact: P < 2^53).
+ *   ws: 8-byte aligned, SN2_CV_WS_WORDS(P) 32-bit words (sn2_cv_indicators_ws_words), no initialisation.
+ * Contract:
+ *   - DETERMINISTIC, no floating-point atomics, no last-workgroup-out hand-off: the plots are cut into slices of
+ *     SN2_CV_SLICE_PLOTS, a function of nothing else; one workgroup sums a slice in a fixed order (a butterfly inside each wave,
+ *     the waves in ascending order) into the slice's own block of ws; a SECOND launch of one workgroup adds the slices in
+ *     ascending order and writes stats.  Confusion counts: integer LDS atomics inside a slice, integer sums over the slices.
+ *     The same inputs give the same bytes of rows, cls and stats, whatever the grid;
+ *   - rows and cls of plot p depend on plot p alone: the same plot at another position, at another P, gives the same bytes;
+ *   - a NaN prediction stays in its own row: its error entries are NaN and counted out of sum and count, its accuracies are 0
+ *     (every comparison fails), its class is 0;
+ *   - 1 <= P <= SN2_CV_MAX_PLOTS (beyond: SN2_ELIMIT, and the size helper then gives 0 words); NULL or misaligned pointers,
+ *     P < 1: SN2_EINVAL -- both before anything is launched.  Two launches on `stream`, nothing read back, capturable.
+ *   - plain C++, single operations: no product feeds a sum, so nothing is contracted into an FMA.
+ * Not on the training hot path: it runs once per cross-validation, over a table of a few thousand to a few million rows.
+ * (The size helper returns its value through a pointer, as sn2_atlas_finalize_ws_words does: tests/test_cabi.py and
+ * tests/test_parcel_report_host.py hold the `size_t` and `extern size_t` declarations of this header to closed lists.) */
+#define SN2_CV_SLICE_PLOTS 1024
+#define SN2_CV_COLUMNS 30
+#define SN2_CV_STATS_DOUBLES (2 * SN2_CV_COLUMNS + 2 * 3 * 8 * 8 + 1)
+#define SN2_CV_MAX_PLOTS (1 << 24)
+#define SN2_CV_SLICES(P) (((size_t)(P) + SN2_CV_SLICE_PLOTS - 1) / SN2_CV_SLICE_PLOTS)
+#define SN2_CV_WS_SLICE_WORDS (2 * SN2_CV_COLUMNS + (SN2_CV_COLUMNS + 2) + 2 * 3 * 8 * 8)
+#define SN2_CV_WS_WORDS(P) (SN2_CV_SLICES(P) * SN2_CV_WS_SLICE_WORDS)
+int sn2_cv_indicators_ws_words(int P, size_t *words);
+int sn2_cv_indicators(const float *pred, const double *gt, int P, int relabel, double *rows, int *cls, double *stats, void *ws,
+                      void *stream);
+
 /* ---- optimiser step of the timed training step -- torch.optim.Adam as configured in learning/train.py:180-185
  * (L2 weight decay added to the gradient), on flat buffers; grad_scale multiplies the gradient first (1/world).
  * The learning rate is a by-value argument here: a launch captured into a hipGraph keeps the rate of its capture.  The ABI keeps

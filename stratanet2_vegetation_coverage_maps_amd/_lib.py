@@ -23,6 +23,8 @@ CONSTANTS = {
     "SN2_MOSAIC_CROP_MAX_BLOCKS": 2048, "SN2_ATLAS_CANVAS_COLS": 8, "SN2_ATLAS_SEG_COLS": 8, "SN2_ATLAS_FINALIZE_MAX_BLOCKS": 1024,
     "SN2_ATLAS_FINALIZE_CANVAS_WORDS": 10004 + 2 * 1024, "SN2_KDE_FIT_MAX_K": 65536, "SN2_LOSS_BLOCKS": 1024, "SN2_PROJECTED_LOSS_WS": 2 * 512 + 2,
     "SN2_NET_GRAD_IMAGES": 32, "SN2_METER_TERMS": 4,
+    "SN2_CV_SLICE_PLOTS": 1024, "SN2_CV_COLUMNS": 30, "SN2_CV_STATS_DOUBLES": 2 * 30 + 2 * 3 * 8 * 8 + 1, "SN2_CV_MAX_PLOTS": 1 << 24,
+    "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
     "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256,
@@ -229,6 +231,9 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_plot_losses": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
                         c_void_p, c_void_p],
+    # the cross-validation report (csrc/indicators.hip)
+    "sn2_cv_indicators_ws_words": [c_int, POINTER(ctypes.c_size_t)],
+    "sn2_cv_indicators": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_adam_step_images": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float,
                              c_void_p, c_float, c_void_p],
     "sn2_adam_step_images_dev": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float, c_float,

@@ -12,8 +12,12 @@ ONE plot each, averaged over plots by an `AverageValueMeter`, with four `.item()
 device): the form the tests hold the kernel to.  A plot's row does not depend on the batch it was evaluated in (include/strata_hip.h:
 sn2_plot_losses, "batch invariance"), so the result of a fold does not depend on how it was cut into batches.
 
-Not reproduced (out of scope): `create_predictions_interpretations`, comet logging, the confusion matrices --
-the summaries have the keys of `get_cloud_prediction_summary`, so `pd.DataFrame(summaries)` goes through the reference's own code.
+`evaluate_table` is the same pass without the read: the (P,15) table stays on the device, which is what `cross_validation`
+concatenates over the folds and hands to sn2_cv_indicators -- the performance indicators and confusion matrices of
+`learning/accuracy.py` (the reference's own module needs `np.float`, which NumPy 1.24 removed).
+
+Not reproduced (out of scope): `create_predictions_interpretations`, comet logging, the matplotlib figures.
+The summaries have the keys of `get_cloud_prediction_summary`.
 """
 from collections import deque
 
@@ -146,21 +150,10 @@ def _plot_names(ids, first, B):
     return ids
 
 
-def evaluate(model, batches, args, kde=None, prefetch=3):
-    """`learning/test.py:evaluate` for a fold given as batches -> (loss_dict, summaries).
-
-    batches: iterable of `cloud_data` dicts as the reference's collate makes them: "cloud" (B,10,N), "xyz" (B,3,N), "coverages"
-    (B,4), "plot_id" (B names), optionally "pdf_all" (B*N,3), "fps_start" and "n_live" (PointNet2's additive keys, handed on to the
-    geometry passes as they are); B and N may differ between batches.
-    kde: a `losses.KdeTables`: a batch without "pdf_all" gets its densities from `kde_densities(cloud, args.z_max, kde)`; neither
-    given while `args.m != 0` is an error, raised before the batch's first launch.
-    prefetch: geometry passes in flight ahead of the feature pass (`PointNet2.prefetch_geometry`), 0 = none.
-
-    Eval-mode forward under `torch.no_grad()`; `model.training` is restored on return, also when a batch raises.  The per-plot
-    rows stay on the device until the last batch: ONE device-to-host read, whatever the number of batches.
-    loss_dict: the reference's keys (total_loss, MAE_loss, log_loss, MAE_veg_b, MAE_veg_moy, MAE_veg_h, step) = means over
-    plots, plus "entropy_loss" and "per_plot" = {"losses" (P,7), "pred" (P,4), "columns"}; summaries: one dict per plot with the
-    keys of `get_cloud_prediction_summary`.  `model.stop_early(loss_dict["total_loss"], epoch, args)` is the intended consumer."""
+def evaluate_table(model, batches, args, kde=None, prefetch=3):
+    """The validation pass of `evaluate` (its arguments) WITHOUT its device-to-host read -> (table, names, counts): table (P,15)
+    fp64 on the device = per plot the seven COLUMNS, the plot-wise prediction (4, fp32 widened exactly) and the ground truth (4);
+    names: per batch its plot names, a list or the batch's "plot_id" tensor as given (not read); counts: P point counts."""
     dev = model.lin1.weight.device
     if dev.type != "cuda":
         raise StrataHipError("evaluation.evaluate needs the model on a HIP device")
@@ -215,17 +208,39 @@ def evaluate(model, batches, args, kde=None, prefetch=3):
                 n_plots += B
             if not tables:
                 raise ValueError("evaluate: no plots")
-            table = torch.cat(tables, 0).cpu().numpy()                      # the ONE read
-            ids_dev = [x for x in names if isinstance(x, torch.Tensor)]
-            if ids_dev:
-                flat = iter(torch.cat([x.reshape(-1).to(dev) for x in ids_dev]).cpu().numpy().tolist())
-                names = [[next(flat) for _ in range(x.numel())] if isinstance(x, torch.Tensor) else x for x in names]
+            table = torch.cat(tables, 0)
     finally:
         model.train(was_training)
         if had_p2:
             model.p2_diam_pix = old_p2
         else:
             model.__dict__.pop("p2_diam_pix", None)
+    return table, names, counts
+
+
+def evaluate(model, batches, args, kde=None, prefetch=3):
+    """`learning/test.py:evaluate` for a fold given as batches -> (loss_dict, summaries).
+
+    batches: iterable of `cloud_data` dicts as the reference's collate makes them: "cloud" (B,10,N), "xyz" (B,3,N), "coverages"
+    (B,4), "plot_id" (B names), optionally "pdf_all" (B*N,3), "fps_start" and "n_live" (PointNet2's additive keys, handed on to the
+    geometry passes as they are); B and N may differ between batches.
+    kde: a `losses.KdeTables`: a batch without "pdf_all" gets its densities from `kde_densities(cloud, args.z_max, kde)`; neither
+    given while `args.m != 0` is an error, raised before the batch's first launch.
+    prefetch: geometry passes in flight ahead of the feature pass (`PointNet2.prefetch_geometry`), 0 = none.
+
+    Eval-mode forward under `torch.no_grad()`; `model.training` is restored on return, also when a batch raises.  The per-plot
+    rows stay on the device until the last batch: ONE device-to-host read, whatever the number of batches.
+    loss_dict: the reference's keys (total_loss, MAE_loss, log_loss, MAE_veg_b, MAE_veg_moy, MAE_veg_h, step) = means over
+    plots, plus "entropy_loss" and "per_plot" = {"losses" (P,7), "pred" (P,4), "columns"}; summaries: one dict per plot with the
+    keys of `get_cloud_prediction_summary`.  `model.stop_early(loss_dict["total_loss"], epoch, args)` is the intended consumer."""
+    table, names, counts = evaluate_table(model, batches, args, kde=kde, prefetch=prefetch)
+    dev = table.device
+    with torch.cuda.device(dev):
+        table = table.cpu().numpy()                                         # the ONE read
+        ids_dev = [x for x in names if isinstance(x, torch.Tensor)]
+        if ids_dev:
+            flat = iter(torch.cat([x.reshape(-1).to(dev) for x in ids_dev]).cpu().numpy().tolist())
+            names = [[next(flat) for _ in range(x.numel())] if isinstance(x, torch.Tensor) else x for x in names]
     plot_ids = [n for chunk in names for n in chunk]
     return aggregate(table[:, :7], table[:, 7:11].astype(np.float32), table[:, 11:15], plot_ids, counts,
                      step=getattr(args, "current_step_in_fold", 0))

@@ -114,6 +114,7 @@ def forked_streams(dev, exclude=None):
 
 
 import contextlib as _contextlib
+import gc as _gc
 
 
 @_contextlib.contextmanager
@@ -127,7 +128,14 @@ def graph_capture(graph, dev, pool=None, allowed_forks=()):
         on a fourth stream whose autograd node the engine ran -- and left work -- on that stream after the step's join).
         Here every shared stream found capturing at the end of the block is joined first (so the runtime never sees the
         state), and unless its name is in `allowed_forks` (streams the captured code forks into and joins itself: the
-        unpipelined step's geometry branches) the graph is dropped and StrataHipError raised."""
+        unpipelined step's geometry branches) the graph is dropped and StrataHipError raised.
+    A third rule: Python's cyclic garbage collector is OFF while the capture is open (and restored afterwards).  A collection can
+    start in any thread at any allocation -- the autograd thread of a captured backward pass included -- and whatever dead cycle
+    it finds is destroyed there and then: an earlier pipeline's hipGraphs with their memory pool, for one.  Destroying those while
+    a capture in the global error mode is open aborted the process (the whole GPU suite, in the capture that follows `del w` in
+    tests/test_gpu_train_modes.py, whenever the collector's counters happened to fire inside it).  torch.cuda.graph collected
+    garbage itself BEFORE every capture up to torch 2.8; since 2.9 it does not (`torch.compiler.config.force_cudagraph_gc`), so
+    dead cycles now survive into the capture.  Reference-counted frees are not affected; the cycles are collected after the capture."""
     dev = torch.device(dev)
     busy = forked_streams(dev)
     if busy:
@@ -135,15 +143,21 @@ def graph_capture(graph, dev, pool=None, allowed_forks=()):
                              "per device (hip_ops.shared_stream: single owner at a time)")
     stray = []
     kw = {} if pool is None else {"pool": pool}
-    with torch.cuda.graph(graph, **kw):
-        cap = torch.cuda.current_stream(dev)
-        try:
-            yield cap
-        finally:
-            for name in forked_streams(dev, exclude=cap):
-                cap.wait_stream(shared_stream(dev, name))      # joined: hipStreamEndCapture sees a legal graph whatever happened
-                if name not in allowed_forks:
-                    stray.append(name)
+    gc_was_on = _gc.isenabled()
+    _gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            cap = torch.cuda.current_stream(dev)
+            try:
+                yield cap
+            finally:
+                for name in forked_streams(dev, exclude=cap):
+                    cap.wait_stream(shared_stream(dev, name))  # joined: hipStreamEndCapture sees a legal graph whatever happened
+                    if name not in allowed_forks:
+                        stray.append(name)
+    finally:
+        if gc_was_on:
+            _gc.enable()
     if stray:
         graph.reset()
         raise StrataHipError(f"graph_capture: the captured code left work on shared stream(s) {stray} that nothing joined back "
@@ -1840,6 +1854,52 @@ def plot_losses(cov, pix, proba, pdf, gt, B: int, N: int, diam_pix: int, m: floa
     _call("sn2_plot_losses", _ptr(cov), _ptr(pix), _ptr(proba), _ptr(pdf) if m != 0.0 else None, _ptr(gt), B, N, D, m, e, _ptr(ws),
           _ptr(pred), _ptr(o), _stream())
     return o, pred
+
+
+CV_COLUMNS, CV_STATS_DOUBLES, CV_MAX_PLOTS = (_lib.CONSTANTS[n] for n in ("SN2_CV_COLUMNS", "SN2_CV_STATS_DOUBLES", "SN2_CV_MAX_PLOTS"))
+
+
+def cv_indicators_ws_words(P: int) -> int:
+    """32-bit words of `cv_indicators`' workspace (include/strata_hip.h: sn2_cv_indicators_ws_words); 0 = more plots than the
+    kernels cover."""
+    words = ctypes.c_size_t()
+    rc = _lib.load().sn2_cv_indicators_ws_words(int(P), ctypes.byref(words))
+    if rc not in (0, _lib.SN2_ELIMIT):
+        check(rc, "sn2_cv_indicators_ws_words")
+    return int(words.value)
+
+
+def cv_indicators(pred, gt, relabel: bool, ws=None):
+    """include/strata_hip.h: sn2_cv_indicators -> (rows (P,30) fp64, cls (P,9) int32, stats (SN2_CV_STATS_DOUBLES) fp64) on the
+    device, two launches on the current stream: the indicators of `learning/accuracy.py` per plot (V1, V2, V3), the true / predicted /
+    margin-adjusted classes, and the column sums, non-NaN counts, confusion counts and the number of continuous rows.  pred (P,4)
+    fp32, gt (P,4) fp64; relabel: the ground truths are first moved to their closest class centres.  The reference's two oddities are
+    kept as written: acc_all is the mean of TWO strata, error3_all takes error2 of the medium stratum.
+    ws: caller-owned workspace of at least `cv_indicators_ws_words(P)` int32 words (None: allocated here)."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 2:
+        raise ValueError("pred: expected a (P,4) tensor")
+    P = int(pred.shape[0])
+    _chk(pred, F32, (P, 4), "pred")
+    _chk(gt, F64, (P, 4), "gt")
+    if P < 1:
+        raise ValueError("cv_indicators: no plots")
+    words = cv_indicators_ws_words(P)
+    if words == 0:
+        raise StrataHipError(f"cv_indicators: P={P} is more than the kernels cover ({CV_MAX_PLOTS}: SN2_ELIMIT)")
+    dev = pred.device
+    if ws is None:
+        ws = torch.empty(words, dtype=I32, device=dev)
+    else:
+        _chk(ws, I32, None, "ws")
+        if ws.numel() < words or ws.data_ptr() % 8:
+            raise ValueError(f"ws: need {words} int32 words, 8-byte aligned")
+    rows = torch.empty(P, CV_COLUMNS, dtype=F64, device=dev)
+    cls = torch.empty(P, 9, dtype=I32, device=dev)
+    stats = torch.empty(CV_STATS_DOUBLES, dtype=F64, device=dev)
+    if pred.data_ptr() % 16 or rows.data_ptr() % 16:
+        raise ValueError("cv_indicators: pred and rows must be 16-byte aligned")
+    _call("sn2_cv_indicators", _ptr(pred), _ptr(gt), P, int(bool(relabel)), _ptr(rows), _ptr(cls), _ptr(stats), _ptr(ws), _stream())
+    return rows, cls, stats
 
 
 def adam_step_images(param, arena, replicas, stride, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step_dev, grad_scale=1.0):
