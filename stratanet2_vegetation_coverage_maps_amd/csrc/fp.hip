@@ -428,27 +428,42 @@ __global__ __launch_bounds__(WAVES * 64) void interp_gather_long_kernel(int n_sr
 // The row kernels use QH = ceil(CO/4) consecutive lanes per row, one float4 quad each: a load or store instruction covers
 // 64/QH whole rows = ~1 KB of consecutive bytes, and nothing but the lane's own quad constants lives in registers.
 // Results differ from the row-per-lane form by fp32 re-association only.
-// (the rows' accessors, the source table and the input stream of the row passes: fp_rows.h)
+// (the rows' accessors, the source table, the input stream and the (row, quad) arithmetic of the row passes: fp_rows.h)
+
+// batch statistics of a row pass (256 lanes, QH lanes per row, lane (g, q) holding the sums of channels 4 q .. 4 q + 3 over its
+// rows): per-lane partials -> LDS -> one slot per workgroup ([sum(C) | sumsq(C)], as stats_to_slot)
+template <int CO>
+__device__ __forceinline__ void row_quads_stats_to_slot(float (&s_part)[8][256], bool on, const float (&ssum)[4], const float (&ssq)[4],
+                                                        float* __restrict__ slots) {
+    constexpr int QH = (CO + 3) / 4, G = 64 / QH;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        s_part[t][threadIdx.x] = on ? ssum[t] : 0.f;
+        s_part[4 + t][threadIdx.x] = on ? ssq[t] : 0.f;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 2 * CO; e += 256) {
+        const int which = e / CO, c = e - which * CO, cq = c >> 2, ct = c & 3;
+        float acc = 0.f;
+        for (int w = 0; w < 4; ++w)
+            for (int gg = 0; gg < G; ++gg) acc += s_part[which * 4 + ct][w * 64 + cq + QH * gg];
+        slots[(size_t)blockIdx.x * 2 * CO + e] = acc;
+    }
+}
+
 template <int CA, int CB, int CO, bool BF>
 __global__ __launch_bounds__(256) void fp_fwd_rows_kernel(int R, int R_per_plot, int S_per_plot, int skip_stride,
                                                           const float* __restrict__ T, const int* __restrict__ knn_idx,
                                                           const float* __restrict__ knn_w, const float* __restrict__ skip,
                                                           const float* __restrict__ Wg, const float* __restrict__ biasg,
                                                           float* __restrict__ h, float* __restrict__ slots) {
-    constexpr int CI = CA + CB, QH = (CO + 3) / 4, HS = 4 * QH, G = 64 / QH, QB = CB / 4, U = 2;
+    constexpr int QH = (CO + 3) / 4, HS = 4 * QH, G = 64 / QH, QB = CB / 4, U = 2;
     static_assert(CB > 0 && CB % 4 == 0, "skip quads");
     __shared__ float s_part[8][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane % QH, g = lane / QH;
     const bool on = lane < G * QH;
-    float wB[4][CB], b4[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int o = 4 * q + t;
-        b4[t] = o < CO ? biasg[o] : 0.f;
-#pragma unroll
-        for (int k = 0; k < CB; ++k) wB[t][k] = o < CO ? Wg[o * CI + CA + k] : 0.f;
-    }
+    const FpQuadW<CB> fw = fp_quad_w<CA, CB, CO>(Wg, biasg, q);
     float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
     // (a wave's turn = U groups of G rows = one "iteration" of row_iters)
     const RowIters ri = row_iters((int)(((long)R + G * U - 1) / (G * U)), wave);
@@ -466,47 +481,20 @@ __global__ __launch_bounds__(256) void fp_fwd_rows_kernel(int R, int R_per_plot,
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             in[u] = nx[u];
-            const unsigned base = (in[u].rr / (unsigned)R_per_plot) * (unsigned)S_per_plot;
-#if defined(SN2_FR_DIAG) && (SN2_FR_DIAG & 2)
-            // (diagnostic: no table gathers -- values made from the indices)
-            ta[u][0] = make_float4((float)(base + in[u].i0), 1.f, 2.f, 3.f);
-            ta[u][1] = make_float4((float)in[u].i1, 1.f, 2.f, 3.f);
-            ta[u][2] = make_float4((float)in[u].i2, 1.f, 2.f, 3.f);
-#else
-            ta[u][0] = reinterpret_cast<const float4*>(T + (size_t)(base + in[u].i0) * HS)[q];
-            ta[u][1] = reinterpret_cast<const float4*>(T + (size_t)(base + in[u].i1) * HS)[q];
-            ta[u][2] = reinterpret_cast<const float4*>(T + (size_t)(base + in[u].i2) * HS)[q];
-#endif
+            fp_table_rows<HS>(T, (in[u].rr / (unsigned)R_per_plot) * (unsigned)S_per_plot, in[u].i0, in[u].i1, in[u].i2, q, ta[u]);
         }
         const long grp1 = grp0 + n_waves * U;
 #pragma unroll
         for (int u = 0; u < U; ++u) nx[u] = fp_row_in<QB>((grp1 + u) * G + g, on && grp1 < n_grp, R, knn_idx, knn_w, skip, skip_stride);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float w0 = in[u].w0, w1 = in[u].w1, w2 = in[u].w2;
-            const float inv = 1.0f / ((w0 + w1) + w2);
-            const float4 a = ta[u][0], b = ta[u][1], c = ta[u][2];
-            float v[4] = {interp_bias(a.x, b.x, c.x, w0, w1, w2, inv, b4[0]), interp_bias(a.y, b.y, c.y, w0, w1, w2, inv, b4[1]),
-                          interp_bias(a.z, b.z, c.z, w0, w1, w2, inv, b4[2]), interp_bias(a.w, b.w, c.w, w0, w1, w2, inv, b4[3])};
+            float v[4];
+            fp_row_quad<CB, CO>(fw, ta[u], in[u].w0, in[u].w1, in[u].w2, in[u].sk, in[u].valid, q, v);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                float acc = v[t];
-#if defined(SN2_FR_DIAG) && (SN2_FR_DIAG & 4)
-                acc += in[u].sk[0].x + in[u].sk[QB - 1].w;          // (diagnostic: no skip contraction)
-#else
-#pragma unroll
-                for (int b2 = 0; b2 < QB; ++b2) {
-                    acc = fmaf(wB[t][4 * b2 + 0], in[u].sk[b2].x, acc);
-                    acc = fmaf(wB[t][4 * b2 + 1], in[u].sk[b2].y, acc);
-                    acc = fmaf(wB[t][4 * b2 + 2], in[u].sk[b2].z, acc);
-                    acc = fmaf(wB[t][4 * b2 + 3], in[u].sk[b2].w, acc);
-                }
-#endif
-                acc = (in[u].valid && 4 * q + t < CO) ? fmaxf(acc, 0.f) : 0.f;
-                if constexpr (BF) acc = bf16_round(acc);     // the batch statistics describe the rows as they are stored
-                ssum[t] += acc;
-                ssq[t] = fmaf(acc, acc, ssq[t]);
-                v[t] = acc;
+                if constexpr (BF) v[t] = bf16_round(v[t]);   // the batch statistics describe the rows as they are stored
+                ssum[t] += v[t];
+                ssq[t] = fmaf(v[t], v[t], ssq[t]);
             }
 #if defined(SN2_FR_DIAG) && (SN2_FR_DIAG & 1)
             if (in[u].valid && v[0] == 12345.678f) row_quad_st<BF>(h, in[u].rr, HS, q, v[0], v[1], v[2], v[3]);   // (diagnostic: no stores)
@@ -515,21 +503,7 @@ __global__ __launch_bounds__(256) void fp_fwd_rows_kernel(int R, int R_per_plot,
 #endif
         }
     }
-    if (!slots) return;
-    // batch statistics: per-lane partials -> LDS -> one slot per workgroup ([sum(C) | sumsq(C)], as stats_to_slot)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        s_part[t][threadIdx.x] = on ? ssum[t] : 0.f;
-        s_part[4 + t][threadIdx.x] = on ? ssq[t] : 0.f;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 2 * CO; e += 256) {
-        const int which = e / CO, c = e - which * CO, cq = c >> 2, ct = c & 3;
-        float acc = 0.f;
-        for (int w = 0; w < 4; ++w)
-            for (int gg = 0; gg < G; ++gg) acc += s_part[which * 4 + ct][w * 64 + cq + QH * gg];
-        slots[(size_t)blockIdx.x * 2 * CO + e] = acc;
-    }
+    if (slots) row_quads_stats_to_slot<CO>(s_part, on, ssum, ssq, slots);
 }
 
 // The same row pass with its INPUT STREAM decoupled from the lanes that consume it (round 5).  fp_fwd_rows_kernel's nine lanes of a
@@ -622,16 +596,7 @@ __global__ __launch_bounds__(256, SN2_FR_OCC) void fp_fwd_rows2_kernel(int R, in
             const unsigned rr = valid ? (unsigned)row : 0u;
             const int i0 = valid ? __float_as_int(xw[3 * rl + 0]) : 0, i1 = valid ? __float_as_int(xw[3 * rl + 1]) : 0,
                       i2 = valid ? __float_as_int(xw[3 * rl + 2]) : 0;
-            const unsigned base = (rr / (unsigned)R_per_plot) * (unsigned)S_per_plot;
-#if defined(SN2_FR_DIAG) && (SN2_FR_DIAG & 2)
-            ta[u][0] = make_float4((float)(base + i0), 1.f, 2.f, 3.f);      // (diagnostic: no table gathers)
-            ta[u][1] = make_float4((float)i1, 1.f, 2.f, 3.f);
-            ta[u][2] = make_float4((float)i2, 1.f, 2.f, 3.f);
-#else
-            ta[u][0] = reinterpret_cast<const float4*>(T + (size_t)(base + i0) * HS)[q];
-            ta[u][1] = reinterpret_cast<const float4*>(T + (size_t)(base + i1) * HS)[q];
-            ta[u][2] = reinterpret_cast<const float4*>(T + (size_t)(base + i2) * HS)[q];
-#endif
+            fp_table_rows<HS>(T, (rr / (unsigned)R_per_plot) * (unsigned)S_per_plot, i0, i1, i2, q, ta[u]);
         }
     };
     auto compute = [&](int buf, int it, const float4 (&ta)[U][3]) {
@@ -713,20 +678,8 @@ __global__ __launch_bounds__(256, SN2_FR_OCC) void fp_fwd_rows2_kernel(int R, in
         for (int kb = 0; kb < n_blocks; ++kb) for_each_stage([&](auto S) { step(S, kb); }, Stages{});
     }
     if (!slots) return;
-    // batch statistics: per-lane partials -> LDS -> one slot per workgroup ([sum(C) | sumsq(C)], as stats_to_slot)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        s_part[t][threadIdx.x] = on ? ssum[t >> 1][t & 1] : 0.f;
-        s_part[4 + t][threadIdx.x] = on ? ssq[t >> 1][t & 1] : 0.f;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 2 * CO; e += 256) {
-        const int which = e / CO, c = e - which * CO, cq = c >> 2, ct = c & 3;
-        float acc = 0.f;
-        for (int w = 0; w < 4; ++w)
-            for (int gg = 0; gg < G; ++gg) acc += s_part[which * 4 + ct][w * 64 + cq + QH * gg];
-        slots[(size_t)blockIdx.x * 2 * CO + e] = acc;
-    }
+    const float s1[4] = {ssum[0][0], ssum[0][1], ssum[1][0], ssum[1][1]}, s2[4] = {ssq[0][0], ssq[0][1], ssq[1][0], ssq[1][1]};
+    row_quads_stats_to_slot<CO>(s_part, on, s1, s2, slots);
 }
 
 // Where the d pre-activation rows of the source-side backward live (du_scratch).  With 33 or 34 channels a 36-float row

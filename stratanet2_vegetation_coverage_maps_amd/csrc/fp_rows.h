@@ -1,6 +1,6 @@
 // fp_rows.h -- what the dense-row units share (fp.hip, head.hip, global_level.hip, global_level_bwd.hip, interp_index.hip): the accessors of a row of
-// per-point activations in either storage precision, the spelled-out interpolation arithmetic and the input stream of the
-// source-side row passes, the two source-table kernels with their launcher, the staging of a 64-row block's inputs, the host
+// per-point activations in either storage precision, the spelled-out interpolation arithmetic, the input stream and the
+// (row, quad) arithmetic of the source-side row passes (fp_table_rows, fp_row_quad), the two source-table kernels with their launcher, the staging of a 64-row block's inputs, the host
 // view of the inverted interpolation index, and the small host helpers of the dispatch code.  Templates are instantiated
 // where they are used.
 #pragma once
@@ -256,6 +256,65 @@ __device__ __forceinline__ FpRowIn<QB> fp_row_in(long row, bool on, int R, const
 #pragma unroll
     for (int b = 0; b < QB; ++b) in.sk[b] = reinterpret_cast<const float4*>(skip + (size_t)in.rr * skip_stride)[b];
     return in;
+}
+// quad q of the three table rows a row interpolates (rows of HS floats; base = the first source row of the row's plot)
+// (SN2_FR_DIAG: timing builds of the row passes, scripts/time_fp1.py -- 1 no stores, 2 no table gathers, 4 no skip contraction)
+template <int HS>
+__device__ __forceinline__ void fp_table_rows(const float* __restrict__ T, unsigned base, int i0, int i1, int i2, int q, float4 (&ta)[3]) {
+#if defined(SN2_FR_DIAG) && (SN2_FR_DIAG & 2)
+    ta[0] = make_float4((float)(base + i0), 1.f, 2.f, 3.f);      // (diagnostic: values made from the indices)
+    ta[1] = make_float4((float)i1, 1.f, 2.f, 3.f);
+    ta[2] = make_float4((float)i2, 1.f, 2.f, 3.f);
+#else
+    ta[0] = reinterpret_cast<const float4*>(T + (size_t)(base + i0) * HS)[q];
+    ta[1] = reinterpret_cast<const float4*>(T + (size_t)(base + i1) * HS)[q];
+    ta[2] = reinterpret_cast<const float4*>(T + (size_t)(base + i2) * HS)[q];
+#endif
+}
+// The row side of the source-side form for one (row, quad) lane, stated once for fp_fwd_rows_kernel and the two eval kernels of
+// head.hip (same operations in the same order: the same bits): the lane's skip weights W_B and bias, output channels 4 q .. 4 q + 3
+// (zero past CO), in registers for the whole kernel --
+template <int CB>
+struct FpQuadW {
+    float wB[4][CB], b4[4];
+};
+template <int CA, int CB, int CO>
+__device__ __forceinline__ FpQuadW<CB> fp_quad_w(const float* __restrict__ Wg, const float* __restrict__ biasg, int q) {
+    FpQuadW<CB> w;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int o = 4 * q + t;
+        w.b4[t] = o < CO ? biasg[o] : 0.f;
+#pragma unroll
+        for (int k = 0; k < CB; ++k) w.wB[t][k] = o < CO ? Wg[o * (CA + CB) + CA + k] : 0.f;
+    }
+    return w;
+}
+// -- and the quad itself: v = relu(interp_bias(table rows, 3-NN weights) + W_B skip), zero where the row is not valid or the
+// channel lies past CO
+template <int CB, int CO>
+__device__ __forceinline__ void fp_row_quad(const FpQuadW<CB>& w, const float4 (&ta)[3], float w0, float w1, float w2,
+                                            const float4 (&sk)[CB / 4], bool valid, int q, float (&v)[4]) {
+    const float inv = 1.0f / ((w0 + w1) + w2);
+    const float4 a = ta[0], b = ta[1], c = ta[2];
+    v[0] = interp_bias(a.x, b.x, c.x, w0, w1, w2, inv, w.b4[0]), v[1] = interp_bias(a.y, b.y, c.y, w0, w1, w2, inv, w.b4[1]);
+    v[2] = interp_bias(a.z, b.z, c.z, w0, w1, w2, inv, w.b4[2]), v[3] = interp_bias(a.w, b.w, c.w, w0, w1, w2, inv, w.b4[3]);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        float acc = v[t];
+#if defined(SN2_FR_DIAG) && (SN2_FR_DIAG & 4)
+        acc += sk[0].x + sk[CB / 4 - 1].w;          // (diagnostic: no skip contraction)
+#else
+#pragma unroll
+        for (int b2 = 0; b2 < CB / 4; ++b2) {
+            acc = fmaf(w.wB[t][4 * b2 + 0], sk[b2].x, acc);
+            acc = fmaf(w.wB[t][4 * b2 + 1], sk[b2].y, acc);
+            acc = fmaf(w.wB[t][4 * b2 + 2], sk[b2].z, acc);
+            acc = fmaf(w.wB[t][4 * b2 + 3], sk[b2].w, acc);
+        }
+#endif
+        v[t] = (valid && 4 * q + t < CO) ? fmaxf(acc, 0.f) : 0.f;
+    }
 }
 
 // The four waves of a 64-row workgroup build the rows' inputs [u | 1] together in LDS, s_q[64][QS]; wave g builds the rows

@@ -1,83 +1,14 @@
 // head.hip -- the pointwise head (lin1 -> ReLU -> dropout -> lin2 -> softmax x sigmoid) forward and backward on the matrix
 // cores, the eval kernels that fuse the per-point layer FP1 (source-side form) with the head, and the BatchNorm gradient sums
 // taken from the consumer's weight gradients.  Entry points: sn2_head_forward, sn2_fp_head_eval, sn2_head_bn_sums,
-// sn2_fp_bn_sums, sn2_head_backward.  Replaces the head of PointNet2.forward.  The rows' accessors, WAVE_LDS_SYNC, the row side's
-// input stream and the source table come from fp_rows.h.
+// sn2_fp_bn_sums, sn2_head_backward.  Replaces the head of PointNet2.forward.  The three forward kernels (head_fwd_mfma_kernel,
+// fp_head_eval_kernel, fp_head_eval2_kernel) fill a wave's LDS tile in their own way and share ONE head turn on it (HeadLaneW,
+// head_fwd_turn).  The rows' accessors, WAVE_LDS_SYNC, the row side's input stream and arithmetic (fp_row_quad, fp_table_rows)
+// and the source table come from fp_rows.h.
 #include "fp_rows.h"
 #include "loss_grad.h"
 
 namespace {
-
-struct HeadOut {
-    float y[35];   // fa*f+fc | 1
-    float z1[17];  // relu(lin1) | 1
-    float p[4];
-    float dens;
-};
-
-// drop_mask / drop_scale: F.dropout(relu(lin1), p) of model/point_net2.py:142 -- bit j of the row's word set = channel j kept
-// and scaled by 1/(1-p); drop_mask == nullptr: no dropout.  z1 holds the values lin2 reads (after the dropout).
-// fv: the row's nine float4 quads (36 floats, 34 used)
-template <class WP>
-__device__ __forceinline__ void head_row_v(const float4 (&fv)[9], WP fa, WP fc, WP W1, WP b1, WP W2, WP b2, size_t r,
-                                           HeadOut& o, const int* __restrict__ drop_mask = nullptr, float drop_scale = 1.f) {
-#pragma unroll
-    for (int q = 0; q < 9; ++q) {
-        const float4 v = fv[q];
-        const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (4 * q + t < 34) o.y[4 * q + t] = fmaf(fa[4 * q + t], vv[t], fc[4 * q + t]);
-    }
-    o.y[34] = 1.f;
-    // two accumulators per output (even / odd inputs): pairs of consecutive weights and inputs are packed FMAs
-    // (v_pk_fma_f32: 2 x the rate of the scalar-operand FMA; one chain per output left 544 of the kernel's 1250 unpacked)
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        f32x2 acc = {b1[j], 0.f};
-#pragma unroll
-        for (int k = 0; k < 34; k += 2) {
-            const f32x2 w = {W1[j * 34 + k], W1[j * 34 + k + 1]}, y2 = {o.y[k], o.y[k + 1]};
-            acc = __builtin_elementwise_fma(w, y2, acc);
-        }
-        o.z1[j] = fmaxf(acc[0] + acc[1], 0.f);
-    }
-    if (drop_mask) {
-        const int keep = drop_mask[r];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o.z1[j] = ((keep >> j) & 1) ? o.z1[j] * drop_scale : 0.f;
-    }
-    o.z1[16] = 1.f;
-    float s[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        float acc = b2[i];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc = fmaf(W2[i * 16 + j], o.z1[j], acc);
-        s[i] = acc;
-    }
-    const float m = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
-    float e[4], den = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        e[i] = expf(s[i] - m);
-        den += e[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o.p[i] = e[i] / den;
-    o.dens = 1.0f / (1.0f + expf(-s[4]));
-}
-
-template <bool BF = false, class WP = cfp>
-__device__ __forceinline__ void head_row(const float* __restrict__ f, int f_stride, WP fa, WP fc, WP W1, WP b1, WP W2,
-                                         WP b2, size_t r, HeadOut& o, const int* __restrict__ drop_mask = nullptr,
-                                         float drop_scale = 1.f) {
-    float4 fv[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) fv[q] = row_quad_ld<BF>(f, r, f_stride, q);
-    head_row_v(fv, fa, fc, W1, b1, W2, b2, r, o, drop_mask, drop_scale);
-}
 
 // a wave re-reads LDS words other lanes of the SAME wave wrote: the LDS executes a wave's instructions in order, the compiler
 // must not move the accesses across this point (the regions are reused under different element types)
@@ -93,7 +24,107 @@ constexpr int HEAD_T_QUADS = 64 * 9;   // a wave's 64 consecutive rows of 36 flo
 // form (24-28 us for 92 MB either way: the kernel streams at 3.3-3.8 TB/s and fp32 MFMA has the packed-VALU rate, 2 x the
 // scalar-operand FMA rate); it frees the VALU and scalar cache for whatever runs beside it.  The backward
 // (head_bwd_mfma_kernel, round 4) is built the same way.
-// workgroups per CU the kernel is compiled for = its register budget.  At 4 (128 VGPRs, one spilled) the compiler issued the nine
+// The three forward kernels differ in how the tile is filled -- head_fwd_mfma_kernel loads 64 stored rows, the eval kernels compute
+// 63 rows of FP1 into it --; what follows the WAVE_LDS_SYNC that publishes the tile is head_fwd_turn, stated once.
+
+// the head's weights of lane (n, kq) in the MFMA operand layout, in registers for the whole kernel: column n of W1^T and of W2^T
+// and the rows' affine (fa, fc) at the k indices 4 ks + kq of the lane's k-steps; the biases the accumulators start from
+struct HeadLaneW {
+    float w1[9], ak[9], ck[9], w2[4], bias1, bias2;
+};
+__device__ __forceinline__ HeadLaneW head_lane_w(const float* __restrict__ fa, const float* __restrict__ fc,
+                                                 const float* __restrict__ W1, const float* __restrict__ b1,
+                                                 const float* __restrict__ W2, const float* __restrict__ b2, int n, int kq) {
+    HeadLaneW hw;
+#pragma unroll
+    for (int ks = 0; ks < 9; ++ks) {
+        const int k = 4 * ks + kq;
+        hw.w1[ks] = k < 34 ? W1[n * 34 + k] : 0.f;
+        hw.ak[ks] = k < 34 ? fa[k] : 0.f;
+        hw.ck[ks] = k < 34 ? fc[k] : 0.f;
+    }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) hw.w2[ks] = n < 5 ? W2[n * 16 + 4 * ks + kq] : 0.f;
+    hw.bias1 = b1[n], hw.bias2 = n < 5 ? b2[n] : 0.f;
+    return hw;
+}
+
+// The head's turn on a wave's filled tile st [64][36] (rows r0 .. r0 + ROWS - 1 of R; the caller has published the tile with
+// WAVE_LDS_SYNC): lin1 -> ReLU (+ dropout) -> zt -> lin2 -> sc -> softmax, sigmoid, two float4 stores of the rows < ROWS.
+// drop_mask / drop_scale: F.dropout(relu(lin1), p) of model/point_net2.py:142 -- bit j of the row's word set = channel j kept and
+// scaled by 1/(1-p); a caller that passes nullptr (the eval kernels) compiles no dropout.
+template <int ROWS>
+__device__ __forceinline__ void head_fwd_turn(const HeadLaneW& hw, float* __restrict__ st, long r0, int R, float* __restrict__ cov,
+                                              float* __restrict__ proba, const int* __restrict__ drop_mask, float drop_scale) {
+    static_assert(ROWS > 0 && ROWS <= 64, "at most the tile's 64 rows");
+    const int lane = threadIdx.x & 63, n = lane & 15, kq = lane >> 4;
+    float* zt = st;                    // [64][20] after lin1 has read the rows
+    float* sc = st + 64 * 20;          // [64][8]
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        acc[t] = f32x4{hw.bias1, hw.bias1, hw.bias1, hw.bias1};
+#pragma unroll
+        for (int ks = 0; ks < 9; ++ks) {
+            const float v = st[(16 * t + n) * 36 + 4 * ks + kq];
+            const float a = (4 * ks + kq < 34) ? fmaf(hw.ak[ks], v, hw.ck[ks]) : 0.f;
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, hw.w1[ks], acc[t], 0, 0, 0);
+        }
+    }
+    WAVE_LDS_SYNC();
+    // acc[t][j]: row 16 t + 4 kq + j, hidden channel n
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = 16 * t + 4 * kq + j;
+            float z = fmaxf(acc[t][j], 0.f);
+            if (drop_mask) {
+                const long r = r0 + row;
+                const int keep = drop_mask[r < R ? r : R - 1];
+                z = ((keep >> n) & 1) ? z * drop_scale : 0.f;
+            }
+            zt[row * 20 + n] = z;
+        }
+    WAVE_LDS_SYNC();
+    f32x4 s2[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        s2[t] = f32x4{hw.bias2, hw.bias2, hw.bias2, hw.bias2};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+            s2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(zt[(16 * t + n) * 20 + 4 * ks + kq], hw.w2[ks], s2[t], 0, 0, 0);
+    }
+    if (n < 8) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sc[(16 * t + 4 * kq + j) * 8 + n] = s2[t][j];
+    }
+    WAVE_LDS_SYNC();
+    const long r = r0 + lane;
+    const float4 s03 = *reinterpret_cast<const float4*>(&sc[lane * 8]);
+    const float s4 = sc[lane * 8 + 4];
+    WAVE_LDS_SYNC();
+    const float sv[4] = {s03.x, s03.y, s03.z, s03.w};
+    const float m = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
+    float e[4], den = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        e[i] = expf(sv[i] - m);
+        den += e[i];
+    }
+    float pr[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pr[i] = e[i] / den;
+    const float dens = 1.0f / (1.0f + expf(-s4));
+    if ((ROWS == 64 || lane < ROWS) && r < R) {
+        reinterpret_cast<float4*>(proba)[r] = make_float4(pr[0], pr[1], pr[2], pr[3]);
+        reinterpret_cast<float4*>(cov)[r] = make_float4(pr[0] * dens, pr[1] * dens, pr[2] * dens, pr[3] * dens);
+    }
+}
+
+// workgroups per CU head_fwd_mfma_kernel is compiled for = its register budget.  At 4 (128 VGPRs, one spilled) the compiler issued the nine
 // row loads of a turn ONE BY ONE, each behind an s_waitcnt vmcnt(0) of its own (every load into the same four registers): 23.4 us
 // at config 2; at 3 / 2 the loads are in flight together: 22.3 / 22.1 us (scripts/time_head_fwd.py)
 #ifndef SN2_HF_OCC
@@ -113,21 +144,7 @@ __global__ __launch_bounds__(256, SN2_HF_OCC) void head_fwd_mfma_kernel(int R, c
         for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nzero4; i += (long)gridDim.x * 256) zero4[i] = float4{0.f, 0.f, 0.f, 0.f};
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float4* st4 = s_t + wave * HEAD_T_QUADS;
-    float* st = reinterpret_cast<float*>(st4);
-    float* zt = st;                    // [64][20] after lin1 has read the rows
-    float* sc = st + 64 * 20;          // [64][8]
-    const int n = lane & 15, kq = lane >> 4;
-    float w1[9], ak[9], ck[9], w2[4];
-#pragma unroll
-    for (int ks = 0; ks < 9; ++ks) {
-        const int k = 4 * ks + kq;
-        w1[ks] = k < 34 ? W1[n * 34 + k] : 0.f;
-        ak[ks] = k < 34 ? fa[k] : 0.f;
-        ck[ks] = k < 34 ? fc[k] : 0.f;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) w2[ks] = n < 5 ? W2[n * 16 + 4 * ks + kq] : 0.f;
-    const float bias1 = b1[n], bias2 = n < 5 ? b2[n] : 0.f;
+    const HeadLaneW hw = head_lane_w(fa, fc, W1, b1, W2, b2, lane & 15, lane >> 4);
     for (long r0 = ((long)blockIdx.x * 4 + wave) * 64; r0 < R; r0 += (long)gridDim.x * 256) {
         {
             const long lim = (R - r0) * 9;
@@ -144,76 +161,15 @@ __global__ __launch_bounds__(256, SN2_HF_OCC) void head_fwd_mfma_kernel(int R, c
             for (int k = 0; k < 9; ++k) st4[lane + 64 * k] = t[k];
         }
         WAVE_LDS_SYNC();
-        f32x4 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            acc[t] = f32x4{bias1, bias1, bias1, bias1};
-#pragma unroll
-            for (int ks = 0; ks < 9; ++ks) {
-                const float v = st[(16 * t + n) * 36 + 4 * ks + kq];
-                const float a = (4 * ks + kq < 34) ? fmaf(ak[ks], v, ck[ks]) : 0.f;
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w1[ks], acc[t], 0, 0, 0);
-            }
-        }
-        WAVE_LDS_SYNC();
-        // acc[t][j]: row 16 t + 4 kq + j, hidden channel n
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = 16 * t + 4 * kq + j;
-                float z = fmaxf(acc[t][j], 0.f);
-                if (drop_mask) {
-                    const long r = r0 + row;
-                    const int keep = drop_mask[r < R ? r : R - 1];
-                    z = ((keep >> n) & 1) ? z * drop_scale : 0.f;
-                }
-                zt[row * 20 + n] = z;
-            }
-        WAVE_LDS_SYNC();
-        f32x4 s2[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            s2[t] = f32x4{bias2, bias2, bias2, bias2};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                s2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(zt[(16 * t + n) * 20 + 4 * ks + kq], w2[ks], s2[t], 0, 0, 0);
-        }
-        if (n < 8) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sc[(16 * t + 4 * kq + j) * 8 + n] = s2[t][j];
-        }
-        WAVE_LDS_SYNC();
-        const long r = r0 + lane;
-        const float4 s03 = *reinterpret_cast<const float4*>(&sc[lane * 8]);
-        const float s4 = sc[lane * 8 + 4];
-        WAVE_LDS_SYNC();
-        const float sv[4] = {s03.x, s03.y, s03.z, s03.w};
-        const float m = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
-        float e[4], den = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            e[i] = expf(sv[i] - m);
-            den += e[i];
-        }
-        float pr[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pr[i] = e[i] / den;
-        const float dens = 1.0f / (1.0f + expf(-s4));
-        if (r < R) {
-            reinterpret_cast<float4*>(proba)[r] = make_float4(pr[0], pr[1], pr[2], pr[3]);
-            reinterpret_cast<float4*>(cov)[r] = make_float4(pr[0] * dens, pr[1] * dens, pr[2] * dens, pr[3] * dens);
-        }
+        head_fwd_turn<64>(hw, reinterpret_cast<float*>(st4), r0, R, cov, proba, drop_mask, drop_scale);
     }
 }
 
 // EVAL: the per-point layer FP1 (source-side form: fp_fwd_rows_kernel's row side) and the head in ONE kernel.  An eval pass keeps
 // nothing for a backward, so the 144-byte rows of h1 need not exist: a wave computes 63 consecutive rows (nine groups of seven,
 // nine lanes per row as in fp_fwd_rows_kernel) straight into the LDS tile head_fwd_mfma_kernel reads its rows from, and runs
-// that kernel's turn on it (row 63 of the tile is padding).  Same operations in the same order as the two kernels: the same
-// bits.  Saves the write and the read of h1 (parcel inference: 740 MB per launch of 256 plots) and a launch.
+// that kernel's turn on it (row 63 of the tile is padding).  The row side (fp_table_rows, fp_row_quad) and the turn (head_fwd_turn)
+// are the device functions the two kernels call -- the same operations in the same order: the same bits.  Saves the write and the read of h1 (parcel inference: 740 MB per launch of 256 plots) and a launch.
 template <int CA, int CB, int CO>
 __global__ __launch_bounds__(256, 2) void fp_head_eval_kernel(int R, int R_per_plot, int S_per_plot, int skip_stride,
                                                               const float* __restrict__ T, const int* __restrict__ knn_idx,
@@ -223,38 +179,17 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval_kernel(int R, int R_per_p
                                                               const float* __restrict__ W1, const float* __restrict__ b1,
                                                               const float* __restrict__ W2, const float* __restrict__ b2,
                                                               float* __restrict__ cov, float* __restrict__ proba) {
-    constexpr int CI = CA + CB, QH = (CO + 3) / 4, HS = 4 * QH, G = 64 / QH, QB = CB / 4, U = 3, ROWS = G * 9;
+    constexpr int QH = (CO + 3) / 4, HS = 4 * QH, G = 64 / QH, QB = CB / 4, U = 3, ROWS = G * 9;
     static_assert(CO == 34 && HS == 36 && G == 7 && ROWS == 63, "the head reads rows of 36 floats, 63 per turn");
     static_assert(CB > 0 && CB % 4 == 0, "skip quads");
     __shared__ float4 s_t[4 * HEAD_T_QUADS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float4* st4 = s_t + wave * HEAD_T_QUADS;
-    float* st = reinterpret_cast<float*>(st4);
-    float* zt = st;                    // [64][20] after lin1 has read the rows
-    float* sc = st + 64 * 20;          // [64][8]
     const int q = lane % QH, g = lane / QH;
     const bool on = lane < G * QH;
-    const int n = lane & 15, kq = lane >> 4;
     // the row side's weights (fp_fwd_rows_kernel) and the head's (head_fwd_mfma_kernel), in registers for the whole kernel
-    float wB[4][CB], b4[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int o = 4 * q + t;
-        b4[t] = o < CO ? biasg[o] : 0.f;
-#pragma unroll
-        for (int k = 0; k < CB; ++k) wB[t][k] = o < CO ? Wg[o * CI + CA + k] : 0.f;
-    }
-    float w1[9], ak[9], ck[9], w2[4];
-#pragma unroll
-    for (int ks = 0; ks < 9; ++ks) {
-        const int k = 4 * ks + kq;
-        w1[ks] = k < 34 ? W1[n * 34 + k] : 0.f;
-        ak[ks] = k < 34 ? fa[k] : 0.f;
-        ck[ks] = k < 34 ? fc[k] : 0.f;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) w2[ks] = n < 5 ? W2[n * 16 + 4 * ks + kq] : 0.f;
-    const float bias1 = b1[n], bias2 = n < 5 ? b2[n] : 0.f;
+    const FpQuadW<CB> fw = fp_quad_w<CA, CB, CO>(Wg, biasg, q);
+    const HeadLaneW hw = head_lane_w(fa, fc, W1, b1, W2, b2, lane & 15, lane >> 4);
     const long n_turns = ((long)R + ROWS - 1) / ROWS;
     for (long turn = (long)blockIdx.x * 4 + wave; turn < n_turns; turn += (long)gridDim.x * 4) {
         const long r0 = turn * ROWS;
@@ -266,90 +201,19 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval_kernel(int R, int R_per_p
 #pragma unroll
             for (int u = 0; u < U; ++u) in[u] = fp_row_in<QB>(r0 + (long)(g0 + u) * G + g, on, R, knn_idx, knn_w, skip, skip_stride);
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const unsigned base = (in[u].rr / (unsigned)R_per_plot) * (unsigned)S_per_plot;
-                ta[u][0] = reinterpret_cast<const float4*>(T + (size_t)(base + in[u].i0) * HS)[q];
-                ta[u][1] = reinterpret_cast<const float4*>(T + (size_t)(base + in[u].i1) * HS)[q];
-                ta[u][2] = reinterpret_cast<const float4*>(T + (size_t)(base + in[u].i2) * HS)[q];
-            }
+            for (int u = 0; u < U; ++u)
+                fp_table_rows<HS>(T, (in[u].rr / (unsigned)R_per_plot) * (unsigned)S_per_plot, in[u].i0, in[u].i1, in[u].i2, q, ta[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const float w0 = in[u].w0, wa = in[u].w1, wb = in[u].w2;
-                const float inv = 1.0f / ((w0 + wa) + wb);
-                const float4 a = ta[u][0], b = ta[u][1], c = ta[u][2];
-                // (interp_bias: the one spelled-out order of operations of the row kernels -- the same bits as the separate pass)
-                float v[4] = {interp_bias(a.x, b.x, c.x, w0, wa, wb, inv, b4[0]), interp_bias(a.y, b.y, c.y, w0, wa, wb, inv, b4[1]),
-                              interp_bias(a.z, b.z, c.z, w0, wa, wb, inv, b4[2]), interp_bias(a.w, b.w, c.w, w0, wa, wb, inv, b4[3])};
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    float acc = v[t];
-#pragma unroll
-                    for (int b2q = 0; b2q < QB; ++b2q) {
-                        acc = fmaf(wB[t][4 * b2q + 0], in[u].sk[b2q].x, acc);
-                        acc = fmaf(wB[t][4 * b2q + 1], in[u].sk[b2q].y, acc);
-                        acc = fmaf(wB[t][4 * b2q + 2], in[u].sk[b2q].z, acc);
-                        acc = fmaf(wB[t][4 * b2q + 3], in[u].sk[b2q].w, acc);
-                    }
-                    v[t] = (in[u].valid && 4 * q + t < CO) ? fmaxf(acc, 0.f) : 0.f;
-                }
+                float v[4];
+                fp_row_quad<CB, CO>(fw, ta[u], in[u].w0, in[u].w1, in[u].w2, in[u].sk, in[u].valid, q, v);
                 if (on) st4[((g0 + u) * G + g) * QH + q] = make_float4(v[0], v[1], v[2], v[3]);
             }
         }
         if (lane < QH) st4[ROWS * QH + lane] = make_float4(0.f, 0.f, 0.f, 0.f);      // row 63: padding
         WAVE_LDS_SYNC();
-        // ---- the head on the tile: head_fwd_mfma_kernel's turn
-        f32x4 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            acc[t] = f32x4{bias1, bias1, bias1, bias1};
-#pragma unroll
-            for (int ks = 0; ks < 9; ++ks) {
-                const float v = st[(16 * t + n) * 36 + 4 * ks + kq];
-                const float a = (4 * ks + kq < 34) ? fmaf(ak[ks], v, ck[ks]) : 0.f;
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w1[ks], acc[t], 0, 0, 0);
-            }
-        }
-        WAVE_LDS_SYNC();
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) zt[(16 * t + 4 * kq + j) * 20 + n] = fmaxf(acc[t][j], 0.f);
-        WAVE_LDS_SYNC();
-        f32x4 s2[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            s2[t] = f32x4{bias2, bias2, bias2, bias2};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                s2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(zt[(16 * t + n) * 20 + 4 * ks + kq], w2[ks], s2[t], 0, 0, 0);
-        }
-        if (n < 8) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sc[(16 * t + 4 * kq + j) * 8 + n] = s2[t][j];
-        }
-        WAVE_LDS_SYNC();
-        const long r = r0 + lane;
-        const float4 s03 = *reinterpret_cast<const float4*>(&sc[lane * 8]);
-        const float s4 = sc[lane * 8 + 4];
-        WAVE_LDS_SYNC();
-        const float sv[4] = {s03.x, s03.y, s03.z, s03.w};
-        const float m = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
-        float e[4], den = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            e[i] = expf(sv[i] - m);
-            den += e[i];
-        }
-        float pr[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pr[i] = e[i] / den;
-        const float dens = 1.0f / (1.0f + expf(-s4));
-        if (lane < ROWS && r < R) {
-            reinterpret_cast<float4*>(proba)[r] = make_float4(pr[0], pr[1], pr[2], pr[3]);
-            reinterpret_cast<float4*>(cov)[r] = make_float4(pr[0] * dens, pr[1] * dens, pr[2] * dens, pr[3] * dens);
-        }
+        // ---- the head on the tile
+        head_fwd_turn<ROWS>(hw, reinterpret_cast<float*>(st4), r0, R, cov, proba, nullptr, 1.f);
     }
 }
 
@@ -370,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
                                                                const float* __restrict__ W1, const float* __restrict__ b1,
                                                                const float* __restrict__ W2, const float* __restrict__ b2,
                                                                float* __restrict__ cov, float* __restrict__ proba) {
-    constexpr int CI = CA + CB, QH = (CO + 3) / 4, HS = 4 * QH, G = 64 / QH, QB = CB / 4, U = 3, ROWS = G * 9;
+    constexpr int QH = (CO + 3) / 4, HS = 4 * QH, G = 64 / QH, QB = CB / 4, U = 3, ROWS = G * 9;
     static_assert(CO == 34 && HS == 36 && G == 7 && ROWS == 63, "the head reads rows of 36 floats, 63 per turn");
     static_assert(CB > 0 && CB % 4 == 0 && QB == 2, "two skip quads per row: 126 quads per turn = two per lane");
     constexpr int XW = 3 * ROWS + 3 * ROWS + 4 * ROWS * QB + 2;                // idx | w | skip quads (16-byte aligned: 378 % 4 = 2 -> +2)
@@ -381,32 +245,11 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
     __shared__ __attribute__((aligned(16))) float s_x[4][(XW + 3) / 4 * 4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float4* st4 = s_t + wave * HEAD_T_QUADS;
-    float* st = reinterpret_cast<float*>(st4);
-    float* zt = st;                    // [64][20] after lin1 has read the rows
-    float* sc = st + 64 * 20;          // [64][8]
     float* xw = s_x[wave];
     const int q = lane % QH, g = lane / QH;
     const bool on = lane < G * QH;
-    const int n = lane & 15, kq = lane >> 4;
-    float wB[4][CB], b4[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int o = 4 * q + t;
-        b4[t] = o < CO ? biasg[o] : 0.f;
-#pragma unroll
-        for (int k = 0; k < CB; ++k) wB[t][k] = o < CO ? Wg[o * CI + CA + k] : 0.f;
-    }
-    float w1[9], ak[9], ck[9], w2[4];
-#pragma unroll
-    for (int ks = 0; ks < 9; ++ks) {
-        const int k = 4 * ks + kq;
-        w1[ks] = k < 34 ? W1[n * 34 + k] : 0.f;
-        ak[ks] = k < 34 ? fa[k] : 0.f;
-        ck[ks] = k < 34 ? fc[k] : 0.f;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) w2[ks] = n < 5 ? W2[n * 16 + 4 * ks + kq] : 0.f;
-    const float bias1 = b1[n], bias2 = n < 5 ? b2[n] : 0.f;
+    const FpQuadW<CB> fw = fp_quad_w<CA, CB, CO>(Wg, biasg, q);
+    const HeadLaneW hw = head_lane_w(fa, fc, W1, b1, W2, b2, lane & 15, lane >> 4);
     const int n_turns = (R + ROWS - 1) / ROWS;
     const RowIters ri = row_iters(n_turns, wave);
     // ---- a turn's inputs, one element per lane and load, unconditional from clamped addresses
@@ -454,10 +297,7 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
             const unsigned rr = valid ? (unsigned)row : 0u;
             const int i0 = valid ? __float_as_int(xw[3 * rl + 0]) : 0, i1 = valid ? __float_as_int(xw[3 * rl + 1]) : 0,
                       i2 = valid ? __float_as_int(xw[3 * rl + 2]) : 0;
-            const unsigned base = (rr / (unsigned)R_per_plot) * (unsigned)S_per_plot;
-            ta[u][0] = reinterpret_cast<const float4*>(T + (size_t)(base + i0) * HS)[q];
-            ta[u][1] = reinterpret_cast<const float4*>(T + (size_t)(base + i1) * HS)[q];
-            ta[u][2] = reinterpret_cast<const float4*>(T + (size_t)(base + i2) * HS)[q];
+            fp_table_rows<HS>(T, (rr / (unsigned)R_per_plot) * (unsigned)S_per_plot, i0, i1, i2, q, ta[u]);
         }
     };
     auto rows_of = [&](int turn, int bt, const float4 (&ta)[U][3]) {
@@ -466,26 +306,11 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
             const int rl = on ? (3 * bt + u) * G + g : 0;
             const int row = turn * ROWS + rl;
             const bool valid = on && row < R;
-            const float w0 = xw[XO_W + 3 * rl + 0], wa = xw[XO_W + 3 * rl + 1], wb = xw[XO_W + 3 * rl + 2];
             float4 sk[QB];
 #pragma unroll
             for (int b = 0; b < QB; ++b) sk[b] = reinterpret_cast<const float4*>(xw + XO_S)[rl * QB + b];
-            const float inv = 1.0f / ((w0 + wa) + wb);
-            const float4 a = ta[u][0], b = ta[u][1], c = ta[u][2];
-            float v[4] = {interp_bias(a.x, b.x, c.x, w0, wa, wb, inv, b4[0]), interp_bias(a.y, b.y, c.y, w0, wa, wb, inv, b4[1]),
-                          interp_bias(a.z, b.z, c.z, w0, wa, wb, inv, b4[2]), interp_bias(a.w, b.w, c.w, w0, wa, wb, inv, b4[3])};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                float acc = v[t];
-#pragma unroll
-                for (int b2q = 0; b2q < QB; ++b2q) {
-                    acc = fmaf(wB[t][4 * b2q + 0], sk[b2q].x, acc);
-                    acc = fmaf(wB[t][4 * b2q + 1], sk[b2q].y, acc);
-                    acc = fmaf(wB[t][4 * b2q + 2], sk[b2q].z, acc);
-                    acc = fmaf(wB[t][4 * b2q + 3], sk[b2q].w, acc);
-                }
-                v[t] = (valid && 4 * q + t < CO) ? fmaxf(acc, 0.f) : 0.f;
-            }
+            float v[4];
+            fp_row_quad<CB, CO>(fw, ta[u], xw[XO_W + 3 * rl + 0], xw[XO_W + 3 * rl + 1], xw[XO_W + 3 * rl + 2], sk, valid, q, v);
             if (on) st4[((3 * bt + u) * G + g) * QH + q] = make_float4(v[0], v[1], v[2], v[3]);
         }
     };
@@ -504,59 +329,8 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
         if (lane < QH) st4[ROWS * QH + lane] = make_float4(0.f, 0.f, 0.f, 0.f);      // row 63: padding
         WAVE_LDS_SYNC();
         fetch(turn + ri.stride);                              // the NEXT turn's inputs travel while the head runs (clamped past the end)
-        // ---- the head on the tile: head_fwd_mfma_kernel's turn
-        f32x4 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            acc[t] = f32x4{bias1, bias1, bias1, bias1};
-#pragma unroll
-            for (int ks = 0; ks < 9; ++ks) {
-                const float v = st[(16 * t + n) * 36 + 4 * ks + kq];
-                const float a = (4 * ks + kq < 34) ? fmaf(ak[ks], v, ck[ks]) : 0.f;
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w1[ks], acc[t], 0, 0, 0);
-            }
-        }
-        WAVE_LDS_SYNC();
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) zt[(16 * t + 4 * kq + j) * 20 + n] = fmaxf(acc[t][j], 0.f);
-        WAVE_LDS_SYNC();
-        f32x4 s2[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            s2[t] = f32x4{bias2, bias2, bias2, bias2};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                s2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(zt[(16 * t + n) * 20 + 4 * ks + kq], w2[ks], s2[t], 0, 0, 0);
-        }
-        if (n < 8) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sc[(16 * t + 4 * kq + j) * 8 + n] = s2[t][j];
-        }
-        WAVE_LDS_SYNC();
-        const long r = r0 + lane;
-        const float4 s03 = *reinterpret_cast<const float4*>(&sc[lane * 8]);
-        const float s4 = sc[lane * 8 + 4];
-        WAVE_LDS_SYNC();
-        const float sv[4] = {s03.x, s03.y, s03.z, s03.w};
-        const float m = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
-        float e[4], den = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            e[i] = expf(sv[i] - m);
-            den += e[i];
-        }
-        float pr[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pr[i] = e[i] / den;
-        const float dens = 1.0f / (1.0f + expf(-s4));
-        if (lane < ROWS && r < R) {
-            reinterpret_cast<float4*>(proba)[r] = make_float4(pr[0], pr[1], pr[2], pr[3]);
-            reinterpret_cast<float4*>(cov)[r] = make_float4(pr[0] * dens, pr[1] * dens, pr[2] * dens, pr[3] * dens);
-        }
+        // ---- the head on the tile
+        head_fwd_turn<ROWS>(hw, reinterpret_cast<float*>(st4), r0, R, cov, proba, nullptr, 1.f);
     }
 }
 

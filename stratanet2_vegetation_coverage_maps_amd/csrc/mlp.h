@@ -55,8 +55,6 @@ __device__ __forceinline__ f32x4 contract(f32x4 acc, FA a, FB b) {
     return acc;
 }
 
-// out[o] = (relu) ( b[o] + sum_k W[o*CI+k] * in[k] ).  W, b are wave-uniform constant-address-space pointers (common.h):
-// the loads are s_load_dwordx* and the FMAs take SGPR operands.
 // ---- BatchNorm1d from the sums of a batch (torch defaults: eps 1e-5, momentum 0.1, biased variance to normalise, unbiased
 // variance into running_var -- model/point_net2.py:45-53): one channel.  Used by bn_finalize_kernel (misc.hip) and by the
 // kernels that finalise their own statistics (global_level.hip: global_level_fwd_kernel).
@@ -78,6 +76,8 @@ __device__ __forceinline__ void sn2_bn_from_sums(double s1, double s2, double n,
     c = beta - mean * a;
 }
 
+// out[o] = (relu) ( b[o] + sum_k W[o*CI+k] * in[k] ).  W, b are wave-uniform constant-address-space pointers (common.h):
+// the loads are s_load_dwordx* and the FMAs take SGPR operands.
 template <int CI, int CO, bool RELU>
 __device__ __forceinline__ void dense(cfp W, cfp b, const float (&in)[CI], float (&out)[CO]) {
 #pragma unroll
