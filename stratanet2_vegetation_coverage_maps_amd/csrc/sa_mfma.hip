@@ -138,7 +138,9 @@ __device__ __forceinline__ bool sa_item(SaItem& it, const int* __restrict__ orde
             it.ln[t] = it.ln[t] >= 0 ? cn[t] : -1;
             it.nmax = max(it.nmax, __builtin_amdgcn_readfirstlane(it.ln[t]));
         }
-        return it.nmax > 0;
+        // (a quad of four EMPTY centroids is still an item: no step runs, but the forward owes its rows ext = 0 / arg = -1 /
+        // out = 0 -- with a table the HEX item that carries them does that.  Skipped as "empty", the rows kept what was there.)
+        return true;
     }
     // turn qi -> (plot b, item k): the plots are taken G at a time (all of them when they are few), the items of a group
     // interleaved heaviest first; the SOLO / QUAD items of all groups come before the packed ones.  (The table itself keeps
