@@ -1,5 +1,12 @@
-// sa_mfma.hip -- set-abstraction FORWARD passes with the shared MLP on the matrix cores.
-// (PointConv(local_nn) message + max aggregation, /root/reference/model/point_net2.py:19,21-29.)
+// sa_mfma.hip -- set-abstraction FORWARD and BACKWARD passes with the shared MLP on the matrix cores.
+// (PointConv(local_nn) message + max aggregation, model/point_net2.py:19,21-29 of the reference.)
+//
+// Two kernels, sa_mfma_fwd_kernel and sa_mfma_bwd_kernel; the backward recomputes the forward, and what the two have in common --
+// the MESSAGE TURN -- stands once, in front of both: the level's geometry (SaGeom; sa_geom / sa_grid on the host), the operand
+// registers of the two layers (SaL1W / sa_l1_w, SaL2W / sa_l2_w), the walk over the work items (sa_first, sa_item, sa_walk), a
+// step's loads with layer 1 (SaStep; sa_first_idx, sa_step_l1) and block 0's affine with layer 2 (sa_affine_l2).  The kernels keep
+// what is their own: statistics and the signed extremum (forward); BatchNorm backward, input gradients and the weight-gradient
+// contraction over LDS images (backward).
 //
 // Layout: one wave per work item (sn2_sa_order), 64 messages per step = 4 tiles of 16.  A SOLO item is one centroid with a
 // long list: tile t takes messages e0 + 16 t + c, 64 per step.  A QUAD item is four centroids with short lists of similar
@@ -25,10 +32,15 @@
 
 namespace {
 
-struct SaFwdArgs {
+// the level's geometry, the same for every pass of both directions (sa_geom fills it)
+struct SaGeom {
     int B, Nsrc, M, cap, feat_stride, spos_stride, group;
     const float *feat, *spos, *cpos;
     const int *nbr, *cnt, *order;
+};
+
+struct SaFwdArgs {
+    SaGeom g;
     const float *W0, *b0, *a0, *c0, *gamma0;
     const float *W1, *b1, *gamma1;
     float *slots;  // statistics slots of the block this pass measures, or nullptr
@@ -41,20 +53,6 @@ struct SaFwdArgs {
 };
 
 // every lane ends up with the reduction over its DPP row (16 lanes)
-__device__ __forceinline__ float row_max(float v) {
-    v = fmaxf(v, __int_as_float(SN2_DPP(__float_as_int(v), 0xB1, 0xF)));
-    v = fmaxf(v, __int_as_float(SN2_DPP(__float_as_int(v), 0x4E, 0xF)));
-    v = fmaxf(v, __int_as_float(SN2_DPP(__float_as_int(v), 0x141, 0xF)));
-    v = fmaxf(v, __int_as_float(SN2_DPP(__float_as_int(v), 0x140, 0xF)));
-    return v;
-}
-__device__ __forceinline__ unsigned row_min_u32(unsigned v) {
-    v = min(v, (unsigned)SN2_DPP((int)v, 0xB1, 0xF));
-    v = min(v, (unsigned)SN2_DPP((int)v, 0x4E, 0xF));
-    v = min(v, (unsigned)SN2_DPP((int)v, 0x141, 0xF));
-    v = min(v, (unsigned)SN2_DPP((int)v, 0x140, 0xF));
-    return v;
-}
 __device__ __forceinline__ float row_sum(float v) {
     v += __int_as_float(SN2_DPP(__float_as_int(v), 0xB1, 0xF));
     v += __int_as_float(SN2_DPP(__float_as_int(v), 0x4E, 0xF));
@@ -90,9 +88,11 @@ struct SaFirst {
     int nA, nB;
     int rec[4];
 };
-__device__ __forceinline__ SaFirst sa_first(const int* __restrict__ order, const int* __restrict__ fallback, int B, int M, int wave) {
+__device__ __forceinline__ SaFirst sa_first(const SaGeom& g, int wave) {
     SaFirst f;
-    const int ncent = B * M;
+    const int* __restrict__ order = g.order;
+    const int* __restrict__ fallback = g.cnt;
+    const int B = g.B, M = g.M, ncent = B * M;
     const int* trailer = order ? order + (size_t)4 * ncent + (size_t)16 * B * SN2_SA_PACKED_ITEMS(M) : nullptr;
     const int* base = order ? order : fallback;                // (unconditional loads: a valid address either way)
     const int* tr = trailer ? trailer : fallback;
@@ -186,6 +186,172 @@ __device__ __forceinline__ bool sa_item(SaItem& it, const int* __restrict__ orde
     return it.nmax > 0;
 }
 
+// The walk of a wave over its work items: body(it) for every position of the wave that is not empty.
+template <class Body>
+__device__ __forceinline__ void sa_walk(const SaGeom& g, const SaFirst& first, int wave, int nwaves, int c, Body&& body) {
+    // positions of the order table: nA per plot for SOLO / QUAD items, then nB per plot for the packed ones (OCT / HEX)
+    const int nA = first.nA, nB = first.nB;
+    const int G = g.group > 0 && g.group < g.B ? g.group : g.B;
+    const int nitems = g.order ? (nA + nB) * G * ((g.B + G - 1) / G) : (g.B * g.M + 3) >> 2;
+    // items are ordered heaviest first: the waves take them in a snake (round 0: item w, round 1: item 2W-1-w, ...), so the
+    // wave with the longest item of a round gets the shortest of the next.  (A shared work counter was tried: 8000 atomics
+    // on one address cost more than the imbalance they removed.  Round 5: dealing the positions so that an XCD's waves take
+    // the items of TWO of the sixteen plots -- 3 MB of feature rows per L2 instead of four plots' 6 MB on two XCDs each --
+    // made all six SA kernels 1-4 % slower: whole plots per XCD are not equal work.)
+    for (int round = 0;; ++round) {
+        const int qi = round * nwaves + ((round & 1) ? nwaves - 1 - wave : wave);
+        if (round * nwaves >= nitems) break;
+        if (qi >= nitems) continue;
+        SaItem it;
+        if (!sa_item(it, g.order, g.cnt, g.B, g.M, nA, nB, G, qi, c, round == 0 ? first.rec : nullptr)) continue;      // an empty position
+        body(it);
+    }
+}
+
+// ---- operand registers, loaded once per kernel (lane = (q, c))
+// Layer 1: W0 as A operands.  The bias of the first layer rides in the weight matrix against the constant-1 column of the gathered
+// input -- in fp32.  With bf16 operands it stays OUT of the contraction (it would be rounded to bfloat16) and starts the accumulator.
+template <int CF, int C1>
+struct SaL1W {
+    float A[C1 / 16][CF / 4 + 1], bias[C1 / 16][4];
+};
+template <int CF, int C1, bool BF16>
+__device__ __forceinline__ SaL1W<CF, C1> sa_l1_w(const float* __restrict__ W0, const float* __restrict__ b0, int q, int c) {
+    constexpr int CIN = CF + 3;
+    SaL1W<CF, C1> w;
+#pragma unroll
+    for (int io = 0; io < C1 / 16; ++io) {
+#pragma unroll
+        for (int kb = 0; kb < CF / 4 + 1; ++kb) {
+            const int k = 4 * kb + q, o = 16 * io + c;
+            w.A[io][kb] = k < CIN ? W0[o * CIN + k] : ((k == CIN && !BF16) ? b0[o] : 0.f);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w.bias[io][r] = BF16 ? b0[16 * io + 4 * q + r] : 0.f;
+    }
+    return w;
+}
+// Layer 2 (nl == 2): W1 pre-permuted to take layer 1's result tile as its B operand, its bias (the accumulator start), and block
+// 0's BatchNorm affine (a1, c1) on this lane's four channels of every tile
+template <int C1, int C2>
+struct SaL2W {
+    float A[C2 / 16][C1 / 16][4], bias[C2 / 16][4], a1[C1 / 16][4], c1[C1 / 16][4];
+};
+template <int C1, int C2>
+__device__ __forceinline__ SaL2W<C1, C2> sa_l2_w(const float* __restrict__ W1, const float* __restrict__ b1,
+                                                 const float* __restrict__ a0, const float* __restrict__ c0, int q, int c) {
+    SaL2W<C1, C2> w;
+#pragma unroll
+    for (int io = 0; io < C2 / 16; ++io) {
+#pragma unroll
+        for (int is = 0; is < C1 / 16; ++is)
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) w.A[io][is][kb] = W1[(16 * io + c) * C1 + 16 * is + 4 * q + kb];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w.bias[io][r] = b1[16 * io + 4 * q + r];
+    }
+#pragma unroll
+    for (int is = 0; is < C1 / 16; ++is)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            w.a1[is][r] = a0[16 * is + 4 * q + r];
+            w.c1[is][r] = c0[16 * is + 4 * q + r];
+        }
+    return w;
+}
+
+// ---- a step of an item: 64 messages, 4 tiles of 16
+// What layer 1 leaves of a step: the ReLU'd result tiles D1, whether slot (t, c) is a message of its list (val), and -- for the
+// backward, which contracts and scatters with them -- the gathered B operand bk ([feat | pos_j - pos_i | 1] at k = 4 kb + q) and the
+// source rows.
+template <int CF, int C1>
+struct SaStep {
+    f32x4 D1[C1 / 16][4];
+    float bk[4][CF / 4 + 1];
+    size_t rows[4];
+    bool val[4];
+};
+// the neighbour indices of a step are fetched one step ahead: index load -> row gather -> MFMA chain is what a step waits for, and
+// the first link does not depend on the step before.  The FIRST step's indices are requested together with the counts (the address
+// needs the centroid only; entries past the count are masked afterwards)
+__device__ __forceinline__ void sa_first_idx(const SaGeom& g, const SaItem& it, int (&jn)[4]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int e = it.le0 + it.eoff * t;
+        jn[t] = g.nbr[(size_t)it.lc[t] * g.cap + (e < g.cap ? e : 0)];     // (unconditional: masked below)
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) jn[t] = it.le0 + it.eoff * t < it.ln[t] ? jn[t] : 0;
+}
+// The step at entry e0: jn holds its indices on entry and the next step's on return; cpq = the tiles' centroid position, component q.
+template <int CF, int C1, bool BF16>
+__device__ __forceinline__ void sa_step_l1(const SaGeom& g, const SaItem& it, const SaL1W<CF, C1>& w, const float (&cpq)[4], int e0,
+                                           int q, int (&jn)[4], SaStep<CF, C1>& s) {
+    constexpr int KB1 = CF / 4 + 1, TO1 = C1 / 16;
+    // every load of a step is issued HERE, unconditional, before any of them is waited for: the four tiles' rows and the
+    // next step's four indices (from a clamped slot, masked afterwards).  As `en < n ? nbr[..] : 0` the index prefetch was a
+    // load under a branch -- the compiler then cannot count what is outstanding and drained everything behind each tile's
+    // gathers: four memory round trips per step, one after the other, where one is needed (scripts/isa_scan.py; round 5).
+    // (Gathering a step's ROWS one step ahead as well -- scripts/sa_stamps.py has the five-step items that decide the
+    // kernels' duration at 3.5 us per step -- made all four SA1 kernels slower, 15.1 -> 18.3 us the statistics pass: most
+    // items are ONE step, and each then gathers a second set of rows nobody reads.  In the EVAL variant alone -- the parcel
+    // loop: three or four steps per item -- it was slower too: 2139 -> 2241 us per launch for SA1, 701 -> 796 for SA2.)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int jc = jn[t];
+        const int en = e0 + it.estep + it.le0 + it.eoff * t;
+        const bool more = en < it.ln[t];
+        const int jr = g.nbr[(size_t)it.lc[t] * g.cap + (more ? en : 0)];
+        jn[t] = more ? jr : 0;
+        s.rows[t] = (size_t)it.bt[t] * g.Nsrc + jc;
+#pragma unroll
+        for (int kb = 0; kb < KB1 - 1; ++kb) s.bk[t][kb] = g.feat[s.rows[t] * g.feat_stride + 4 * kb + q];
+        s.bk[t][KB1 - 1] = g.spos[s.rows[t] * g.spos_stride + (q < 3 ? q : 0)];
+    }
+    // (the instruction scheduler keeps that order only if told to: with loads and contractions in one block it sank every gather
+    // of the 256-register kernels to its MFMA, each behind a full drain -- 22 to 29 serialised loads per step in the assembly)
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- layer 1: the rows were gathered straight into the B-operand layout
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int e = e0 + it.le0 + it.eoff * t;                            // slot in the list of this lane's centroid
+        s.val[t] = e < it.ln[t];
+        s.bk[t][KB1 - 1] = q < 3 ? s.bk[t][KB1 - 1] - cpq[t] : 1.0f;       // pos_j - pos_i | bias column
+#pragma unroll
+        for (int io = 0; io < TO1; ++io) {
+            f32x4 acc = {w.bias[io][0], w.bias[io][1], w.bias[io][2], w.bias[io][3]};
+            acc = contract<BF16, KB1>(acc, [&](int kb) { return w.A[io][kb]; }, [&](int kb) { return s.bk[t][kb]; });
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.f);
+            s.D1[io][t] = acc;
+        }
+    }
+}
+// Layer 2 (nl == 2): block 0's BatchNorm affine Y1 = a1 D1 + c1, then H2 = relu(W1 Y1 + b1), the affine's result being the next
+// contraction's B operand as it stands.  Out of place: the backward needs D1 afterwards, the forward's is dead.
+template <int C1, int C2, bool BF16>
+__device__ __forceinline__ void sa_affine_l2(const SaL2W<C1, C2>& w, const f32x4 (&D1)[C1 / 16][4], f32x4 (&Y1)[C1 / 16][4],
+                                             f32x4 (&H2)[C2 / 16][4]) {
+    constexpr int TO1 = C1 / 16, TO2 = C2 / 16;
+#pragma unroll
+    for (int is = 0; is < TO1; ++is)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Y1[is][t][r] = fmaf(w.a1[is][r], D1[is][t][r], w.c1[is][r]);
+#pragma unroll
+    for (int io = 0; io < TO2; ++io)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            f32x4 acc = {w.bias[io][0], w.bias[io][1], w.bias[io][2], w.bias[io][3]};
+            acc = contract<BF16, 4 * TO1>(acc, [&](int kk) { return w.A[io][kk >> 2][kk & 3]; },
+                                          [&](int kk) { return Y1[kk >> 2][t][kk & 3]; });
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.f);
+            H2[io][t] = acc;
+        }
+}
+
 // PASS 0: statistics of block 0 only (nl == 2);  PASS 1: full forward, statistics of the last block, extremum
 // STATS = false (an EVAL pass: BatchNorm on its running statistics, nothing kept for a backward): no statistic sums and no
 // arg-max slots -- a quarter of the vector instructions of a step, which is what bounds the parcel loop's SA1 pass (64 M
@@ -195,49 +361,20 @@ __device__ __forceinline__ bool sa_item(SaItem& it, const int* __restrict__ orde
 template <int CF, int NL, int C1, int C2, int PASS, bool BF16, bool STATS = true>
 __global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_fwd_kernel(const SaFwdArgs a) {
     static_assert(STATS || PASS == 1, "pass 0 IS the statistics pass");
-    constexpr int CIN = CF + 3, KB1 = CF / 4 + 1, TO1 = C1 / 16, TO2 = C2 / 16;
+    constexpr int TO1 = C1 / 16;
     constexpr int CL = NL == 2 ? C2 : C1, TOL = CL / 16, CS = PASS == 0 ? C1 : CL, TOS = CS / 16;
     static_assert(CF % 4 == 0 && C1 % 16 == 0 && C2 % 16 == 0, "tile shapes");
     __shared__ float s_red[4][2 * CS];          // per wave: added in wave order => the statistics are the same on every run
     const int lane = threadIdx.x & 63, q = lane >> 4, c = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     const int nwaves = gridDim.x * 4;
-    const int ncent = a.B * a.M;
-    const SaFirst first = sa_first(a.order, a.cnt, a.B, a.M, wave);
+    const SaGeom& g = a.g;
+    const SaFirst first = sa_first(g, wave);
 
     // ---- operand registers, loaded once
-    // the bias of the first layer rides in the weight matrix against the constant-1 column of the gathered input -- in fp32.
-    // With bf16 operands it stays OUT of the contraction (it would be rounded to bfloat16) and starts the accumulator.
-    float A1[TO1][KB1], bias1[TO1][4];
-#pragma unroll
-    for (int io = 0; io < TO1; ++io) {
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) {
-            const int k = 4 * kb + q, o = 16 * io + c;
-            A1[io][kb] = k < CIN ? a.W0[o * CIN + k] : ((k == CIN && !BF16) ? a.b0[o] : 0.f);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bias1[io][r] = BF16 ? a.b0[16 * io + 4 * q + r] : 0.f;
-    }
-    float A2[NL == 2 ? TO2 : 1][TO1][4], bias2[NL == 2 ? TO2 : 1][4], a1v[TO1][4], c1v[TO1][4];
-    if constexpr (NL == 2 && PASS == 1) {
-#pragma unroll
-        for (int io = 0; io < TO2; ++io) {
-#pragma unroll
-            for (int is = 0; is < TO1; ++is)
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) A2[io][is][kb] = a.W1[(16 * io + c) * C1 + 16 * is + 4 * q + kb];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) bias2[io][r] = a.b1[16 * io + 4 * q + r];
-        }
-#pragma unroll
-        for (int is = 0; is < TO1; ++is)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                a1v[is][r] = a.a0[16 * is + 4 * q + r];
-                c1v[is][r] = a.c0[16 * is + 4 * q + r];
-            }
-    }
+    const SaL1W<CF, C1> w1 = sa_l1_w<CF, C1, BF16>(a.W0, a.b0, q, c);
+    SaL2W<C1, C2> w2;
+    if constexpr (NL == 2 && PASS == 1) w2 = sa_l2_w<C1, C2>(a.W1, a.b1, a.a0, a.c0, q, c);
     float sgn[TOL][4];
     if constexpr (PASS == 1) {
         const float* gl = NL == 2 ? a.gamma1 : a.gamma0;
@@ -259,25 +396,11 @@ __global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_f
 #pragma unroll
         for (int r = 0; r < 4; ++r) ssum[io][r] = ssq[io][r] = 0.f;
 
-    // positions of the order table: nA per plot for SOLO / QUAD items, then nB per plot for the packed ones (OCT / HEX)
-    const int nA = first.nA, nB = first.nB;
-    const int G = a.group > 0 && a.group < a.B ? a.group : a.B;
-    const int nitems = a.order ? (nA + nB) * G * ((a.B + G - 1) / G) : (ncent + 3) >> 2;
-    // items are ordered heaviest first: the waves take them in a snake (round 0: item w, round 1: item 2W-1-w, ...), so the
-    // wave with the longest item of a round gets the shortest of the next.  (A shared work counter was tried: 8000 atomics
-    // on one address cost more than the imbalance they removed.  Round 5: dealing the positions so that an XCD's waves take
-    // the items of TWO of the sixteen plots -- 3 MB of feature rows per L2 instead of four plots' 6 MB on two XCDs each --
-    // made all six SA kernels 1-4 % slower: whole plots per XCD are not equal work.)
-    for (int round = 0;; ++round) {
-        const int qi = round * nwaves + ((round & 1) ? nwaves - 1 - wave : wave);
-        if (round * nwaves >= nitems) break;
-        if (qi >= nitems) continue;
-        SaItem it;
-        if (!sa_item(it, a.order, a.cnt, a.B, a.M, nA, nB, G, qi, c, round == 0 ? first.rec : nullptr)) continue;      // an empty position
+    sa_walk(g, first, wave, nwaves, c, [&](const SaItem& it) {
         const int nmax = it.nmax, estep = it.estep;
         float cpq[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) cpq[t] = a.cpos[(size_t)it.lc[t] * 4 + (q < 3 ? q : 0)];
+        for (int t = 0; t < 4; ++t) cpq[t] = g.cpos[(size_t)it.lc[t] * 4 + (q < 3 ? q : 0)];
         float best[4][TOL][4];
         int barg[4][TOL][4];
 #pragma unroll
@@ -289,60 +412,13 @@ __global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_f
                     best[t][io][r] = -INFINITY;
                     barg[t][io][r] = 0x7FFFFFFF;
                 }
-        // the neighbour indices of a step are fetched one step ahead: index load -> row gather -> MFMA chain is what a
-        // step waits for, and the first link does not depend on the step before.  The FIRST step's indices are requested
-        // together with the counts (the address needs the centroid only; entries past the count are masked afterwards)
         int jn[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int e = it.le0 + it.eoff * t;
-            jn[t] = a.nbr[(size_t)it.lc[t] * a.cap + (e < a.cap ? e : 0)];     // (unconditional: masked below)
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) jn[t] = it.le0 + it.eoff * t < it.ln[t] ? jn[t] : 0;
+        sa_first_idx(g, it, jn);
         for (int e0 = 0; e0 < nmax; e0 += estep) {
-            // ---- layer 1: gather straight into the B-operand layout, 4 message tiles
-            f32x4 D1[TO1][4];
-            bool val[4];
-            int jc[4];
-            // every load of a step is issued HERE, unconditional, before any of them is waited for: the four tiles' rows and the
-            // next step's four indices (from a clamped slot, masked afterwards).  As `en < n ? nbr[..] : 0` the index prefetch was a
-            // load under a branch -- the compiler then cannot count what is outstanding and drained everything behind each tile's
-            // gathers: four memory round trips per step, one after the other, where one is needed (scripts/isa_scan.py; round 5).
-            // (Gathering a step's ROWS one step ahead as well -- scripts/sa_stamps.py has the five-step items that decide the
-            // kernels' duration at 3.5 us per step -- made all four SA1 kernels slower, 15.1 -> 18.3 us the statistics pass: most
-            // items are ONE step, and each then gathers a second set of rows nobody reads.  In the EVAL variant alone -- the parcel
-            // loop: three or four steps per item -- it was slower too: 2139 -> 2241 us per launch for SA1, 701 -> 796 for SA2.)
-            float bkt[4][KB1];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                jc[t] = jn[t];
-                const int en = e0 + estep + it.le0 + it.eoff * t;
-                const bool more = en < it.ln[t];
-                const int jr = a.nbr[(size_t)it.lc[t] * a.cap + (more ? en : 0)];
-                jn[t] = more ? jr : 0;
-                const size_t row = (size_t)it.bt[t] * a.Nsrc + jc[t];
-#pragma unroll
-                for (int kb = 0; kb < KB1 - 1; ++kb) bkt[t][kb] = a.feat[row * a.feat_stride + 4 * kb + q];
-                bkt[t][KB1 - 1] = a.spos[row * a.spos_stride + (q < 3 ? q : 0)];
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int e = e0 + it.le0 + it.eoff * t;                            // slot in the list of this lane's centroid
-                val[t] = e < it.ln[t];
-                float bk[KB1];
-#pragma unroll
-                for (int kb = 0; kb < KB1 - 1; ++kb) bk[kb] = bkt[t][kb];
-                bk[KB1 - 1] = q < 3 ? bkt[t][KB1 - 1] - cpq[t] : 1.0f;   // pos_j - pos_i | bias column
-#pragma unroll
-                for (int io = 0; io < TO1; ++io) {
-                    f32x4 acc = {bias1[io][0], bias1[io][1], bias1[io][2], bias1[io][3]};
-                    acc = contract<BF16, KB1>(acc, [&](int kb) { return A1[io][kb]; }, [&](int kb) { return bk[kb]; });
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.f);
-                    D1[io][t] = acc;
-                }
-            }
+            SaStep<CF, C1> s;
+            sa_step_l1<CF, C1, BF16>(g, it, w1, cpq, e0, q, jn, s);
+            const auto& D1 = s.D1;
+            const auto& val = s.val;
             if constexpr (PASS == 0) {
 #pragma unroll
                 for (int io = 0; io < TO1; ++io)
@@ -355,26 +431,11 @@ __global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_f
                             ssq[io][r] = fmaf(h, h, ssq[io][r]);
                         }
             } else {
-                // ---- layer 2 (nl == 2): BN affine of block 0, then the next contraction on the same registers
+                // ---- the last block's result: layer 2 (nl == 2), or layer 1's as it stands
                 f32x4 DL[TOL][4];
                 if constexpr (NL == 2) {
-#pragma unroll
-                    for (int is = 0; is < TO1; ++is)
-#pragma unroll
-                        for (int t = 0; t < 4; ++t)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) D1[is][t][r] = fmaf(a1v[is][r], D1[is][t][r], c1v[is][r]);
-#pragma unroll
-                    for (int io = 0; io < TO2; ++io)
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            f32x4 acc = {bias2[io][0], bias2[io][1], bias2[io][2], bias2[io][3]};
-                            acc = contract<BF16, 4 * TO1>(acc, [&](int kk) { return A2[io][kk >> 2][kk & 3]; },
-                                                          [&](int kk) { return D1[kk >> 2][t][kk & 3]; });
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.f);
-                            DL[io][t] = acc;
-                        }
+                    f32x4 Y1[TO1][4];
+                    sa_affine_l2<C1, C2, BF16>(w2, D1, Y1, DL);
                 } else {
 #pragma unroll
                     for (int io = 0; io < TOL; ++io)
@@ -459,7 +520,7 @@ __global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_f
                 }
             }
         }
-    }
+    });
 
     // ---- batch statistics: row sums (over the 16 message lanes), then workgroup slot
     if (STATS && a.slots) {
@@ -486,8 +547,8 @@ __global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_f
 
 
 // ---------------------------------------------------------------------------------------------- backward passes
-// Same layout.  The forward is recomputed on the matrix cores; what is new:
-//   * BatchNorm(train)+ReLU backward per element with three per-lane constants per channel,
+// Same layout.  The forward is recomputed on the matrix cores, by the message turn above; what is new:
+//   * BatchNorm(train)+ReLU backward per element with three per-lane constants per channel (SaBnBwd, sa_dpre),
 //         dpre = [h > 0] * (A*dy - C*h + D),  A = gamma*is,  C = gamma*is^2*dgamma/E,  D = gamma*is*(mean*is*dgamma - dbeta)/E
 //     (dy is non-zero only on the slot that attained the extremum);
 //   * the input gradient of a layer, dy1 = W2^T dp2, is again an MFMA whose B operand is the register tile dp2 as it
@@ -495,9 +556,8 @@ __global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_f
 //   * weight gradients contract over MESSAGES: both factors go through a wave-private LDS image [message][channel]
 //     (one ds_write_b128 per tile for a register tile) and come back in A/B layout with the message index as K.
 struct SaBwdArgs {
-    int B, Nsrc, M, cap, feat_stride, spos_stride, group, frozen;
-    const float *feat, *spos, *cpos;
-    const int *nbr, *cnt, *order;
+    SaGeom g;
+    int frozen;
     const unsigned long long* total;
     const float *W0, *b0, *a0, *c0, *gamma0, *mean0, *invstd0, *dgamma0, *dbeta0;   // dgamma0/dbeta0: read in pass D only
     const float *W1, *b1, *gamma1, *mean1, *invstd1, *dgamma1, *dbeta1;
@@ -536,6 +596,17 @@ struct SaBwdLds {
     static constexpr int FLOATS = OWN + ((LAST2 && !BF16) ? 2 * 64 * 16 : 0);
 };
 
+// the BatchNorm-backward constants (A, C, D) of a channel, and the element rule they serve (on = valid and h > 0)
+struct SaBnBwd {
+    float A, C, D;
+};
+__device__ __forceinline__ SaBnBwd sa_bn_bwd(float g, float s, float m, float dg, float db, float invE) {
+    return SaBnBwd{g * s, g * s * s * dg * invE, g * s * (m * s * dg - db) * invE};
+}
+__device__ __forceinline__ float sa_dpre(bool on, const SaBnBwd& k, float dy, float h) {
+    return on ? fmaf(k.A, dy, fmaf(-k.C, h, k.D)) : 0.f;
+}
+
 // PASS 2 = "C" (nl == 2): dW/db of block 1, dgamma/dbeta of block 0.   PASS 3 = "D": dW/db of block 0 (+ dfeat).
 //
 // ONE-PASS ROUTE of pass C (a.ws given: no feature gradient wanted, fp32 operands).  Pass D exists as a launch of its own only
@@ -570,8 +641,8 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
     const int wib = threadIdx.x >> 6;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + wib));
     const int nwaves = gridDim.x * 4;
-    const int ncent = a.B * a.M;
-    const SaFirst first = sa_first(a.order, a.cnt, a.B, a.M, wave);
+    const SaGeom& g = a.g;
+    const SaFirst first = sa_first(g, wave);
     float* lds_p = smem + wib * WAVE_LDS;
     float* lds_q = lds_p + 64 * PS;
     float* lds_x0 = lds_p + Acc::LDS_FLOATS;                 // one-pass round: m xhat [64][16], then `in` [64][16];
@@ -584,21 +655,10 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
     const float invE = (etot > 0 && !a.frozen) ? (float)(1.0 / (double)etot) : 0.f;
 
     // ---- operand registers
-    float A1[TO1][KB1], bias1[TO1][4];      // bias of the first layer: inside the contraction in fp32, outside with bf16 operands
-#pragma unroll
-    for (int io = 0; io < TO1; ++io) {
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) {
-            const int k = 4 * kb + q, o = 16 * io + c;
-            A1[io][kb] = k < CIN ? a.W0[o * CIN + k] : ((k == CIN && !BF16) ? a.b0[o] : 0.f);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bias1[io][r] = BF16 ? a.b0[16 * io + 4 * q + r] : 0.f;
-    }
-    float A2[NL == 2 ? TO2 : 1][TO1][4], A2T[TO1][NL == 2 ? TO2 : 1][4], bias2[NL == 2 ? TO2 : 1][4], a1v[TO1][4], c1v[TO1][4];
-    // BN-backward constants: block 0 (index 0) and, for nl == 2, block 1 (index 1)
-    float cA0[TO1][4], cC0[TO1][4], cD0[TO1][4], mu0[TO1][4], is0[TO1][4];
-    float cA1[NL == 2 ? TO2 : 1][4], cC1[NL == 2 ? TO2 : 1][4], cD1[NL == 2 ? TO2 : 1][4];
+    const SaL1W<CF, C1> w1 = sa_l1_w<CF, C1, BF16>(a.W0, a.b0, q, c);
+    // BN-backward constants: block 0 (pass D; pass C sums its dgamma0, dbeta0 first) and, for nl == 2, block 1
+    float mu0[TO1][4], is0[TO1][4];
+    SaBnBwd k0[TO1][4], k1[NL == 2 ? TO2 : 1][4];
 #pragma unroll
     for (int is = 0; is < TO1; ++is)
 #pragma unroll
@@ -606,35 +666,23 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
             const int ch = 16 * is + 4 * q + r;
             mu0[is][r] = a.mean0[ch];
             is0[is][r] = a.invstd0[ch];
-            a1v[is][r] = NL == 2 ? a.a0[ch] : 0.f;
-            c1v[is][r] = NL == 2 ? a.c0[ch] : 0.f;
-            if (NL == 1 || PASS == 3) {
-                const float g = a.gamma0[ch], dg = a.dgamma0[ch], db = a.dbeta0[ch], m = mu0[is][r], s = is0[is][r];
-                cA0[is][r] = g * s;
-                cC0[is][r] = g * s * s * dg * invE;
-                cD0[is][r] = g * s * (m * s * dg - db) * invE;
-            } else {
-                cA0[is][r] = cC0[is][r] = cD0[is][r] = 0.f;
-            }
+            k0[is][r] = (NL == 1 || PASS == 3) ? sa_bn_bwd(a.gamma0[ch], is0[is][r], mu0[is][r], a.dgamma0[ch], a.dbeta0[ch], invE)
+                                               : SaBnBwd{0.f, 0.f, 0.f};
         }
+    SaL2W<C1, C2> w2;
+    float A2T[TO1][NL == 2 ? TO2 : 1][4];                    // W1^T as A operands: dy1 = W1^T dp2
     if constexpr (NL == 2) {
+        w2 = sa_l2_w<C1, C2>(a.W1, a.b1, a.a0, a.c0, q, c);
 #pragma unroll
         for (int io = 0; io < TO2; ++io) {
 #pragma unroll
             for (int is = 0; is < TO1; ++is)
 #pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    A2[io][is][kb] = a.W1[(16 * io + c) * C1 + 16 * is + 4 * q + kb];
-                    A2T[is][io][kb] = a.W1[(16 * io + 4 * q + kb) * C1 + 16 * is + c];
-                }
+                for (int kb = 0; kb < 4; ++kb) A2T[is][io][kb] = a.W1[(16 * io + 4 * q + kb) * C1 + 16 * is + c];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ch = 16 * io + 4 * q + r;
-                bias2[io][r] = a.b1[ch];
-                const float g = a.gamma1[ch], dg = a.dgamma1[ch], db = a.dbeta1[ch], m = a.mean1[ch], s = a.invstd1[ch];
-                cA1[io][r] = g * s;
-                cC1[io][r] = g * s * s * dg * invE;
-                cD1[io][r] = g * s * (m * s * dg - db) * invE;
+                k1[io][r] = sa_bn_bwd(a.gamma1[ch], a.invstd1[ch], a.mean1[ch], a.dgamma1[ch], a.dbeta1[ch], invE);
             }
         }
     }
@@ -674,19 +722,7 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
     constexpr int CL = NL == 2 ? C2 : C1, TOL = CL / 16;
     SASTAMP(1);
     unsigned long long n_items_dbg = 0, n_steps_dbg = 0;
-    // positions of the order table: nA per plot for SOLO / QUAD items, then nB per plot for the packed ones (OCT / HEX)
-    const int nA = first.nA, nB = first.nB;
-    const int G = a.group > 0 && a.group < a.B ? a.group : a.B;
-    const int nitems = a.order ? (nA + nB) * G * ((a.B + G - 1) / G) : (ncent + 3) >> 2;
-    // items are ordered heaviest first: the waves take them in a snake (round 0: item w, round 1: item 2W-1-w, ...), so the
-    // wave with the longest item of a round gets the shortest of the next.  (A shared work counter was tried: 8000 atomics
-    // on one address cost more than the imbalance they removed.)
-    for (int round = 0;; ++round) {
-        const int qi = round * nwaves + ((round & 1) ? nwaves - 1 - wave : wave);
-        if (round * nwaves >= nitems) break;
-        if (qi >= nitems) continue;
-        SaItem it;
-        if (!sa_item(it, a.order, a.cnt, a.B, a.M, nA, nB, G, qi, c, round == 0 ? first.rec : nullptr)) continue;      // an empty position
+    sa_walk(g, first, wave, nwaves, c, [&](const SaItem& it) {
         if (n_items_dbg == 0) { SASTAMP(2); }
         ++n_items_dbg;
         n_steps_dbg += (it.nmax + it.estep - 1) / it.estep;
@@ -697,7 +733,7 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
         int arv[4][TOL][4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            cpq[t] = a.cpos[(size_t)it.lc[t] * 4 + (q < 3 ? q : 0)];
+            cpq[t] = g.cpos[(size_t)it.lc[t] * 4 + (q < 3 ? q : 0)];
 #pragma unroll
             for (int io = 0; io < TOL; ++io) {
                 const size_t o = (size_t)it.lc[t] * CL + 16 * io + 4 * q;
@@ -707,48 +743,15 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
                 arv[t][io][0] = av.x; arv[t][io][1] = av.y; arv[t][io][2] = av.z; arv[t][io][3] = av.w;
             }
         }
-        int jn[4];                                 // neighbour indices, fetched one step ahead (the first step's: with the counts)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int e = it.le0 + it.eoff * t;
-            jn[t] = a.nbr[(size_t)it.lc[t] * a.cap + (e < a.cap ? e : 0)];     // (unconditional: masked below)
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) jn[t] = it.le0 + it.eoff * t < it.ln[t] ? jn[t] : 0;
+        int jn[4];
+        sa_first_idx(g, it, jn);
         for (int e0 = 0; e0 < nmax; e0 += estep) {
-            f32x4 D1[TO1][4];
-            float bks[4][KB1];
-            bool val[4];
-            size_t rows[4];
-            int jc[4];
-            // (every load of a step issued before any is waited for, the index prefetch unconditional from a clamped slot: see the
-            // forward kernel)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                jc[t] = jn[t];
-                const int en = e0 + estep + it.le0 + it.eoff * t;
-                const bool more = en < it.ln[t];
-                const int jr = a.nbr[(size_t)it.lc[t] * a.cap + (more ? en : 0)];
-                jn[t] = more ? jr : 0;
-                rows[t] = (size_t)it.bt[t] * a.Nsrc + jc[t];
-#pragma unroll
-                for (int kb = 0; kb < KB1 - 1; ++kb) bks[t][kb] = a.feat[rows[t] * a.feat_stride + 4 * kb + q];
-                bks[t][KB1 - 1] = a.spos[rows[t] * a.spos_stride + (q < 3 ? q : 0)];
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int e = e0 + it.le0 + it.eoff * t;                            // slot in the list of this lane's centroid
-                val[t] = e < it.ln[t];
-                bks[t][KB1 - 1] = q < 3 ? bks[t][KB1 - 1] - cpq[t] : 1.0f;
-#pragma unroll
-                for (int io = 0; io < TO1; ++io) {
-                    f32x4 v = {bias1[io][0], bias1[io][1], bias1[io][2], bias1[io][3]};
-                    v = contract<BF16, KB1>(v, [&](int kb) { return A1[io][kb]; }, [&](int kb) { return bks[t][kb]; });
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                    D1[io][t] = v;
-                }
-            }
+            SaStep<CF, C1> s;
+            sa_step_l1<CF, C1, BF16>(g, it, w1, cpq, e0, q, jn, s);
+            const auto& D1 = s.D1;
+            const auto& bks = s.bk;
+            const auto& val = s.val;
+            const auto& rows = s.rows;
             unsigned onm = 0;    // one-pass route: bit 4 t + r = [valid and h > 0] of this lane's channel r, tile t
             if constexpr (ONE) {
                 if (one) {
@@ -770,26 +773,18 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
             }
             f32x4 dy1[TO1][4];   // d loss / d (BN output of block 0)
             if constexpr (NL == 2) {
-                f32x4 Y1[TO1][4], dp2[TO2][4];
-#pragma unroll
-                for (int is = 0; is < TO1; ++is)
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) Y1[is][t][r] = fmaf(a1v[is][r], D1[is][t][r], c1v[is][r]);
+                f32x4 Y1[TO1][4], dp2[TO2][4];               // dp2: block 1's result h first, then d loss / d (its pre-activation)
+                sa_affine_l2<C1, C2, BF16>(w2, D1, Y1, dp2);
 #pragma unroll
                 for (int io = 0; io < TO2; ++io)
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
-                        f32x4 v = {bias2[io][0], bias2[io][1], bias2[io][2], bias2[io][3]};
-                        v = contract<BF16, 4 * TO1>(v, [&](int kk) { return A2[io][kk >> 2][kk & 3]; },
-                                                    [&](int kk) { return Y1[kk >> 2][t][kk & 3]; });
                         const int e = e0 + it.le0 + it.eoff * t;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float h = fmaxf(v[r], 0.f);
+                            const float h = dp2[io][t][r];
                             const float dy = (val[t] && arv[t][io][r] == e) ? dov[t][io][r] : 0.f;
-                            dp2[io][t][r] = (val[t] && h > 0.f) ? fmaf(cA1[io][r], dy, fmaf(-cC1[io][r], h, cD1[io][r])) : 0.f;
+                            dp2[io][t][r] = sa_dpre(val[t] && h > 0.f, k1[io][r], dy, h);
                         }
                     }
                 // d loss / d y1 = W2^T dp2
@@ -851,8 +846,7 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const float h = D1[is][t][r];
-                            dp1[is][t][r] = (val[t] && h > 0.f)
-                                                ? fmaf(cA0[is][r], dy1[is][t][r], fmaf(-cC0[is][r], h, cD0[is][r])) : 0.f;
+                            dp1[is][t][r] = sa_dpre(val[t] && h > 0.f, k0[is][r], dy1[is][t][r], h);
                         }
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
@@ -958,7 +952,7 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
             }
         }
         if (n_items_dbg == 1) { SASTAMP(3); }
-    }
+    });
     SASTAMP(4);
     SACOUNT(8, n_items_dbg);
     SACOUNT(9, n_steps_dbg);
@@ -1004,7 +998,7 @@ __global__ __launch_bounds__(256, (NL == 2 && PASS == 2 && !BF16) ? 2 : 1) void 
             for (int i = 0; i < 3; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (c < QK0) slab[NW + NB + NG + (16 * i + 4 * q + r) * QK0 + c] = acc0[i][r] * a1v[0][r];
+                    if (c < QK0) slab[NW + NB + NG + (16 * i + 4 * q + r) * QK0 + c] = acc0[i][r] * w2.a1[0][r];
         }
     }
     SASTAMP(5);
@@ -1054,14 +1048,28 @@ static int sa_plot_group(int B) {
     return B <= 32 ? B : 8;
 }
 
+static SaGeom sa_geom(const sn2_sa* p) {
+    SaGeom g;
+    g.B = p->B; g.Nsrc = p->Nsrc; g.M = p->M; g.cap = p->cap; g.feat_stride = p->feat_stride; g.spos_stride = p->spos_stride;
+    g.group = sa_plot_group(p->B);
+    g.feat = p->feat; g.spos = p->spos; g.cpos = p->cpos; g.nbr = p->nbr; g.cnt = p->cnt; g.order = p->order;
+    return g;
+}
+
+// one wave per quad of centroids, four waves per workgroup -- and no more workgroups than the chip holds at once (`occ` per CU:
+// waves per SIMD by the kernels' register counts): the items are dealt heaviest first, a second wave of workgroups would start on
+// the light tail when the first is done with the heads
+static int sa_grid(const sn2_sa* p, int occ) {
+    const int blocks = sn2_cdiv((long)p->B * p->M, 16);
+    return blocks > sn2_cu_count() * occ ? sn2_cu_count() * occ : blocks;
+}
+
 // launched from sa.hip
 template <int CF, int NL, int C1, int C2, int PASS>
 int sa_mfma_launch_fwd(const sn2_sa* p, int training, hipStream_t st, int* nblocks_out) {
     const bool bf16 = p->blk[0].mma_bf16 != 0;
     SaFwdArgs a;
-    a.B = p->B; a.Nsrc = p->Nsrc; a.M = p->M; a.cap = p->cap; a.feat_stride = p->feat_stride; a.spos_stride = p->spos_stride;
-    a.feat = p->feat; a.spos = p->spos; a.cpos = p->cpos; a.nbr = p->nbr; a.cnt = p->cnt; a.order = p->order;
-    a.group = sa_plot_group(p->B);
+    a.g = sa_geom(p);
     const sn2_block& k0 = p->blk[0];
     const sn2_block& k1 = p->blk[NL == 2 ? 1 : 0];
     a.W0 = k0.W; a.b0 = k0.b; a.a0 = k0.a; a.c0 = k0.c; a.gamma0 = k0.gamma;
@@ -1069,13 +1077,10 @@ int sa_mfma_launch_fwd(const sn2_sa* p, int training, hipStream_t st, int* nbloc
     a.slots = training == 1 ? (PASS == 0 ? k0.stat_slots : k1.stat_slots) : nullptr;     // (SN2_BN_FROZEN_KEEP: no sums wanted)
     a.ext = p->ext; a.arg = p->arg;
     a.al = k1.a; a.cl = k1.c; a.out = p->out;
-    int blocks = sn2_cdiv((long)p->B * p->M, 16);          // one wave per quad of centroids, four waves per workgroup
-    if (blocks > SN2_STAT_SLOTS) blocks = SN2_STAT_SLOTS;
-    // .. and no more workgroups than the chip holds at once (waves per SIMD by the kernels' register counts): the items are
-    // dealt heaviest first, a second wave of workgroups would start on the light tail when the first is done with the heads
     static const int occ_env = getenv("SN2_SA_FWD_OCC") ? atoi(getenv("SN2_SA_FWD_OCC")) : 0;
     const int occ = occ_env > 0 ? occ_env : (CF == 8 ? (PASS == 0 ? 4 : 3) : (CF == 16 ? 2 : 1));
-    if (blocks > sn2_cu_count() * occ) blocks = sn2_cu_count() * occ;
+    int blocks = sa_grid(p, occ);
+    if (blocks > SN2_STAT_SLOTS) blocks = SN2_STAT_SLOTS;  // a workgroup writes its statistics into a slot of its own
     if (nblocks_out) *nblocks_out = blocks;
     if constexpr (PASS == 1) {
         if (!training) {           // eval: the variant without the statistic sums and the arg-max slots
@@ -1099,9 +1104,8 @@ template <int CF, int NL, int C1, int C2, int PASS>
 int sa_mfma_launch_bwd(const sn2_sa* p, float* ws, hipStream_t st) {
     if (ws && (PASS != 2 || NL != 2 || p->blk[0].mma_bf16)) return SN2_EINVAL;
     SaBwdArgs a;
-    a.B = p->B; a.Nsrc = p->Nsrc; a.M = p->M; a.cap = p->cap; a.feat_stride = p->feat_stride; a.spos_stride = p->spos_stride;
-    a.feat = p->feat; a.spos = p->spos; a.cpos = p->cpos; a.nbr = p->nbr; a.cnt = p->cnt; a.order = p->order; a.total = p->total;
-    a.group = sa_plot_group(p->B);
+    a.g = sa_geom(p);
+    a.total = p->total;
     const sn2_block& k0 = p->blk[0];
     const sn2_block& k1 = p->blk[NL == 2 ? 1 : 0];
     a.frozen = (k0.frozen_stats || k1.frozen_stats) ? 1 : 0;      // (one forward pass = one mode for the module's blocks)
@@ -1114,10 +1118,9 @@ int sa_mfma_launch_bwd(const sn2_sa* p, float* ws, hipStream_t st) {
     a.rep_k = k0.grad_replicas; a.rep_stride = k0.grad_replica_stride;
     a.dfeat = p->dfeat;
     a.ws = ws;
-    int blocks = sn2_cdiv((long)p->B * p->M, 16);
     static const int occ_env = getenv("SN2_SA_BWD_OCC") ? atoi(getenv("SN2_SA_BWD_OCC")) : 0;
     const int occ = occ_env > 0 ? occ_env : (CF == 8 ? 2 : 1);            // workgroups per CU that are resident together
-    if (blocks > sn2_cu_count() * occ) blocks = sn2_cu_count() * occ;
+    const int blocks = sa_grid(p, occ);
     const size_t lds = (size_t)(p->blk[0].mma_bf16 ? SaBwdLds<CF, NL, C1, C2, PASS, true>::FLOATS
                                                    : SaBwdLds<CF, NL, C1, C2, PASS, false>::FLOATS) * 4 * sizeof(float);
     auto kern = p->blk[0].mma_bf16 ? &sa_mfma_bwd_kernel<CF, NL, C1, C2, PASS, true> : &sa_mfma_bwd_kernel<CF, NL, C1, C2, PASS, false>;
