@@ -362,6 +362,59 @@ int sn2_parcel_znorm(const float *cloud, long T, float x_min, float y_min, float
                      float disc_radius, const int *offsets, const float *centers, int P, const int *point_index, long sum_n,
                      int *ws, size_t ws_words, float *raw, void *stream);
 
+/* ---- the plots of K parcels in one pass (csrc/parcels.hip; host side parcel.py: ParcelClouds, prepare_parcels).  What a
+ * prepared plot is does not change: every rule above is stated once (csrc/parcel_rules.h) and executed here with the parcel's own
+ * columns, centres, centre grid and z-norm cells, so parcel k's plots are the bytes sn2_parcel_count / _fill / _znorm give for
+ * parcel k alone, and a parcel's points never see another parcel's centres or points, even where two parcels overlap in space.
+ * The output bytes do not depend on arrival order (the order in which waves run): integer counts and cursors, min / max over
+ * floats through order-preserving integers, no floating-point add atomics.
+ * CLOUD ARENA.  (10, T_all) fp32, channel-major; parcel k owns the columns [t0_k, t0_k + T_k); every T_k > 0, T_all < 2^31.
+ * PARCEL TABLE.  (K+1) rows of SN2_PARCELS_COLS int64, written by sn2_parcels_table (host arithmetic, no device):
+ *   [0] t0_k  [1] T_k  [2] first row (a row = L consecutive points of ONE parcel, rows_k = ceil(T_k / L); 0 rows when P_k = 0)
+ *   [3] c0_k: first centre  [4] P_k (0 is legal: the parcel owns no rows, no entries and no cells)
+ *   [5] first (plot, row) entry; parcel k's entries are plot-major, P_k rows_k of them
+ *   [6] first word of its centre-grid CSR in cell_start (GX GY + 1 words; the values index cell_items of ALL parcels, the items are
+ *       centre ids relative to c0_k)  [7] GX  [8] GY  [9..11] the fp64 bits of gx0, gy0, cell_inv
+ *   [12] first z-norm cell  [13] fp32 bits of x_min | y_min << 32  [14] of x_max | y_max << 32  [15] z-norm GX | GY << 32
+ *   row K: [0] T_all  [1] L  [2] rows  [3] centres  [4] K  [5] entries  [6] CSR words  [12] z-norm cells
+ *          [13] fp32 bits of radius | z-norm radius << 32; the rest 0.
+ *   One L for the set: max(2048, ceil(sum T_k P_k / 2^26) rounded up to 64), as parcel.prepare_parcel grows it.
+ * Every entry point but sn2_parcels_bbox takes the table twice, table_host and its copy table_dev, and before it launches checks
+ * that the builder makes the same words of the host copy's own sizes, grids and boxes (else SN2_EINVAL: T_k <= 0, bases that are
+ * not the prefixes, cells narrower than the radius, a radius that is not the table's; SN2_ELIMIT: T_all >= 2^31, 2^28 entries or
+ * CSR words, more than 2^26 z-norm cells).  NULL pointers, K <= 0, a misaligned or short workspace: SN2_EINVAL.
+ *
+ * sn2_parcels_bbox: ONE launch.  starts (2, K+1) int64, on the host and on the device: point_start, then the exclusive prefix of
+ *   ceil(T_k / SN2_PARCELS_BBOX_CHUNK): parcel k is cut into that many workgroups, each found by binary search on the prefix.
+ *   state (K,4) uint32, in and out: the order-preserving integers (negative floats: ~bits; others: bits | 2^31) of x_min, y_min,
+ *   x_max, y_max, folded in by integer atomic min / max.  The caller initialises it to (~0, ~0, 0, 0) per parcel; a state that
+ *   already holds the boxes of the same arena is left as it is.  Decoded, the box is cloud[:2].min(1) / .max(1) of finite values.
+ * sn2_parcels_table: host only.  T (K), P (K), GX, GY (K), grid (K,3) = gx0, gy0, cell_inv (read where P_k > 0), boxes (K,4) fp32
+ *   -> table, L, and the workspace words of sn2_parcels_count and sn2_parcels_znorm.
+ * sn2_parcels_count: clear + ONE pass over all rows (a wave finds its parcel from its global row, wave-uniformly) + one scan
+ *   over all entries + a gather: prefix (entries + 1) as sn2_parcel_count's per parcel, total[0] = all hits (int64),
+ *   plot_start (P_all + 1) int64 = the first entry's value of every plot, then the total.  centers (P_all,2).  ws 8-byte aligned.
+ * sn2_parcels_fill: ONE launch; plot_base (P_all), INT_MIN = dropped; slot = plot_base[p] + the entry's cursor + rank.
+ *   point_index[slot] = i - t0_k: the column in the parcel's own cloud.
+ * sn2_parcels_znorm: the launches of sn2_parcel_znorm, once.  offsets (P+1), centers (P,2), plot_parcel (P) int32 of the KEPT
+ *   plots; radius = the table's z-norm radius, disc_radius = its radius.  ws 16-byte aligned. */
+#define SN2_PARCELS_COLS 16
+#define SN2_PARCELS_BBOX_CHUNK 4096
+int sn2_parcels_table(int K, const long long *T, const int *P, const int *GX, const int *GY, const double *grid,
+                      const float *boxes, float radius, float zradius, long long *table, int *L, size_t *count_ws_words,
+                      size_t *znorm_ws_words);
+int sn2_parcels_bbox(const float *arena, long T_all, int K, const long long *starts_host, const long long *starts_dev,
+                     unsigned *state, void *stream);
+int sn2_parcels_count(const float *arena, int K, const long long *table_host, const long long *table_dev, const float *centers,
+                      const int *cell_start, const int *cell_items, float radius, int *ws, size_t ws_words, int *prefix,
+                      long long *total, long long *plot_start, void *stream);
+int sn2_parcels_fill(const float *arena, int K, const long long *table_host, const long long *table_dev, const float *centers,
+                     const int *cell_start, const int *cell_items, float radius, int *prefix, const int *plot_base, long sum_n,
+                     float *raw, int *point_index, void *stream);
+int sn2_parcels_znorm(const float *arena, int K, const long long *table_host, const long long *table_dev, float radius,
+                      float disc_radius, const int *offsets, const float *centers, const int *plot_parcel, int P,
+                      const int *point_index, long sum_n, int *ws, size_t ws_words, float *raw, void *stream);
+
 /* ---- set abstraction: gather + shared MLP + BN + max -- SAModule/PointConv, model/point_net2.py:19,21-29 --- */
 typedef struct sn2_sa {
     int B, Nsrc, M, cap;            /* plots, source points per plot, centroids per plot, stride of nbr        */

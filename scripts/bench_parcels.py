@@ -9,10 +9,16 @@ run alternately, --pairs times each after a warm-up, in two forms: "whole" (the 
 "phases" (prepare, predict and report timed apart, a synchronise between them; the loop's phases are the three calls
 `predict_parcel_cloud` is made of).  Prints one JSON line: median and range per contender and phase, plots/s over the predict
 phase, the share of the prepare phase, and whether the set's predict + report time lies below the loop's in every pair.
+The prepare phase has two contenders of its own, timed in every pair right after one another: `prepare_parcels(batched=False)`
+(the loop over `prepare_parcel`) and `prepare_parcels(batched=True)` (one pass over a cloud arena, the arena's concatenation
+included); "prepare" reports both, whether the batched one lies below the loop in every pair, and the share of the batched
+prepare spent in the host lattice / centre-grid code (host clock around `parcel._host_lattices`).  The set's own phases and its
+whole job use the default (`batched=None`).
 The clouds are on the device before the clock starts (as in bench_parcel.py).  Kernel times: run it under
-`rocprofv3 --kernel-trace --stats`.
+`rocprofv3 --kernel-trace --stats`; `--one-prepare` makes ONE batched prepare after the clouds are built and exits, so that such a
+trace holds the launches of exactly one.
 
-    python scripts/bench_parcels.py [--parcels 16] [--pairs 5] [--batch 512] [--side 100]
+    python scripts/bench_parcels.py [--parcels 16] [--pairs 5] [--batch 512] [--side 100] [--one-prepare]
 """
 import argparse
 import json
@@ -43,6 +49,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--side", type=float, default=100.0)
+    ap.add_argument("--one-prepare", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_parcels: needs the GPU")
@@ -60,6 +67,31 @@ def main():
         rings.append([np.array([[x0 + 5, y0 + 5], [x1 - 5, y0 + 5], [x1 - 5, y1 - 5], [x0 + 5, y1 - 5]])])
         clouds.append(torch.from_numpy(c).to(dev))
     kw = dict(fps_start=0, sampler="device", seed=SEED)
+    if a.one_prepare:
+        torch.cuda.synchronize()
+        plots = parcel.prepare_parcels(clouds, args, shapes=rings, batched=True)
+        torch.cuda.synchronize()
+        print(json.dumps({"one_batched_prepare": True, "parcels": K, "plots": len(plots)}))
+        return
+    host = {"s": 0.0}
+    lattices = parcel._host_lattices
+
+    def timed_lattices(*p, **k):
+        t0 = time.perf_counter()
+        out = lattices(*p, **k)
+        host["s"] += time.perf_counter() - t0
+        return out
+    parcel._host_lattices = timed_lattices
+
+    def prepare_pair():
+        t0 = clock()
+        pl = parcel.prepare_parcels(clouds, args, shapes=rings, batched=False)
+        t1 = clock()
+        host["s"] = 0.0
+        pb = parcel.prepare_parcels(clouds, args, shapes=rings, batched=True)
+        t2 = clock()
+        assert len(pl) == len(pb)
+        return {"loop": t1 - t0, "batched": t2 - t1, "host": host["s"]}
 
     def loop_whole(key=lambda k: 0):
         t0 = clock()
@@ -110,9 +142,10 @@ def main():
     _, rep = set_whole()
     equal = all(reps[k].band_means.tobytes() == rep.band_means[k].tobytes() and np.array_equal(reps[k].band_counts, rep.band_counts[k])
                 and reps[k].threshold == rep.thresholds[k] for k in range(K))
-    loop_phases(), set_phases(), loop_whole()
+    loop_phases(), set_phases(), loop_whole(), prepare_pair()
 
     runs = {"loop": [], "set": []}
+    prep = []
     plots_n = 0
     for _ in range(a.pairs):
         lw, sw = loop_whole()[0], set_whole()[0]
@@ -120,6 +153,7 @@ def main():
         assert plots_n == n2
         runs["loop"].append({**lw, **lp})
         runs["set"].append({**sw, **sp})
+        prep.append(prepare_pair())
 
     def stat(v):
         return {"median": round(statistics.median(v) * 1e3, 3), "min": round(min(v) * 1e3, 3), "max": round(max(v) * 1e3, 3)}
@@ -143,6 +177,12 @@ def main():
                       "set_below_loop_in_every_pair": bool(below), "ranges_apart": bool(apart),
                       "whole_loop_over_set": round(statistics.median([r["whole"] for r in runs["loop"]]) /
                                                    statistics.median([r["whole"] for r in runs["set"]]), 3),
+                      "prepare": {"loop_ms": stat([r["loop"] for r in prep]), "batched_ms": stat([r["batched"] for r in prep]),
+                                  "loop_over_batched": round(statistics.median([r["loop"] for r in prep]) /
+                                                             statistics.median([r["batched"] for r in prep]), 3),
+                                  "batched_below_loop_in_every_pair": bool(all(r["batched"] < r["loop"] for r in prep)),
+                                  "host_lattice_ms": stat([r["host"] for r in prep]),
+                                  "host_lattice_share_of_batched": round(statistics.median([r["host"] / r["batched"] for r in prep]), 3)},
                       "loop": out["loop"], "set": out["set"]}))
 
 

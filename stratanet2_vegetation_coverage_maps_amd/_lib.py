@@ -22,7 +22,7 @@ CONSTANTS = {
     "SN2_MOSAIC_HIST_WORDS": 10004, "SN2_MOSAIC_CROP_MAX_BANDS": 8, "SN2_MOSAIC_CROP_MAX_EDGES": 1 << 20,
     "SN2_MOSAIC_CROP_MAX_BLOCKS": 2048, "SN2_ATLAS_CANVAS_COLS": 8, "SN2_ATLAS_SEG_COLS": 8, "SN2_ATLAS_FINALIZE_MAX_BLOCKS": 1024,
     "SN2_ATLAS_FINALIZE_CANVAS_WORDS": 10004 + 2 * 1024, "SN2_KDE_FIT_MAX_K": 65536, "SN2_LOSS_BLOCKS": 1024, "SN2_PROJECTED_LOSS_WS": 2 * 512 + 2,
-    "SN2_NET_GRAD_IMAGES": 32, "SN2_METER_TERMS": 4,
+    "SN2_NET_GRAD_IMAGES": 32, "SN2_METER_TERMS": 4, "SN2_PARCELS_COLS": 16, "SN2_PARCELS_BBOX_CHUNK": 4096,
     "SN2_CV_SLICE_PLOTS": 1024, "SN2_CV_COLUMNS": 30, "SN2_CV_STATS_DOUBLES": 2 * 30 + 2 * 3 * 8 * 8 + 1, "SN2_CV_MAX_PLOTS": 1 << 24,
     "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
@@ -160,6 +160,16 @@ SIGNATURES = {
                         c_double, c_float, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
     "sn2_parcel_znorm": [c_void_p, c_long, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int,
                          c_void_p, c_long, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    # K parcels at once (csrc/parcels.hip); table_host, starts_host are host pointers
+    "sn2_parcels_table": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,
+                          POINTER(c_int), POINTER(ctypes.c_size_t), POINTER(ctypes.c_size_t)],
+    "sn2_parcels_bbox": [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_parcels_count": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, ctypes.c_size_t,
+                          c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_parcels_fill": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_long,
+                         c_void_p, c_void_p, c_void_p],
+    "sn2_parcels_znorm": [c_void_p, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                          c_long, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     "sn2_subsample_form": [c_int, c_int],
     "sn2_subsample": [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_void_p, ctypes.c_size_t,
                       c_void_p, c_void_p],

@@ -847,6 +847,147 @@ def parcel_znorm(cloud: torch.Tensor, bbox, radius: float, disc_radius: float, o
     return raw
 
 
+# ---- K parcels at once (include/strata_hip.h, "the plots of K parcels in one pass"; csrc/parcels.hip) --------------------------
+def pack_upload(arrays, device):
+    """Host arrays -> their device copies through ONE host-to-device copy: the arrays' bytes laid end to end at 16-byte
+    boundaries, uploaded, and viewed again with each array's dtype and shape."""
+    arrays = [np.ascontiguousarray(a) for a in arrays]
+    offs, n = [], 0
+    for a in arrays:
+        offs.append(n)
+        n += (a.nbytes + 15) // 16 * 16
+    blob = np.zeros(max(n, 16), dtype=np.uint8)
+    for a, o in zip(arrays, offs):
+        blob[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    dev = torch.from_numpy(blob).to(device)
+    return [dev[o:o + a.nbytes].view(torch.from_numpy(a).dtype).view(a.shape) for a, o in zip(arrays, offs)]
+
+
+def parcels_bbox_starts(T) -> np.ndarray:
+    """The (2, K+1) int64 `starts` of sn2_parcels_bbox for clouds of T[k] points: point_start, then the workgroup prefix."""
+    T = np.asarray(T, dtype=np.int64).reshape(-1)
+    chunk = _lib.SN2_PARCELS_BBOX_CHUNK
+    return np.stack([np.concatenate([[0], np.cumsum(T)]), np.concatenate([[0], np.cumsum((T + chunk - 1) // chunk)])]).astype(np.int64)
+
+
+def parcels_bbox_identity(K: int) -> np.ndarray:
+    """(K,4) uint32: the state sn2_parcels_bbox starts from (nothing folded in yet), as int32 words."""
+    return np.tile(np.array([-1, -1, 0, 0], dtype=np.int32), (int(K), 1))
+
+
+def parcels_bbox_decode(state: np.ndarray) -> np.ndarray:
+    """The order-preserving integers of sn2_parcels_bbox's state -> (K,4) float32 x_min, y_min, x_max, y_max."""
+    u = np.ascontiguousarray(state).view(np.uint32)
+    return np.where(u >> 31 == 1, u & np.uint32(0x7FFFFFFF), ~u).astype(np.uint32).view(np.float32)
+
+
+def parcels_bbox(arena: torch.Tensor, starts_host: np.ndarray, starts_dev: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+    """include/strata_hip.h: sn2_parcels_bbox.  arena (10,T_all) f32; starts as `parcels_bbox_starts`, on the host and on the
+    device; state (K,4) i32 words, folded into in place (one launch) and returned: `parcels_bbox_decode` its host copy."""
+    _, T_all = arena.shape
+    _chk(arena, F32, (10, T_all), "arena")
+    K = starts_host.shape[1] - 1
+    _chk(starts_dev, I64, (2, K + 1), "starts")
+    _chk(state, I32, (K, 4), "state")
+    starts_host = np.ascontiguousarray(starts_host, dtype=np.int64)
+    _call("sn2_parcels_bbox", _ptr(arena), T_all, K, starts_host.ctypes.data, _ptr(starts_dev), _ptr(state), _stream())
+    return state
+
+
+class ParcelTable:
+    """The parcel table of K clouds in one arena on the host (`host`, numpy (K+1, SN2_PARCELS_COLS) int64) and, once uploaded, on
+    the device (`dev`): what the sn2_parcels_* entry points take.  T, P: points and plot centres per parcel; grids: per parcel
+    `parcel.center_grid`'s tuple or None (P[k] = 0); boxes (K,4) fp32; radius, zradius: disc and z-norm radius.  Host arithmetic
+    (sn2_parcels_table); SN2_EINVAL / SN2_ELIMIT raise.  L, count_ws_words, znorm_ws_words as the library states them."""
+
+    def __init__(self, T, P, grids, boxes, radius: float, zradius: float):
+        T = np.ascontiguousarray(np.asarray(T, dtype=np.int64).reshape(-1))
+        K = len(T)
+        P = np.ascontiguousarray(np.asarray(P, dtype=np.int64).reshape(-1))
+        boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+        if len(P) != K or len(grids) != K or len(boxes) != K:
+            raise ValueError("ParcelTable: T, P, grids and boxes need one entry per parcel")
+        if K and (P.max() >= 2 ** 31 or P.min() < 0):
+            raise ValueError("ParcelTable: P must fit a non-negative int32")
+        gxy = np.zeros((K, 2), dtype=np.int32)
+        geo = np.zeros((K, 3), dtype=np.float64)
+        for k, g in enumerate(grids):
+            if (g is None) != (P[k] == 0):
+                raise ValueError("ParcelTable: a parcel has a centre grid iff it has centres")
+            if g is not None:
+                gxy[k] = g[2:4]
+                geo[k] = g[4:7]
+        GX, GY = np.ascontiguousarray(gxy[:, 0]), np.ascontiguousarray(gxy[:, 1])
+        self.host = np.zeros((K + 1, _lib.SN2_PARCELS_COLS), dtype=np.int64)
+        L, cw, zw = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
+        p32 = P.astype(np.int32)
+        check(_lib.load().sn2_parcels_table(K, T.ctypes.data, p32.ctypes.data, GX.ctypes.data, GY.ctypes.data, geo.ctypes.data,
+                                            boxes.ctypes.data, float(radius), float(zradius), self.host.ctypes.data, ctypes.byref(L),
+                                            ctypes.byref(cw), ctypes.byref(zw)), "sn2_parcels_table")
+        self.K, self.L, self.count_ws_words, self.znorm_ws_words = K, L.value, cw.value, zw.value
+        self.radius, self.zradius = float(radius), float(zradius)
+        last = self.host[K]
+        self.T_all, self.rows, self.P_all, self.entries, self.csr_words, self.zcells = (int(last[c]) for c in (0, 2, 3, 5, 6, 12))
+        self.dev = None
+
+
+def _chk_parcels(arena, table: ParcelTable):
+    _chk(arena, F32, (10, table.T_all), "arena")
+    _chk(table.dev, I64, (table.K + 1, _lib.SN2_PARCELS_COLS), "table.dev")
+
+
+def parcels_count(arena: torch.Tensor, table: ParcelTable, centers: torch.Tensor, cell_start: torch.Tensor, cell_items: torch.Tensor):
+    """include/strata_hip.h: sn2_parcels_count.  centers (P_all,2) f32, cell_start (csr_words) i32, cell_items i32: the parcels'
+    centres and centre grids end to end -> (prefix (entries+1) i32, plot_start (P_all+1) i64 with the total last)."""
+    _chk_parcels(arena, table)
+    _chk(centers, F32, (table.P_all, 2), "centers")
+    _chk(cell_start, I32, (table.csr_words,), "cell_start")
+    _chk(cell_items, I32, None, "cell_items")
+    dev = arena.device
+    ws = torch.empty(table.count_ws_words + 4, dtype=I32, device=dev)
+    prefix = torch.empty(table.entries + 1, dtype=I32, device=dev)
+    starts = torch.empty(table.P_all + 2, dtype=I64, device=dev)           # plot_start, then the scan's own total word
+    _call("sn2_parcels_count", _ptr(arena), table.K, table.host.ctypes.data, _ptr(table.dev), _ptr(centers), _ptr(cell_start),
+          _ptr(cell_items), table.radius, _ptr(ws), table.count_ws_words, _ptr(prefix), _ptr(starts[table.P_all + 1:]), _ptr(starts),
+          _stream())
+    return prefix, starts[:table.P_all + 1]
+
+
+def parcels_fill(arena: torch.Tensor, table: ParcelTable, centers: torch.Tensor, cell_start: torch.Tensor, cell_items: torch.Tensor,
+                 prefix: torch.Tensor, plot_base: torch.Tensor, sum_n: int):
+    """include/strata_hip.h: sn2_parcels_fill.  prefix: parcels_count's (consumed); plot_base (P_all) i32, INT_MIN = plot dropped
+    -> raw (10,sum_n) f32 (z row not written: parcels_znorm), point_index (sum_n) i32, relative to the plot's own parcel."""
+    _chk_parcels(arena, table)
+    _chk(centers, F32, (table.P_all, 2), "centers")
+    _chk(cell_start, I32, (table.csr_words,), "cell_start")
+    _chk(cell_items, I32, None, "cell_items")
+    _chk(prefix, I32, (table.entries + 1,), "prefix")
+    _chk(plot_base, I32, (table.P_all,), "plot_base")
+    raw = torch.empty(10, sum_n, dtype=F32, device=arena.device)
+    pidx = torch.empty(sum_n, dtype=I32, device=arena.device)
+    _call("sn2_parcels_fill", _ptr(arena), table.K, table.host.ctypes.data, _ptr(table.dev), _ptr(centers), _ptr(cell_start),
+          _ptr(cell_items), table.radius, _ptr(prefix), _ptr(plot_base), int(sum_n), _ptr(raw), _ptr(pidx), _stream())
+    return raw, pidx
+
+
+def parcels_znorm(arena: torch.Tensor, table: ParcelTable, offsets: torch.Tensor, centers: torch.Tensor, plot_parcel: torch.Tensor,
+                  point_index: torch.Tensor, raw: torch.Tensor):
+    """include/strata_hip.h: sn2_parcels_znorm.  offsets (P+1) i32, centers (P,2) f32, plot_parcel (P) i32 of the KEPT plots.
+    Writes raw's z row in place, plot by plot as `parcel_znorm` does for the plot's own parcel."""
+    _chk_parcels(arena, table)
+    P = centers.shape[0]
+    _chk(centers, F32, (P, 2), "centers")
+    _chk(offsets, I32, (P + 1,), "offsets")
+    _chk(plot_parcel, I32, (P,), "plot_parcel")
+    sum_n = point_index.shape[0]
+    _chk(point_index, I32, (sum_n,), "point_index")
+    _chk(raw, F32, (10, sum_n), "raw")
+    ws = torch.empty(table.znorm_ws_words + 4, dtype=I32, device=arena.device)
+    _call("sn2_parcels_znorm", _ptr(arena), table.K, table.host.ctypes.data, _ptr(table.dev), table.zradius, table.radius, _ptr(offsets),
+          _ptr(centers), _ptr(plot_parcel), P, _ptr(point_index), sum_n, _ptr(ws), table.znorm_ws_words, _ptr(raw), _stream())
+    return raw
+
+
 def sa_order_len(B: int, M: int) -> int:
     """SN2_SA_ORDER_WORDS of include/strata_hip.h."""
     return _host("sn2_sa_order_words", int(B), int(M))

@@ -6,6 +6,7 @@ by `predict.py`, without the GIS file I/O.
     for batch in plots.batches(args, 20): ...           # the dicts `inference.predict_parcel` takes
     mosaic, plots = predict_parcel_cloud(model, cloud, args, shape=[exterior, *holes])
     report = mosaic.report([exterior, *holes])          # bands cropped to the polygon, PRED_BASSE / PRED_INTER / PRED_HAUTE
+    plots = prepare_parcels(clouds, args, shapes=shapes) # K parcels in one pass over a cloud arena (ParcelClouds, csrc/parcels.hip)
 
 Rules kept from the reference (the centres in `parcel_plot_centers`, the discs and the z-normalisation in
 csrc/parcel.hip):
@@ -348,22 +349,168 @@ class ParcelSet(ParcelPlots):
             yield d
 
 
-def prepare_parcels(clouds, args, shapes=None, keeps=None, device=None, min_points: int = MIN_POINTS) -> ParcelSet:
-    """`prepare_parcel` of every cloud, unchanged, concatenated into a `ParcelSet`.  shapes: per parcel the rings of its
-    polygon or None -- the lattice is filtered by `polygon_keep(shape, shape_buffer(args))` --; keeps: per parcel a `keep`
-    callable or None, which goes before the shape."""
-    K = len(clouds)
+@dataclass
+class ParcelClouds:
+    """K parcel clouds in ONE (10, T_all) fp32 device array, channel-major: parcel k owns the columns point_start[k] ..
+    point_start[k+1] (host, int64).  What the batched `prepare_parcels` works on (csrc/parcels.hip).  The arena is not to be
+    written after `from_clouds`: `boxes` folds into a state that already holds what it found before."""
+    arena: torch.Tensor
+    point_start: np.ndarray
+    _starts_host: np.ndarray = None
+    _starts_dev: torch.Tensor = None
+    _box_state: torch.Tensor = None
+
+    @property
+    def K(self) -> int:
+        return len(self.point_start) - 1
+
+    @classmethod
+    def from_clouds(cls, clouds, device=None) -> "ParcelClouds":
+        """clouds: K arrays (10,T>0), numpy or tensors -> one concatenation; host arrays are joined on the host and uploaded
+        once.  device: None = that of the first device tensor, else the current HIP device."""
+        clouds = list(clouds)
+        if len(clouds) == 0:
+            raise ValueError("ParcelClouds: no parcel")
+        for c in clouds:
+            if len(getattr(c, "shape", ())) != 2 or c.shape[0] != 10 or c.shape[1] == 0:
+                raise ValueError(f"ParcelClouds: expected (10,T) with T > 0, got {tuple(getattr(c, 'shape', ()))}")
+        T = np.array([c.shape[1] for c in clouds], dtype=np.int64)
+        if T.sum() >= 2 ** 31:
+            raise ValueError("ParcelClouds: at most 2^31 - 1 points in all")
+        on_dev = [c for c in clouds if isinstance(c, torch.Tensor) and c.is_cuda]
+        dev = torch.device(device) if device is not None else (on_dev[0].device if on_dev else torch.device("cuda"))
+        if not on_dev:
+            host = np.concatenate([np.asarray(c, dtype=np.float32) for c in clouds], axis=1)
+            arena = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+        else:
+            arena = torch.cat([torch.as_tensor(c).to(device=dev, dtype=torch.float32) for c in clouds], dim=1).contiguous()
+        starts = ops.parcels_bbox_starts(T)
+        starts_dev, state = ops.pack_upload([starts, ops.parcels_bbox_identity(len(T))], dev)
+        return cls(arena, starts[0].copy(), starts, starts_dev, state)
+
+    def cloud(self, k: int) -> torch.Tensor:
+        """parcel k's (10,T_k) view of the arena"""
+        return self.arena[:, int(self.point_start[k]):int(self.point_start[k + 1])]
+
+    def boxes(self) -> np.ndarray:
+        """(K,4) fp32 = x_min, y_min, x_max, y_max of every parcel (`cloud[:2].min(1)`, `.max(1)`): one launch, one read."""
+        with torch.cuda.device(self.arena.device):
+            state = ops.parcels_bbox(self.arena, self._starts_host, self._starts_dev, self._box_state)
+        return ops.parcels_bbox_decode(state.cpu().numpy())
+
+
+def _keep_of(k, args, shapes, keeps):
+    keep = keeps[k] if keeps is not None else None
+    if keep is None and shapes is not None and shapes[k] is not None:
+        keep = polygon_keep(shapes[k], shape_buffer(args))
+    return keep
+
+
+def _host_lattices(boxes, args, shapes, keeps, radius):
+    """Per parcel, on the host and by the functions `prepare_parcel` uses: (centres (P,2) fp32, `center_grid`'s tuple or None)."""
+    out = []
+    for k, box in enumerate(boxes):
+        centers = parcel_plot_centers(box[0], box[2], box[1], box[3], args, _keep_of(k, args, shapes, keeps))
+        centers = np.ascontiguousarray(np.asarray(centers, dtype=np.float32).reshape(-1, 2))
+        out.append((centers, center_grid(centers, radius, (box[0], box[1], box[2], box[3])) if len(centers) else None))
+    return out
+
+
+def _empty_set(K, dev) -> ParcelSet:
+    e = _empty(dev)
+    return ParcelSet(e.raw, e.offsets, e.point_index, e.centers, e.n_points, e.plot_index, [], e.centers_host,
+                     np.zeros(0, dtype=np.int64), np.zeros(K + 1, dtype=np.int64))
+
+
+def _prepare_batched(pc: ParcelClouds, args, shapes, keeps, min_points: int, strict: bool):
+    """The batched sequence of `prepare_parcels` -> ParcelSet; None when a limit of the arena kernels is exceeded and `strict` is
+    off (the caller then loops)."""
+    K, dev = pc.K, pc.arena.device
+    radius = args.diam_meters // 2
+    zradius = float(getattr(args, "znorm_radius_in_meters", 1.5))
+    boxes = pc.boxes()                                                                   # read 1
+    lat = _host_lattices(boxes, args, shapes, keeps, radius)
+    centers = [c if g is not None else c[:0] for c, g in lat]                            # no centre within reach: none at all
+    grids = [g for _, g in lat]
+    try:
+        table = ops.ParcelTable(np.diff(pc.point_start), [len(c) for c in centers], grids, boxes, radius, zradius)
+    except ops.StrataHipError as e:
+        if strict or "SN2_ELIMIT" not in str(e):
+            raise
+        return None
+    if table.P_all == 0:
+        return _empty_set(K, dev)
+    cen_all = np.concatenate(centers).astype(np.float32).reshape(-1, 2)
+    item0 = np.concatenate([[0], np.cumsum([len(g[1]) for g in grids if g is not None])])
+    cell_start = np.concatenate([g[0] + np.int32(o) for g, o in zip([g for g in grids if g is not None], item0)]).astype(np.int32)
+    cell_items = np.concatenate([g[1] for g in grids if g is not None]).astype(np.int32)
+    with torch.cuda.device(dev):
+        table.dev, cen_dev, start_dev, items_dev = ops.pack_upload([table.host, cen_all, cell_start, cell_items], dev)
+        prefix, plot_start = ops.parcels_count(pc.arena, table, cen_dev, start_dev, items_dev)
+        starts = plot_start.cpu().numpy()                                                # read 2
+        if starts[-1] >= 2 ** 31:
+            raise ValueError(f"prepare_parcels: {starts[-1]} plot points in all discs of all parcels, at most 2^31 - 1 in one "
+                             "batched pass: prepare the parcels with batched=False")
+        counts = np.diff(starts)
+        kept = counts >= min_points
+        if not kept.any():
+            return _empty_set(K, dev)
+        n_points = counts[kept].astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum(n_points)])
+        base = np.full(table.P_all, INT_MIN, dtype=np.int64)
+        base[kept] = offsets[:-1] - starts[:-1][kept]
+        parcel_all = np.repeat(np.arange(K, dtype=np.int64), [len(c) for c in centers])
+        parcel_of = parcel_all[kept]
+        centers_kept = np.ascontiguousarray(cen_all[kept])
+        base_dev, offsets_dev, cen_kept, of_dev = ops.pack_upload(
+            [base.astype(np.int32), offsets.astype(np.int32), centers_kept, parcel_of.astype(np.int32)], dev)
+        raw, pidx = ops.parcels_fill(pc.arena, table, cen_dev, start_dev, items_dev, prefix, base_dev, int(offsets[-1]))
+        ops.parcels_znorm(pc.arena, table, offsets_dev, cen_kept, of_dev, pidx, raw)
+    c0 = table.host[:K, 3]
+    plot_index = np.nonzero(kept)[0] - c0[parcel_of]                                     # the plot's index among its parcel's centres
+    per_parcel = np.bincount(parcel_of, minlength=K).astype(np.int64)
+    return ParcelSet(raw, offsets_dev, pidx, cen_kept, n_points, plot_index.astype(np.int64),
+                     [plot_id(i, c) for i, c in zip(plot_index, centers_kept)], centers_kept, parcel_of,
+                     np.concatenate([[0], np.cumsum(per_parcel)]))
+
+
+def prepare_parcels(clouds, args, shapes=None, keeps=None, device=None, min_points: int = MIN_POINTS, batched=None) -> ParcelSet:
+    """The plots of K parcels as a `ParcelSet`.  clouds: a list of (10,T) clouds or a `ParcelClouds`.  shapes: per parcel the
+    rings of its polygon or None -- the lattice is filtered by `polygon_keep(shape, shape_buffer(args))` --; keeps: per parcel a
+    `keep` callable or None, which goes before the shape.
+    batched=False: `prepare_parcel` of every cloud, unchanged, concatenated.  batched=True: all parcels in one pass over a cloud
+    arena (csrc/parcels.hip) -- the boxes (device-to-host read 1), the lattices and centre grids on the host by the functions
+    `prepare_parcel` uses, one packed upload, count, the plots' starts (read 2), kept / offsets / plot_base on the host, one
+    packed upload, fill, z-norm -- about 16 launches and 2 reads for the set instead of as many per parcel.  The `ParcelSet` is
+    the loop's, byte for byte.  More than 2^31 - 1 hits over all parcels raise ValueError (the loop's limit is per parcel).
+    batched=None: batched when K >= 2 and the arena kernels' limits hold (2^31 points, 2^28 (plot, row) entries and centre
+    cells, 2^26 z-norm cells in all), else the loop."""
+    pc = clouds if isinstance(clouds, ParcelClouds) else None
+    K = pc.K if pc is not None else len(clouds)
     if K == 0:
         raise ValueError("prepare_parcels: no parcel")
     for name, v in (("shapes", shapes), ("keeps", keeps)):
         if v is not None and len(v) != K:
             raise ValueError(f"prepare_parcels: {name} needs one entry per parcel")
-    parts = []
-    for k, cloud in enumerate(clouds):
-        keep = keeps[k] if keeps is not None else None
-        if keep is None and shapes is not None and shapes[k] is not None:
-            keep = polygon_keep(shapes[k], shape_buffer(args))
-        parts.append(prepare_parcel(cloud, args, keep=keep, device=device, min_points=min_points))
+    min_points = int(min_points)
+    if min_points < 1:
+        raise ValueError("prepare_parcels: min_points must be at least 1")
+    if batched is None:
+        batched = K >= 2 and (pc is not None or (all(len(getattr(c, "shape", ())) == 2 for c in clouds) and
+                                                 sum(int(c.shape[1]) for c in clouds) < 2 ** 31))
+        strict = False
+    else:
+        strict = True
+    if batched:
+        if pc is None:
+            pc = ParcelClouds.from_clouds(clouds, device)
+        out = _prepare_batched(pc, args, shapes, keeps, min_points, strict)
+        if out is not None:
+            return out
+    if pc is not None:
+        clouds = [pc.cloud(k) for k in range(K)]
+    parts = [prepare_parcel(cloud, args, keep=_keep_of(k, args, shapes, keeps), device=device, min_points=min_points)
+             for k, cloud in enumerate(clouds)]
     dev = parts[0].raw.device
     counts = np.array([len(p) for p in parts], dtype=np.int64)
     n_points = np.concatenate([p.n_points for p in parts]).astype(np.int64)
@@ -378,14 +525,14 @@ def prepare_parcels(clouds, args, shapes=None, keeps=None, device=None, min_poin
 
 
 def predict_parcels(model, clouds, args, shapes=None, batch_size: int = 512, sampler="device", seed=None,
-                    fps_start: Optional[int] = None, prefetch: int = 3, n_live: bool = True, rs=np.random):
-    """K parcels predicted in shared batches: `prepare_parcels`, a `MosaicAtlas` with one canvas per parcel, and
+                    fps_start: Optional[int] = None, prefetch: int = 3, n_live: bool = True, rs=np.random, batched=None):
+    """K parcels predicted in shared batches: `prepare_parcels` (batched: as there), a `MosaicAtlas` with one canvas per parcel, and
     `inference.predict_parcel`'s prefetching loop over the set's batches, which cut across parcels -- each batch ends in ONE
     `atlas.add` -> (MosaicAtlas, ParcelSet).  `atlas.report(shapes)` gives every parcel's cropped bands and band means with one
     device-to-host read.  Canvas k holds the bytes of `predict_parcel_cloud(model, clouds[k], ..., key_base=k << 32)`'s mosaic
     (an eval forward of a plot does not depend on the batch it is in)."""
     check_sampler(sampler)
-    plots = prepare_parcels(clouds, args, shapes=shapes)
+    plots = prepare_parcels(clouds, args, shapes=shapes, batched=batched)
     atlas = MosaicAtlas.for_plots(plots, args)
     if len(plots):
         predict_batches(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live), args,
