@@ -127,15 +127,13 @@ size_t sn2_fps_ws_ctl_offset(int B, int N);
 size_t sn2_fps_ws_rank_offset(int B, int N);
 int sn2_fps(const float *pos_soa, int B, int N, int M, const int *start, int *idx, float *cpos_soa,
             float *cpos_aos, int *order_ws, void *stream);
-/* The same with a choice of kernel for the bucketed path.  waves = 0 (what sn2_fps passes): the shortest pass -- the
- * multi-workgroup kernel wherever the batch fits the chip (B * P workgroups resident at once), else one workgroup of 16 waves
- * per plot.  16 / 8: one workgroup of 16 / 8 waves per plot (8: a 9 % longer pass that leaves half of each occupied CU to
- * concurrent kernels: the setting of a pipelined loop where the pass runs beside another batch's feature kernels).
- * 4: four waves per plot, for passes over hundreds of plots of at most 16 384 points (two or more FPS workgroups per CU:
- * parcel inference); larger plots take 8.
- * 32 + P / 64 + P, P = 2, 4, 8: P workgroups of 16 / 8 waves per plot (each owns every P-th bucket of the plot's Morton order;
- * one exchange of tagged 8-byte granules through L2 per super-round; falls back to 16 when B * P workgroups do not fit).
- * 1: one sample per arg-max round (round 1's kernel, kept for cross-checks and timing comparisons).
+/* The same with a choice of kernel for the bucketed path.  waves = 0 (what sn2_fps passes): the shortest pass.  16 / 8 / 4: one
+ * workgroup of that many waves per plot (8: a 9 % longer pass that leaves half of each occupied CU to concurrent kernels: the
+ * setting of a pipelined loop where the pass runs beside another batch's feature kernels; 4: for passes over hundreds of small
+ * plots, two or more FPS workgroups per CU: parcel inference).  32 + P / 64 + P, P = 2, 4, 8: P workgroups of 16 / 8 waves per
+ * plot (each owns every P-th bucket of the plot's Morton order; one exchange of tagged 8-byte granules through L2 per
+ * super-round).  1: one sample per arg-max round (round 1's kernel, kept for cross-checks and timing comparisons).
+ * What a request becomes for a given size -- the kernel, and every fall-back -- is sn2_fps_route ("Routes" below).
  * Same indices whichever runs. */
 int sn2_fps_waves(const float *pos_soa, int B, int N, int M, const int *start, int *idx, float *cpos_soa,
                   float *cpos_aos, int *order_ws, int waves, void *stream);
@@ -1184,6 +1182,38 @@ int sn2_adam_step_images_dev(float *param, float *grad_images, int replicas, int
  * (at most 131 072), unless the plots are many (B > 32) and small (N <= 4096), M > 16, B*N a multiple of 4.  Otherwise the
  * brute-force kernels run and the workspace is NOT touched: nobody may hand it to sn2_ball_query / sn2_three_nn. */
 int sn2_fps_fills_ws(int B, int N, int M);
+/* Which kernel sn2_fps_live (and so sn2_fps, sn2_fps_waves, sn2_fps_status) launches: the plan the entry point itself runs before
+ * its first launch, with have_ws = "a 16-byte aligned order_ws was given" and cus = the device's compute units.  0 and *out, or
+ * the negative code of the entry point (no pointer but `out` is dereferenced): SN2_EINVAL for B, N, M <= 0, M > N or an unknown
+ * `waves`, then SN2_ELIMIT for more than 32 768 points without a bucketed route (which ends at 131 072).
+ *   BRUTE    !(have_ws && sn2_fps_fills_ws): fps_kernel<rung = points per thread, 64 * nw threads> -- 1, 2, 4 points on 256 threads
+ *            up to 1024 points, then 2 .. 32 on 1024 threads (32: the form that keeps z in LDS); more than 32 plots of 2049 ..
+ *            4096 points: 16 points on 256 threads.  `waves` only has to be a known code.
+ *   CLUSTER  fps_cluster_kernel<rung, nw, p, lds_points>: p workgroups of nw waves per plot, then a REPAIR launch (SPEC with 16
+ *            waves and `repair` slots, gated by the workspace's control words).  Asked for with waves = 32 + p (16 waves) or
+ *            64 + p (8 waves), p = 2, 4, 8, and taken where it FITS: B * p <= cus, 2 * p * nw <= buckets <= 512 * p, buckets =
+ *            ceil(N / 64); waves = 0 takes the first of p = 8, 4, 2 with 8 waves that fits.  rung = the slots per wave that hold
+ *            ceil(buckets / p) buckets: 2, 4 .. 64 (16 waves: .. 32).  lds_points: the workgroup's points stay in LDS (they
+ *            and the sample log fit 150 KB, at most 96 slots per workgroup).
+ *   SPEC     fps_spec_kernel<rung, nw>: one workgroup per plot.  waves = 16, 8, 4; 0 and the cluster codes where nothing fits
+ *            (16 waves).  4 waves exist up to 16 384 points and become 8 above, 8 exist up to 32 768 and become 16.  rung = the
+ *            slots per wave that hold the buckets, at least 4 / 8 / 32 with 16 / 8 / 4 waves (.. 128 / 64 / 64).
+ *   ROUND    fps_bucket_kernel<rung, 16>: waves = 1, one sample per arg-max round; rung as SPEC's with 16 waves.
+ * Same indices whichever runs. */
+#define SN2_FPS_FORM_BRUTE 0
+#define SN2_FPS_FORM_ROUND 1
+#define SN2_FPS_FORM_SPEC 2
+#define SN2_FPS_FORM_CLUSTER 3
+typedef struct {
+    int form;       /* SN2_FPS_FORM_* */
+    int nw;         /* waves per workgroup */
+    int p;          /* workgroups per plot: 1 unless CLUSTER */
+    int rung;       /* the template rung: bucket slots per wave (bucketed forms), points per thread (BRUTE) */
+    int lds_points; /* CLUSTER: the workgroup's points stay in LDS */
+    int repair;     /* CLUSTER: slots per wave of the repair launch that follows; 0: no repair launch */
+    int fills_ws;   /* order_ws is filled (every form but BRUTE) */
+} sn2_fps_route_t;
+int sn2_fps_route(int B, int N, int M, int waves, int have_ws, int cus, sn2_fps_route_t *out);
 /* the grid search of sn2_three_nn_xy (and of sn2_three_nn with ws + dst_fps_ws) applies: 128 <= S <= 8192 sources and T > 2048
  * targets; otherwise the full scan of sn2_three_nn runs */
 int sn2_three_nn_uses_grid(int S, int T);

@@ -26,6 +26,7 @@ CONSTANTS = {
     "SN2_CV_SLICE_PLOTS": 1024, "SN2_CV_COLUMNS": 30, "SN2_CV_STATS_DOUBLES": 2 * 30 + 2 * 3 * 8 * 8 + 1, "SN2_CV_MAX_PLOTS": 1 << 24,
     "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
+    "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
     "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256,
 }
@@ -63,6 +64,10 @@ class FP(Structure):  # sn2_fp
                 ("dsrc_stride", c_int), ("dskip", c_void_p), ("dskip_stride", c_int), ("du_scratch", c_void_p),
                 ("scatter_ws", c_void_p), ("scatter_ready", c_int), ("bn_sums_done", c_void_p), ("src_ws", c_void_p),
                 ("act_bf16", c_int), ("row_perm", c_void_p)]
+
+
+class FpsRoute(Structure):  # sn2_fps_route_t
+    _fields_ = [(n, c_int) for n in ("form", "nw", "p", "rung", "lds_points", "repair", "fills_ws")]
 
 
 class LossGrad(Structure):  # sn2_loss_grad
@@ -259,6 +264,7 @@ SIGNATURES = {
     "sn2_net_backward": [POINTER(NetModel), POINTER(NetDims), POINTER(NetGeo), POINTER(NetAct), POINTER(NetBwd), c_void_p],
     # the route predicates ("Routes" of the header): host-only arithmetic, they return 0 / 1
     "sn2_fps_fills_ws": [c_int, c_int, c_int],
+    "sn2_fps_route": [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(FpsRoute)],   # 0 and the route, or the entry point's negative code
     "sn2_three_nn_uses_grid": [c_int, c_int],
     "sn2_fp_rows_small": [c_long],
     "sn2_fp_source_side": [c_long, c_int, c_int],

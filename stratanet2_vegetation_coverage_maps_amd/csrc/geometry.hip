@@ -146,10 +146,21 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ pos, i
     }
 }
 
+// the arguments of sn2_fps_live (include/strata_hip.h), as every launcher below takes them
+struct fps_call {
+    const float* pos;
+    int B, N, M;
+    const int *start, *nl;
+    int* idx;
+    float *cs, *ca;
+    int *ws, *nlo;
+    unsigned* status;
+    hipStream_t st;
+};
+
 template <int PPT, int T, bool ZLDS = false>
-static int launch_fps(const float* pos, int B, int N, int M, const int* start, int* idx, float* cs, float* ca,
-                      const int* nl, int* nlo, hipStream_t st) {
-    hipLaunchKernelGGL((fps_kernel<PPT, T, ZLDS>), dim3(B), dim3(T), 0, st, pos, N, M, start, idx, cs, ca, nl, nlo);
+static int launch_fps(const fps_call& a) {
+    hipLaunchKernelGGL((fps_kernel<PPT, T, ZLDS>), dim3(a.B), dim3(T), 0, a.st, a.pos, a.N, a.M, a.start, a.idx, a.cs, a.ca, a.nl, a.nlo);
     SN2_RETURN_LAUNCH();
 }
 
@@ -973,20 +984,31 @@ static size_t fps_spec_lds_bytes() {
                           // with 12, 5.6 with 16 -- the prefix mostly ends at a candidate touched by an earlier one -- while
                           // the selection's cost grows with K)
 #endif
+// the parts of the workspace (include/strata_hip.h: SN2_FPS_WS_WORDS)
+struct fps_ws_parts {
+    int* order;          // B*N ints
+    float4* sorted;      // B*N float4 (16-byte aligned: B*N*4 bytes offset from a 16-byte aligned base with B*N % 4 == 0)
+    int* grid;           // B*GRID_WORDS ints
+    unsigned* xchg;      // B*FPS_XCHG_WORDS + FPS_CTL_WORDS
+    unsigned* ctl;
+};
+static fps_ws_parts fps_ws_carve(int* ws, int B, int N) {
+    int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);
+    return {ws, reinterpret_cast<float4*>(ws + (size_t)B * N), grid, reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS),
+            reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N))};
+}
+static void launch_spatial_order(const fps_call& a, const fps_ws_parts& w) {
+    launch_spatial_order(a.pos, a.B, a.N, w.order, w.sorted, w.grid, w.xchg, w.ctl, a.nl, a.st);
+}
+
 template <int SPW, int NW = 16>
-static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* start, int* ws, int* idx, float* cs,
-                             float* ca, const int* nl, int* nlo, hipStream_t st, bool speculate = true, bool repair = false,
-                             unsigned* status = nullptr) {
-    int* order = ws;                                               // B*N ints
-    float4* sorted = reinterpret_cast<float4*>(ws + (size_t)B * N);   // B*N float4 (16-byte aligned: B*N*4 bytes offset
-                                                                   // from a 16-byte aligned base with B*N % 4 == 0)
-    int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);                   // B*GRID_WORDS ints
-    unsigned* xchg = reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS);      // B*FPS_XCHG_WORDS + FPS_CTL_WORDS
-    unsigned* ctl = reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N));
+static int launch_fps_bucket(const fps_call& a, bool speculate = true, bool repair = false) {
+    const fps_ws_parts w = fps_ws_carve(a.ws, a.B, a.N);
     // repair = this launch follows fps_cluster_kernel on the same workspace: the tables are there, and the kernel returns at once
-    // unless the control words say that the multi-workgroup pass gave up
-    const unsigned* gate = repair ? ctl : nullptr;
-    if (!repair) launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, nl, st);
+    // unless the control words say that the multi-workgroup pass gave up (the count then goes to the status word)
+    const unsigned* gate = repair ? w.ctl : nullptr;
+    unsigned* status = repair ? a.status : nullptr;
+    if (!repair) launch_spatial_order(a, w);
     if (speculate) {
         constexpr int K = SN2_FPS_K;
         const size_t lds = fps_spec_lds_bytes<SPW, NW, K>();
@@ -995,12 +1017,12 @@ static int launch_fps_bucket(const float* pos, int B, int N, int M, const int* s
         // (Round 4 tried the FPS waves at the highest wave priority, `s_setprio 3`: beside the feature kernels a super-round takes
         // three times as long as alone, and what the pass costs the step follows the time it is resident -- no effect, 0.7652
         // against 0.762 ms per step; round 3 had tried the opposite, the feature kernels raised: none either.)
-        hipLaunchKernelGGL((fps_spec_kernel<SPW, NW, K>), dim3(B), dim3(NW * 64), lds, st, pos, N, M, start, (const int*)order,
-                           sorted, idx, cs, ca, gate, status, nl, nlo);
+        hipLaunchKernelGGL((fps_spec_kernel<SPW, NW, K>), dim3(a.B), dim3(NW * 64), lds, a.st, a.pos, a.N, a.M, a.start,
+                           (const int*)w.order, w.sorted, a.idx, a.cs, a.ca, gate, status, a.nl, a.nlo);
         SN2_RETURN_LAUNCH();
     }
-    hipLaunchKernelGGL((fps_bucket_kernel<SPW, NW>), dim3(B), dim3(NW * 64), 0, st, pos, N, M, start, (const int*)order,
-                       sorted, idx, cs, ca, nlo);
+    hipLaunchKernelGGL((fps_bucket_kernel<SPW, NW>), dim3(a.B), dim3(NW * 64), 0, a.st, a.pos, a.N, a.M, a.start,
+                       (const int*)w.order, w.sorted, a.idx, a.cs, a.ca, a.nlo);
     SN2_RETURN_LAUNCH();
 }
 
@@ -1729,78 +1751,163 @@ extern "C" int sn2_debug_fps_spin_limit(unsigned sweeps) {
     fps_cluster_spin_limit = sweeps ? sweeps : FC_SPIN_LIMIT;
     return 0;
 }
-template <int SPW, int NW, int P>
-static int launch_fps_cluster(const float* pos, int B, int N, int M, const int* start, int* ws, int* idx, float* cs,
-                              float* ca, const int* nl, int* nlo, hipStream_t st) {
-    constexpr int NBL = SPW * NW, NE = FC_TP * P;
-    int* order = ws;
-    float4* sorted = reinterpret_cast<float4*>(ws + (size_t)B * N);
-    int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);
-    unsigned* xchg = reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS);
-    unsigned* ctl = reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N));
-    launch_spatial_order(pos, B, N, order, sorted, grid, xchg, ctl, nl, st);
-    const int log_cap = M <= 4096 ? M : 0;           // the samples of a plot stay in LDS until the end (16 B each) when they fit
-    const size_t lds0 = (size_t)NBL * 16 + 8 * 16 + 2 * (size_t)(NE + 16) * 16 + 2 * FC_TP * 16 + (size_t)NBL * 4 * 9 + 72 * 4 + 8 * 4 + 16 +
-                        (size_t)log_cap * 16;
-    // the workgroup's points in LDS (64 KB at 8 x 8 x 8) when they fit beside the rest: phase B then never waits for L2
-    constexpr bool can_lp = (size_t)NBL * 64 * 16 <= 96 * 1024;
-    if (can_lp && lds0 + (size_t)NBL * 64 * 16 <= 150 * 1024 && fps_cluster_lds_points) {
-        const size_t lds = lds0 + (size_t)NBL * 64 * 16;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_cluster_kernel<SPW, NW, P, can_lp>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((fps_cluster_kernel<SPW, NW, P, can_lp>), dim3(B * P), dim3(NW * 64), lds, st, pos, B, N, M, start,
-                           (const int*)order, sorted, idx, cs, ca, reinterpret_cast<fc_u64*>(xchg), ctl, log_cap, fps_cluster_tau_keep,
-                           fps_cluster_spin_limit, nlo);
-        SN2_RETURN_LAUNCH();
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_cluster_kernel<SPW, NW, P, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0);
-    hipLaunchKernelGGL((fps_cluster_kernel<SPW, NW, P, false>), dim3(B * P), dim3(NW * 64), lds0, st, pos, B, N, M, start,
-                       (const int*)order, sorted, idx, cs, ca, reinterpret_cast<fc_u64*>(xchg), ctl, log_cap, fps_cluster_tau_keep,
-                       fps_cluster_spin_limit, nlo);
-    SN2_RETURN_LAUNCH();
-}
-
-// P workgroups of NW waves per plot; the slots per wave follow from the plot size
-template <int NW, int P>
-static int dispatch_fps_cluster(const float* pos, int B, int N, int M, const int* start, int* ws, int* idx, float* cs,
-                                float* ca, const int* nl, int* nlo, hipStream_t st) {
-    const int nbl = sn2_cdiv(sn2_cdiv(N, 64), P);          // buckets per workgroup
-    const int spw = sn2_cdiv(nbl, NW);
-    if (spw <= 2) return launch_fps_cluster<2, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
-    if (spw <= 4) return launch_fps_cluster<4, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
-    if (spw <= 8) return launch_fps_cluster<8, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
-    if (spw <= 16) return launch_fps_cluster<16, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
-    if (spw <= 32) return launch_fps_cluster<32, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
-    if constexpr (NW <= 8) {     // (64 slots x 16 waves = 16 bucket values per lane of the selecting wave: spills at 128 VGPRs)
-        if (spw <= 64) return launch_fps_cluster<64, NW, P>(pos, B, N, M, start, ws, idx, cs, ca, nl, nlo, st);
-    }
-    return SN2_ELIMIT;
-}
-
-// the single-workgroup kernel for a plot of N points, 16 waves (what `waves = 16` runs); repair = behind fps_cluster_kernel
-static int dispatch_fps_bucket16(const float* pos_soa, int B, int N, int M, const int* start, int* order_ws, int* idx,
-                                 float* cpos_soa, float* cpos_aos, const int* nl, int* nlo, hipStream_t st, bool spec, bool repair,
-                                 unsigned* status) {
-    if (N <= 4096) return launch_fps_bucket<4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
-    if (N <= 8192) return launch_fps_bucket<8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
-    if (N <= 16384) return launch_fps_bucket<16>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
-    if (N <= 32768) return launch_fps_bucket<32>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
-    if (N <= 65536) return launch_fps_bucket<64>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
-    if (N <= 131072) return launch_fps_bucket<128>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, repair, status);
-    return SN2_ELIMIT;
+// dynamic LDS of fps_cluster_kernel: its tables and records, the plot's samples until the end when they fit (16 B each), and
+// -- `points` -- the workgroup's own points (64 KB at 8 x 8 x 8) when they fit beside the rest: phase B then never waits for L2
+static int fps_cluster_log_cap(int M) { return M <= 4096 ? M : 0; }
+static constexpr bool fps_cluster_points_fit(int nbl) { return (size_t)nbl * 64 * 16 <= 96 * 1024; }
+static size_t fps_cluster_lds(int nbl, int P, int log_cap, bool points) {
+    return (size_t)nbl * 16 + 8 * 16 + 2 * (size_t)(FC_TP * P + 16) * 16 + 2 * FC_TP * 16 + (size_t)nbl * 4 * 9 + 72 * 4 + 8 * 4 + 16 +
+           (size_t)log_cap * 16 + (points ? (size_t)nbl * 64 * 16 : 0);
 }
 
 // Routes (include/strata_hip.h).  Many small plots (the parcel loop's level 2: 256 .. 512 plots of 2 500 points -> 625): the
 // bucketed kernel has 40 buckets to prune among and takes 2 us per sample with 16 waves per plot (1.1 ms at half of every CU's
 // wave slots); the brute-force kernel with the plot's points in the registers of FOUR waves takes the whole plot per round and
-// is shorter.  N <= 131 072: 128 bucket slots per wave, the largest single-workgroup kernel (dispatch_fps_bucket16) -- larger
-// plots are SN2_ELIMIT with or without a workspace: the brute-force kernels that sn2_fps_status falls through to end at
-// 32 768 points.
+// is shorter.  N <= 131 072: 128 bucket slots per wave, the largest single-workgroup kernel -- larger plots are SN2_ELIMIT with
+// or without a workspace: the brute-force kernels end at 32 768 points.
 static bool fps_many_small(int B, int N) { return N <= 4096 && B > 32; }
 extern "C" int sn2_fps_fills_ws(int B, int N, int M) {
     return N > 2048 && !fps_many_small(B, N) && M > 16 && ((long)B * N) % 4 == 0 && N <= 131072;
 }
+// the template rung: the smallest `lo` * 2^k slots (points) per wave at which nw waves hold the plot's 64-point buckets
+static int fps_rung(int buckets, int nw, int lo) {
+    while (lo * nw < buckets) lo *= 2;
+    return lo;
+}
+
+// THE route of sn2_fps_live, decided before any launch (include/strata_hip.h, sn2_fps_route, states the rule): host arithmetic
+extern "C" int sn2_fps_route(int B, int N, int M, int waves, int have_ws, int cus, sn2_fps_route_t* out) {
+    if (!out || B <= 0 || N <= 0 || M <= 0 || M > N) return SN2_EINVAL;
+    sn2_fps_route_t r = {SN2_FPS_FORM_SPEC, 16, 1};         // the request: one workgroup of nw waves per plot, or p workgroups
+    switch (waves) {
+    case 0: case 16: break;
+    case 1: r.form = SN2_FPS_FORM_ROUND; break;             // round 1's kernel; cross-checks and timing comparisons
+    case 8: case 4: r.nw = waves; break;
+    case 34: case 36: case 40: r.p = waves - 32; break;
+    case 66: case 68: case 72: r.nw = 8, r.p = waves - 64; break;
+    default: return SN2_EINVAL;
+    }
+    const int buckets = sn2_cdiv(N, 64);
+    r.fills_ws = have_ws && sn2_fps_fills_ws(B, N, M);
+    if (!r.fills_ws) {                  // the plot in the registers of one workgroup: rung = points per thread, 256 or 1024 threads
+        const bool small = N <= 1024, many = N > 2048 && fps_many_small(B, N);
+        r = {SN2_FPS_FORM_BRUTE, small || many ? 4 : 16, 1, many ? 16 : fps_rung(buckets, small ? 4 : 16, small ? 1 : 2)};
+        if (r.rung > 32) return SN2_ELIMIT;
+        *out = r;
+        return 0;
+    }
+    // bucketed (exact, see above): up to 128 bucket slots per wave = 131 072 points per plot.
+    // p workgroups per plot: all B * p resident at once, at least two buckets per wave; else the single-workgroup kernel, 16 waves
+    auto fits = [&](int p, int nw) { return (long)B * p <= cus && buckets >= 2 * p * nw && buckets <= 512 * p; };
+    // 0 = the shortest pass: several workgroups per plot wherever that fits (measured at 16 x 32 768 -> 1024: 8 workgroups of 8
+    // waves 0.87 ms, 4 of 8 0.99, the single workgroup 1.24; scripts/time_fps_cluster.py)
+    for (int p = 8; waves == 0 && p >= 2 && r.p == 1; p >>= 1)
+        if (fits(p, 8)) r.nw = 8, r.p = p;
+    if (r.p > 1 && !fits(r.p, r.nw)) r.nw = 16, r.p = 1;
+    if (r.p > 1) {
+        r.form = SN2_FPS_FORM_CLUSTER;
+        r.rung = fps_rung(sn2_cdiv(buckets, r.p), r.nw, 2);
+        // (64 slots x 16 waves = 16 bucket values per lane of the selecting wave: spills at 128 VGPRs)
+        if (r.rung > (r.nw <= 8 ? 64 : 32)) return SN2_ELIMIT;
+        r.lds_points = fps_cluster_points_fit(r.rung * r.nw) && fps_cluster_lds_points &&
+                       fps_cluster_lds(r.rung * r.nw, r.p, fps_cluster_log_cap(M), true) <= 150 * 1024;
+        // the repair launch: B workgroups of the 16-wave kernel that read control word 1 and leave -- unless a wait of the pass
+        // gave up (its workgroups are not guaranteed to be resident together), in which case they sample every plot again
+        r.repair = fps_rung(buckets, 16, 4);
+    } else {
+        // waves = 8: half the waves per plot.  Alone the pass is 9 % slower (1.37 vs 1.26 ms at 32 x 32 768: fewer loads in
+        // flight), but it leaves half of its CU's wave slots to whatever else runs: beside the feature pass of a pipelined
+        // training loop the STEP is 2.4 % shorter (0.918 vs 0.940 ms; 4 waves: 2.07 ms alone, 0.922 ms per step).
+        // waves = 4 (plots of at most 16 384 points): half the wave slots again, for passes that share the chip with MANY other
+        // workgroups (the parcel loop: 512 plots per launch = two FPS workgroups per CU); larger plots take the 8-wave kernel
+        // (four waves at 32 768 points -- launch_fps_bucket<128, 4> -- were measured in the training loop: 0.773 against 0.769 ms
+        // per step with eight; not instantiated), and above 32 768 points there are 16 waves or none
+        if (r.nw == 4 && N > 16384) r.nw = 8;
+        if (r.nw == 8 && N > 32768) r.nw = 16;
+        r.rung = fps_rung(buckets, r.nw, r.nw == 16 ? 4 : r.nw == 8 ? 8 : 32);
+    }
+    *out = r;
+    return 0;
+}
+
+// One launcher per form: the route's integers -> the template instantiation, and nothing else
+static int launch_fps_brute(const fps_call& a, const sn2_fps_route_t& r) {
+    switch (r.nw * 100 + r.rung) {
+    case 401: return launch_fps<1, 256>(a);
+    case 402: return launch_fps<2, 256>(a);
+    case 404: return launch_fps<4, 256>(a);
+    case 416: return launch_fps<16, 256>(a);
+    case 1602: return launch_fps<2, 1024>(a);
+    case 1604: return launch_fps<4, 1024>(a);
+    case 1608: return launch_fps<8, 1024>(a);
+    case 1616: return launch_fps<16, 1024>(a);
+    case 1632: return launch_fps<32, 1024, true>(a);
+    default: return SN2_ELIMIT;
+    }
+}
+// SPEC, ROUND (16 waves only) and the repair launch behind CLUSTER (SPEC, 16 waves, gated by the workspace's control words)
+static int launch_fps_single(const fps_call& a, int nw, int spw, bool spec, bool repair) {
+    switch (nw * 1000 + spw) {
+    case 4032: return launch_fps_bucket<32, 4>(a);
+    case 4064: return launch_fps_bucket<64, 4>(a);
+    case 8008: return launch_fps_bucket<8, 8>(a);
+    case 8016: return launch_fps_bucket<16, 8>(a);
+    case 8032: return launch_fps_bucket<32, 8>(a);
+    case 8064: return launch_fps_bucket<64, 8>(a);
+    case 16004: return launch_fps_bucket<4>(a, spec, repair);
+    case 16008: return launch_fps_bucket<8>(a, spec, repair);
+    case 16016: return launch_fps_bucket<16>(a, spec, repair);
+    case 16032: return launch_fps_bucket<32>(a, spec, repair);
+    case 16064: return launch_fps_bucket<64>(a, spec, repair);
+    case 16128: return launch_fps_bucket<128>(a, spec, repair);
+    default: return SN2_ELIMIT;
+    }
+}
+template <int SPW, int NW, int P>
+static int launch_fps_cluster(const fps_call& a, const sn2_fps_route_t& r) {
+    const fps_ws_parts w = fps_ws_carve(a.ws, a.B, a.N);
+    launch_spatial_order(a, w);
+    const int log_cap = fps_cluster_log_cap(a.M);
+    auto launch = [&](auto lp) {
+        constexpr bool LP = decltype(lp)::value;
+        const size_t lds = fps_cluster_lds(SPW * NW, P, log_cap, LP);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_cluster_kernel<SPW, NW, P, LP>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((fps_cluster_kernel<SPW, NW, P, LP>), dim3(a.B * P), dim3(NW * 64), lds, a.st, a.pos, a.B, a.N, a.M, a.start,
+                           (const int*)w.order, w.sorted, a.idx, a.cs, a.ca, reinterpret_cast<fc_u64*>(w.xchg), w.ctl, log_cap,
+                           fps_cluster_tau_keep, fps_cluster_spin_limit, a.nlo);
+        SN2_RETURN_LAUNCH();
+    };
+    if constexpr (fps_cluster_points_fit(SPW * NW)) {
+        if (r.lds_points) return launch(std::true_type{});
+    }
+    return launch(std::false_type{});
+}
+template <int NW, int P>
+static int launch_fps_cluster_slots(const fps_call& a, const sn2_fps_route_t& r) {
+    switch (r.rung) {
+    case 2: return launch_fps_cluster<2, NW, P>(a, r);
+    case 4: return launch_fps_cluster<4, NW, P>(a, r);
+    case 8: return launch_fps_cluster<8, NW, P>(a, r);
+    case 16: return launch_fps_cluster<16, NW, P>(a, r);
+    case 32: return launch_fps_cluster<32, NW, P>(a, r);
+    case 64:
+        if constexpr (NW <= 8) return launch_fps_cluster<64, NW, P>(a, r);
+    }
+    return SN2_ELIMIT;
+}
+static int launch_fps_cluster_form(const fps_call& a, const sn2_fps_route_t& r) {
+    switch (r.nw * 100 + r.p) {
+    case 1602: return launch_fps_cluster_slots<16, 2>(a, r);
+    case 1604: return launch_fps_cluster_slots<16, 4>(a, r);
+    case 1608: return launch_fps_cluster_slots<16, 8>(a, r);
+    case 802: return launch_fps_cluster_slots<8, 2>(a, r);
+    case 804: return launch_fps_cluster_slots<8, 4>(a, r);
+    case 808: return launch_fps_cluster_slots<8, 8>(a, r);
+    default: return SN2_ELIMIT;
+    }
+}
+
 static bool nn_grid_sources(int S) { return S >= 128 && S <= 8192; }      // what the per-plot x,y grid of three_nn_grid_kernel holds in LDS
 extern "C" int sn2_three_nn_uses_grid(int S, int T) { return nn_grid_sources(S) && T > 2048; }
 
@@ -1822,77 +1929,19 @@ extern "C" int sn2_fps_status(const float* pos_soa, int B, int N, int M, const i
     return sn2_fps_live(pos_soa, B, N, M, start, nullptr, idx, cpos_soa, cpos_aos, order_ws, waves, nullptr, status, stream);
 }
 
-// nl = n_live, nlo = n_live_out (include/strata_hip.h): every kernel form below honours both
+// nl = n_live, nlo = n_live_out (include/strata_hip.h): every kernel form honours both
 extern "C" int sn2_fps_live(const float* pos_soa, int B, int N, int M, const int* start, const int* nl, int* idx, float* cpos_soa,
                             float* cpos_aos, int* order_ws, int waves, int* nlo, unsigned* status, void* stream) {
     if (!pos_soa || !idx || !cpos_soa || !cpos_aos || B <= 0 || N <= 0 || M <= 0 || M > N) return SN2_EINVAL;
-    bool cluster = waves == 34 || waves == 36 || waves == 40 || waves == 66 || waves == 68 || waves == 72;
-    if (waves != 0 && waves != 16 && waves != 8 && waves != 4 && waves != 1 && !cluster) return SN2_EINVAL;
-    if (waves == 0) {
-        // the shortest pass: several workgroups per plot wherever that fits (measured at 16 x 32 768 -> 1024: 8 workgroups of 8
-        // waves 0.87 ms, 4 of 8 0.99, the single workgroup 1.24; scripts/time_fps_cluster.py)
-        const int nbk = sn2_cdiv(N, 64);
-        for (int Pc = 8; Pc >= 2 && !cluster; Pc >>= 1) {
-            if ((long)B * Pc <= sn2_cu_count() && nbk >= 2 * Pc * 8 && nbk <= 512 * Pc) {
-                waves = 64 + Pc;
-                cluster = true;
-            }
-        }
+    sn2_fps_route_t r;
+    int rc = sn2_fps_route(B, N, M, waves, order_ws && ((size_t)order_ws) % 16 == 0, sn2_cu_count(), &r);
+    if (rc != 0) return rc;
+    const fps_call a = {pos_soa, B, N, M, start, nl, idx, cpos_soa, cpos_aos, order_ws, nlo, status, (hipStream_t)stream};
+    switch (r.form) {
+    case SN2_FPS_FORM_BRUTE: return launch_fps_brute(a, r);
+    case SN2_FPS_FORM_CLUSTER: rc = launch_fps_cluster_form(a, r); return rc != 0 ? rc : launch_fps_single(a, 16, r.repair, true, true);
+    default: return launch_fps_single(a, r.nw, r.rung, r.form == SN2_FPS_FORM_SPEC, false);
     }
-    const bool spec = waves != 1;      // 1: the one-sample-per-round kernel (round 1's; cross-checks and timing comparisons)
-    hipStream_t st = (hipStream_t)stream;
-    if (order_ws && (((size_t)order_ws) % 16 == 0) && sn2_fps_fills_ws(B, N, M)) {
-        // 32 + P / 64 + P: P = 2, 4 or 8 workgroups of 16 / 8 waves per plot (fps_cluster_kernel); needs at least two buckets
-        // per wave and all B * P workgroups resident at once, else the single-workgroup kernel below runs
-        if (cluster) {
-            const int P = waves & 15, NWc = (waves & 64) ? 8 : 16;
-            const bool fits = (long)B * P <= sn2_cu_count() && sn2_cdiv(N, 64) >= 2 * P * NWc && sn2_cdiv(N, 64) <= 512 * P;
-            if (fits) {
-                int rc;
-                if (waves == 34) rc = dispatch_fps_cluster<16, 2>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-                else if (waves == 36) rc = dispatch_fps_cluster<16, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-                else if (waves == 40) rc = dispatch_fps_cluster<16, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-                else if (waves == 66) rc = dispatch_fps_cluster<8, 2>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-                else if (waves == 68) rc = dispatch_fps_cluster<8, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-                else rc = dispatch_fps_cluster<8, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-                if (rc != 0) return rc;
-                // the repair launch: B workgroups that read control word 1 and leave -- unless a wait of the pass above gave
-                // up (its workgroups are not guaranteed to be resident together), in which case they sample every plot again
-                return dispatch_fps_bucket16(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, true, true, status);
-            }
-            waves = 16;
-        }
-        // bucketed path (exact, see above): up to 128 bucket slots per wave = 131 072 points per plot.
-        // waves = 8: half the waves per plot.  Alone the pass is 9 % slower (1.37 vs 1.26 ms at 32 x 32 768: fewer loads in
-        // flight), but it leaves half of its CU's wave slots to whatever else runs: beside the feature pass of a pipelined
-        // training loop the STEP is 2.4 % shorter (0.918 vs 0.940 ms; 4 waves: 2.07 ms alone, 0.922 ms per step).
-        // waves = 4 (plots of at most 16 384 points): half the wave slots again, for passes that share the chip with MANY other
-        // workgroups (the parcel loop: 512 plots per launch = two FPS workgroups per CU); larger plots take the 8-wave kernel
-        if (waves == 4 && N <= 16384) {
-            if (N <= 8192) return launch_fps_bucket<32, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-            return launch_fps_bucket<64, 4>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-        }
-        // (four waves at 32 768 points -- launch_fps_bucket<128, 4> -- were measured in the training loop: 0.773 against 0.769 ms
-        // per step with eight; not instantiated)
-        if (waves == 4) waves = 8;
-        if (waves == 8 && N <= 32768) {
-            if (N <= 4096) return launch_fps_bucket<8, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-            if (N <= 8192) return launch_fps_bucket<16, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-            if (N <= 16384) return launch_fps_bucket<32, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-            return launch_fps_bucket<64, 8>(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st);
-        }
-        return dispatch_fps_bucket16(pos_soa, B, N, M, start, order_ws, idx, cpos_soa, cpos_aos, nl, nlo, st, spec, false, nullptr);
-    }
-    if (N <= 256) return launch_fps<1, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (N <= 512) return launch_fps<2, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (N <= 1024) return launch_fps<4, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (N <= 2048) return launch_fps<2, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (fps_many_small(B, N)) return launch_fps<16, 256>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (N <= 4096) return launch_fps<4, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (N <= 8192) return launch_fps<8, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (N <= 16384) return launch_fps<16, 1024>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    if (N <= 32768) return launch_fps<32, 1024, true>(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, nl, nlo, st);
-    return SN2_ELIMIT;
 }
 
 extern "C" int sn2_fps(const float* pos_soa, int B, int N, int M, const int* start, int* idx, float* cpos_soa,

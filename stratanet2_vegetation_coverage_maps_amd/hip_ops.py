@@ -5,7 +5,9 @@ kernel is launched (a kernel that faults can take the whole node down) and raise
 Names follow the reference's third-party call sites (model/point_net2.py:9): fps, radius -> ball_query,
 knn_interpolate -> three_nn + the interpolation inside `fp_forward`, PointConv -> `sa_forward`.
 """
+import collections
 import ctypes
+import functools
 import math
 from typing import Optional
 
@@ -344,6 +346,27 @@ def fps_fills_ws(B: int, N: int, m: int) -> bool:
     starts) that ball_query / three_nn may then walk (sn2_fps_fills_ws, the test sn2_fps_status itself makes): handing those
     kernels a workspace nobody filled would send them through garbage cell lists."""
     return bool(_host("sn2_fps_fills_ws", int(B), int(N), int(m)))
+
+
+FPS_FORM_BRUTE, FPS_FORM_ROUND, FPS_FORM_SPEC, FPS_FORM_CLUSTER = (_lib.SN2_FPS_FORM_BRUTE, _lib.SN2_FPS_FORM_ROUND, _lib.SN2_FPS_FORM_SPEC,
+                                                                   _lib.SN2_FPS_FORM_CLUSTER)
+FpsRoute = collections.namedtuple("FpsRoute", [n for n, _ in _lib.FpsRoute._fields_])
+
+
+@functools.lru_cache(maxsize=4096)
+def _fps_route(B, N, m, waves, have_ws, cus) -> FpsRoute:
+    r = _lib.FpsRoute()
+    check(_lib.load().sn2_fps_route(B, N, m, waves, have_ws, cus, r), "sn2_fps_route")
+    return FpsRoute(*(getattr(r, n) for n in FpsRoute._fields))
+
+
+def fps_route(B: int, N: int, m: int, waves: int = 0, bucketed: bool = True, device=None) -> FpsRoute:
+    """sn2_fps_route: the kernel `fps(pos_soa (B,3,N), m, waves=waves, bucketed=bucketed)` launches on `device` (None: the current
+    one) -- form (FPS_FORM_*), waves per workgroup, workgroups per plot, template rung, whether the multi-workgroup kernel keeps its
+    points in LDS, the repair launch's rung, whether the workspace is filled.  The plan sn2_fps_live itself runs: host arithmetic,
+    nothing is launched.  bucketed=False = no workspace handed over, which is how `fps` forces the brute-force kernel."""
+    cus = torch.cuda.get_device_properties(device if device is not None else torch.cuda.current_device()).multi_processor_count
+    return _fps_route(int(B), int(N), int(m), int(waves), int(bool(bucketed)), int(cus))
 
 
 _FPS_STATUS = {}          # device index -> [status word (1,) int32 on the device, count already reported]

@@ -38,9 +38,9 @@ def test_struct_layouts_match_the_header_abi():
     import subprocess
     import tempfile
     from stratanet2_vegetation_coverage_maps_amd import _lib
-    src = ('#include <stdio.h>\n#include "strata_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
+    src = ('#include <stdio.h>\n#include "strata_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
            'sizeof(sn2_block),sizeof(sn2_sa),sizeof(sn2_fp),sizeof(sn2_head),sizeof(sn2_net_layer),sizeof(sn2_net_model),'
-           'sizeof(sn2_net_dims),sizeof(sn2_net_geo),sizeof(sn2_net_act),sizeof(sn2_net_bwd),sizeof(sn2_net_io));return 0;}\n')
+           'sizeof(sn2_net_dims),sizeof(sn2_net_geo),sizeof(sn2_net_act),sizeof(sn2_net_bwd),sizeof(sn2_net_io),sizeof(sn2_fps_route_t));return 0;}\n')
     with tempfile.TemporaryDirectory() as d:
         c = os.path.join(d, "s.c")
         open(c, "w").write(src)
@@ -48,7 +48,7 @@ def test_struct_layouts_match_the_header_abi():
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
         sizes = [int(x) for x in subprocess.check_output([exe]).split()]
     assert sizes == [ctypes.sizeof(c) for c in (_lib.Block, _lib.SA, _lib.FP, _lib.Head, _lib.NetLayer, _lib.NetModel, _lib.NetDims,
-                                                _lib.NetGeo, _lib.NetAct, _lib.NetBwd, _lib.NetIO)]
+                                                _lib.NetGeo, _lib.NetAct, _lib.NetBwd, _lib.NetIO, _lib.FpsRoute)]
 
 
 # (B, N, M1, M2): the metric's shape and a tiny batch
@@ -155,6 +155,13 @@ def test_route_predicates_on_each_side_of_every_boundary():
     # plots beyond the largest bucketed kernel: SN2_ELIMIT with a workspace as without one, before any device work
     assert lib.sn2_fps_status(fake, 1, 131076, 64, None, fake, fake, fake, fake, 0, None, None) == -2
     assert lib.sn2_fps_status(fake, 1, 131076, 64, None, fake, fake, fake, None, 0, None, None) == -2
+    # the plan behind those two refusals, and on each side of the workspace predicate (tests/test_fps_route_host.py: the whole table)
+    r = _lib.FpsRoute()
+    for ws in (1, 0):
+        assert lib.sn2_fps_route(1, 131076, 64, 0, ws, 256, r) == -2 and lib.sn2_fps_route(1, 131072, 64, 3, ws, 256, r) == -1
+    for a, want in fps.items():
+        assert lib.sn2_fps_route(*a, 16, 1, 256, r) == (0 if a[1] <= 131072 else -2), a
+        assert a[1] > 131072 or (r.fills_ws == want and (r.form != _lib.SN2_FPS_FORM_BRUTE) == bool(want)), a
 
 
 def test_argument_checks_return_before_any_device_work():

@@ -15,7 +15,7 @@ from oracle import primitives as P
 from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
 
 import _boundary_plots as bp
-from test_gpu_fps_live import FORMS
+from test_gpu_fps_live import FORMS, assert_form_route
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -66,6 +66,8 @@ def test_fps_every_form_on_mixed_batches(which, waves, bucketed):
     xyz = bp.batch(kinds, N1)
     B = xyz.shape[0]
     assert ops.fps_fills_ws(B, N1, M1) and not ops.fps_fills_ws(B, M1, M2)
+    assert_form_route(B, N1, M1, waves, bucketed)
+    assert ops.fps_route(B, M1, M2, waves=waves, bucketed=bucketed, device=DEV).form == ops.FPS_FORM_BRUTE       # level 2, every form
     dev = xyz.to(DEV)
     for row in (0, 1):
         start, ref, ref_cs = _fps_ref(kinds, N1, M1, row)
@@ -112,6 +114,7 @@ def test_fps_many_small_plots():
     """40 x 2500 -> 625: more than 32 plots of at most 4096 points take the brute-force kernel with 256 threads per plot."""
     kinds, xyz, start, ref, ref_cs = _many_small()
     assert not ops.fps_fills_ws(40, 2500, 625) and ops.fps_fills_ws(32, 2500, 625)
+    assert tuple(ops.fps_route(40, 2500, 625, device=DEV))[:4] == (ops.FPS_FORM_BRUTE, 4, 1, 16)         # fps_kernel<16, 256>
     got = ops.fps(xyz.to(DEV), 625, _dev(start, I32), return_ws=True)
     _assert_fps(got, ref, ref_cs, "40 x 2500")
     assert got[3] is None
@@ -125,7 +128,10 @@ def test_fps_two_bucket_slots_per_lane():
     assert ops.fps_fills_ws(2, n, m)
     start = torch.tensor([n - 1, 7])
     ref = P.fps_batched(xyz.permute(0, 2, 1).contiguous(), m, start)
+    # 16: fps_spec_kernel<128, 16>, the two-slots-per-lane kernel; 0: eight workgroups of 8 waves (1025 buckets), whose repair launch it is
+    routes = {16: (ops.FPS_FORM_SPEC, 16, 1, 128, 0, 0, 1), 0: (ops.FPS_FORM_CLUSTER, 8, 8, 32, 0, 128, 1)}
     for waves in (16, 0):
+        assert tuple(ops.fps_route(2, n, m, waves=waves, device=DEV)) == routes[waves]
         got = ops.fps(xyz.to(DEV), m, _dev(start, I32), waves=waves, return_ws=True)
         _assert_fps(got, ref, bp.gather_soa(xyz, ref), waves)
         assert got[3] is not None and int(ops.fps_ws_ctl(got[3], 2, n)[1]) == 0

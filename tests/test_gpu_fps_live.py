@@ -14,10 +14,20 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 I32 = torch.int32
 
-# every kernel form at N = 2304: (waves, bucketed).  0 = what sn2_fps picks, 1 = one sample per round, 4 / 8 / 16 = the speculative
-# kernel, 34 / 66 = two workgroups of 16 / 8 waves per plot (2304 points = 36 buckets: the widest split with two buckets per wave),
-# bucketed=False = the brute-force kernel
-FORMS = [(0, True), (1, True), (4, True), (8, True), (16, True), (34, True), (66, True), (0, False)]
+# every kernel form at N = 2304: (waves, bucketed) -> the (form, waves per workgroup, workgroups per plot) sn2_fps_route names for it.
+# 2304 points = 36 buckets: two workgroups of 8 waves are the widest split with two buckets per wave, which is also what 0 (sn2_fps)
+# picks; two workgroups of 16 waves (34) would need 64 buckets, so that request runs the single workgroup of 16 waves, as 16 does.
+# 1 = one sample per round, 4 / 8 / 16 = the speculative kernel, bucketed=False = the brute-force kernel (1024 threads at this size)
+FORM_ROUTES = {(0, True): (ops.FPS_FORM_CLUSTER, 8, 2), (1, True): (ops.FPS_FORM_ROUND, 16, 1), (4, True): (ops.FPS_FORM_SPEC, 4, 1),
+               (8, True): (ops.FPS_FORM_SPEC, 8, 1), (16, True): (ops.FPS_FORM_SPEC, 16, 1), (34, True): (ops.FPS_FORM_SPEC, 16, 1),
+               (66, True): (ops.FPS_FORM_CLUSTER, 8, 2), (0, False): (ops.FPS_FORM_BRUTE, 16, 1)}
+FORMS = list(FORM_ROUTES)
+
+
+def assert_form_route(B, N, m, waves, bucketed):
+    """The kernel this call launches is the one the form list claims (B plots of N = 2304 points)."""
+    assert tuple(ops.fps_route(B, N, m, waves=waves, bucketed=bucketed, device=DEV))[:3] == FORM_ROUTES[(waves, bucketed)], (waves, bucketed)
+
 NS = (2304, 1, 37, 365, 700, 600)
 STARTS = (5, 0, 2000, 1999, 3, 11)              # two in the tail (plots 2 and 3)
 N1, M1, M2 = 2304, 600, 150
@@ -46,6 +56,7 @@ def test_equals_full_fps_on_repeated_tails(tails, waves, bucketed):
     B = len(NS)
     st, nl = _dev_i32(start), _dev_i32(NS)
     out = torch.full((B,), -1, dtype=I32, device=DEV)
+    assert_form_route(B, N1, M1, waves, bucketed)
     full = ops.fps(xyz, M1, st, bucketed=bucketed, waves=waves)
     live = ops.fps(xyz, M1, st, bucketed=bucketed, waves=waves, n_live=nl, n_live_out=out)
     assert torch.equal(full[0].cpu().long(), ref)
@@ -123,6 +134,7 @@ def test_definition_when_the_tail_is_not_copies():
     xyz = pos.permute(0, 2, 1).contiguous().to(DEV)
     first = None
     for waves, bucketed in FORMS:
+        assert_form_route(B, N1, M1, waves, bucketed)
         out = torch.empty(B, dtype=I32, device=DEV)
         got = ops.fps(xyz, M1, _dev_i32(start), bucketed=bucketed, waves=waves, n_live=_dev_i32([n] * B), n_live_out=out)
         assert torch.equal(got[0].cpu().long(), ref), (waves, bucketed)
@@ -158,7 +170,13 @@ def test_nearly_equal_maxima_of_distinct_points():
     start = torch.tensor([400, 2460, 13, 366])
     ref = P.fps_batched(pos, m, start)
     xyz, st, nl = pos.permute(0, 2, 1).contiguous().to(DEV), _dev_i32(start), _dev_i32([367] * 4)
-    for waves, bucketed in ((0, True), (68, True), (66, True), (36, True), (8, True), (1, True), (0, False)):
+    # 4096 points = 64 buckets: four workgroups of 8 waves fit (68, and what 0 picks), two do (66); four of 16 waves (36) would need
+    # 128 buckets and run the single workgroup of 16 waves
+    C, S, R, F = ops.FPS_FORM_CLUSTER, ops.FPS_FORM_SPEC, ops.FPS_FORM_ROUND, ops.FPS_FORM_BRUTE
+    routes = {(0, True): (C, 8, 4), (68, True): (C, 8, 4), (66, True): (C, 8, 2), (36, True): (S, 16, 1), (8, True): (S, 8, 1),
+              (1, True): (R, 16, 1), (0, False): (F, 16, 1)}
+    for (waves, bucketed), route in routes.items():
+        assert tuple(ops.fps_route(4, n, m, waves=waves, bucketed=bucketed, device=DEV))[:3] == route, (waves, bucketed)
         assert torch.equal(ops.fps(xyz, m, st, waves=waves, bucketed=bucketed)[0].cpu().long(), ref), (waves, bucketed)
         assert torch.equal(ops.fps(xyz, m, st, waves=waves, bucketed=bucketed, n_live=nl)[0].cpu().long(), ref), (waves, bucketed, "live")
 
@@ -171,6 +189,8 @@ def test_repair_launch_honours_the_live_prefix():
     pos, start = repeated_tail_plots(N, ns, (13, 30000, 990, 3), dup_plots=(2,), seed=5)
     xyz, st, nl = pos.permute(0, 2, 1).contiguous().to(DEV), _dev_i32(start), _dev_i32(ns)
     k0 = torch.empty(B, dtype=I32, device=DEV)
+    assert tuple(ops.fps_route(B, N, M, waves=72, device=DEV))[:3] == (ops.FPS_FORM_CLUSTER, 8, 8)
+    assert tuple(ops.fps_route(B, N, M, waves=16, device=DEV))[:3] == (ops.FPS_FORM_SPEC, 16, 1)
     want = ops.fps(xyz, M, st, waves=16)
     calm = ops.fps(xyz, M, st, waves=72, n_live=nl, n_live_out=k0, return_ws=True)
     assert _same(calm, want) and int(ops.fps_ws_ctl(calm[3], B, N)[1]) == 0

@@ -39,6 +39,21 @@ def test_bucketed_fps_equals_brute_force_and_oracle(B, N, M):
     xyz[:, :, N - q:] = xyz[:, :, :q]                                     # duplicates far apart in index
     start = torch.tensor([(977 * b + 13) % N for b in range(B)])
     dev = xyz.to(DEV)
+    # which kernel each `waves` below launches at this size (sn2_fps_route: form, waves per workgroup, workgroups per plot)
+    C, S, R, F = ops.FPS_FORM_CLUSTER, ops.FPS_FORM_SPEC, ops.FPS_FORM_ROUND, ops.FPS_FORM_BRUTE
+    six = {34: (C, 16, 2), 36: (C, 16, 4), 40: (C, 16, 8), 66: (C, 8, 2), 68: (C, 8, 4), 72: (C, 8, 8)}
+    singles = {8: (S, 8, 1), 4: (S, 4 if N <= 16384 else 8, 1), 1: (R, 16, 1), 16: (S, 16, 1)}
+    want_route = {
+        (2, 32768): {0: (C, 8, 8), **singles, **six},                       # 512 buckets: all six multi-workgroup forms
+        # 79 buckets: four or eight workgroups of 16 waves and eight of 8 would need 128, 256 and 128 -> one workgroup of 16 waves
+        (3, 5000): {0: (C, 8, 4), **singles, **six, 36: (S, 16, 1), 40: (S, 16, 1), 72: (S, 16, 1)},
+        (2, 20000): {0: (C, 8, 8), **singles, **six},                       # 313 buckets
+        # B*N is no multiple of 4: no bucketed kernel, every `waves` launches the brute-force kernel (and `bucketed` changes nothing)
+        (1, 2049): {w: (F, 16, 1) for w in (0, *singles, *six)},
+    }[(B, N)]
+    for w, r in want_route.items():
+        assert tuple(ops.fps_route(B, N, M, waves=w, device=DEV))[:3] == r, f"waves={w}"
+    assert tuple(ops.fps_route(B, N, M, bucketed=False, device=DEV))[:3] == (F, 16, 1)
     i_b, cs_b, _ = ops.fps(dev, M, start.to(DEV, torch.int32), bucketed=True)
     i_f, cs_f, _ = ops.fps(dev, M, start.to(DEV, torch.int32), bucketed=False)
     assert torch.equal(i_b, i_f) and torch.equal(cs_b, cs_f)
@@ -54,7 +69,8 @@ def test_bucketed_fps_equals_brute_force_and_oracle(B, N, M):
     assert torch.equal(i_1, i_f) and torch.equal(cs_1, cs_f)
     i_16, cs_16, _ = ops.fps(dev, M, start.to(DEV, torch.int32), waves=16)    # one workgroup of 16 waves per plot
     assert torch.equal(i_16, i_f) and torch.equal(cs_16, cs_f)
-    # several workgroups per plot (P = 2, 4, 8 of 16 or 8 waves; what waves = 0 picks where the batch fits the chip): the same
+    # several workgroups per plot (P = 2, 4, 8 of 16 or 8 waves; what waves = 0 picks where the batch fits the chip) wherever
+    # `want_route` says CLUSTER -- all six at 2 x 32 768 and 2 x 20 000, three of them at 3 x 5000, none at 1 x 2049 --: the same
     # samples, and no wait of the exchange ever gave up (control word 1 of the workspace counts the timeouts)
     for w in (34, 36, 40, 66, 68, 72):
         i_c, cs_c, ca_c, ws_c = ops.fps(dev, M, start.to(DEV, torch.int32), waves=w, return_ws=True)
@@ -93,6 +109,10 @@ def test_bucketed_fps_on_dense_plots(B, N, M):
     q = N // 8
     xyz[:, :, N - q:] = xyz[:, :, :q]
     start = torch.tensor([(977 * b + 13) % N for b in range(B)])
+    C = ops.FPS_FORM_CLUSTER
+    routes = {0: (C, 8, 8), 16: (ops.FPS_FORM_SPEC, 16, 1), 36: (C, 16, 4), 72: (C, 8, 8)}
+    for w, r in routes.items():
+        assert tuple(ops.fps_route(B, N, M, waves=w, device=DEV))[:3] == r, f"waves={w}"
     i_b, cs_b, ca_b, ws = ops.fps(xyz.to(DEV), M, start.to(DEV, torch.int32), return_ws=True)
     assert ws is not None
     ref = P.fps_batched(xyz.permute(0, 2, 1).contiguous(), M, start)
@@ -128,6 +148,7 @@ def test_multi_workgroup_fps_gives_up_safely_and_is_repaired():
     try:
         assert lib.sn2_debug_fps_spin_limit(1) == 0
         for w in (72, 36, 0):
+            assert ops.fps_route(B, N, M, waves=w, device=DEV).form == ops.FPS_FORM_CLUSTER, f"waves={w}"
             out = (torch.full((B, M), -7, dtype=torch.int32, device=DEV), torch.full((B, 3, M), float("nan"), device=DEV),
                    torch.full((B * M, 4), float("nan"), device=DEV), torch.empty(ops.fps_ws_words(B, N), dtype=torch.int32, device=DEV))
             idx, cs, ca, ws = ops.fps(dev, M, start.to(DEV, torch.int32), out=out, waves=w, return_ws=True)
