@@ -104,6 +104,11 @@ int sn2_grad_reduce(float *flat, int n, int replicas, int stride, void *stream);
 /* (cloud (B,C,N), xyz (B,3,N)) -> rows0 (B*N,12) = [cloud rows 2..9 | x y z 0]
  * replaces the long-form/concat glue of PointNet2.forward, model/point_net2.py:107-124 (C must be 10). */
 int sn2_pack_rows(const float *cloud, const float *xyz, int B, int C, int N, float *rows0, void *stream);
+/* The same for a model that reads F point features (model/point_net2.py:77: n_input_feats = len(args.input_feats) - 2):
+ * rows0 (B*N,F+4) = [F features | x y z 0].  (C, F) = (10, 8): cloud rows 2..9, sn2_pack_rows itself;  (6, 4): cloud rows 2..5,
+ * the reference's rule for a six-row cloud;  (10, 4): cloud rows 2, 7, 8, 9 -- the reference's ten-row layout with the four
+ * colour rows (red, green, blue, nir) never read.  Any other pair: SN2_ELIMIT. */
+int sn2_pack_rows_feat(const float *cloud, const float *xyz, int B, int C, int N, int F, float *rows0, void *stream);
 
 /* farthest point sampling -- torch_cluster.fps, model/point_net2.py:22.
  * start (B) local start index per plot or NULL (= 0, i.e. random_start=False).
@@ -440,7 +445,8 @@ typedef struct sn2_sa {
                                        backward is linear in + a one-workgroup combine kernel) instead of a pass of
                                        their own; otherwise it is not touched                                   */
 } sn2_sa;
-/* sn2_sa.bwd_ws: replicas of the two 16 x 12 images [sum m xhat (x) in | sum m (x) in] of the nl = 2 module (MLP[11,16,16]) */
+/* sn2_sa.bwd_ws: replicas of the two 16 x 12 images [sum m xhat (x) in | sum m (x) in] of the nl = 2 module (MLP[11,16,16]);
+ * with four point features (MLP[7,16,16]) the images are 16 x 8 and use the front of every replica pair */
 #define SN2_SA_BWD_WS_REPLICAS 32
 #define SN2_SA_BWD_WS_WORDS (SN2_SA_BWD_WS_REPLICAS * 2 * 16 * 12)
 /* Work items of the SA passes (position-only: part of the geometry pass).  A wave step is four 16-message tiles; a plot's
@@ -1020,7 +1026,9 @@ int sn2_adam_step_dev(float *param, const float *grad, float *exp_avg, float *ex
  * for bit (tests/test_gpu_executor.py).
  *
  * The reference architecture only (model/point_net2.py:81-99): SA1 MLP[11,16,16], SA2 MLP[19,32], global SA MLP[35,64],
- * FP3 MLP[96,64] k=1, FP2 MLP[80,34] k=3, FP1 MLP[42,34] k=3, lin1 34->16, lin2 16->5. */
+ * FP3 MLP[96,64] k=1, FP2 MLP[80,34] k=3, FP1 MLP[42,34] k=3, lin1 34->16, lin2 16->5 -- and the same architecture over
+ * F = 4 point features instead of 8 (n_input_feats = 6, :77-90): SA1 MLP[7,16,16], FP1 MLP[38,34], rows0 (B*N,8).  F is read off
+ * the model: sa1[0].cin - 3, and fp1.cin must be 34 + F. */
 
 /* one (Linear -> ReLU -> BatchNorm1d) block of the model: its parameters and buffers (device), and where its four gradients
  * live inside the flat parameter gradient (offsets in floats; parameters() order of the reference module) */
@@ -1070,7 +1078,7 @@ typedef struct sn2_net_geo {
     float *inv3, *inv2, *inv1;                           /* SN2_INTERP_WS_WORDS each */
     int *nn_ws2, *nn_ws1;                                /* SN2_THREE_NN_XY_WS_WORDS or NULL (full scan) */
     const int *rank1;                                    /* sn2_fp.row_perm of FP1 or NULL */
-    float *rows0;                                        /* (B*N,12) sn2_pack_rows */
+    float *rows0;                                        /* (B*N,F+4) sn2_pack_rows_feat, F = model.sa1[0].cin - 3 (8: (B*N,12)) */
     int *p2_pix; float *p2_mm;                           /* sn2_plot_pixels or NULL */
 } sn2_net_geo;
 
@@ -1127,9 +1135,11 @@ typedef struct sn2_net_bwd {
 #define SN2_NET_WITH_GEOMETRY 128 /* forward: run the geometry pass first (forked when io.ctx and the side streams are given), the
                                      row packing beside the level-1 FPS */
 #define SN2_NET_HAS_INVERTED 256 /* forward (training): geo.inv* are already built (else they are built here) */
+#define SN2_NET_CLOUD10 512     /* geometry, forward: io.cloud has the reference's ten rows although the model reads four features
+                                   (sn2_pack_rows_feat's (10, 4) form); without it io.cloud is (B,F+2,N) */
 
 typedef struct sn2_net_io {
-    const float *cloud;                  /* (B,10,N) features on the device, or NULL where not needed */
+    const float *cloud;                  /* (B,F+2,N) features on the device ((B,10,N) under SN2_NET_CLOUD10), or NULL where not needed */
     const int *fps_start;                /* (2,B) start indices of the two FPS calls, or NULL (= 0) */
     unsigned *fps_status;                /* sn2_fps_status's word or NULL */
     unsigned long long *gl_xchg; unsigned *gl_ctl;   /* sn2_global_level_forward's exchange area, or NULL: separate launches */

@@ -28,14 +28,14 @@ CONSTANTS = {
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
-    "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256,
+    "SN2_NET_HAS_ROWS0": 32, "SN2_NET_JOIN_PENDING": 64, "SN2_NET_WITH_GEOMETRY": 128, "SN2_NET_HAS_INVERTED": 256, "SN2_NET_CLOUD10": 512,
 }
 globals().update(CONSTANTS)
 # the names the package has used so far
 MAX_NEIGHBORS, STAT_SLOTS, BN_FROZEN_KEEP = CONSTANTS["SN2_MAX_NEIGHBORS"], CONSTANTS["SN2_STAT_SLOTS"], CONSTANTS["SN2_BN_FROZEN_KEEP"]
 (NET_FORK, NET_SHARED, NET_INVERTED, NET_DEFER_JOIN, NET_INPUT_ONLY, NET_HAS_ROWS0, NET_JOIN_PENDING, NET_WITH_GEOMETRY,
- NET_HAS_INVERTED) = (CONSTANTS["SN2_NET_" + n] for n in ("FORK", "SHARED", "INVERTED", "DEFER_JOIN", "INPUT_ONLY", "HAS_ROWS0",
-                                                          "JOIN_PENDING", "WITH_GEOMETRY", "HAS_INVERTED"))
+ NET_HAS_INVERTED, NET_CLOUD10) = (CONSTANTS["SN2_NET_" + n] for n in ("FORK", "SHARED", "INVERTED", "DEFER_JOIN", "INPUT_ONLY", "HAS_ROWS0",
+                                                                       "JOIN_PENDING", "WITH_GEOMETRY", "HAS_INVERTED", "CLOUD10"))
 
 
 class Block(Structure):  # sn2_block
@@ -143,6 +143,7 @@ SIGNATURES = {
     "sn2_debug_stream_probe": [c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p],
     "sn2_debug_mfma_probe": [c_int, c_int, c_void_p, POINTER(c_double), c_void_p],
     "sn2_pack_rows": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "sn2_pack_rows_feat": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "sn2_fps": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_fps_waves": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "sn2_fps_status": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],

@@ -1691,6 +1691,8 @@ int fp_form_t(const sn2_fp* p, int pass) {
         if (knn && p->ca == 64 && p->cb == 32 && p->blk.cout == 64) return FN<64, 32, 64, true>(__VA_ARGS__);     \
         if (knn && p->ca == 64 && p->cb == 16 && p->blk.cout == 34) return FN<64, 16, 34, true>(__VA_ARGS__);     \
         if (knn && p->ca == 34 && p->cb == 8 && p->blk.cout == 34) return FN<34, 8, 34, true>(__VA_ARGS__);       \
+        /* FP1 over four point features (n_input_feats = 6): one skip quad per row instead of two */              \
+        if (knn && p->ca == 34 && p->cb == 4 && p->blk.cout == 34) return FN<34, 4, 34, true>(__VA_ARGS__);       \
         /* the two extra blocks of the 3sa-arch variant: global SA on [x3 | pos3], FP4 on [global | x3] */       \
         if (!knn && p->ca == 64 && p->cb == 3 && p->blk.cout == 64) return FN<64, 3, 64, false>(__VA_ARGS__);     \
         if (knn && p->ca == 64 && p->cb == 64 && p->blk.cout == 64) return FN<64, 64, 64, true>(__VA_ARGS__);     \

@@ -32,6 +32,36 @@ extern "C" int sn2_pack_rows(const float* cloud, const float* xyz, int B, int C,
     SN2_RETURN_LAUNCH();
 }
 
+// pack_rows_feat: the same rows for a model that reads F = 4 point features -- rows0 (B*N,8) = [4 features | x y z 0].
+// SIX = false: a ten-row cloud in the reference's layout, the features are its rows 2, 7, 8, 9 (z, intensity, return_num,
+// num_returns: the colour rows 3..6 are never read);  SIX = true: a six-row cloud, its rows 2..5.
+// Reads 28 B/point coalesced (7 channel rows), writes 32 B/point as 2 x 16 B per lane.
+template <bool SIX>
+__global__ __launch_bounds__(256) void pack_rows4_kernel(const float* __restrict__ cloud, const float* __restrict__ xyz,
+                                                         int N, float* __restrict__ rows0) {
+    constexpr int C = SIX ? 6 : 10, R1 = SIX ? 3 : 7;            // cloud rows of features 1..3: R1, R1 + 1, R1 + 2
+    const int b = blockIdx.y;
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const float* cl = cloud + (size_t)b * C * N + n;
+    const float* xp = xyz + (size_t)b * 3 * N + n;
+    float4 v0 = make_float4(cl[2 * (size_t)N], cl[R1 * (size_t)N], cl[(R1 + 1) * (size_t)N], cl[(R1 + 2) * (size_t)N]);
+    float4 v1 = make_float4(xp[0], xp[(size_t)N], xp[2 * (size_t)N], 0.f);
+    float4* o = reinterpret_cast<float4*>(rows0 + ((size_t)b * N + n) * 8);
+    o[0] = v0;
+    o[1] = v1;
+}
+
+extern "C" int sn2_pack_rows_feat(const float* cloud, const float* xyz, int B, int C, int N, int F, float* rows0, void* stream) {
+    if (!cloud || !xyz || !rows0 || B <= 0 || C <= 0 || N <= 0 || F <= 0) return SN2_EINVAL;
+    if (C == 10 && F == 8) return sn2_pack_rows(cloud, xyz, B, C, N, rows0, stream);
+    if (F != 4 || (C != 6 && C != 10)) return SN2_ELIMIT;
+    dim3 grid(sn2_cdiv(N, 256), B);
+    if (C == 6) hipLaunchKernelGGL(pack_rows4_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, cloud, xyz, N, rows0);
+    else hipLaunchKernelGGL(pack_rows4_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, cloud, xyz, N, rows0);
+    SN2_RETURN_LAUNCH();
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // fps: one workgroup per plot; the plot's points and their running min-distance stay in VGPRs (PPT per lane);
 // per round: PPT canonical distance updates per lane, a per-lane running (max, slot), a 64-bit wave max over

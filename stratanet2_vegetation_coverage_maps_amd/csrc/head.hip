@@ -220,7 +220,8 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval_kernel(int R, int R_per_p
 // The same kernel with the row side's INPUT STREAM decoupled from the lanes that consume it, as fp_fwd_rows2_kernel (round 5).  The
 // first form's nine lanes of a row load the row's 3-NN entry and skip columns themselves, then gather, then compute, three groups
 // of seven rows at a time: six memory round trips per 63-row turn, one after the other, in front of the head's arithmetic.  Here
-// a wave fetches a whole turn's 189 indices, 189 weights and 63 x QB skip quads with one element per lane and load (eight loads),
+// a wave fetches a whole turn's 189 indices, 189 weights and 63 x QB skip quads with one element per lane and load (3 + 3 + NSK loads: eight
+// with two skip quads per row, seven with one),
 // ONE TURN AHEAD (the loads are issued in front of the head phase of the turn before), hands them to the (row, quad) lanes
 // through LDS, and asks for a batch's table rows before it computes the batch before: one round trip per turn is left in the
 // open.  Turns dealt XCD-aware (row_iters: an XCD's L2 holds its own plots' table rows).  Same operations in the same order:
@@ -236,7 +237,8 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
                                                                float* __restrict__ cov, float* __restrict__ proba) {
     constexpr int QH = (CO + 3) / 4, HS = 4 * QH, G = 64 / QH, QB = CB / 4, U = 3, ROWS = G * 9;
     static_assert(CO == 34 && HS == 36 && G == 7 && ROWS == 63, "the head reads rows of 36 floats, 63 per turn");
-    static_assert(CB > 0 && CB % 4 == 0 && QB == 2, "two skip quads per row: 126 quads per turn = two per lane");
+    static_assert(CB > 0 && CB % 4 == 0, "skip quads");
+    constexpr int NSK = (ROWS * QB + 63) / 64;                                 // skip quads per lane and turn (QB = 2: 126 quads = two per lane; QB = 1: one)
     constexpr int XW = 3 * ROWS + 3 * ROWS + 4 * ROWS * QB + 2;                // idx | w | skip quads (16-byte aligned: 378 % 4 = 2 -> +2)
     constexpr int XO_W = 3 * ROWS, XO_S = 6 * ROWS + 2;
     static_assert(XO_S % 4 == 0, "the skip quads start 16-byte aligned");
@@ -255,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
     // ---- a turn's inputs, one element per lane and load, unconditional from clamped addresses
     int p_idx[3];
     float p_w[3];
-    f32x4v p_sk[2];
+    f32x4v p_sk[NSK];
     const int last_e = 3 * R - 1;
     auto fetch = [&](int turn) {
         const int tc = turn < ri.it_hi ? turn : ri.it_hi - 1;
@@ -267,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
             p_w[k] = knn_w[e];
         }
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
+        for (int k = 0; k < NSK; ++k) {
             const int el = lane + 64 * k < ROWS * QB ? lane + 64 * k : ROWS * QB - 1;
             const int r0 = tc * ROWS + el / QB, r = r0 < R ? r0 : R - 1;
             p_sk[k] = reinterpret_cast<const f32x4v*>(skip + (size_t)r * skip_stride)[el % QB];
@@ -281,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void fp_head_eval2_kernel(int R, int R_per_
             xw[XO_W + el] = p_w[k];
         }
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
+        for (int k = 0; k < NSK; ++k) {
             const int el = lane + 64 * k < ROWS * QB ? lane + 64 * k : ROWS * QB - 1;
             reinterpret_cast<f32x4v*>(xw + XO_S)[el] = p_sk[k];
         }
@@ -928,6 +930,33 @@ extern "C" int sn2_head_forward(const sn2_head* p, void* stream) {
     SN2_RETURN_LAUNCH();
 }
 
+// the launches of sn2_fp_head_eval, over the layer's skip width (checked by the caller)
+template <int CB>
+static int fp_head_eval_t(const sn2_fp* p, const sn2_head* hd, hipStream_t st) {
+    const int R = hd->R, n_src = p->B * p->S_per_plot;
+    // the layer's BatchNorm on its running statistics -> (a, c) = what the head applies to the rows (hd->fa, hd->fc name the
+    // same two vectors: p->blk.a, p->blk.c)
+    SN2_TRY(sn2_bn_finalize(&p->blk, 0, nullptr, R, 0, st));
+    SN2_TRY((launch_src_table<34, CB, 34>(n_src, p->src_stride, p->src, p->src_a, p->src_c, p->blk.W, p->src_ws, st)));
+    const long turns = ((long)R + 62) / 63;
+    int grid = sn2_cdiv(turns, 4);
+    if (g_fp_rows_form != 0 && grid >= 2 * sn2_cu_count()) {
+        // (round 5) the pipelined form: as many workgroups as are resident together (two per CU by its registers), each wave
+        // several turns with the next turn's inputs in flight
+        grid = 2 * sn2_cu_count();
+        hipLaunchKernelGGL((fp_head_eval2_kernel<34, CB, 34>), dim3(grid), dim3(256), 0, st, R, p->R_per_plot, p->S_per_plot,
+                           p->skip_stride, (const float*)p->src_ws, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.b, hd->fa, hd->fc,
+                           hd->W1, hd->b1, hd->W2, hd->b2, hd->coverages, hd->proba);
+        SN2_RETURN_LAUNCH();
+    }
+    const int cap = 4 * sn2_cu_count();
+    if (grid > cap) grid = cap;
+    hipLaunchKernelGGL((fp_head_eval_kernel<34, CB, 34>), dim3(grid), dim3(256), 0, st, R, p->R_per_plot, p->S_per_plot,
+                       p->skip_stride, (const float*)p->src_ws, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.b, hd->fa, hd->fc,
+                       hd->W1, hd->b1, hd->W2, hd->b2, hd->coverages, hd->proba);
+    SN2_RETURN_LAUNCH();
+}
+
 extern "C" int sn2_fp_head_eval(const sn2_fp* p, const sn2_head* hd, void* stream) {
     // (neither p->h nor hd->f is read: the rows stay in LDS)
     if (!p || !hd || p->B <= 0 || p->R_per_plot <= 0 || p->S_per_plot <= 0 || !p->src || !p->blk.W || !p->blk.b || !p->skip ||
@@ -935,31 +964,10 @@ extern "C" int sn2_fp_head_eval(const sn2_fp* p, const sn2_head* hd, void* strea
         return SN2_EINVAL;
     if (hd->R <= 0 || hd->cin != 34 || !hd->fa || !hd->fc || !hd->W1 || !hd->b1 || !hd->W2 || !hd->b2) return SN2_EINVAL;
     if (!hd->coverages || !hd->proba || hd->drop_mask || hd->act_bf16 || p->act_bf16) return SN2_EINVAL;
-    if (!(p->knn_idx && p->ca == 34 && p->cb == 8 && p->blk.cout == 34 && hd->R == p->B * p->R_per_plot)) return SN2_ELIMIT;
+    if (!(p->knn_idx && p->ca == 34 && (p->cb == 8 || p->cb == 4) && p->blk.cout == 34 && hd->R == p->B * p->R_per_plot)) return SN2_ELIMIT;
     if (!fp_source_side_ok<34, 34>(p, /*with_h=*/false)) return SN2_ELIMIT;       // (hd->R == B * R_per_plot: the line above)
-    hipStream_t st = (hipStream_t)stream;
-    const int R = hd->R, n_src = p->B * p->S_per_plot;
-    // the layer's BatchNorm on its running statistics -> (a, c) = what the head applies to the rows (hd->fa, hd->fc name the
-    // same two vectors: p->blk.a, p->blk.c)
-    SN2_TRY(sn2_bn_finalize(&p->blk, 0, nullptr, R, 0, st));
-    SN2_TRY((launch_src_table<34, 8, 34>(n_src, p->src_stride, p->src, p->src_a, p->src_c, p->blk.W, p->src_ws, st)));
-    const long turns = ((long)R + 62) / 63;
-    int grid = sn2_cdiv(turns, 4);
-    if (g_fp_rows_form != 0 && grid >= 2 * sn2_cu_count()) {
-        // (round 5) the pipelined form: as many workgroups as are resident together (two per CU by its registers), each wave
-        // several turns with the next turn's inputs in flight
-        grid = 2 * sn2_cu_count();
-        hipLaunchKernelGGL((fp_head_eval2_kernel<34, 8, 34>), dim3(grid), dim3(256), 0, st, R, p->R_per_plot, p->S_per_plot,
-                           p->skip_stride, (const float*)p->src_ws, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.b, hd->fa, hd->fc,
-                           hd->W1, hd->b1, hd->W2, hd->b2, hd->coverages, hd->proba);
-        SN2_RETURN_LAUNCH();
-    }
-    const int cap = 4 * sn2_cu_count();
-    if (grid > cap) grid = cap;
-    hipLaunchKernelGGL((fp_head_eval_kernel<34, 8, 34>), dim3(grid), dim3(256), 0, st, R, p->R_per_plot, p->S_per_plot,
-                       p->skip_stride, (const float*)p->src_ws, p->knn_idx, p->knn_w, p->skip, p->blk.W, p->blk.b, hd->fa, hd->fc,
-                       hd->W1, hd->b1, hd->W2, hd->b2, hd->coverages, hd->proba);
-    SN2_RETURN_LAUNCH();
+    // (eight point features, or four: one skip quad per row)
+    return p->cb == 4 ? fp_head_eval_t<4>(p, hd, (hipStream_t)stream) : fp_head_eval_t<8>(p, hd, (hipStream_t)stream);
 }
 
 extern "C" int sn2_head_bn_sums(const sn2_head* p, const float* gamma, const float* beta, const float* mean,

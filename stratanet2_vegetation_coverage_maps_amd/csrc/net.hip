@@ -33,6 +33,11 @@ inline bool fused_eval_head(const sn2_net_model* m, const sn2_net_dims* d, int t
     return !training && m->fuse_eval_head && !d->act_bf16 && m->source_side;
 }
 inline int gl_bf16(const sn2_net_model* m) { return m->sa3.mma_bf16 || m->fp3.mma_bf16; }
+// the point features the model reads (model/point_net2.py:77: n_input_feats): 8, or 4 for LiDAR-only plots.  The level-0 rows are
+// [F features | x y z 0]: F + 4 floats
+inline int n_feat(const sn2_net_model* m) { return m->sa1[0].cin - 3; }
+// rows of io.cloud: F + 2, or the reference's ten under SN2_NET_CLOUD10 (sn2_pack_rows_feat's (10, 4) form)
+inline int cloud_rows(const sn2_net_model* m, int flags) { return (flags & SN2_NET_CLOUD10) ? 10 : n_feat(m) + 2; }
 
 // bump allocator over a caller-owned arena; base == nullptr: the "pointers" are offsets
 struct Carver {
@@ -56,10 +61,12 @@ int check_dims(const sn2_net_model* m, const sn2_net_dims* d) {
     const int c1 = m->max_neighbors < d->N ? m->max_neighbors : d->N, c2 = m->max_neighbors < d->M1 ? m->max_neighbors : d->M1;
     if (d->cap1 != c1 || d->cap2 != c2) return SN2_EINVAL;
     if ((long)d->B * d->N >= (1L << 31) / 64) return SN2_ELIMIT;
-    const int cin[7] = {11, 16, 19, 35, 96, 80, 42};
+    const int F = n_feat(m);
+    if (F != 8 && F != 4) return SN2_ELIMIT;
+    const int cin[7] = {F + 3, 16, 19, 35, 96, 80, 34 + F};
     const sn2_net_layer* L[7] = {&m->sa1[0], &m->sa1[1], &m->sa2, &m->sa3, &m->fp3, &m->fp2, &m->fp1};
     for (int i = 0; i < 7; ++i)
-        if (L[i]->cin != cin[i] || L[i]->cout != WIDTHS[i]) return SN2_ELIMIT;     // the reference architecture only
+        if (L[i]->cin != cin[i] || L[i]->cout != WIDTHS[i]) return SN2_ELIMIT;     // the reference architecture only, over 8 or 4 features
     return 0;
 }
 
@@ -111,8 +118,9 @@ inline float* aux_row(const sn2_net_act* a, int k, int row) {      // row 0..3 =
 void sa1_desc(sn2_sa* s, const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_geo* g, const sn2_net_act* a,
               GradDst gd, const float* dout, float* bwd_ws = nullptr) {
     memset(s, 0, sizeof(*s));
-    s->B = d->B, s->Nsrc = d->N, s->M = d->M1, s->cap = d->cap1, s->cf = 8, s->nl = 2;
-    s->feat = g->rows0, s->feat_stride = 12, s->spos = g->rows0 + 8, s->spos_stride = 12;
+    const int F = n_feat(m);
+    s->B = d->B, s->Nsrc = d->N, s->M = d->M1, s->cap = d->cap1, s->cf = F, s->nl = 2;
+    s->feat = g->rows0, s->feat_stride = F + 4, s->spos = g->rows0 + F, s->spos_stride = F + 4;
     s->cpos = g->pos1_aos, s->nbr = g->nbr1, s->cnt = g->cnt1, s->total = g->tot1, s->order = g->ord1;
     fill_block(&s->blk[0], &m->sa1[0], 0, a, gd);
     fill_block(&s->blk[1], &m->sa1[1], 1, a, gd);
@@ -184,10 +192,10 @@ FpIn fp2_in(const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_geo* g,
 }
 FpIn fp1_in(const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_geo* g, const sn2_net_act* a, float* src_ws) {
     FpIn in{};
-    in.k = 6, in.L = &m->fp1, in.Rp = d->N, in.Sp = d->M1, in.ca = 34, in.cb = 8;
+    in.k = 6, in.L = &m->fp1, in.Rp = d->N, in.Sp = d->M1, in.ca = 34, in.cb = n_feat(m);
     in.src = a->h2, in.src_stride = 36, in.src_a = aux_row(a, 5, 0), in.src_c = aux_row(a, 5, 1);
     in.knn_idx = g->knn1_idx, in.knn_w = g->knn1_w;
-    in.skip = g->rows0, in.skip_stride = 12;
+    in.skip = g->rows0, in.skip_stride = n_feat(m) + 4;
     in.h = a->h1;
     in.src_ws = src_ws;
     in.act_bf16 = d->act_bf16;
@@ -296,9 +304,9 @@ int geometry_impl(const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_g
     // the input-only pieces of the feature pass
     if (flags & SN2_NET_INPUT_ONLY) {
         if (!io->cloud) return SN2_EINVAL;
-        SN2_TRY(sn2_pack_rows(io->cloud, g->xyz, B, 10, N, g->rows0, cur));
+        SN2_TRY(sn2_pack_rows_feat(io->cloud, g->xyz, B, cloud_rows(m, flags), N, n_feat(m), g->rows0, cur));
         if (d->p2_diam_pix > 0 && g->p2_pix && g->p2_mm)
-            SN2_TRY(sn2_plot_pixels(io->cloud, 10L * N, B, N, d->p2_diam_pix, g->p2_mm, g->p2_pix, cur));
+            SN2_TRY(sn2_plot_pixels(io->cloud, (long)cloud_rows(m, flags) * N, B, N, d->p2_diam_pix, g->p2_mm, g->p2_pix, cur));
     }
     // (a)
     SN2_TRY(sn2_ball_query(g->xyz, B, N, g->pos1_soa, M1, m->r1_sq, d->cap1, g->nbr1, g->cnt1, inverted ? g->tot1 : nullptr, ws1, cur));
@@ -370,7 +378,7 @@ extern "C" int sn2_net_geo_carve(const sn2_net_model* m, const sn2_net_dims* d, 
     g->inv1 = c.take<float>(SN2_INTERP_WS_WORDS(B, N, M1));
     g->nn_ws2 = sn2_three_nn_uses_grid(d->M2, d->M1) ? c.take<int>(SN2_THREE_NN_XY_WS_WORDS(B, M2, M1)) : nullptr;
     g->nn_ws1 = sn2_three_nn_uses_grid(d->M1, d->N) ? c.take<int>(SN2_THREE_NN_XY_WS_WORDS(B, M1, N)) : nullptr;
-    g->rows0 = c.take<float>(B * N * 12);
+    g->rows0 = c.take<float>(B * N * (size_t)(n_feat(m) + 4));
     if (d->p2_diam_pix > 0) g->p2_pix = c.take<int>(B * N), g->p2_mm = c.take<float>(B * 4);
     // xyz, pos3 (a constant zero vector) and rank1 (a view of ws1) are the caller's
     *bytes = c.bytes();
@@ -392,7 +400,7 @@ extern "C" int sn2_net_act_carve(const sn2_net_model* m, const sn2_net_dims* d, 
     a->h2 = c.take<float>(B * M1 * 36);
     const bool fused_eval = fused_eval_head(m, d, training);
     if (!fused_eval) a->h1 = d->act_bf16 ? (void*)c.take<unsigned short>(B * N * 36) : (void*)c.take<float>(B * N * 36);
-    if (fp_src_ws_wanted(m, (long)B * N, 8, fused_eval)) a->src_ws1 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, N, M1, 34));
+    if (fp_src_ws_wanted(m, (long)B * N, n_feat(m), fused_eval)) a->src_ws1 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, N, M1, 34));
     if (fp_src_ws_wanted(m, (long)B * M1, 16, false)) a->src_ws2 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, M1, M2, 34));
     *bytes = c.bytes();
     return 0;
@@ -427,7 +435,7 @@ extern "C" int sn2_net_bwd_carve(const sn2_net_model* m, const sn2_net_dims* d, 
     }
     b->du2 = c.take<float>(B * M1 * 64), b->du3 = c.take<float>(B * M2 * 64);
     b->bn_ok = c.take<int>(4);
-    if (fp_src_ws_wanted(m, (long)B * N, 8, false)) b->src_ws1 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, N, M1, 34));
+    if (fp_src_ws_wanted(m, (long)B * N, n_feat(m), false)) b->src_ws1 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, N, M1, 34));
     if (fp_src_ws_wanted(m, (long)B * M1, 16, false)) b->src_ws2 = c.take<float>(SN2_FP_SRC_WS_WORDS(B, M1, M2, 34));
     *scratch_bytes = c.bytes();
     return 0;
@@ -478,7 +486,7 @@ extern "C" int sn2_net_forward(const sn2_net_model* m, const sn2_net_dims* d, co
                 hipStream_t sp = (hipStream_t)io->stream_pack;
                 NET_HIP(hipEventRecord(ctx->pack_fork, cur));
                 NET_HIP(hipStreamWaitEvent(sp, ctx->pack_fork, 0));
-                SN2_TRY(sn2_pack_rows(io->cloud, g->xyz, B, 10, N, g->rows0, sp));
+                SN2_TRY(sn2_pack_rows_feat(io->cloud, g->xyz, B, cloud_rows(m, flags), N, n_feat(m), g->rows0, sp));
                 NET_HIP(hipEventRecord(ctx->packed, sp));
                 wait_pack = have_rows0 = true;
             }
@@ -500,11 +508,11 @@ extern "C" int sn2_net_forward(const sn2_net_model* m, const sn2_net_dims* d, co
             SN2_TRY(inverted_tables(d, g, 3, cur));
         }
     }
-    // ---- level 0 rows: [8 features | x y z 0]
+    // ---- level 0 rows: [F features | x y z 0]
     if (wait_pack) NET_HIP(hipStreamWaitEvent(cur, ctx->packed, 0));
     if (!have_rows0) {
         if (!io->cloud) return SN2_EINVAL;
-        SN2_TRY(sn2_pack_rows(io->cloud, g->xyz, B, 10, N, g->rows0, cur));
+        SN2_TRY(sn2_pack_rows_feat(io->cloud, g->xyz, B, cloud_rows(m, flags), N, n_feat(m), g->rows0, cur));
     }
     // ---- SA1, SA2                                                                           (point_net2.py:131-132, 21-29)
     sn2_sa sa;

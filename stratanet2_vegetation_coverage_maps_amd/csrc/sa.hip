@@ -106,8 +106,9 @@ int check(const sn2_sa* p) {
     if (!p->feat || !p->spos || !p->cpos || !p->nbr || !p->cnt || !p->total || !p->ext || !p->arg || !p->out)
         return SN2_EINVAL;
     if (p->feat_stride < p->cf || (p->feat_stride & 3) || p->spos_stride < 4 || (p->spos_stride & 3)) return SN2_EINVAL;
-    const bool sa1 = p->cf == 8 && p->nl == 2 && p->blk[0].cin == 11 && p->blk[0].cout == 16 && p->blk[1].cin == 16 &&
-                     p->blk[1].cout == 16;
+    // SA1 over eight point features (the reference's ten-row clouds) or four (LiDAR-only plots: MLP[7,16,16])
+    const bool sa1 = (p->cf == 8 || p->cf == 4) && p->nl == 2 && p->blk[0].cin == p->cf + 3 && p->blk[0].cout == 16 &&
+                     p->blk[1].cin == 16 && p->blk[1].cout == 16;
     const bool sa2 = p->cf == 16 && p->nl == 1 && p->blk[0].cin == 19 && p->blk[0].cout == 32;
     // a third ball-query level, MLP[35,64]: not in the reference (BASELINE config 2 names it: the "3sa-arch" variant)
     const bool sa3 = p->cf == 32 && p->nl == 1 && p->blk[0].cin == 35 && p->blk[0].cout == 64;
@@ -284,6 +285,7 @@ static int sa_order_impl(const int* cnt, int G, int B, int M, int* order, size_t
 extern "C" int sn2_sa_forward(const sn2_sa* p, int training, void* stream) {
     SN2_TRY(check(p));
     if (training < 0 || training > SN2_BN_FROZEN_KEEP) return SN2_EINVAL;
+    if (p->nl == 2 && p->cf == 4) return forward_t<4, 2, 16, 16>(p, training, (hipStream_t)stream);
     if (p->nl == 2) return forward_t<8, 2, 16, 16>(p, training, (hipStream_t)stream);
     if (p->cf == 32) return forward_t<32, 1, 64, 64>(p, training, (hipStream_t)stream);
     return forward_t<16, 1, 32, 32>(p, training, (hipStream_t)stream);
@@ -292,6 +294,7 @@ extern "C" int sn2_sa_forward(const sn2_sa* p, int training, void* stream) {
 extern "C" int sn2_sa_backward(const sn2_sa* p, void* stream) {
     SN2_TRY(check(p));
     if (!p->dout) return SN2_EINVAL;
+    if (p->nl == 2 && p->cf == 4) return backward_t<4, 2, 16, 16>(p, (hipStream_t)stream);
     if (p->nl == 2) return backward_t<8, 2, 16, 16>(p, (hipStream_t)stream);
     if (p->cf == 32) return backward_t<32, 1, 64, 64>(p, (hipStream_t)stream);
     return backward_t<16, 1, 32, 32>(p, (hipStream_t)stream);

@@ -359,7 +359,7 @@ __device__ __forceinline__ void sa_affine_l2(const SaL2W<C1, C2>& w, const f32x4
 // are known before the launch, so the ext / arg arrays and the pass over them (parcel loop: 410 MB per launch for SA1
 // where 82 MB of output do) fall away
 template <int CF, int NL, int C1, int C2, int PASS, bool BF16, bool STATS = true>
-__global__ __launch_bounds__(256, (PASS == 1 && CF == 8) ? 3 : 1) void sa_mfma_fwd_kernel(const SaFwdArgs a) {
+__global__ __launch_bounds__(256, (PASS == 1 && CF <= 8) ? 3 : 1) void sa_mfma_fwd_kernel(const SaFwdArgs a) {
     static_assert(STATS || PASS == 1, "pass 0 IS the statistics pass");
     constexpr int TO1 = C1 / 16;
     constexpr int CL = NL == 2 ? C2 : C1, TOL = CL / 16, CS = PASS == 0 ? C1 : CL, TOS = CS / 16;
@@ -1078,7 +1078,7 @@ int sa_mfma_launch_fwd(const sn2_sa* p, int training, hipStream_t st, int* nbloc
     a.ext = p->ext; a.arg = p->arg;
     a.al = k1.a; a.cl = k1.c; a.out = p->out;
     static const int occ_env = getenv("SN2_SA_FWD_OCC") ? atoi(getenv("SN2_SA_FWD_OCC")) : 0;
-    const int occ = occ_env > 0 ? occ_env : (CF == 8 ? (PASS == 0 ? 4 : 3) : (CF == 16 ? 2 : 1));
+    const int occ = occ_env > 0 ? occ_env : (CF <= 8 ? (PASS == 0 ? 4 : 3) : (CF == 16 ? 2 : 1));     // (CF <= 8: the level-0 module, 8 or 4 point features)
     int blocks = sa_grid(p, occ);
     if (blocks > SN2_STAT_SLOTS) blocks = SN2_STAT_SLOTS;  // a workgroup writes its statistics into a slot of its own
     if (nblocks_out) *nblocks_out = blocks;
@@ -1096,6 +1096,8 @@ int sa_mfma_launch_fwd(const sn2_sa* p, int training, hipStream_t st, int* nbloc
 
 template int sa_mfma_launch_fwd<8, 2, 16, 16, 0>(const sn2_sa*, int, hipStream_t, int*);
 template int sa_mfma_launch_fwd<8, 2, 16, 16, 1>(const sn2_sa*, int, hipStream_t, int*);
+template int sa_mfma_launch_fwd<4, 2, 16, 16, 0>(const sn2_sa*, int, hipStream_t, int*);     // four point features: MLP[7,16,16], two K-blocks
+template int sa_mfma_launch_fwd<4, 2, 16, 16, 1>(const sn2_sa*, int, hipStream_t, int*);
 template int sa_mfma_launch_fwd<16, 1, 32, 32, 1>(const sn2_sa*, int, hipStream_t, int*);
 template int sa_mfma_launch_fwd<32, 1, 64, 64, 1>(const sn2_sa*, int, hipStream_t, int*);   // third ball-query level (3sa-arch)
 
@@ -1119,7 +1121,7 @@ int sa_mfma_launch_bwd(const sn2_sa* p, float* ws, hipStream_t st) {
     a.dfeat = p->dfeat;
     a.ws = ws;
     static const int occ_env = getenv("SN2_SA_BWD_OCC") ? atoi(getenv("SN2_SA_BWD_OCC")) : 0;
-    const int occ = occ_env > 0 ? occ_env : (CF == 8 ? 2 : 1);            // workgroups per CU that are resident together
+    const int occ = occ_env > 0 ? occ_env : (CF <= 8 ? 2 : 1);            // workgroups per CU that are resident together
     const int blocks = sa_grid(p, occ);
     const size_t lds = (size_t)(p->blk[0].mma_bf16 ? SaBwdLds<CF, NL, C1, C2, PASS, true>::FLOATS
                                                    : SaBwdLds<CF, NL, C1, C2, PASS, false>::FLOATS) * 4 * sizeof(float);
@@ -1132,5 +1134,7 @@ int sa_mfma_launch_bwd(const sn2_sa* p, float* ws, hipStream_t st) {
 
 template int sa_mfma_launch_bwd<8, 2, 16, 16, 2>(const sn2_sa*, float*, hipStream_t);
 template int sa_mfma_launch_bwd<8, 2, 16, 16, 3>(const sn2_sa*, float*, hipStream_t);
+template int sa_mfma_launch_bwd<4, 2, 16, 16, 2>(const sn2_sa*, float*, hipStream_t);
+template int sa_mfma_launch_bwd<4, 2, 16, 16, 3>(const sn2_sa*, float*, hipStream_t);
 template int sa_mfma_launch_bwd<16, 1, 32, 32, 3>(const sn2_sa*, float*, hipStream_t);
 template int sa_mfma_launch_bwd<32, 1, 64, 64, 3>(const sn2_sa*, float*, hipStream_t);

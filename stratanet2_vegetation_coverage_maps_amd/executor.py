@@ -27,7 +27,8 @@ _FAKE_BASE = 1 << 40                 # carve against a fake base: a field's offs
 _ITEM = {F32: 4, I32: 4, I64: 8, BF16: 2, U8: 1}
 
 
-def _geo_shapes(B, N, M1, M2, cap1, cap2):
+def _geo_shapes(B, N, M1, M2, cap1, cap2, feats=8):
+    """feats: the point features the model reads (PointNet2.n_input_feats): rows0 is (B*N, feats+4)."""
     return {
         "idx1": (I32, (B, M1)), "pos1_soa": (F32, (B, 3, M1)), "pos1_aos": (F32, (B * M1, 4)), "ws1": (I32, (ops.fps_ws_words(B, N),)),
         "nbr1": (I32, (B * M1, cap1)), "cnt1": (I32, (B * M1,)), "tot1": (I64, (1,)), "ord1": (I32, (ops.sa_order_len(B, M1),)),
@@ -38,7 +39,7 @@ def _geo_shapes(B, N, M1, M2, cap1, cap2):
         "inv3": (F32, (ops.interp_ws_words(B, M2, 1),)), "inv2": (F32, (ops.interp_ws_words(B, M1, M2),)),
         "inv1": (F32, (ops.interp_ws_words(B, N, M1),)),
         "nn_ws2": (I32, (ops.three_nn_ws_words(B, M2, M1),)), "nn_ws1": (I32, (ops.three_nn_ws_words(B, M1, N),)),
-        "rows0": (F32, (B * N, 12)), "p2_pix": (I32, (B * N,)), "p2_mm": (F32, (B, 4)),
+        "rows0": (F32, (B * N, feats + 4)), "p2_pix": (I32, (B * N,)), "p2_mm": (F32, (B, 4)),
     }
 
 
@@ -88,7 +89,7 @@ class Plan:
         g = NetGeo()
         _lib.check(lib.sn2_net_geo_carve(byref(ms), byref(d), _FAKE_BASE, byref(g), byref(sz)), "sn2_net_geo_carve")
         self.geo_bytes = int(sz.value)
-        self.geo_offsets = _offsets(g, _geo_shapes(B, N, M1, M2, d.cap1, d.cap2))
+        self.geo_offsets = _offsets(g, _geo_shapes(B, N, M1, M2, d.cap1, d.cap2, model.n_input_feats))
         self.act_bytes, self.act_offsets = {}, {}
         for training in (0, 1):
             a = NetAct()
@@ -339,6 +340,17 @@ def _io(model, dev, training, flags, cloud=None, fps_start=None, fork=False, n_l
     return io
 
 
+def _cloud_flag(model, cloud, B, N):
+    """Checks `cloud` against the model's feature count -- (B, F+2, N), or for a four-feature model also the reference's ten
+    rows -- and says which it is: SN2_NET_CLOUD10 or 0."""
+    F = model.n_input_feats
+    if F != 8 and tuple(cloud.shape) == (B, 10, N):
+        ops._chk(cloud, F32, (B, 10, N), "cloud")
+        return _lib.NET_CLOUD10
+    ops._chk(cloud, F32, (B, F + 2, N), "cloud")
+    return 0
+
+
 def geometry(model, ms, xyz, fps_start, out=None, fork=None, shared=False, defer_join=False, inverted=True, cloud=None, n_live=None):
     """`PointNet2._geometry` as one call (sn2_net_geometry)."""
     dev = xyz.device
@@ -358,8 +370,7 @@ def geometry(model, ms, xyz, fps_start, out=None, fork=None, shared=False, defer
     if fork and defer_join:
         flags |= _lib.NET_DEFER_JOIN
     if cloud is not None:
-        ops._chk(cloud, F32, (B, 10, N), "cloud")
-        flags |= _lib.NET_INPUT_ONLY
+        flags |= _lib.NET_INPUT_ONLY | _cloud_flag(model, cloud, B, N)
     io = _io(model, dev, model.training, flags, cloud=cloud, fps_start=fps_start, fork=fork, n_live=n_live, geo=g)
     _lib.check(_lib.load().sn2_net_geometry(byref(ms.c), byref(plan.dims), byref(cg), byref(io), ops._stream()), "sn2_net_geometry")
     g.has_inverted = bool(inverted)
@@ -375,7 +386,7 @@ def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None
     dev = xyz.device
     B, _, N = xyz.shape
     ops._chk(xyz, F32, (B, 3, N), "xyz")
-    ops._chk(cloud, F32, (B, 10, N), "cloud")
+    cloud10 = _cloud_flag(model, cloud, B, N)
     plan = ms.plan(model, B, N)
     lib = _lib.load()
     fork = False
@@ -425,7 +436,7 @@ def forward(model, ms, xyz, cloud, fps_start, training, geo=None, drop_keep=None
         # of its own in front of that pass
         bwd_arena = torch.empty(plan.bwd_arena_words, dtype=F32, device=dev)
         ca.bwd_arena, ca.bwd_arena_words = bwd_arena.data_ptr(), plan.bwd_arena_words
-    io = _io(model, dev, mode, flags, cloud=cloud, fps_start=fs, fork=fork, n_live=n_live, geo=geo)
+    io = _io(model, dev, mode, flags | cloud10, cloud=cloud, fps_start=fs, fork=fork, n_live=n_live, geo=geo)
     if training and model.fuse_global_level and plan.gl_forward:
         ws = ops.global_level_ws(dev, owner=model)
         io.gl_xchg, io.gl_ctl = ws[0].data_ptr(), ws[1].data_ptr()

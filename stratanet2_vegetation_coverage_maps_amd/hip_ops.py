@@ -306,12 +306,15 @@ def r2_threshold(r: float) -> float:
 
 
 # ---------------------------------------------------------------------------------------------- geometry
-def pack_rows(cloud: torch.Tensor, xyz: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def pack_rows(cloud: torch.Tensor, xyz: torch.Tensor, out: Optional[torch.Tensor] = None, feats: int = 8) -> torch.Tensor:
+    """include/strata_hip.h: sn2_pack_rows_feat.  cloud (B,C,N), xyz (B,3,N) -> rows0 (B*N, feats+4) = [feats features | x y z 0];
+    (C, feats) = (10, 8), (6, 4) or (10, 4) -- a ten-row cloud whose colour rows a four-feature model never reads."""
     B, C, N = cloud.shape
     _chk(cloud, F32, (B, C, N), "cloud")
     _chk(xyz, F32, (B, 3, N), "xyz")
-    rows0 = torch.empty(B * N, 12, dtype=F32, device=cloud.device) if out is None else _chk(out, F32, (B * N, 12), "out")
-    _call("sn2_pack_rows", _ptr(cloud), _ptr(xyz), B, C, N, _ptr(rows0), _stream())
+    W = int(feats) + 4
+    rows0 = torch.empty(B * N, W, dtype=F32, device=cloud.device) if out is None else _chk(out, F32, (B * N, W), "out")
+    _call("sn2_pack_rows_feat", _ptr(cloud), _ptr(xyz), B, C, N, int(feats), _ptr(rows0), _stream())
     return rows0
 
 

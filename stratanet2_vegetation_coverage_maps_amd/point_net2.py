@@ -192,8 +192,16 @@ class PointNet2(nn.Module):
         # additive extension (not a reference flag): "bf16" = bfloat16 operands on the matrix cores (BASELINE.json
         # configs[4]); default "fp32" = the reference's precision
         self.set_mma_dtype(getattr(args, "mma_dtype", "fp32"))
-        if self.n_class != 4 or self.n_input_feats != 8:
-            raise ValueError("the HIP kernels cover the reference architecture: n_class=4, 10 input features")
+        if self.n_class != 4 or self.n_input_feats not in self.SUPPORTED_FEATS:
+            raise ValueError("the HIP kernels cover the reference architecture with n_class=4 and n_input_feats - 2 in {"
+                             f"{', '.join(str(f) for f in sorted(self.SUPPORTED_FEATS))}}} point features "
+                             f"(got n_class={self.n_class}, n_input_feats={args.n_input_feats})")
+
+    # Point features the kernels are instantiated for (`args.n_input_feats - 2`; model/point_net2.py:77): the reference's eight
+    # (z, red, green, blue, nir, intensity, return_num, num_returns) and four (z, intensity, return_num, num_returns: LiDAR that was
+    # never colourised).  A four-feature model takes `cloud (B,6,N)` -- or the reference's `(B,10,N)`, whose colour rows 3..6 it
+    # never reads (include/strata_hip.h: sn2_pack_rows_feat), so every producer of ten-row clouds serves it as it is.
+    SUPPORTED_FEATS = (4, 8)
 
     # the blocks `mma_dtype = "bf16"` applies to: everything that runs on the matrix cores -- the set-abstraction levels and
     # the dense layers over centroids (SA3, FP3, FP2).  The two per-point layers (FP1 in its source-side form, the head)
@@ -251,8 +259,8 @@ class PointNet2(nn.Module):
         if dev.type != "cuda":
             raise StrataHipError("PointNet2.forward needs a HIP device (args.cuda): the product path has no CPU "
                                  "fallback; the CPU restatement lives in oracle/ and is test infrastructure")
-        if cloud.dim() != 3 or cloud.shape[1] != self.n_input_feats + 2 or xyz.shape != (cloud.shape[0], 3, cloud.shape[2]):
-            raise ValueError(f"expected cloud (B,{self.n_input_feats + 2},N) and xyz (B,3,N), got "
+        if cloud.dim() != 3 or cloud.shape[1] not in self._cloud_rows() or xyz.shape != (cloud.shape[0], 3, cloud.shape[2]):
+            raise ValueError(f"expected cloud {' or '.join(f'(B,{c},N)' for c in self._cloud_rows())} and xyz (B,3,N), got "
                              f"{tuple(cloud.shape)} and {tuple(xyz.shape)}")
         with torch.cuda.device(dev):
             geo = cloud_data.get("geometry", None) if isinstance(cloud_data, dict) else None
@@ -305,6 +313,11 @@ class PointNet2(nn.Module):
         params = self._params()
         self._grad_mode_at_call = torch.is_grad_enabled()
         return _PointNet2Fn.apply(self, xyz_d, cloud_d, None, g, self._dropout_keep(cloud_data, cloud_d), *params)
+
+    def _cloud_rows(self):
+        """The row counts `forward` accepts for `cloud`: F + 2, and for a four-feature model also the reference's ten."""
+        F = self.n_input_feats
+        return (F + 2,) if F == 8 else (F + 2, 10)
 
     def _params(self):
         """The module's parameters in `parameters()` order, walked once (the walk was 0.1 ms of host time per forward and per
@@ -388,7 +401,7 @@ class PointNet2(nn.Module):
     def _fp1_source_side(rows):
         """Whether the per-point layer FP1 runs in its source-side form (hip_ops.fp_desc hands out `src_ws`): only that form
         keeps bfloat16 rows (`_act_dtype`) and a permuted d pre-activation buffer (`rank1`)."""
-        return bool(ops.SOURCE_SIDE) and ops.fp_source_side(rows, 8)
+        return bool(ops.SOURCE_SIDE) and ops.fp_source_side(rows, 8)      # (the rule is the same for FP1's 4 or 8 skip columns)
 
     def _act_dtype(self, rows):
         """Storage type of the three per-point activation buffers (FP1's output h1, the head's gradient dy1, FP1's
@@ -488,7 +501,7 @@ class PointNet2(nn.Module):
 
     def _alloc_input_only(self, g, B, N, dev):
         """Buffers of the input-only pieces a geometry pass may produce (see `p2_diam_pix`)."""
-        g.rows0 = torch.empty(B * N, 12, dtype=F32, device=dev)
+        g.rows0 = torch.empty(B * N, self.n_input_feats + 4, dtype=F32, device=dev)
         g.has_rows0 = False
         g.p2_pix, g.p2_mm, g.p2_diam_pix = None, None, None
         if self.p2_diam_pix is not None:
@@ -497,7 +510,7 @@ class PointNet2(nn.Module):
 
     def _input_only(self, g, cloud, xyz):
         """The input-only pieces of the feature pass, run with the geometry pass when it is handed the batch's `cloud` (device)."""
-        ops.pack_rows(cloud, xyz, out=g.rows0)
+        ops.pack_rows(cloud, xyz, out=g.rows0, feats=self.n_input_feats)
         g.has_rows0 = True
         if g.p2_pix is not None and self.p2_diam_pix is not None:
             ops.plot_pixels(cloud, self.p2_diam_pix, out=(g.p2_mm, g.p2_pix))
@@ -553,7 +566,7 @@ class PointNet2(nn.Module):
         forward does not need them -- a tenth of the geometry pass of the parcel loop); `g.has_inverted` records it.
         `shared`: the pass runs beside other batches' feature kernels (a pipelined loop, `prefetch_geometry`): the level-1
         FPS takes `fps_waves_shared` waves per plot (include/strata_hip.h: sn2_fps_waves).
-        `cloud` (B,10,N) on the device: also run the input-only pieces of the feature pass here (`_input_only`).
+        `cloud` (B,F+2,N) on the device ((B,10,N) too for F = 4): also run the input-only pieces of the feature pass here (`_input_only`).
         `n_live` (B) int32 on the device or None: the plots' live prefixes (`cloud_data["n_live"]`; include/strata_hip.h:
         sn2_fps_live) -- level 1 samples over them and counts its samples up to a maximum of 0, the next level takes that count.
         Same tables with or without it."""
@@ -800,11 +813,11 @@ class PointNet2(nn.Module):
         if geo is None:
             if self.geometry_fork:
                 # the row packing needs the inputs only: beside the level-1 FPS (16 workgroups) instead of behind it
-                rows0 = torch.empty(B * N, 12, dtype=F32, device=dev)
+                rows0 = torch.empty(B * N, self.n_input_feats + 4, dtype=F32, device=dev)
                 pack_stream = ops.shared_stream(dev, "pack")
                 pack_stream.wait_stream(cur_stream)
                 with torch.cuda.stream(pack_stream):
-                    ops.pack_rows(cloud, xyz, out=rows0)
+                    ops.pack_rows(cloud, xyz, out=rows0, feats=self.n_input_feats)
                     packed = torch.cuda.Event()
                     packed.record(pack_stream)
             geo = self._geometry(xyz, fps_start, defer_join=True, inverted=keep, n_live=n_live)
@@ -850,14 +863,14 @@ class PointNet2(nn.Module):
             bb.frozen = frozen
         e = lambda *shape, dt=F32: torch.empty(*shape, dtype=dt, device=dev)          # noqa: E731
 
-        # ---- level 0 rows: [8 features | x y z 0]
+        # ---- level 0 rows: [F features | x y z 0]
         if packed is not None:
             cur_stream.wait_event(packed)
             s.rows0 = rows0
         elif rows0 is not None:
             s.rows0 = rows0
         else:
-            s.rows0 = ops.pack_rows(cloud, xyz)
+            s.rows0 = ops.pack_rows(cloud, xyz, feats=self.n_input_feats)
         # ---- SA1 .. SAL: gather + MLP + BN + max over the ball-query lists        (point_net2.py:131-132, 21-29)
         for l in range(1, L + 1):
             R, C = B * Ms[l], s.b_sa[l][-1].cout

@@ -44,6 +44,7 @@ class PointNet2ThreeSA(PointNet2):
 
     BF16_BLOCKS = ("sa1_module.conv.local_nn", "sa2_module.conv.local_nn", "sa3_module.conv.local_nn", "sa4_module.nn",
                    "fp4_module.nn", "fp3_module.nn", "fp2_module.nn")
+    SUPPORTED_FEATS = (8,)          # MLP([11, 16, 16]) and MLP([34 + 8, 34]) above are written for the reference's eight point features
     executor = False                # the one-call C executor (csrc/net.hip) covers the reference architecture only
     geometry_fork = False           # its geometry passes run on one stream: forking them is a change that needs a measurement
     # the one-launch global-level kernels are written for 35 -> 64 and 96 -> 64; their route rules ask about B, rows and bf16

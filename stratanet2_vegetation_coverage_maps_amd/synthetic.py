@@ -14,6 +14,9 @@ import torch
 
 BASE_SEED = 20211007
 Z_MAX = 24.24
+# the rows of a ten-row cloud that LiDAR without colour has: x, y, z, intensity, return_num, num_returns.  `cloud[:, LIDAR_ROWS]` is the
+# six-row cloud of a four-feature model (make_args(n_input_feats=6)); the same model reads exactly these rows of the ten-row cloud
+LIDAR_ROWS = (0, 1, 2, 7, 8, 9)
 
 
 def make_args(**kw):
