@@ -2,6 +2,7 @@
 // All discrete decisions use the canonical fp32 squared distance sn2_d2 (common.h) so that the index structures
 // are bit-identical to the oracle's.
 #include "common.h"
+#include "plot_sort.h"
 #include <stdlib.h>
 
 // ------------------------------------------------------------------------------------------------------------
@@ -198,7 +199,7 @@ static int launch_fps(const fps_call& a) {
 // Bucketed FPS (exact).  The brute-force kernel above touches all N points in each of the M sequential rounds
 // (4.1 ms for 16 x 32768 -> 1024 on MI355X: 40 % of a training step).  But a new sample s only lowers the running
 // distance of points closer to s than their current distance, i.e. points near s.  So:
-//   * spatial_order_kernel sorts a plot's points by the Morton code of a 16x16x16 cell grid (LDS counting sort);
+//   * spatial_order_chunk_kernel sorts a plot's points by the Morton code of a 16x16x16 cell grid (LDS counting sort);
 //   * consecutive runs of 64 sorted points form a BUCKET = one VGPR slot of one wave (bucket b -> wave b % 16, slot
 //     b / 16, so spatially adjacent buckets sit in different waves and a round's work spreads over the 16 waves);
 //   * per bucket LDS keeps the bounding box and the maximum running distance; per round each wave tests its <= 32
@@ -229,10 +230,19 @@ static_assert(GRID_WORDS == ORDER_CELLS + 1 + 6 + 1, "cell starts (+ end), lo.xy
 // FPS_CTL_WORDS control words per launch (ticket counter, timeout count).  Zeroed HERE, by the kernel in front of every FPS
 // launch (a kernel boundary: visible to every workgroup behind it; the tags count super-rounds from 1, so 0 = nothing yet).
 constexpr int FPS_XCHG_WORDS = SN2_FPS_WS_XCHG_WORDS, FPS_CTL_WORDS = SN2_FPS_WS_CTL_WORDS;
-// One workgroup of 1024 threads per plot walks the points three times (bounding box, histogram, scatter); a trip fetches U = 16
-// points per thread before it touches the first (two trips per pass at N = 32 768; one DEPENDENT load per trip took 71 us,
-// all 32 points of a thread in registers at once spill at 1024 threads).  What is left (61 us) are the LDS atomics: 55 % of a
-// plot's points are ground points in a few cell layers, and a wave's adds onto one counter serialise.
+// the Morton cell of a point (lo, sc: as the grid header keeps them)
+__device__ __forceinline__ unsigned order_cell(const float (&lo)[3], const float (&sc)[3], float x, float y, float z) {
+    int cx = (int)((x - lo[0]) * sc[0]), cy = (int)((y - lo[1]) * sc[1]), cz = (int)((z - lo[2]) * sc[2]);
+    cx = cx < 0 ? 0 : (cx > ORDER_GX - 1 ? ORDER_GX - 1 : cx);
+    cy = cy < 0 ? 0 : (cy > ORDER_GX - 1 ? ORDER_GX - 1 : cy);
+    cz = cz < 0 ? 0 : (cz > ORDER_GZ - 1 ? ORDER_GZ - 1 : cz);
+    return morton_cell((unsigned)cx, (unsigned)cy, (unsigned)cz);
+}
+
+// One workgroup per plot walks the points three times (bounding box, histogram, scatter: the counting sort of plot_sort.h); a
+// trip fetches U points per thread before it touches the first (two trips per pass at N = 32 768 with U = 16 and 1024 threads:
+// one DEPENDENT load per trip took 71 us, all 32 points of a thread in registers at once spill).  What is left (61 us) are the
+// LDS atomics: 55 % of a plot's points are ground points in a few cell layers, and a wave's adds onto one counter serialise.
 // rank (or NULL): rank[plot * N + i] = sorted position of point i -- the inverse of `order` (sn2_fp.row_perm)
 template <int U, int NT>
 __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __restrict__ pos, int N, int* __restrict__ order,
@@ -246,7 +256,8 @@ __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __
     const float* px = pos + (size_t)b * 3 * N;
     const float* py = px + N;
     const float* pz = py + N;
-    // fn(i, x, y, z) for every point i of the plot, U points per thread and trip
+    // fn(i, x, y, z) for every point i of the plot, U points per thread and trip (plot_sort.h's loader, box and cell scan written
+    // out: built from its functions this kernel measured 0.5 - 2.4 % slower, profiles/plot_sort)
     auto for_points = [&](auto fn) {
         for (int i0 = 0; i0 < N; i0 += NT * U) {
             float vx[U], vy[U], vz[U];
@@ -296,14 +307,7 @@ __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __
         const float ext = fmaxf(h - l, 1e-6f);
         sc[a] = (a < 2 ? (float)ORDER_GX : (float)ORDER_GZ) / ext;
     }
-    auto cell_of = [&](float vx, float vy, float vz) -> unsigned {     // the arithmetic of spatial_order_kernel, bit for bit
-        int cx = (int)((vx - lo[0]) * sc[0]), cy = (int)((vy - lo[1]) * sc[1]), cz = (int)((vz - lo[2]) * sc[2]);
-        cx = cx < 0 ? 0 : (cx > ORDER_GX - 1 ? ORDER_GX - 1 : cx);
-        cy = cy < 0 ? 0 : (cy > ORDER_GX - 1 ? ORDER_GX - 1 : cy);
-        cz = cz < 0 ? 0 : (cz > ORDER_GZ - 1 ? ORDER_GZ - 1 : cz);
-        return morton_cell((unsigned)cx, (unsigned)cy, (unsigned)cz);
-    };
-    for_points([&](int, float vx, float vy, float vz) { atomicAdd(&s_hist[cell_of(vx, vy, vz)], 1); });
+    for_points([&](int, float vx, float vy, float vz) { atomicAdd(&s_hist[order_cell(lo, sc, vx, vy, vz)], 1); });
     __syncthreads();
     // exclusive scan over the cells: PER consecutive cells per thread, wave scan, 16 wave totals
     constexpr int PER = ORDER_CELLS / NT;
@@ -313,12 +317,7 @@ __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __
         loc[k] = s_hist[tid * PER + k];
         sum += loc[k];
     }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
+    const int incl = wave_scan_incl(sum);
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
     int base = 0;
@@ -342,7 +341,7 @@ __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __
     float4* sb = sorted + (size_t)b * N;
     const int nlive = fps_live_count(n_live, b, N);
     for_points([&](int i, float vx, float vy, float vz) {
-        const int p = atomicAdd(&s_hist[cell_of(vx, vy, vz)], 1);
+        const int p = atomicAdd(&s_hist[order_cell(lo, sc, vx, vy, vz)], 1);
         ob[p] = i;
         sb[p] = make_float4(vx, vy, vz, i < nlive ? INFINITY : 0.f);      // .w = running FPS distance (dead points: 0 throughout)
         if (rank) rank[(size_t)b * N + i] = p;
@@ -421,7 +420,7 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
     const float* py = px + N;
     const float* pz = py + N;
     const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_kernel; dead: 0)
+    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_chunk_kernel; dead: 0)
     if (tid == 0 && n_live_out) n_live_out[b] = M;     // unless the maximum reaches 0 first (fps_fill_zero)
     float* my_box = s_box + wave * SPW;                // + component * NBK + slot
     for (int k = 0; k < SPW; ++k) {
@@ -688,7 +687,7 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
     const float* py = px + N;
     const float* pz = py + N;
     const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_kernel; dead: 0)
+    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_chunk_kernel; dead: 0)
     if (gate) {
         // REPAIR launch behind fps_cluster_kernel (gate = that launch's control words): nothing to do unless one of its waits
         // gave up (gate[1] = the count); then every plot is sampled again by this kernel, which waits for nobody.  The running
@@ -1217,7 +1216,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
     const float* py = px + N;
     const float* pz = py + N;
     const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_kernel)
+    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_chunk_kernel)
     fc_u64* xchg = xchg_all + (size_t)b * (2 * FC_COPY_U64);
     float* my_box = s_box + wave * SPW;                // + component * NBL + slot
     for (int k = 0; k < SPW; ++k) {
@@ -2038,7 +2037,7 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Grid ball query (exact): the sources were already sorted into 16^3 Morton cells by spatial_order_kernel (FPS level 1
+// Grid ball query (exact): the sources were already sorted into 16^3 Morton cells by spatial_order_chunk_kernel (FPS level 1
 // runs on the same points).  One wave per centroid walks only the cells that can intersect the ball -- the cell range of
 // [c - r, c + r] per axis under the same monotone fp32 cell function, so no point with d2 < r2 is missed --, tests the
 // cells' points with the canonical sn2_d2, compacts the hits into a wave-private LDS list, rank-sorts them by ORIGINAL
@@ -2123,12 +2122,7 @@ __global__ __launch_bounds__(256) void ball_query_grid_kernel(const float* __res
             p0 = gb[cell];
             len = gb[cell + 1] - p0;
         }
-        int incl = len;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const int incl = wave_scan_incl(len);
         const int T = __shfl(incl, 63);
         s_pre[wib][lane + 1] = incl;   // exclusive prefix of cell i = s_pre[i]
         if (lane == 0) s_pre[wib][0] = 0;
@@ -2224,12 +2218,7 @@ __global__ __launch_bounds__(256) void ball_query_grid_kernel(const float* __res
                 unsigned word = (w0 + lane < nwords) ? bits[w0 + lane] : 0u;
                 const int c = __popc(word);
                 if (__ballot(c != 0) == 0ull) continue;
-                int incl = c;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int tt = __shfl_up(incl, o);
-                    if (lane >= o) incl += tt;
-                }
+                const int incl = wave_scan_incl(c);
                 int pos = n + incl - c;
                 while (word) {
                     const int bit = __ffs(word) - 1;
@@ -2415,72 +2404,37 @@ __global__ __launch_bounds__(256) void nn_grid_build_kernel(const float* __restr
                                                             float4* __restrict__ tbl, int* __restrict__ hdr) {
     __shared__ int s_hist[NN_GMAX * NN_GMAX + 1];
     __shared__ float s_mm[4][4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* sx = src + (size_t)b * 3 * S;
     const float* sy = sx + S;
     const float* sz = sy + S;
-    float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
-    for (int i = tid; i < S; i += 256) {
-        mnx = fminf(mnx, sx[i]); mxx = fmaxf(mxx, sx[i]);
-        mny = fminf(mny, sy[i]); mxy = fmaxf(mxy, sy[i]);
-    }
-    mnx = wave_min(mnx); mny = wave_min(mny); mxx = wave_max(mxx); mxy = wave_max(mxy);
-    if (lane == 0) { s_mm[0][wave] = mnx; s_mm[1][wave] = mny; s_mm[2][wave] = mxx; s_mm[3][wave] = mxy; }
-    for (int i = tid; i <= G * G; i += 256) s_hist[i] = 0;
-    __syncthreads();
-    const float x0 = fminf(fminf(s_mm[0][0], s_mm[0][1]), fminf(s_mm[0][2], s_mm[0][3]));
-    const float y0 = fminf(fminf(s_mm[1][0], s_mm[1][1]), fminf(s_mm[1][2], s_mm[1][3]));
-    const float x1 = fmaxf(fmaxf(s_mm[2][0], s_mm[2][1]), fmaxf(s_mm[2][2], s_mm[2][3]));
-    const float y1 = fmaxf(fmaxf(s_mm[3][0], s_mm[3][1]), fmaxf(s_mm[3][2], s_mm[3][3]));
-    const float ex = fmaxf(x1 - x0, 1e-6f), ey = fmaxf(y1 - y0, 1e-6f);
+    auto load = [&](int i) { return make_float3(sx[i], sy[i], sz[i]); };
+    float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+    for_plot_points<1, 256>(S, load, [&](int, float3 v) {
+        lo[0] = fminf(lo[0], v.x); hi[0] = fmaxf(hi[0], v.x);
+        lo[1] = fminf(lo[1], v.y); hi[1] = fmaxf(hi[1], v.y);
+    });
+    block_minmax<256, 2>(lo, hi, s_mm);
+    const float x0 = lo[0], y0 = lo[1];
+    const float ex = fmaxf(hi[0] - x0, 1e-6f), ey = fmaxf(hi[1] - y0, 1e-6f);
     const float ix = (float)G / ex, iy = (float)G / ey;
-    auto cell_of = [&](int i) {
-        int cx = (int)((sx[i] - x0) * ix), cy = (int)((sy[i] - y0) * iy);
-        cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
-        cy = cy < 0 ? 0 : (cy > G - 1 ? G - 1 : cy);
-        return cy * G + cx;
-    };
-    for (int i = tid; i < S; i += 256) atomicAdd(&s_hist[cell_of(i)], 1);
-    __syncthreads();
-    {   // exclusive scan over the <= 1024 cells: 4 consecutive cells per thread, wave scan, 4 wave totals
-        __shared__ int s_wsum[4];
-        int loc[4], sum = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            loc[c] = (tid * 4 + c < G * G) ? s_hist[tid * 4 + c] : 0;
-            sum += loc[c];
-        }
-        int incl = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        int run = incl - sum;
-        for (int k = 0; k < wave; ++k) run += s_wsum[k];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (tid * 4 + c < G * G) s_hist[tid * 4 + c] = run;
-            run += loc[c];
-        }
-        if (tid == 255) s_hist[G * G] = run;     // = S: thread 255 ends the scan whatever G is (empty tail cells add 0)
-    }
-    __syncthreads();
     int* hb = hdr + (size_t)b * NN_HDR;
-    for (int i = tid; i <= G * G; i += 256) hb[i] = s_hist[i];
     if (tid == 0) {
         float* hf = reinterpret_cast<float*>(hb + NN_GMAX * NN_GMAX + 1);
         hf[0] = x0; hf[1] = y0; hf[2] = ix; hf[3] = iy; hf[4] = fminf(ex, ey) / (float)G;
         hb[NN_GMAX * NN_GMAX + 1 + 5] = G;
     }
-    __syncthreads();
     float4* tb = tbl + (size_t)b * S;
-    for (int i = tid; i < S; i += 256) {
-        const int p = atomicAdd(&s_hist[cell_of(i)], 1);
-        tb[p] = make_float4(sx[i], sy[i], sz[i], __int_as_float(i));
-    }
+    plot_counting_sort<1, 256, NN_GMAX * NN_GMAX, true>(
+        s_hist, G * G, S, load,
+        [&](float3 v) {
+            int cx = (int)((v.x - x0) * ix), cy = (int)((v.y - y0) * iy);
+            cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
+            cy = cy < 0 ? 0 : (cy > G - 1 ? G - 1 : cy);
+            return cy * G + cx;
+        },
+        [&](int cell, int start) { hb[cell] = start; },       // cell starts + end word (= S)
+        [&](int i, int p, float3 v) { tb[p] = make_float4(v.x, v.y, v.z, __int_as_float(i)); });
 }
 
 #ifdef SN2_NN_STAMPS
@@ -2649,62 +2603,14 @@ extern "C" int sn2_count_sum(const int* cnt, int n, unsigned long long* total, v
 // Morton order of a 16^3 grid, the boxes averaged 7 cells and reached 72: 162 candidates per wave on average, 726 in
 // the slowest, and the slowest wave is the kernel.)  The order inside a cell is whatever the cursor atomics give: the
 // search is exact, so its results do not depend on it.
-__global__ __launch_bounds__(1024) void nn_target_sort_kernel(const float* __restrict__ dst, int T, const int* __restrict__ hdr,
-                                                              int* __restrict__ order, float4* __restrict__ sorted) {
-    __shared__ int s_hist[NN_GMAX * NN_GMAX + 1];
-    __shared__ int s_wsum[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int* hb = hdr + (size_t)b * NN_HDR;
-    const int G = hb[NN_GMAX * NN_GMAX + 1 + 5];
-    const float* hf = reinterpret_cast<const float*>(hb + NN_GMAX * NN_GMAX + 1);
-    const float x0 = hf[0], y0 = hf[1], ix = hf[2], iy = hf[3];
-    const float* dx = dst + (size_t)b * 3 * T;
-    const float* dy = dx + T;
-    const float* dz = dy + T;
-    auto key_of = [&](int i) {
-        const float vx = dx[i] - x0, vy = dy[i] - y0;
-        int cx = (int)(vx * ix), cy = (int)(vy * iy);
-        cx = (vx < 0.f || cx < 0) ? 0 : (cx > G - 1 ? G - 1 : cx);
-        cy = (vy < 0.f || cy < 0) ? 0 : (cy > G - 1 ? G - 1 : cy);
-        return cy * G + ((cy & 1) ? G - 1 - cx : cx);
-    };
-    for (int i = tid; i <= G * G; i += 1024) s_hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < T; i += 1024) atomicAdd(&s_hist[key_of(i)], 1);
-    __syncthreads();
-    {   // exclusive scan over the <= 1024 cells: one cell per thread, wave scan, 16 wave totals
-        const int v = tid < G * G ? s_hist[tid] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        int run = incl - v;
-        for (int k = 0; k < wave; ++k) run += s_wsum[k];
-        __syncthreads();
-        if (tid < G * G) s_hist[tid] = run;
-    }
-    __syncthreads();
-    int* ob = order + (size_t)b * T;
-    float4* sb = sorted + (size_t)b * T;
-    for (int i = tid; i < T; i += 1024) {
-        const int p = atomicAdd(&s_hist[key_of(i)], 1);
-        ob[p] = i;
-        sb[p] = make_float4(dx[i], dy[i], dz[i], 0.f);
-    }
-}
-
-// nn_target_sort_kernel with U loads per coordinate in flight (the loop form spends a trip of dependent loads per point and
-// pass: 54 us at T = 32 768); same keys, same tables
+// U loads per coordinate in flight (a loop of one point per thread and trip spends a trip of dependent loads per point and
+// pass: 54 us at T = 32 768).  A target below the sources' box on an axis (vx < 0) goes to the first cell of that axis.
 template <int U, int NT>
 __global__ __launch_bounds__(NT) void nn_target_sort_chunk_kernel(const float* __restrict__ dst, int T, const int* __restrict__ hdr,
                                                                     int* __restrict__ order, float4* __restrict__ sorted) {
-    __shared__ int s_hist[NN_GMAX * NN_GMAX + 1];
+    __shared__ int s_hist[NN_GMAX * NN_GMAX];
     __shared__ int s_wsum[NT / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* dx = dst + (size_t)b * 3 * T;
     const float* dy = dx + T;
     const float* dz = dy + T;
@@ -2712,15 +2618,16 @@ __global__ __launch_bounds__(NT) void nn_target_sort_chunk_kernel(const float* _
     const int G = hb[NN_GMAX * NN_GMAX + 1 + 5];
     const float* hf = reinterpret_cast<const float*>(hb + NN_GMAX * NN_GMAX + 1);
     const float x0 = hf[0], y0 = hf[1], ix = hf[2], iy = hf[3];
-    auto key_of = [&](float px_, float py_) {                       // nn_target_sort_kernel's key, bit for bit
+    auto key_of = [&](float px_, float py_) {
         const float vx = px_ - x0, vy = py_ - y0;
         int cx = (int)(vx * ix), cy = (int)(vy * iy);
         cx = (vx < 0.f || cx < 0) ? 0 : (cx > G - 1 ? G - 1 : cx);
         cy = (vy < 0.f || cy < 0) ? 0 : (cy > G - 1 ? G - 1 : cy);
         return cy * G + ((cy & 1) ? G - 1 - cx : cx);
     };
-    for (int i = tid; i <= G * G; i += NT) s_hist[i] = 0;
+    for (int i = tid; i < G * G; i += NT) s_hist[i] = 0;
     __syncthreads();
+    // (plot_sort.h's loader written out: through it the 256-thread form measured 3 % slower, profiles/plot_sort)
     for (int i0 = 0; i0 < T; i0 += NT * U) {
         float vx[U], vy[U];
 #pragma unroll
@@ -2733,32 +2640,7 @@ __global__ __launch_bounds__(NT) void nn_target_sort_chunk_kernel(const float* _
             if (i0 + u * NT + tid < T) atomicAdd(&s_hist[key_of(vx[u], vy[u])], 1);
     }
     __syncthreads();
-    {   // exclusive scan over the <= 1024 cells: CPT consecutive cells per thread, wave scan, NT / 64 wave totals
-        constexpr int CPT = (NN_GMAX * NN_GMAX + NT - 1) / NT;
-        int v[CPT], sum = 0;
-#pragma unroll
-        for (int c = 0; c < CPT; ++c) {
-            v[c] = tid * CPT + c < G * G ? s_hist[tid * CPT + c] : 0;
-            sum += v[c];
-        }
-        int incl = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        int run = incl - sum;
-        for (int k = 0; k < wave; ++k) run += s_wsum[k];
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CPT; ++c) {
-            if (tid * CPT + c < G * G) s_hist[tid * CPT + c] = run;
-            run += v[c];
-        }
-    }
-    __syncthreads();
+    block_scan_cells<NT, NN_GMAX * NN_GMAX, false>(s_hist, G * G, s_wsum, [](int, int) {});
     int* ob = order + (size_t)b * T;
     float4* sb = sorted + (size_t)b * T;
     for (int i0 = 0; i0 < T; i0 += NT * U) {
@@ -2865,7 +2747,7 @@ __global__ __launch_bounds__(256) void znorm_cell_kernel(const float* __restrict
 // exclusive scan of hist (ncell <= 2^20) by one workgroup; start[c], and cursor[c] = start[c] for the scatter
 __global__ __launch_bounds__(1024) void znorm_scan_kernel(const int* __restrict__ hist, int ncell, int* __restrict__ start,
                                                           int* __restrict__ cursor) {
-    __shared__ int s_tot[1024];
+    __shared__ int s_wsum[16];
     const int tid = threadIdx.x;
     const int per = (ncell + 1023) / 1024;
     int sum = 0;
@@ -2873,14 +2755,7 @@ __global__ __launch_bounds__(1024) void znorm_scan_kernel(const int* __restrict_
         const int c = tid * per + k;
         if (c < ncell) sum += hist[c];
     }
-    s_tot[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int t = 0; t < 1024; ++t) { const int v = s_tot[t]; s_tot[t] = run; run += v; }
-    }
-    __syncthreads();
-    int run = s_tot[tid];
+    int run = block_scan_excl<1024>(sum, s_wsum);
     for (int k = 0; k < per; ++k) {
         const int c = tid * per + k;
         if (c < ncell) {

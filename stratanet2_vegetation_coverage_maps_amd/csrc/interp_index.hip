@@ -15,6 +15,7 @@
 // No floating-point atomics anywhere (LDS float atomics ran at ~0.4 lane-ops/clk/CU here: 275 us for FP1; global float
 // atomics onto random rows are worse), and dsrc is written exactly once per row.
 #include "fp_rows.h"
+#include "plot_sort.h"
 
 namespace {
 
@@ -78,6 +79,7 @@ __global__ __launch_bounds__(1024) void inv_scan_kernel(int R_per_plot, int S, i
     int* __restrict__ cnt = x.cnt;
     if (threadIdx.x == 0) s_carry = b * 3 * R_per_plot;
     __syncthreads();
+    // (block_scan_excl of plot_sort.h written out: through the function this kernel measured 3 % slower, profiles/plot_sort)
     for (int s0 = 0; s0 < S; s0 += 1024) {
         const int s = s0 + threadIdx.x;
         int tot = 0;
@@ -90,12 +92,7 @@ __global__ __launch_bounds__(1024) void inv_scan_kernel(int R_per_plot, int S, i
             }
             cnt[(size_t)b * S + s] = tot;
         }
-        int incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const int incl = wave_scan_incl(tot);
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();
         int base = s_carry;
@@ -159,10 +156,9 @@ __device__ __forceinline__ unsigned spread10(unsigned v) {
 __global__ __launch_bounds__(1024) void inv_order_kernel(const float4* __restrict__ pos, int S, int CM, int R_per_plot,
                                                          float* __restrict__ ws, int Bb, size_t ws_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned s_key[];   // [S rounded up to 4] keys | [S] source of every rank
-    __shared__ float s_lo[3][16], s_hi[3][16];
+    __shared__ float s_mm[6][16];
     __shared__ int s_w[16];
-    __shared__ int s_carry;
-    const int bg = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bg = blockIdx.x;
     const int hb = bg / Bb, b = bg - hb * Bb;
     const InvWs x = inv_ws_of(ws + (size_t)hb * ws_stride, Bb, R_per_plot, S);
     const int* __restrict__ off = x.off;
@@ -179,24 +175,10 @@ __global__ __launch_bounds__(1024) void inv_order_kernel(const float4* __restric
             lo[0] = fminf(lo[0], p.x), lo[1] = fminf(lo[1], p.y), lo[2] = fminf(lo[2], p.z);
             hi[0] = fmaxf(hi[0], p.x), hi[1] = fmaxf(hi[1], p.y), hi[2] = fmaxf(hi[2], p.z);
         }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                lo[a] = fminf(lo[a], __shfl_xor(lo[a], o));
-                hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o));
-            }
-            if (lane == 0) s_lo[a][wave] = lo[a], s_hi[a][wave] = hi[a];
-        }
-        __syncthreads();
+        block_minmax<1024, 3>(lo, hi, s_mm);
         float sc[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            float l = s_lo[a][0], h = s_hi[a][0];
-            for (int w = 1; w < 16; ++w) l = fminf(l, s_lo[a][w]), h = fmaxf(h, s_hi[a][w]);
-            lo[a] = l;
-            sc[a] = h > l ? 1023.999f / (h - l) : 0.f;
-        }
+        for (int a = 0; a < 3; ++a) sc[a] = hi[a] > lo[a] ? 1023.999f / (hi[a] - lo[a]) : 0.f;
         for (int i = threadIdx.x; i < S4; i += 1024) {
             unsigned key = 0xFFFFFFFFu;                                    // padding sorts last
             if (i < S) {
@@ -223,8 +205,8 @@ __global__ __launch_bounds__(1024) void inv_order_kernel(const float4* __restric
     } else {                                                           // no positions: identity
         for (int i = threadIdx.x; i < S; i += 1024) s_ord[i] = i;
     }
-    if (threadIdx.x == 0) s_carry = 0;
     __syncthreads();
+    int carry = 0;                                                     // chunks so far
     for (int k0 = 0; k0 < S; k0 += 1024) {
         const int k = k0 + threadIdx.x;
         int id = 0, o = 0, n = 0, nch = 0;
@@ -233,27 +215,16 @@ __global__ __launch_bounds__(1024) void inv_order_kernel(const float4* __restric
             o = off[id], n = cnt[id];
             nch = (n + INV_CHUNK - 1) / INV_CHUNK;
         }
-        int incl = nch;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        int base = s_carry;
-        for (int w = 0; w < wave; ++w) base += s_w[w];
-        const int first = base + incl - nch;
+        int next;
+        const int first = block_scan_excl<1024>(nch, s_w, carry, next);
         if (k < S) {
             items[(size_t)b * S + k] = make_int4(id, o, n, first);
             for (int c = 0; c < nch; ++c)
                 chunks[(size_t)b * CM + first + c] = make_int4(id, o + c * INV_CHUNK, min(INV_CHUNK, n - c * INV_CHUNK), b);
         }
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = base + incl;
-        __syncthreads();
+        carry = next;
     }
-    for (int j = s_carry + threadIdx.x; j < CM; j += 1024) chunks[(size_t)b * CM + j] = make_int4(0, 0, 0, 0);
+    for (int j = carry + threadIdx.x; j < CM; j += 1024) chunks[(size_t)b * CM + j] = make_int4(0, 0, 0, 0);
 }
 
 }  // namespace

@@ -5,6 +5,7 @@
 // Kernels and host helpers here have internal linkage: every unit that includes the header gets its own copy.
 #pragma once
 #include "common.h"
+#include "plot_sort.h"
 
 #include <limits.h>
 
@@ -37,7 +38,7 @@ static __global__ __launch_bounds__(256) void pscan_reduce_kernel(const int* __r
 // one workgroup: exclusive scan of the nb block sums in place; total[0] = their sum, out[n] = (int)total
 static __global__ __launch_bounds__(1024) void pscan_sums_kernel(long long* __restrict__ bsum, int nb, long long* __restrict__ total,
                                                                  int* __restrict__ out, long n) {
-    __shared__ long long s_tot[1024];
+    __shared__ long long s_wsum[16];
     const int tid = threadIdx.x;
     const int per = (nb + 1023) / 1024;
     long long sum = 0;
@@ -45,16 +46,12 @@ static __global__ __launch_bounds__(1024) void pscan_sums_kernel(long long* __re
         const int c = tid * per + k;
         if (c < nb) sum += bsum[c];
     }
-    s_tot[tid] = sum;
-    __syncthreads();
+    long long all;
+    long long run = block_scan_excl<1024>(sum, s_wsum, 0ll, all);
     if (tid == 0) {
-        long long run = 0;
-        for (int t = 0; t < 1024; ++t) { const long long v = s_tot[t]; s_tot[t] = run; run += v; }
-        total[0] = run;
-        out[n] = (int)run;
+        total[0] = all;
+        out[n] = (int)all;
     }
-    __syncthreads();
-    long long run = s_tot[tid];
     for (int k = 0; k < per; ++k) {
         const int c = tid * per + k;
         if (c < nb) {

@@ -21,6 +21,7 @@
 //                    of one workgroup on another.
 #include "common.h"
 #include "philox.h"
+#include "plot_sort.h"
 
 namespace {
 
@@ -96,17 +97,7 @@ __device__ __forceinline__ void scan_buckets(int* h, int nb, int N, int* s_wave,
     if (tid == 0) *t_out = nb - 1;                         // never read as such: some bucket below holds rank N - 1
     int sum = 0;
     for (int c = c0; c < c1; ++c) sum += h[c];
-    int inc = sum;                                         // inclusive scan over the wave, then over the waves
-    const int lane = tid & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) s_wave[tid >> 6] = inc;
-    __syncthreads();
-    int run = inc - sum;
-    for (int w = 0; w < (tid >> 6); ++w) run += s_wave[w];
+    int run = block_scan_excl<1024>(sum, s_wave);
     for (int c = c0; c < c1; ++c) {
         const int v = h[c];
         h[c] = run;

@@ -403,7 +403,9 @@ def test_sa_work_items_order(B, M):
 
 
 @pytest.mark.parametrize("B,R,S,with_pos", [(2, 5000, 37, True), (3, 2049, 100, False), (1, 70000, 1024, True), (2, 300, 1, False),
-                                             (1, 32768, 8192, True)])       # S = 8192: the limit (64 KB of dynamic LDS)
+                                             (1, 32768, 8192, True),        # S = 8192: the limit (64 KB of dynamic LDS)
+                                             # S > 1024: the running totals of both scans cross rounds of 1024 sources
+                                             (1, 3000, 1025, True), (2, 2100, 2049, False), (1, 9000, 8192, True)])
 def test_inverted_index_and_its_chunk_table(B, R, S, with_pos):
     """sn2_interp_index (csrc/interp_index.hip): every (row, slot) of the 3-NN table is on its source's list exactly once with the normalised weight,
     the item table is a permutation of the plot's sources, and the chunk table cuts every list into consecutive pieces of at

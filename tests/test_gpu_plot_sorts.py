@@ -1,0 +1,101 @@
+"""The per-plot counting sorts of csrc/geometry.hip (csrc/plot_sort.h) against their definitions, in every template form of
+the kernels and at the smallest sizes that cross a trip boundary of the point loader.  Everything is equality."""
+import numpy as np
+import pytest
+import torch
+
+from stratanet2_vegetation_coverage_maps_amd import hip_ops as ops
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+F = np.float32
+CELLS, GRID_WORDS = 4096, 4104        # 16 x 16 x 16 Morton cells; header = 4097 cell starts, lo.xyz, scale.xyz, pad
+
+
+def _points(B, N, kind, seed):
+    """(B,3,N) fp32: uniform in a 20 x 20 x 8 m box; "dup": the last quarter of a plot repeats its first; "line": the last plot
+    has one y for all its points."""
+    g = torch.Generator().manual_seed(seed)
+    pos = torch.rand(B, 3, N, generator=g) * torch.tensor([20.0, 20.0, 8.0]).view(1, 3, 1)
+    if kind == "dup":
+        pos[:, :, N - N // 4:] = pos[:, :, :N // 4]
+    if kind == "line":
+        pos[B - 1, 1, :] = 7.25
+    return pos.contiguous()
+
+
+def _host_cells(xyz, lo, sc):
+    """The Morton cell of xyz (N,3) in the grid (lo, sc): every step rounded to fp32 on its own, as order_cell has it."""
+    c = ((xyz - lo).astype(F) * sc).astype(F).astype(np.int32).clip(0, 15)       # (int) truncates; clamp to 0..15
+    m = np.zeros(len(xyz), np.int32)
+    for bit in (3, 2, 1, 0):
+        m = (m << 3) | (((c[:, 0] >> bit) & 1) << 2) | (((c[:, 1] >> bit) & 1) << 1) | ((c[:, 2] >> bit) & 1)
+    return m
+
+
+# (B, N): the kernel form that sorts it (sn2_small_sort_wg: B > 32 -> 256 threads; U = 8 up to 8192 points) and its trips
+SPATIAL = [(2, 2052),        # <8,1024>: one partial trip
+           (2, 8192),        # <8,1024>: one full trip
+           (2, 8196),        # <16,1024>: one partial trip
+           (1, 16388),       # <16,1024>: a second trip of 4 points
+           (33, 4100),       # <16,256>: a second trip of 4 points
+           (33, 16384)]      # <16,256>: four full trips
+
+
+@pytest.mark.parametrize("kind", ["uniform", "dup", "line"])
+@pytest.mark.parametrize("B,N", SPATIAL)
+def test_spatial_order_tables_match_their_definition(B, N, kind):
+    """spatial_order_chunk_kernel: grid header, cell starts, order, rank and sorted table of sn2_fps's workspace against a numpy
+    fp32 restatement.  Nothing is asserted about the order inside a cell nor about sorted[].w (the running FPS distance)."""
+    assert (B * N) % 4 == 0 and ops.fps_fills_ws(B, N, 64)
+    pos = _points(B, N, kind, 100 * B + N)
+    start = torch.tensor([(977 * b + 13) % N for b in range(B)], dtype=torch.int32)
+    ws = ops.fps(pos.to(DEV), 64, start.to(DEV), waves=16, return_ws=True)[3]
+    assert ws is not None
+    torch.cuda.synchronize()
+    order = ws[:B * N].view(B, N).cpu().numpy()
+    sorted_ = ws[B * N:5 * B * N].view(torch.float32).view(B, N, 4).cpu().numpy()
+    grid = ops.fps_ws_grid(ws, B, N).view(B, GRID_WORDS).cpu().numpy()
+    rank = ops.fps_ws_rank(ws, B, N).view(B, N).cpu().numpy()
+    p = pos.numpy().transpose(0, 2, 1)                                            # (B,N,3)
+    for b in range(B):
+        lo, hi = p[b].min(0), p[b].max(0)
+        sc = (F(16) / np.maximum((hi - lo).astype(F), F(1e-6))).astype(F)
+        assert np.array_equal(grid[b, CELLS + 1:CELLS + 4], lo.view(np.int32)), (b, "lo")
+        assert np.array_equal(grid[b, CELLS + 4:CELLS + 7], sc.view(np.int32)), (b, "scale")
+        cell = _host_cells(p[b], lo, sc)
+        if kind == "line" and b == B - 1:
+            assert not ((cell >> 1) & 0o1111).any(), "the line plot lies in the cells of y index 0"
+        count = np.bincount(cell, minlength=CELLS)
+        starts = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+        assert np.array_equal(grid[b, :CELLS + 1], starts) and starts[CELLS] == N, (b, "cell starts and end word")
+        assert grid[b, GRID_WORDS - 1] == 0, (b, "pad word")
+        assert np.array_equal(np.sort(order[b]), np.arange(N)), (b, "order is a permutation")
+        assert np.array_equal(rank[b][order[b]], np.arange(N)), (b, "rank is its inverse")
+        assert np.array_equal(sorted_[b, :, :3].view(np.int32), p[b][order[b]].view(np.int32)), (b, "sorted = pos[order]")
+        assert np.array_equal(_host_cells(sorted_[b, :, :3], lo, sc), np.repeat(np.arange(CELLS), count)), (b, "cell of every position")
+
+
+# (B, S, T): the source grid (G = sqrt(S / 4) up to 32) and the form of the target sort
+THREE_NN = [(2, 128, 2052),        # G = 5: 25 cells; <8,1024>, one partial trip
+            (1, 8192, 8196),       # G = 32: all 1024 cells, four per thread of the build, one per thread of the sort; <16,1024>
+            (1, 1024, 16388),      # <16,1024>: a second trip of 4 points
+            (33, 128, 4100),       # <16,256>: a second trip of 4 points
+            (2, 4097, 8192)]       # <8,1024>: one full trip
+
+
+@pytest.mark.parametrize("B,S,T", THREE_NN)
+def test_target_sort_and_source_grid_give_the_full_scan(B, S, T):
+    """nn_grid_build_kernel + nn_target_sort_chunk_kernel + the grid walk against the full scan, bit for bit.  A tenth of the
+    targets lie outside the sources' bounding box on the low side in x and y (the key's `vx < 0` guard)."""
+    assert ops.three_nn_uses_grid(S, T)
+    src = _points(B, S, "uniform", 7 * B + S)
+    dst = _points(B, T, "uniform", 11 * B + T)
+    g = torch.Generator().manual_seed(T)
+    dst[:, :2, :T // 10] = -5.0 * torch.rand(B, 2, T // 10, generator=g) - 0.01
+    s, d = src.to(DEV), dst.to(DEV)
+    idx_g, w_g = ops.three_nn(s, d, 3)
+    idx_f, w_f = ops.three_nn(s, d, 3, grid=False)
+    torch.cuda.synchronize()
+    assert torch.equal(idx_g, idx_f)
+    assert torch.equal(w_g.view(torch.int32), w_f.view(torch.int32))
