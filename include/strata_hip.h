@@ -203,10 +203,20 @@ int sn2_three_nn(const float *src_soa, int B, int S, const float *dst_soa, int T
  * 128 <= S <= 8192 (the S range of sn2_three_nn_uses_grid; else SN2_ELIMIT); ws = 16-byte aligned workspace of
  * SN2_THREE_NN_XY_WS_WORDS(B,S,T) 32-bit words.  Same results as
  * sn2_three_nn, bit for bit. */
-#define SN2_THREE_NN_XY_WS_WORDS(B, S, T) ((size_t)(B) * (4 * (size_t)(S) + 5 * (size_t)(T) + 1032))
+#define SN2_THREE_NN_XY_WS_WORDS(B, S, T) ((size_t)(B) * (4 * (size_t)(S) + 11 * (size_t)(T) + 1032))
 size_t sn2_three_nn_xy_ws_words(int B, int S, int T);
 int sn2_three_nn_xy(const float *src_soa, int B, int S, const float *dst_soa, int T, int k, int *idx, float *w,
                     void *ws, void *stream);
+/* What the call leaves in ws for the inverted index (sn2_interp_index_ordered), as word offsets into ws:
+ * *order_words: order (B*T) int32 -- per plot the permutation of 0..T-1 that walks the targets cell by cell of the source grid
+ * (rows of cells in a snake), the order the search itself works in;
+ * *copy_words (may be NULL): idx_sorted (B*T,3) int32, then w_sorted (B*T,3) at *copy_words + 3*B*T -- the result rows in
+ * that order (row p of plot b = row order[b*T + p] of idx / w), written only by sn2_three_nn_xy_copy with sorted_copy != 0
+ * (24 bytes per target more; a pass that builds no inverted index leaves it out).
+ * Both stay valid until the next call with the same ws.  Returns 0, or SN2_EINVAL. */
+int sn2_three_nn_xy_order_offset(int B, int S, int T, size_t *order_words, size_t *copy_words);
+int sn2_three_nn_xy_copy(const float *src_soa, int B, int S, const float *dst_soa, int T, int k, int *idx, float *w,
+                         void *ws, int sorted_copy, void *stream);
 
 /* Input pipeline of a batch: load_cloud of the reference DataLoader, data_loader/loader.py:73-87 --
  * centre, append the fake ground points, keep xyz, [train: rotate about z, flip, add noise], rescale, gather the subsample --
@@ -540,6 +550,15 @@ int sn2_interp_index_perm(const int *knn_idx, const float *knn_w, const float *s
  * pipelined loop covers several batches per launch: 12 launches per pass instead of 12 per batch. */
 int sn2_interp_index_group(const int *knn_idx, const float *knn_w, const float *src_pos, const int *row_perm, int G, int B,
                            int R_per_plot, int S_per_plot, float *ws, size_t ws_stride_words, void *stream);
+/* the same, built in a given ORDER of the target rows: row_order (G*B*R) int32, per plot a permutation of 0..R-1, or NULL (then
+ * exactly sn2_interp_index_group).  The lists hold the same entries; only the order inside a list, which is arrival order
+ * either way, differs.  Meant for the order sn2_three_nn_xy leaves in its workspace (sn2_three_nn_xy_order_offset): walked
+ * cell by cell of the source grid, a slice of 2048 rows names about a hundred sources and writes whole lines of their lists.
+ * idx_sorted / w_sorted (with row_order; both or neither): the table's rows in that order (row p of plot b = row
+ * row_order[b*R + p] of knn_idx / knn_w; sn2_three_nn_xy_copy writes them), read instead of a gather through row_order. */
+int sn2_interp_index_ordered(const int *knn_idx, const float *knn_w, const float *src_pos, const int *row_perm,
+                             const int *row_order, const int *idx_sorted, const float *w_sorted, int G, int B,
+                             int R_per_plot, int S_per_plot, float *ws, size_t ws_stride_words, void *stream);
 int sn2_fp_forward(const sn2_fp *p, int training, void *stream);
 int sn2_fp_backward(const sn2_fp *p, void *stream);
 

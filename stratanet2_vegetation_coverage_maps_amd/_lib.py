@@ -156,6 +156,8 @@ SIGNATURES = {
     "sn2_count_sum": [c_void_p, c_int, c_void_p, c_void_p],
     "sn2_count_sum_group": [c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_three_nn_xy": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_three_nn_xy_copy": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "sn2_three_nn_xy_order_offset": [c_int, c_int, c_int, POINTER(ctypes.c_size_t), POINTER(ctypes.c_size_t)],
     "sn2_prepare_plots": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p, c_void_p],
     "sn2_znorm": [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
@@ -196,6 +198,8 @@ SIGNATURES = {
     "sn2_interp_index": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "sn2_interp_index_perm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "sn2_interp_index_group": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
+    "sn2_interp_index_ordered": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_fp_forward": [POINTER(FP), c_int, c_void_p],
     "sn2_fp_backward": [POINTER(FP), c_void_p],
     "sn2_plot_max_forward": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],

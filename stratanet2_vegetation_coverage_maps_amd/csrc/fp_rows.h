@@ -14,9 +14,11 @@ extern int g_fp_rows_form;
 extern int g_fp_table_form;
 
 // the inverted index of a 3-NN table (interp_index.hip): G batches of B plots each in one set of launches (G = 1: one batch);
-// batch h's workspace at ws + h * ws_stride words
+// batch h's workspace at ws + h * ws_stride words.  row_order (G*B*Rp, per plot a permutation of 0..Rp-1) or nullptr: the order
+// the rows are walked in; idx_sorted / w_sorted (with row_order, both or neither): the table's rows in that order
 int build_interp_index(const int* knn_idx, const float* knn_w, const float* src_pos, int B, int Rp, int S, float* ws,
-                       hipStream_t st, const int* row_perm = nullptr, int G = 1, size_t ws_stride = 0);
+                       hipStream_t st, const int* row_perm = nullptr, int G = 1, size_t ws_stride = 0, const int* row_order = nullptr,
+                       const int* idx_sorted = nullptr, const float* w_sorted = nullptr);
 
 namespace {
 

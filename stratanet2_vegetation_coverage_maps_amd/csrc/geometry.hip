@@ -2447,7 +2447,8 @@ extern "C" int sn2_debug_nn_stamps(unsigned long long* out, int n) {
 __global__ __launch_bounds__(256) void three_nn_grid_kernel(const float4* __restrict__ tbl, const int* __restrict__ hdr, int S,
                                                             int T, int k, const int* __restrict__ dst_order,
                                                             const float4* __restrict__ dst_sorted,
-                                                            int* __restrict__ idx, float* __restrict__ w, int B, int gx) {
+                                                            int* __restrict__ idx, float* __restrict__ w, int B, int gx,
+                                                            int* __restrict__ idx_sorted, float* __restrict__ w_sorted) {
     extern __shared__ __attribute__((aligned(16))) float4 s_tbl[];      // S entries, then the cell starts
     // XCD-aware placement (as ball_query_grid_kernel): with B = 0 the grid is (gx, plots) as before; with B > 0 it is one-
     // dimensional, workgroup w = (XCD w & 7, turn w >> 3), and plot b is worked on by XCD b % 8 only -- the results go to the
@@ -2577,12 +2578,25 @@ __global__ __launch_bounds__(256) void three_nn_grid_kernel(const float4* __rest
     const int t = dst_order[(size_t)b * T + p];
     const size_t o = ((size_t)b * T + t) * 3;
     const bool u1 = (k >= 2) && (i1 != 0x7FFFFFFF), u2 = (k >= 3) && (i2 != 0x7FFFFFFF);
+    const int j1 = u1 ? i1 : i0, j2 = u2 ? i2 : i0;
+    const float w0 = 1.0f / fmaxf(d0, 1e-16f), w1 = u1 ? 1.0f / fmaxf(d1, 1e-16f) : 0.f, w2 = u2 ? 1.0f / fmaxf(d2, 1e-16f) : 0.f;
     idx[o + 0] = i0;
-    idx[o + 1] = u1 ? i1 : i0;
-    idx[o + 2] = u2 ? i2 : i0;
-    w[o + 0] = 1.0f / fmaxf(d0, 1e-16f);
-    w[o + 1] = u1 ? 1.0f / fmaxf(d1, 1e-16f) : 0.f;
-    w[o + 2] = u2 ? 1.0f / fmaxf(d2, 1e-16f) : 0.f;
+    idx[o + 1] = j1;
+    idx[o + 2] = j2;
+    w[o + 0] = w0;
+    w[o + 1] = w1;
+    w[o + 2] = w2;
+    // the same row once more at its SORTED position (sn2_three_nn_xy_copy): 24 bytes per lane, contiguous across the wave --
+    // the table in the order the inverted index is built in (interp_index.hip)
+    if (idx_sorted) {
+        const size_t q = ((size_t)b * T + p) * 3;
+        idx_sorted[q + 0] = i0;
+        idx_sorted[q + 1] = j1;
+        idx_sorted[q + 2] = j2;
+        w_sorted[q + 0] = w0;
+        w_sorted[q + 1] = w1;
+        w_sorted[q + 2] = w2;
+    }
 }
 
 extern "C" int sn2_count_sum_group(const int* cnt, int G, int n, unsigned long long* total, size_t total_stride, void* stream) {
@@ -2662,8 +2676,18 @@ __global__ __launch_bounds__(NT) void nn_target_sort_chunk_kernel(const float* _
     }
 }
 
-extern "C" int sn2_three_nn_xy(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
-                               void* ws, void* stream) {
+// the workspace of sn2_three_nn_xy, in 32-bit words:  tbl [4 B S] | sorted [4 B T] | hdr [B NN_HDR] | order [B T] |
+// idx_sorted [3 B T] | w_sorted [3 B T]
+static_assert(NN_HDR == 1032, "SN2_THREE_NN_XY_WS_WORDS counts 1032 header words per plot");
+extern "C" int sn2_three_nn_xy_order_offset(int B, int S, int T, size_t* order_words, size_t* copy_words) {
+    if (B <= 0 || S <= 0 || T <= 0 || !order_words) return SN2_EINVAL;
+    *order_words = (size_t)B * (4 * (size_t)S + 4 * (size_t)T + NN_HDR);
+    if (copy_words) *copy_words = *order_words + (size_t)B * T;
+    return 0;
+}
+
+extern "C" int sn2_three_nn_xy_copy(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
+                                    void* ws, int sorted_copy, void* stream) {
     if (!src_soa || !dst_soa || !idx || !w || !ws || B <= 0 || S <= 0 || T <= 0 || k < 1 || k > 3) return SN2_EINVAL;
     if (!nn_grid_sources(S) || (((size_t)ws) % 16) != 0) return SN2_ELIMIT;
     hipStream_t st = (hipStream_t)stream;
@@ -2673,6 +2697,8 @@ extern "C" int sn2_three_nn_xy(const float* src_soa, int B, int S, const float* 
     float4* sorted = tbl + (size_t)B * S;
     int* hdr = reinterpret_cast<int*>(sorted + (size_t)B * T);
     int* order = hdr + (size_t)B * NN_HDR;
+    int* idx_sorted = sorted_copy ? order + (size_t)B * T : nullptr;
+    float* w_sorted = sorted_copy ? reinterpret_cast<float*>(idx_sorted + (size_t)3 * B * T) : nullptr;
     hipLaunchKernelGGL(nn_grid_build_kernel, dim3(B), dim3(256), 0, st, src_soa, S, G, tbl, hdr);
     if (sn2_small_sort_wg(B) && T <= 16 * 1024)        // many plots: 256 threads per plot (common.h)
         hipLaunchKernelGGL((nn_target_sort_chunk_kernel<16, 256>), dim3(B), dim3(256), 0, st, dst_soa, T, (const int*)hdr, order, sorted);
@@ -2689,12 +2715,19 @@ extern "C" int sn2_three_nn_xy(const float* src_soa, int B, int S, const float* 
         static const bool no_xcd = getenv("SN2_NN_NO_XCD") != nullptr;      // (diagnostic switch)
         if (!no_xcd && (B % 8 == 0 || B >= 64))      // plots balance over the XCDs: XCD-aware placement
             hipLaunchKernelGGL(three_nn_grid_kernel, dim3(8 * sn2_cdiv(B, 8) * gx), dim3(256), lds, st, (const float4*)tbl,
-                               (const int*)hdr, S, T, k, (const int*)order, (const float4*)sorted, idx, w, B, gx);
+                               (const int*)hdr, S, T, k, (const int*)order, (const float4*)sorted, idx, w, B, gx, idx_sorted,
+                               w_sorted);
         else
             hipLaunchKernelGGL(three_nn_grid_kernel, dim3(gx, B), dim3(256), lds, st, (const float4*)tbl,
-                               (const int*)hdr, S, T, k, (const int*)order, (const float4*)sorted, idx, w, 0, gx);
+                               (const int*)hdr, S, T, k, (const int*)order, (const float4*)sorted, idx, w, 0, gx, idx_sorted,
+                               w_sorted);
     }
     SN2_RETURN_LAUNCH();
+}
+
+extern "C" int sn2_three_nn_xy(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
+                               void* ws, void* stream) {
+    return sn2_three_nn_xy_copy(src_soa, B, S, dst_soa, T, k, idx, w, ws, 0, stream);
 }
 
 extern "C" int sn2_three_nn(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
@@ -2714,7 +2747,7 @@ extern "C" int sn2_three_nn(const float* src_soa, int B, int S, const float* dst
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(three_nn_grid_kernel, dim3(sn2_cdiv(T, 256), B), dim3(256), lds, st, (const float4*)tbl,
                            (const int*)hdr, S, T, k, dst_fps_ws, reinterpret_cast<const float4*>(dst_fps_ws + (size_t)B * T),
-                           idx, w, 0, sn2_cdiv(T, 256));
+                           idx, w, 0, sn2_cdiv(T, 256), (int*)nullptr, (float*)nullptr);
         SN2_RETURN_LAUNCH();
     }
     dim3 grid(sn2_cdiv(T, 256), B);

@@ -1,7 +1,7 @@
 // interp_index.hip -- the inverted interpolation index: from a 3-NN table (target row -> three sources and weights) to the
 // lists source -> (target row, normalised weight), which the backward kernels of fp.hip walk.  Kernels inv_hist / inv_scan /
 // inv_fill / inv_order, their launcher build_interp_index and the entry points sn2_interp_index, sn2_interp_index_perm,
-// sn2_interp_index_group.  The host view of the workspace (InterpIndex / carve_interp_index) and the slice and chunk sizes
+// sn2_interp_index_group, sn2_interp_index_ordered.  The host view of the workspace (InterpIndex / carve_interp_index) and the slice and chunk sizes
 // are in fp_rows.h.
 //
 // ---------------------------------------------------------------------------------------------- backward (3) of fp.hip
@@ -44,18 +44,41 @@ __host__ __device__ __forceinline__ InvWs inv_ws_of(float* ws, int B, int Rp, in
     return x;
 }
 
+// Where a workgroup of inv_hist / inv_fill works.  GB = 0: the grid is (SL, plots).  GB > 0 (plots that balance over the XCDs,
+// the rule of three_nn_grid_kernel): the grid is one-dimensional, workgroup w = (XCD w & 7, turn w >> 3), and all SL slices
+// of plot bg run on XCD bg % 8 -- the slices of a plot write into ONE list area (3 R entries of 4 + 4 bytes), and only
+// workgroups behind the same L2 fill its lines there before they are written back.  false: nothing to do.
+__device__ __forceinline__ bool inv_place(int SL, int GB, int& bg, int& sl) {
+    if (GB == 0) {
+        bg = blockIdx.y, sl = blockIdx.x;
+        return true;
+    }
+    const int turn = (int)(blockIdx.x >> 3);
+    bg = (int)(blockIdx.x & 7u) + 8 * (turn / SL);
+    sl = turn % SL;
+    return bg < GB;
+}
+
+// THE ORDER OF THE WALK.  Slice sl covers positions [INV_SLICE_ROWS sl, INV_SLICE_ROWS (sl + 1)) of the plot; position p is
+// row row_order[p] (row_order == nullptr: row p).  With the order the 3-NN search sorted its targets in (sn2_three_nn_xy:
+// by the cells of the source grid) a slice names about a hundred sources instead of all of them, a list receives its
+// entries from the two or three slices around its source, and every slice writes ONE contiguous run of it: whole lines
+// from one workgroup.  In the targets' own order every entry is a 4-byte store to a place of its own.
+// The table row of position p is read at p (by_row == 0: knn_idx / knn_w are the search's sorted copy, or there is no
+// order) or at row_order[p] (by_row != 0: a gather from the table in row order).
 __global__ __launch_bounds__(1024) void inv_hist_kernel(int R_per_plot, int S, const int* __restrict__ knn_idx,
                                                         const float* __restrict__ knn_w, float* __restrict__ ws, int Bb,
-                                                        size_t ws_stride) {
+                                                        size_t ws_stride, int SL, int GB, const int* __restrict__ row_order) {
     extern __shared__ int s_hist[];
-    const int bg = blockIdx.y, sl = blockIdx.x, SL = gridDim.x;
+    int bg, sl;
+    if (!inv_place(SL, GB, bg, sl)) return;
     const int hb = bg / Bb, b = bg - hb * Bb;                    // batch of the group, plot of the batch
     int* H = inv_ws_of(ws + (size_t)hb * ws_stride, Bb, R_per_plot, S).H;
     for (int i = threadIdx.x; i < S; i += 1024) s_hist[i] = 0;
     __syncthreads();
     const int r_lo = sl * INV_SLICE_ROWS, r_hi = min(R_per_plot, r_lo + INV_SLICE_ROWS);
     for (int rl = r_lo + threadIdx.x; rl < r_hi; rl += 1024) {
-        const size_t r = (size_t)bg * R_per_plot + rl;
+        const size_t r = (size_t)bg * R_per_plot + (row_order ? row_order[(size_t)bg * R_per_plot + rl] : rl);
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             if (j == 0 || knn_w[r * 3 + j] != 0.f) atomicAdd(&s_hist[knn_idx[r * 3 + j]], 1);
@@ -106,9 +129,11 @@ __global__ __launch_bounds__(1024) void inv_scan_kernel(int R_per_plot, int S, i
 
 __global__ __launch_bounds__(1024) void inv_fill_kernel(int R_per_plot, int S, const int* __restrict__ knn_idx,
                                                         const float* __restrict__ knn_w, float* __restrict__ ws, int Bb,
-                                                        size_t ws_stride, const int* __restrict__ row_perm) {
+                                                        size_t ws_stride, const int* __restrict__ row_perm, int SL, int GB,
+                                                        const int* __restrict__ row_order, int by_row) {
     extern __shared__ int s_cur[];
-    const int bg = blockIdx.y, sl = blockIdx.x, SL = gridDim.x;
+    int bg, sl;
+    if (!inv_place(SL, GB, bg, sl)) return;
     const int hb = bg / Bb, b = bg - hb * Bb;
     const InvWs x = inv_ws_of(ws + (size_t)hb * ws_stride, Bb, R_per_plot, S);
     const int* __restrict__ H = x.H;
@@ -120,7 +145,9 @@ __global__ __launch_bounds__(1024) void inv_fill_kernel(int R_per_plot, int S, c
     __syncthreads();
     const int r_lo = sl * INV_SLICE_ROWS, r_hi = min(R_per_plot, r_lo + INV_SLICE_ROWS);
     for (int rl = r_lo + threadIdx.x; rl < r_hi; rl += 1024) {
-        const size_t r = (size_t)bg * R_per_plot + rl;
+        const size_t r0 = (size_t)bg * R_per_plot;
+        const int row = row_order ? row_order[r0 + rl] : rl;
+        const size_t r = r0 + (by_row ? row : rl);
         const float w0 = knn_w[r * 3 + 0], w1 = knn_w[r * 3 + 1], w2 = knn_w[r * 3 + 2];
         const float inv = 1.0f / ((w0 + w1) + w2);
         const float w[3] = {w0, w1, w2};
@@ -128,7 +155,7 @@ __global__ __launch_bounds__(1024) void inv_fill_kernel(int R_per_plot, int S, c
         for (int j = 0; j < 3; ++j)
             if (j == 0 || w[j] != 0.f) {
                 const int p = atomicAdd(&s_cur[knn_idx[r * 3 + j]], 1);
-                inv_row[p] = row_perm ? row_perm[r] : rl;          // where the row's d pre-activation is kept (sn2_fp.row_perm)
+                inv_row[p] = row_perm ? row_perm[r0 + row] : row;  // where the row's d pre-activation is kept (sn2_fp.row_perm)
                 inv_w[p] = w[j] * inv;
             }
     }
@@ -230,16 +257,31 @@ __global__ __launch_bounds__(1024) void inv_order_kernel(const float4* __restric
 }  // namespace
 
 int build_interp_index(const int* knn_idx, const float* knn_w, const float* src_pos, int B, int Rp, int S, float* ws,
-                       hipStream_t st, const int* row_perm, int G, size_t ws_stride) {
+                       hipStream_t st, const int* row_perm, int G, size_t ws_stride, const int* row_order, const int* idx_sorted,
+                       const float* w_sorted) {
     if (S > 8192) return SN2_ELIMIT;
     if (G < 1 || (G > 1 && (ws_stride & 3))) return SN2_EINVAL;           // (every batch's workspace 16-byte aligned)
     const int SL = sn2_cdiv(Rp, INV_SLICE_ROWS);
     const int CM = inv_chunks_per_plot(Rp, S);
     if ((long)G * B >= 65535) return SN2_ELIMIT;                           // grid.y
-    hipLaunchKernelGGL(inv_hist_kernel, dim3(SL, G * B), dim3(1024), (size_t)S * 4, st, Rp, S, knn_idx, knn_w, ws, B, ws_stride);
+    // (diagnostic switches, so that the parts can be timed apart: SN2_INV_NO_XCD keeps the two-dimensional grid, SN2_INV_NO_ORDER
+    // walks the rows in their own order whatever the caller hands in, SN2_INV_GATHER reads the table in row order through
+    // row_order although the search left its sorted copy)
+    static const bool no_xcd = getenv("SN2_INV_NO_XCD") != nullptr, gather = getenv("SN2_INV_GATHER") != nullptr;
+    static const bool no_order = getenv("SN2_INV_NO_ORDER") != nullptr;
+    if (no_order) row_order = nullptr;
+    const int GB = G * B;
+    // plots balance over the XCDs: the rule of sn2_three_nn_xy (one slice per plot: the two grids place alike, the plain one stays)
+    const bool xcd = !no_xcd && SL > 1 && (GB % 8 == 0 || GB >= 64);
+    const dim3 grid = xcd ? dim3(8 * sn2_cdiv(GB, 8) * SL) : dim3(SL, GB);
+    const bool copy = row_order && idx_sorted && w_sorted && !gather;
+    const int* t_idx = copy ? idx_sorted : knn_idx;
+    const float* t_w = copy ? w_sorted : knn_w;
+    hipLaunchKernelGGL(inv_hist_kernel, grid, dim3(1024), (size_t)S * 4, st, Rp, S, t_idx, t_w, ws, B, ws_stride, SL, xcd ? GB : 0,
+                       copy ? nullptr : row_order);              // (a slice of the copy needs no row numbers to be counted)
     hipLaunchKernelGGL(inv_scan_kernel, dim3(G * B), dim3(1024), 0, st, Rp, S, SL, ws, B, ws_stride);
-    hipLaunchKernelGGL(inv_fill_kernel, dim3(SL, G * B), dim3(1024), (size_t)S * 4, st, Rp, S, knn_idx, knn_w, ws, B, ws_stride,
-                       row_perm);
+    hipLaunchKernelGGL(inv_fill_kernel, grid, dim3(1024), (size_t)S * 4, st, Rp, S, t_idx, t_w, ws, B, ws_stride, row_perm, SL,
+                       xcd ? GB : 0, row_order, (row_order && !copy) ? 1 : 0);
     // keys + the source of every rank: 64 KB of dynamic LDS at the S = 8192 limit (+ ~450 B static): above the 48 KB a kernel
     // gets without asking
     const size_t order_lds = (size_t)(((S + 3) & ~3) + S) * 4;
@@ -271,4 +313,14 @@ extern "C" int sn2_interp_index_group(const int* knn_idx, const float* knn_w, co
     if (!knn_idx || !knn_w || !ws || G <= 0 || B <= 0 || R_per_plot <= 0 || S_per_plot <= 0) return SN2_EINVAL;
     if (G > 1 && ws_stride_words < SN2_INTERP_WS_WORDS(B, R_per_plot, S_per_plot)) return SN2_EINVAL;
     return build_interp_index(knn_idx, knn_w, src_pos, B, R_per_plot, S_per_plot, ws, (hipStream_t)stream, row_perm, G, ws_stride_words);
+}
+
+extern "C" int sn2_interp_index_ordered(const int* knn_idx, const float* knn_w, const float* src_pos, const int* row_perm,
+                                        const int* row_order, const int* idx_sorted, const float* w_sorted, int G, int B,
+                                        int R_per_plot, int S_per_plot, float* ws, size_t ws_stride_words, void* stream) {
+    if (!knn_idx || !knn_w || !ws || G <= 0 || B <= 0 || R_per_plot <= 0 || S_per_plot <= 0) return SN2_EINVAL;
+    if (G > 1 && ws_stride_words < SN2_INTERP_WS_WORDS(B, R_per_plot, S_per_plot)) return SN2_EINVAL;
+    if ((idx_sorted != nullptr) != (w_sorted != nullptr) || (idx_sorted && !row_order)) return SN2_EINVAL;
+    return build_interp_index(knn_idx, knn_w, src_pos, B, R_per_plot, S_per_plot, ws, (hipStream_t)stream, row_perm, G, ws_stride_words,
+                              row_order, idx_sorted, w_sorted);
 }

@@ -225,8 +225,21 @@ void head_desc(sn2_head* h, const sn2_net_model* m, const sn2_net_dims* d, const
         if (e__ != hipSuccess) return (int)e__;               \
     } while (0)
 
-int inverted_tables(const sn2_net_dims* d, const sn2_net_geo* g, int which, void* st) {
+// The inverted index of one grid-searched table in the order the search left in its workspace nn_ws (sn2_three_nn_xy_copy with
+// sorted_copy = 1, the LAST call on nn_ws: geometry_impl, same stream); nn_ws == nullptr or a full-scan level: in row order.
+int inverted_table(const int* knn_idx, const float* knn_w, const float* src_pos, const int* row_perm, int B, int R, int S, float* inv,
+                   const int* nn_ws, void* st) {
+    if (!nn_ws || !sn2_three_nn_uses_grid(S, R)) return sn2_interp_index_perm(knn_idx, knn_w, src_pos, row_perm, B, R, S, inv, st);
+    size_t order = 0, copy = 0;
+    SN2_TRY(sn2_three_nn_xy_order_offset(B, S, R, &order, &copy));
+    return sn2_interp_index_ordered(knn_idx, knn_w, src_pos, row_perm, nn_ws + order, nn_ws + copy,
+                                    reinterpret_cast<const float*>(nn_ws + copy + (size_t)3 * B * R), 1, B, R, S, inv, 0, st);
+}
+
+int inverted_tables(const sn2_net_dims* d, const sn2_net_geo* g, int which, void* st, bool ordered = false) {
     // which: 1 = the two small tables (chain b), 2 = the per-point table (chain c), 3 = all
+    // ordered: called by the geometry pass right behind the searches, whose workspaces then hold the tables' orders (a late
+    // build, which = 3, may find them gone or overwritten: row order)
     if (which == 3) {               // (a late build: the message totals an eval-mode geometry pass did not make)
         SN2_TRY(sn2_count_sum(g->cnt1, d->B * d->M1, g->tot1, st));
         SN2_TRY(sn2_count_sum(g->cnt2, d->B * d->M2, g->tot2, st));
@@ -234,11 +247,11 @@ int inverted_tables(const sn2_net_dims* d, const sn2_net_geo* g, int which, void
     if (which & 1) {
         if (!g->inv3 || !g->inv2) return SN2_EINVAL;
         SN2_TRY(sn2_interp_index_perm(g->knn3_idx, g->knn3_w, nullptr, nullptr, d->B, d->M2, 1, g->inv3, st));
-        SN2_TRY(sn2_interp_index_perm(g->knn2_idx, g->knn2_w, nullptr, nullptr, d->B, d->M1, d->M2, g->inv2, st));
+        SN2_TRY(inverted_table(g->knn2_idx, g->knn2_w, nullptr, nullptr, d->B, d->M1, d->M2, g->inv2, ordered ? g->nn_ws2 : nullptr, st));
     }
     if (which & 2) {
         if (!g->inv1) return SN2_EINVAL;
-        SN2_TRY(sn2_interp_index_perm(g->knn1_idx, g->knn1_w, g->pos1_aos, g->rank1, d->B, d->N, d->M1, g->inv1, st));
+        SN2_TRY(inverted_table(g->knn1_idx, g->knn1_w, g->pos1_aos, g->rank1, d->B, d->N, d->M1, g->inv1, ordered ? g->nn_ws1 : nullptr, st));
     }
     return 0;
 }
@@ -256,8 +269,9 @@ int check_geo_workspaces(const sn2_net_dims* d, const sn2_net_geo* g) {     // w
     return 0;
 }
 
-int three_nn_any(const float* src, int B, int S, const float* dst, int T, int k, int* idx, float* w, int* ws, void* st) {
-    if (sn2_three_nn_uses_grid(S, T)) return sn2_three_nn_xy(src, B, S, dst, T, k, idx, w, ws, st);
+// sorted_copy: an inverted index follows (inverted_table): the grid search also leaves its rows in its own order
+int three_nn_any(const float* src, int B, int S, const float* dst, int T, int k, int* idx, float* w, int* ws, int sorted_copy, void* st) {
+    if (sn2_three_nn_uses_grid(S, T)) return sn2_three_nn_xy_copy(src, B, S, dst, T, k, idx, w, ws, sorted_copy, st);
     return sn2_three_nn(src, B, S, dst, T, k, idx, w, nullptr, nullptr, st);
 }
 
@@ -294,13 +308,13 @@ int geometry_impl(const sn2_net_model* m, const sn2_net_dims* d, const sn2_net_g
     SN2_TRY(sn2_sa_order(g->cnt2, B, M2, g->ord2, sb));
     if (fork) NET_HIP(hipEventRecord(ctx->b_tables, sb));
     SN2_TRY(sn2_three_nn(g->pos3, B, 1, g->pos2_soa, M2, 1, g->knn3_idx, g->knn3_w, nullptr, nullptr, sb));
-    SN2_TRY(three_nn_any(g->pos2_soa, B, M2, g->pos1_soa, M1, 3, g->knn2_idx, g->knn2_w, g->nn_ws2, sb));
+    SN2_TRY(three_nn_any(g->pos2_soa, B, M2, g->pos1_soa, M1, 3, g->knn2_idx, g->knn2_w, g->nn_ws2, inverted, sb));
     if (fork) NET_HIP(hipEventRecord(ctx->b_nn, sb));
-    if (inverted) SN2_TRY(inverted_tables(d, g, 1, sb));
+    if (inverted) SN2_TRY(inverted_tables(d, g, 1, sb, true));
     // (c) the per-point table
-    SN2_TRY(three_nn_any(g->pos1_soa, B, M1, g->xyz, N, 3, g->knn1_idx, g->knn1_w, g->nn_ws1, sc));
+    SN2_TRY(three_nn_any(g->pos1_soa, B, M1, g->xyz, N, 3, g->knn1_idx, g->knn1_w, g->nn_ws1, inverted, sc));
     if (fork) NET_HIP(hipEventRecord(ctx->c_nn, sc));
-    if (inverted) SN2_TRY(inverted_tables(d, g, 2, sc));
+    if (inverted) SN2_TRY(inverted_tables(d, g, 2, sc, true));
     // the input-only pieces of the feature pass
     if (flags & SN2_NET_INPUT_ONLY) {
         if (!io->cloud) return SN2_EINVAL;

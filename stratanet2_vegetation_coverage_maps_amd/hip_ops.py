@@ -522,13 +522,34 @@ def three_nn_uses_grid(S: int, T: int) -> bool:
     return bool(_host("sn2_three_nn_uses_grid", int(S), int(T)))
 
 
+@functools.lru_cache(maxsize=256)
+def _three_nn_order_offsets(B: int, S: int, T: int):
+    order, copy = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.load().sn2_three_nn_xy_order_offset(B, S, T, ctypes.byref(order), ctypes.byref(copy)), "sn2_three_nn_xy_order_offset")
+    return order.value, copy.value
+
+
+def three_nn_order(ws: torch.Tensor, B: int, S: int, T: int, sorted_copy: bool = True):
+    """What the grid search `three_nn(..., ws=ws)` left in its workspace (include/strata_hip.h: sn2_three_nn_xy_order_offset):
+    -> (order (B*T,) int32, idx_sorted (B*T,3) int32 or None, w_sorted (B*T,3) float32 or None), views of `ws` -- valid until the
+    next search with the same workspace.  The sorted copy only where the search was asked for it (`sorted_copy=True` there)."""
+    o, c = _three_nn_order_offsets(int(B), int(S), int(T))
+    n = B * T
+    order = ws[o:o + n]
+    if not sorted_copy:
+        return order, None, None
+    return order, ws[c:c + 3 * n].view(n, 3), ws[c + 3 * n:c + 6 * n].view(torch.float32).view(n, 3)
+
+
 def three_nn(src_soa: torch.Tensor, dst_soa: torch.Tensor, k: int, out=None, grid: bool = True, ws=None,
-             dst_fps_ws: Optional[torch.Tensor] = None):
+             dst_fps_ws: Optional[torch.Tensor] = None, sorted_copy: bool = False):
     """-> idx (B*T,3) int32 local source indices, w (B*T,3) = 1/max(d2,1e-16) (0 on unused slots).
     out = (idx, w): caller-owned result buffers.
     grid=True: where `three_nn_uses_grid(S, T)` the search walks a per-plot x,y grid of the sources, a wave taking
     64 targets of adjacent grid cells (sn2_three_nn_xy sorts the targets by cell itself; same result as the full scan, bit
     for bit); ws: caller-owned workspace of three_nn_ws_words(B, S, T) int32 for it (allocated here when None).
+    sorted_copy: the grid search also leaves its result rows in its own order in `ws`, for the inverted index that follows
+    (`three_nn_order`, `interp_index(..., row_order=)`); ignored where the full scan runs.
     dst_fps_ws (with grid=True): use the order `fps(..., return_ws=True)` left for the TARGET points instead of the
     cell sort (the first form of the grid search, kept for cross-checks); grid=False forces the full scan."""
     B, _, S = src_soa.shape
@@ -549,7 +570,8 @@ def three_nn(src_soa: torch.Tensor, dst_soa: torch.Tensor, k: int, out=None, gri
             ws = torch.empty(n, dtype=I32, device=dev)
         else:
             _chk(ws, I32, (n,), "ws")
-        _call("sn2_three_nn_xy", _ptr(src_soa), B, S, _ptr(dst_soa), T, k, _ptr(idx), _ptr(w), _ptr(ws), _stream(), tag=f"T={T}")
+        _call("sn2_three_nn_xy_copy", _ptr(src_soa), B, S, _ptr(dst_soa), T, k, _ptr(idx), _ptr(w), _ptr(ws), int(bool(sorted_copy)),
+              _stream(), tag=f"T={T}", key="sn2_three_nn_xy")
         return idx, w
     if grid and dst_fps_ws is not None and three_nn_uses_grid(S, T):
         if ws is None:
@@ -1116,12 +1138,23 @@ def fp_source_side(R: int, cb: int, force: bool = False) -> bool:
 
 
 def interp_index(knn, B: int, R_per_plot: int, S_per_plot: int, out: Optional[torch.Tensor] = None,
-                 src_pos: Optional[torch.Tensor] = None, row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 src_pos: Optional[torch.Tensor] = None, row_perm: Optional[torch.Tensor] = None,
+                 row_order: Optional[torch.Tensor] = None, sorted_table=None) -> torch.Tensor:
     """Inverted index of a 3-NN table (source -> list of (target row, normalised weight)): what the backward of the
     interpolation gathers through.  Position-only, so it can be built in the geometry pass.  src_pos (B*S,4): the
     source positions; given, the index also orders every plot's sources along a Morton curve (L2 locality of the
     source-side backward).  row_perm (B*R_per_plot) int32, a permutation of 0..R-1 per plot: the lists name row_perm[row]
-    instead of row -- where `fp_desc(..., row_perm=)` keeps the row's d pre-activation (include/strata_hip.h: sn2_fp.row_perm)."""
+    instead of row -- where `fp_desc(..., row_perm=)` keeps the row's d pre-activation (include/strata_hip.h: sn2_fp.row_perm).
+    row_order (B*R_per_plot) int32, a permutation of 0..R-1 per plot: the order the rows are walked in (same lists, other order
+    inside a list) -- the order the grid search of `three_nn` left (`three_nn_order`) makes the list writes dense;
+    sorted_table = (idx_sorted, w_sorted): the table's rows in that order, read instead of a gather (sn2_interp_index_ordered)."""
+    if row_order is not None or sorted_table is not None:
+        n = interp_ws_words(B, R_per_plot, S_per_plot)
+        if out is None:
+            out = torch.empty(n, dtype=F32, device=knn[0].device)
+        interp_index_group(knn, 1, B, R_per_plot, S_per_plot, out, n, src_pos=src_pos, row_perm=row_perm, row_order=row_order,
+                           sorted_table=sorted_table)
+        return out
     if src_pos is not None:
         _chk(src_pos, F32, (B * S_per_plot, 4), "src_pos")
     if row_perm is not None:
@@ -1140,9 +1173,11 @@ def interp_index(knn, B: int, R_per_plot: int, S_per_plot: int, out: Optional[to
 
 
 def interp_index_group(knn, G: int, B: int, R_per_plot: int, S_per_plot: int, out_all: torch.Tensor, stride: int,
-                       src_pos: Optional[torch.Tensor] = None, row_perm: Optional[torch.Tensor] = None):
+                       src_pos: Optional[torch.Tensor] = None, row_perm: Optional[torch.Tensor] = None,
+                       row_order: Optional[torch.Tensor] = None, sorted_table=None):
     """include/strata_hip.h: sn2_interp_index_group -- the inverted indices of G consecutive batches of B plots in ONE set of four
-    launches; knn / src_pos / row_perm: the group's arrays; batch h's index = out_all[h * stride : h * stride + interp_ws_words(...)]."""
+    launches; knn / src_pos / row_perm: the group's arrays; batch h's index = out_all[h * stride : h * stride + interp_ws_words(...)].
+    row_order / sorted_table (the group's arrays, as `interp_index`): sn2_interp_index_ordered."""
     R = G * B * R_per_plot
     _chk(knn[0], I32, (R, 3), "knn_idx")
     _chk(knn[1], F32, (R, 3), "knn_w")
@@ -1150,9 +1185,22 @@ def interp_index_group(knn, G: int, B: int, R_per_plot: int, S_per_plot: int, ou
         _chk(src_pos, F32, (G * B * S_per_plot, 4), "src_pos")
     if row_perm is not None:
         _chk(row_perm, I32, (R,), "row_perm")
-    if stride % 4 or stride < interp_ws_words(B, R_per_plot, S_per_plot):
+    if G == 1:
+        stride = interp_ws_words(B, R_per_plot, S_per_plot)          # (one batch: no stride)
+    elif stride % 4 or stride < interp_ws_words(B, R_per_plot, S_per_plot):
         raise ValueError("interp_index_group: stride must be a multiple of 4 words and hold one index")
     _chk(out_all, F32, (G * stride,), "out indices")
+    if row_order is not None or sorted_table is not None:
+        if row_order is None:
+            raise ValueError("interp_index_group: sorted_table needs its row_order")
+        _chk(row_order, I32, (R,), "row_order")
+        si, sw = sorted_table if sorted_table is not None else (None, None)
+        if si is not None:
+            _chk(si, I32, (R, 3), "idx_sorted")
+            _chk(sw, F32, (R, 3), "w_sorted")
+        _call("sn2_interp_index_ordered", _ptr(knn[0]), _ptr(knn[1]), _ptr(src_pos), _ptr(row_perm), _ptr(row_order), _ptr(si), _ptr(sw),
+              G, B, R_per_plot, S_per_plot, _ptr(out_all), stride, _stream(), key="sn2_interp_index")
+        return
     _call("sn2_interp_index_group", _ptr(knn[0]), _ptr(knn[1]), _ptr(src_pos), _ptr(row_perm), G, B, R_per_plot, S_per_plot, _ptr(out_all),
           stride, _stream(), key="sn2_interp_index")
 

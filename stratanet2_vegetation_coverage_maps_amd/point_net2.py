@@ -537,16 +537,31 @@ class PointNet2(nn.Module):
         ops.ball_query(pos[l - 1], pos[l], r, MAX_NEIGHBORS, total, fps_ws=_at(g, "ws", l), out=(_at(g, "nbr", l), _at(g, "cnt", l)))
 
     @staticmethod
-    def _nn_table(g, pos, j, k):
-        """knn{j}: for every point of level j-1 its k nearest of level j (FP module j's k: 1 from the plot's global feature)."""
+    def _nn_table(g, pos, j, k, inverted=False):
+        """knn{j}: for every point of level j-1 its k nearest of level j (FP module j's k: 1 from the plot's global feature).
+        inverted: `_search_order` follows (the grid search then leaves its rows in its own order too)."""
         L = len(pos) - 2
-        ops.three_nn(pos[j], pos[j - 1], k, out=_at(g, "knn", j), **({"ws": g.nn_ws[L - j]} if j <= L else {}))
+        ops.three_nn(pos[j], pos[j - 1], k, out=_at(g, "knn", j), **({"ws": g.nn_ws[L - j], "sorted_copy": inverted} if j <= L else {}))
 
     @staticmethod
-    def _inverted_table(g, Ms, j):
-        """inv{j}: the inverted index of knn{j} that the backward pass gathers through."""
+    def _search_order(g, Ms, j):
+        """The order (and the sorted rows) that knn{j}'s search left in its workspace, as keywords of `ops.interp_index*`; nothing
+        where the full scan ran.  Only right behind `_nn_table(..., inverted=True)` of the same level, on the same stream: the
+        next search with that workspace overwrites them."""
+        L = len(Ms) - 1
+        if j > L or g.nn_ws is None or g.nn_ws[L - j] is None or not ops.three_nn_uses_grid(Ms[j], Ms[j - 1]):
+            return {}
+        order, si, sw = ops.three_nn_order(g.nn_ws[L - j], g.B, Ms[j], Ms[j - 1])
+        return {"row_order": order, "sorted_table": (si, sw)}
+
+    @staticmethod
+    def _inverted_table(g, Ms, j, ordered=False):
+        """inv{j}: the inverted index of knn{j} that the backward pass gathers through.  ordered: in the search's order
+        (`_search_order`: the geometry pass itself; a late build takes the rows' own order)."""
         B, L = g.B, len(Ms) - 1
         kw = {"src_pos": g.pos1_aos, "row_perm": getattr(g, "rank1", None)} if j == 1 else {}
+        if ordered:
+            kw.update(PointNet2._search_order(g, Ms, j))
         ops.interp_index(_at(g, "knn", j), B, Ms[j - 1], Ms[j] if j <= L else 1, out=_at(g, "inv", j), **kw)
 
     def _geometry(self, xyz, fps_start, out=None, fork=None, shared=False, defer_join=False, inverted=True, cloud=None, n_live=None):
@@ -600,15 +615,15 @@ class PointNet2(nn.Module):
                 self._ball_level(g, pos, l, sa[l - 1].r, total(l))
                 ops.sa_order(_at(g, "cnt", l), B, Ms[l], out=_at(g, "ord", l))
             for j in range(L + 1, 1, -1):
-                self._nn_table(g, pos, j, fp[j].k)
+                self._nn_table(g, pos, j, fp[j].k, inverted)
             # the inverted 3-NN tables the backward pass gathers through: positions only, so they belong here
             if inverted:
                 for j in range(L + 1, 1, -1):
-                    self._inverted_table(g, Ms, j)
+                    self._inverted_table(g, Ms, j, ordered=True)
         with torch.cuda.stream(sc):                                        # (c) the per-point table
-            self._nn_table(g, pos, 1, fp[1].k)
+            self._nn_table(g, pos, 1, fp[1].k, inverted)
             if inverted:
-                self._inverted_table(g, Ms, 1)
+                self._inverted_table(g, Ms, 1, ordered=True)
         g.has_inverted = bool(inverted)
         g.has_rows0 = False
         if cloud is not None:
@@ -703,7 +718,7 @@ class PointNet2(nn.Module):
         # (the per-point table's targets in the FPS pass's existing Morton order -- `dst_fps_ws=gp.ws1`, no target sort -- made the
         # pipelined step SLOWER, 0.739 against 0.718 ms: the search's query boxes grow more than the sort costs; round 5)
         for j in range(L + 1, 0, -1):
-            self._nn_table(gp, pos, j, fp[j].k)
+            self._nn_table(gp, pos, j, fp[j].k, True)
         grp = gp._grp
         tot_flat = grp.totals.view(-1)                       # (G,L): [h][l-1] = level-l messages of batch h
         for l in range(1, L + 1):
@@ -713,6 +728,7 @@ class PointNet2(nn.Module):
         rank = gp.rank1 if halves[0].rank1 is not None else None
         for j in range(L + 1, 0, -1):
             kw = {"src_pos": gp.pos1_aos, "row_perm": rank} if j == 1 else {}
+            kw.update(self._search_order(gp, Ms, j))        # (every level has a workspace of its own: all still hold their orders)
             ops.interp_index_group(_at(gp, "knn", j), G, B, Ms[j - 1], Ms[j] if j <= L else 1, grp.inv[j], grp.si[j], **kw)
         if cloud2 is not None:
             self._input_only(gp, cloud2, xyz2)                    # one launch each over the whole group
