@@ -854,6 +854,40 @@ int sn2_atlas_crop_stats(float *bands, int C, int K, const long long *canvas_hos
                          const double *edges, const int *edge_start_host, const int *edge_start_dev, void *ws, double *mean,
                          long long *count, void *stream);
 
+/* ---- Per-point scores of a parcel cloud (csrc/points.hip; the rule's functions: csrc/point_rules.h): the network's OWN pointwise
+ * outputs of every batch -- what utils/visualize_predictions.py shows per plot as "Pointwise prediction" and "Score for
+ * most-likely strata" -- scattered back onto the parcel's points and merged over the overlapping plots by the mosaic's radial
+ * weight.  Not a reference output: the reference has no parcel-scale point product.
+ *
+ * CONTRIBUTION.  Sample j of plot b of a batch (B plots of N samples) contributes iff
+ *   j < n_live[b]                                         (the repeats that pad a sparse plot do not count), and
+ *   0 <= c = idx[b,j] < n_b = offsets[b+1] - offsets[b]   (the fake ground points appended after the plot's real points do not).
+ * DESTINATION.  col = (col_base ? col_base[b] : 0) + point_index[offsets[b] + c]: the point's column in the parcel cloud, or in
+ *   an arena of K parcel clouds with col_base[b] = the first column of plot b's parcel.  A (plot, point) pair contributes at
+ *   most once.  offsets are the plots' positions in point_index (sum_n entries), as sn2_prepare_plots takes them.
+ * VALUES.  v_1..v_4 = cov[b N + j, 0:4], v_5..v_8 = proba[b N + j, 0:4] of the eval forward, both (B N,4) fp32.
+ * WEIGHT.  add_weights_band_to_rasters' 1.5 - r taken at the point instead of a pixel centre, in fp64 from the fp32 rows of
+ *   xyz (B,3,N) (centred metres, as sn2_prepare_plots leaves them): dx = xyz[b,0,j], dy = xyz[b,1,j],
+ *   r2 = (double)dx dx + (double)dy dy (both products exact, one rounding), r = sqrt(r2) / diam_meters, w = 1.5 - r.
+ * SUMS.  64-bit integers in units of 2^-32, llrint = round to nearest even:
+ *   acc[col][0] += llrint(w 2^32);   acc[col][k] += llrint(w (double)v_k 2^32), k = 1..8;   hits[col] += 1 (int32).
+ *   Integer sums do not depend on the order of arrival: any batching, plot order or split into launches gives the same bytes.
+ *   No floating-point atomic anywhere; the adds are vector global atomics whose result is not read.
+ * FINALISATION.  scores[k-1][col] = (float)((double)acc[col][k] / (double)acc[col][0]), weight[col] = (float)((double)acc[col][0]
+ *   / 2^32); a point with hits == 0 gets NaN scores and weight 0.  A single contribution returns v_k itself for v_k >= 2^-7.
+ * acc: SN2_POINTS_ACC_WORDS int64 per point, hits: T int32; the caller zeroes both once.  acc is opaque between the two calls
+ * (point col's word k lies at acc[9 col + k]).  scores (8,T) fp32, weight (T) fp32.
+ * sn2_points_merge is ONE launch on `stream` (behind the forward that wrote cov / proba), no synchronisation, no host read;
+ * sn2_points_finalize one launch, acc and hits unchanged.  Inside the kernel nothing is written for a sample whose idx is
+ * outside its plot, whose plot's offsets lie outside [0, sum_n], or whose column lies outside [0, T).
+ * ERRORS, before any launch: SN2_EINVAL on a NULL pointer (col_base may be NULL), B, N, T or sum_n <= 0, diam_meters <= 0 (or
+ * NaN); SN2_ELIMIT on T, sum_n or B N >= 2^31. */
+#define SN2_POINTS_ACC_WORDS 9
+int sn2_points_merge(const float *cov, const float *proba, const float *xyz, const int *idx, const int *n_live, const int *offsets,
+                     const int *point_index, long sum_n, const int *col_base, int B, int N, double diam_meters, long long *acc,
+                     int *hits, long T, void *stream);
+int sn2_points_finalize(const long long *acc, const int *hits, long T, float *scores, float *weight, void *stream);
+
 /* ---- loss block of the timed training step: learning/loss_functions.py:9-57 combined as learning/train.py:58-62,
  *   total = get_absolute_loss(pred, gt) + m * get_NLL_loss(proba, pdf_all) + e * get_entropy_loss(proba)
  * pred (B,4) fp32 plot-wise coverages, gt (B,4) fp64, proba (R,4) fp32 pointwise class probabilities, pdf (R,3) fp64 the

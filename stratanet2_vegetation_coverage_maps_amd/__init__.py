@@ -6,7 +6,7 @@ The HIP library (csrc/libstrata_hip.so) is loaded on first use and is mandatory:
 """
 from .evaluation import evaluate, evaluate_table, plot_losses, plot_losses_torch  # noqa: F401
 from .hip_ops import subsample, subsample_form  # noqa: F401
-from .inference import AtlasReport, MosaicAtlas  # noqa: F401
+from .inference import AtlasReport, MosaicAtlas, PointScoreResult, PointScores  # noqa: F401
 from .parcel import (ParcelClouds, ParcelPlots, ParcelSet, parcel_plot_centers, polygon_keep, predict_parcel_cloud,  # noqa: F401
                      predict_parcels, prepare_parcel, prepare_parcels)
 from .point_net2 import PointNet2  # noqa: F401

@@ -1931,6 +1931,56 @@ def atlas_crop_stats(bands, C: int, table: AtlasTable, pix: float, edges=None, o
     return mean, count
 
 
+# ---- the per-point scores of a parcel cloud (include/strata_hip.h, "Per-point scores"; csrc/points.hip) -------------------------
+POINTS_ACC_WORDS = _lib.SN2_POINTS_ACC_WORDS
+
+
+def points_merge(cov, proba, xyz, idx, n_live, offsets, point_index, acc, hits, diam_meters: float, col_base=None):
+    """include/strata_hip.h: sn2_points_merge.  cov, proba (B*N,4) fp32 of the eval forward, xyz (B,3,N) fp32 centred metres,
+    idx (B,N) int32 the batch's subsample, n_live (B) int32, offsets (B+1) int32 the plots' positions in point_index (sum_n)
+    int32, col_base (B) int32 or None -> the contributions of the batch added into acc (T, POINTS_ACC_WORDS) int64 and hits (T)
+    int32 (both zeroed once by the caller).  One launch on the current stream, no read-back; 64-bit integer atomics, so the sums
+    do not depend on batching or order."""
+    _chk(idx, I32, None, "idx")
+    if idx.dim() != 2:
+        raise ValueError(f"idx: expected (B,N), got {tuple(idx.shape)}")
+    B, N = idx.shape
+    _chk(cov, F32, (B * N, 4), "cov")
+    _chk(proba, F32, (B * N, 4), "proba")
+    _chk(xyz, F32, (B, 3, N), "xyz")
+    _chk(n_live, I32, (B,), "n_live")
+    _chk(offsets, I32, (B + 1,), "offsets")
+    _chk(point_index, I32, None, "point_index")
+    if point_index.dim() != 1:
+        raise ValueError(f"point_index: expected (sum_n,), got {tuple(point_index.shape)}")
+    _chk(hits, I32, None, "hits")
+    if hits.dim() != 1:
+        raise ValueError(f"hits: expected (T,), got {tuple(hits.shape)}")
+    T = hits.shape[0]
+    _chk(acc, I64, (T, POINTS_ACC_WORDS), "acc")
+    if col_base is not None:
+        _chk(col_base, I32, (B,), "col_base")
+    _call("sn2_points_merge", _ptr(cov), _ptr(proba), _ptr(xyz), _ptr(idx), _ptr(n_live), _ptr(offsets), _ptr(point_index),
+          point_index.shape[0], _ptr(col_base), B, N, float(diam_meters), _ptr(acc), _ptr(hits), T, _stream())
+
+
+def points_finalize(acc, hits, out=None):
+    """include/strata_hip.h: sn2_points_finalize.  acc (T, POINTS_ACC_WORDS) int64 and hits (T) int32 of `points_merge` (left as
+    they are) -> (scores (8,T) fp32 = the four coverages then the four class probabilities, weight (T) fp32): NaN scores and
+    weight 0 where hits == 0.  out: a (scores, weight) pair to write into."""
+    _chk(hits, I32, None, "hits")
+    if hits.dim() != 1:
+        raise ValueError(f"hits: expected (T,), got {tuple(hits.shape)}")
+    T = hits.shape[0]
+    _chk(acc, I64, (T, POINTS_ACC_WORDS), "acc")
+    if out is None:
+        scores, weight = torch.empty(8, T, dtype=F32, device=acc.device), torch.empty(T, dtype=F32, device=acc.device)
+    else:
+        scores, weight = _chk(out[0], F32, (8, T), "out[0]"), _chk(out[1], F32, (T,), "out[1]")
+    _call("sn2_points_finalize", _ptr(acc), _ptr(hits), T, _ptr(scores), _ptr(weight), _stream())
+    return scores, weight
+
+
 LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS
 
 

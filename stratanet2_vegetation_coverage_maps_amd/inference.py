@@ -125,21 +125,79 @@ class ParcelReport:
 
 
 @torch.no_grad()
-def predict_parcel(model, batches, mosaic: ParcelMosaic, args, prefetch: int = 3):
+def predict_parcel(model, batches, mosaic: ParcelMosaic, args, prefetch: int = 3, point_sink=None):
     """`batches`: iterable of dicts with "cloud" (B,10,N), "xyz" (B,3,N), "plot_center" (B,2) (the reference DataLoader's
     collate of `inference/predict_utils.py:74-82`), optionally PointNet2's additive keys "fps_start" and "n_live" (`ParcelPlots.batches`
     sets "n_live"), which reach the geometry passes as they are.  Returns the number of plots processed.
     prefetch: how many batches ahead the position-only kernels (FPS, ball query, 3-NN) run, each on its own side stream
     (`PointNet2.prefetch_geometry`), while this batch's feature kernels, rasters and merge run.  FPS is M sequential rounds
     in one workgroup per plot -- 64 plots keep 64 of 256 CUs busy for most of an un-overlapped batch -- so several passes
-    in flight is what fills the chip; 0 = no overlap."""
-    return predict_batches(model, batches, args, lambda rasters, cur: mosaic.add(rasters, cur["plot_center"]), prefetch=prefetch)
+    in flight is what fills the chip; 0 = no overlap.  point_sink: as `predict_batches`."""
+    return predict_batches(model, batches, args, lambda rasters, cur: mosaic.add(rasters, cur["plot_center"]), prefetch=prefetch,
+                           point_sink=point_sink)
+
+
+SCORE_NAMES = ("cov_low", "cov_soil", "cov_med", "cov_high", "proba_0", "proba_1", "proba_2", "proba_3")   # rows of `scores`
+
+
+@dataclass
+class PointScoreResult:
+    """`PointScores.finalize`, all on the device: scores (8,T) fp32 -- rows 0..3 the pointwise coverages, rows 4..7 the pointwise
+    class probabilities, in the network's column order --, weight (T) fp32 the sum of the contributions' weights, hits (T) int32
+    the number of plots that sampled the point.  A point no plot sampled has NaN scores, weight 0 and hits 0."""
+    scores: torch.Tensor
+    weight: torch.Tensor
+    hits: torch.Tensor
+
+
+class PointScores:
+    """The network's pointwise outputs merged back onto the T points of a parcel cloud (or of a `parcel.ParcelClouds` arena), on the
+    device (include/strata_hip.h, "Per-point scores"): every real point a plot's subsample drew gets that plot's (B*N,4) coverages
+    and (B*N,4) class probabilities, and a point drawn by several overlapping plots their average under the mosaic's radial weight
+    1.5 - r, taken at the point.  These are the MODEL's outputs on ITS subsample draws -- what `utils/visualize_predictions.py`
+    plots per plot --, not a reference output: another seed draws other points, and a point no plot drew has no score.
+    The sums are 64-bit integers, so the bytes do not depend on the batch size or the order of the plots.
+    point_start (K+1): the first column of every parcel of an arena (`ParcelClouds.point_start`), for `parcel(k)`."""
+
+    def __init__(self, T: int, device, point_start=None):
+        self.T = int(T)
+        self.acc = torch.zeros(self.T, ops.POINTS_ACC_WORDS, dtype=torch.int64, device=device)
+        self.hits = torch.zeros(self.T, dtype=torch.int32, device=device)
+        self.point_start = None if point_start is None else np.asarray(point_start, dtype=np.int64)
+        self._result = None
+
+    def add(self, cov: torch.Tensor, proba: torch.Tensor, batch: dict):
+        """One batch of `ParcelPlots.batches(..., with_samples=True)` and the eval forward's outputs for it: ONE launch in stream
+        order behind the forward, no synchronisation."""
+        if "sample_index" not in batch:
+            raise ValueError("PointScores.add: the batch carries no samples (ParcelPlots.batches(..., with_samples=True))")
+        with torch.cuda.device(self.acc.device):
+            ops.points_merge(cov.contiguous(), proba.contiguous(), batch["xyz"], batch["sample_index"], batch["sample_live"],
+                             batch["point_offsets"], batch["point_index"], self.acc, self.hits, batch["diam_meters"],
+                             col_base=batch.get("col_base"))
+        self._result = None
+
+    def finalize(self) -> PointScoreResult:
+        if self._result is None:
+            with torch.cuda.device(self.acc.device):
+                scores, weight = ops.points_finalize(self.acc, self.hits)
+            self._result = PointScoreResult(scores, weight, self.hits)
+        return self._result
+
+    def parcel(self, k: int) -> PointScoreResult:
+        """parcel k's views of `finalize()`: scores (8,T_k), weight (T_k), hits (T_k)."""
+        if self.point_start is None:
+            raise ValueError("PointScores.parcel: these scores are of one parcel (no point_start)")
+        r, p0, p1 = self.finalize(), int(self.point_start[k]), int(self.point_start[k + 1])
+        return PointScoreResult(r.scores[:, p0:p1], r.weight[p0:p1], r.hits[p0:p1])
 
 
 @torch.no_grad()
-def predict_batches(model, batches, args, sink, prefetch: int = 3):
+def predict_batches(model, batches, args, sink, prefetch: int = 3, point_sink=None):
     """The prefetching loop of `predict_parcel`: every batch's rasters (B,3,D,D) go to `sink(rasters, batch)` -- a
-    `ParcelMosaic.add`, or a `MosaicAtlas.add` for batches that cut across parcels.  Returns the number of plots processed."""
+    `ParcelMosaic.add`, or a `MosaicAtlas.add` for batches that cut across parcels.  Returns the number of plots processed.
+    point_sink: None, or a callable that gets `(cov, proba, batch)` -- the forward's pointwise outputs, (B*N,4) each -- after the
+    raster sink (`PointScores.add`)."""
     from collections import deque
     model.eval()
     n = 0
@@ -164,11 +222,13 @@ def predict_batches(model, batches, args, sink, prefetch: int = 3):
         cd = dict(cur)
         if geo is not None:
             cd["geometry"] = geo
-        cov, _ = model(cd)
+        cov, proba = model(cd)
         clouds_dev = model._last_cloud_dev[1]
         model._last_cloud_dev = None
         rasters, _ = project_batch_to_2d_rasters(clouds_dev, cov, args)
         sink(rasters, cur)
+        if point_sink is not None:
+            point_sink(cov, proba, cur)
         n += clouds_dev.shape[0]
     # (no check of hip_ops.fps_gave_up here: it reads a device word, i.e. synchronises; callers that synchronise anyway --
     # reading the mosaic back -- may ask for it)

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import hip_ops as ops
-from .inference import MosaicAtlas, ParcelMosaic, predict_batches, predict_parcel
+from .inference import MosaicAtlas, ParcelMosaic, PointScores, predict_batches, predict_parcel
 from .input_pipeline import check_sampler, draw_plot_randoms, draw_seed, fake_ground_xy, live_counts
 
 MIN_POINTS = 51              # prepare_utils.py:67-69 (< 50: None) and prepare.py:93 (> 50)
@@ -168,7 +168,7 @@ class ParcelPlots:
         return len(self.n_points)
 
     def batches(self, args, batch_size: int, rs=np.random, fps_start: Optional[int] = None, sampler="numpy", seed=None,
-                n_live: bool = True, key_base: int = 0):
+                n_live: bool = True, key_base: int = 0, with_samples: bool = False):
         """The input dicts of `inference.predict_parcel` ("cloud", "xyz", "plot_center", "n_live"), built on the device from raw /
         offsets by `sn2_prepare_plots` in eval mode.  Random draws: `draw_plot_randoms` per plot in plot order, so the
         batches equal `input_pipeline.prepare_batch(plots, centers, args, train=False, rs=rs)` on the same plots and seed.
@@ -180,17 +180,22 @@ class ParcelPlots:
         its candidates in order, then repeats (a sparse parcel: half of its plots); the FPS kernels skip the repeats.  n_live=False
         leaves the key out (same predictions; a cross-check and a timing comparison).
         key_base: the device sampler's key of plot i is key_base + i (`plot_keys`); a parcel run with key_base = k << 32 draws
-        the points it draws as parcel k of a `ParcelSet`."""
+        the points it draws as parcel k of a `ParcelSet`.
+        with_samples=True: every dict also says where its samples came from -- what `inference.PointScores.add` scatters the
+        pointwise outputs back by: "sample_index" (B,N) int32 (the subsample it was gathered with), "sample_live" (B) int32
+        (`live_counts`, whatever `n_live` says), "plot_range" (b0, b1) the batch's plots, "point_offsets" (B+1) int32 their
+        positions in "point_index" (this object's, not copied), "diam_meters", and for a `ParcelSet` "col_base" (B) int32, the
+        first arena column of each plot's parcel.  False: the dicts are exactly the ones above."""
         check_sampler(sampler)                       # here, not in the generator: a bad argument fails at the call
         if sampler == "numpy" and seed is not None:
             raise ValueError("seed belongs to sampler='device'")
-        return self._batches(args, batch_size, rs, fps_start, sampler, seed, n_live, int(key_base))
+        return self._batches(args, batch_size, rs, fps_start, sampler, seed, n_live, int(key_base), bool(with_samples))
 
     def plot_keys(self, key_base: int = 0) -> np.ndarray:
         """(P) int64: the Philox key of every plot for `hip_ops.subsample` = key_base + the plot's position."""
         return int(key_base) + np.arange(len(self), dtype=np.int64)
 
-    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True, key_base=0):
+    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True, key_base=0, with_samples=False):
         dev = self.raw.device
         fake = fake_ground_xy(args.diam_meters)
         fake_dev = torch.from_numpy(fake).to(dev)
@@ -215,6 +220,9 @@ class ParcelPlots:
                 d["n_live"] = n_live[b0:b1]
             if fps_start is not None:
                 d["fps_start"] = torch.full((2, b1 - b0), int(fps_start), dtype=torch.int64)
+            if with_samples:
+                d.update(sample_index=idx, sample_live=n_live[b0:b1], plot_range=(b0, b1), point_offsets=self.offsets[b0:b1 + 1],
+                         point_index=self.point_index, diam_meters=float(args.diam_meters))
             yield d
 
 
@@ -301,22 +309,26 @@ def parcel_mosaic(centers_host: np.ndarray, args, device) -> ParcelMosaic:
 
 def predict_parcel_cloud(model, parcel_cloud, args, batch_size: int = 20, rs=np.random, keep=None, prefetch: int = 3,
                          centers=None, fps_start: Optional[int] = None, sampler="numpy", seed=None, n_live: bool = True,
-                         shape=None, key_base: int = 0):
+                         shape=None, key_base: int = 0, points: bool = False):
     """prepare_parcel + a mosaic sized to the plots + `inference.predict_parcel` -> (ParcelMosaic, ParcelPlots).  The mosaic
     is None when the parcel has no kept plot.  `mosaic.finalize()` gives the coverage bands.  sampler, seed, n_live: as
     `ParcelPlots.batches`.  shape: the rings of the parcel polygon (`polygon_edges`); with keep=None the lattice is then
     filtered by `polygon_keep(shape, shape_buffer(args))` as the reference filters it, and `mosaic.report(shape)` gives the
-    bands cropped to the polygon and the parcel's band means.  key_base: as `ParcelPlots.batches`."""
+    bands cropped to the polygon and the parcel's band means.  key_base: as `ParcelPlots.batches`.
+    points=True: -> (ParcelMosaic, ParcelPlots, `inference.PointScores`): the model's pointwise coverages and class
+    probabilities merged back onto the parcel's own points, one more launch per batch; the mosaic's bytes are those of
+    points=False."""
     check_sampler(sampler)
     if shape is not None and keep is None:
         keep = polygon_keep(shape, shape_buffer(args))
     plots = prepare_parcel(parcel_cloud, args, centers=centers, keep=keep)
+    scores = PointScores(parcel_cloud.shape[1], plots.raw.device) if points else None
     if len(plots) == 0:
-        return None, plots
+        return (None, plots, scores) if points else (None, plots)
     mosaic = parcel_mosaic(plots.centers_host, args, plots.raw.device)
-    predict_parcel(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live, key_base), mosaic, args,
-                   prefetch=prefetch)
-    return mosaic, plots
+    predict_parcel(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live, key_base, with_samples=points),
+                   mosaic, args, prefetch=prefetch, point_sink=scores.add if points else None)
+    return (mosaic, plots, scores) if points else (mosaic, plots)
 
 
 @dataclass
@@ -324,9 +336,11 @@ class ParcelSet(ParcelPlots):
     """The kept plots of K parcels as ONE `ParcelPlots` (raw concatenated, offsets shifted; plot ids, centres, n_points and
     plot_index as they are per parcel; point_index relative to the plot's own parcel cloud) plus parcel_of (P): the parcel of
     every plot, and parcel_start (K+1): parcel k owns the plots parcel_start[k] .. parcel_start[k+1] (none is legal).  Both on
-    the host."""
+    the host.  point_start (K+1) int64, host: the first column of every parcel's cloud in the arena of all K (`ParcelClouds.
+    point_start`; what `prepare_parcels` already computes), for scattering per-point results back (`batches(with_samples=True)`)."""
     parcel_of: np.ndarray = None
     parcel_start: np.ndarray = None
+    point_start: np.ndarray = None
 
     @property
     def n_parcels(self) -> int:
@@ -338,13 +352,19 @@ class ParcelSet(ParcelPlots):
         k = self.parcel_of.astype(np.int64)
         return int(key_base) + (k << 32) + (np.arange(len(self), dtype=np.int64) - self.parcel_start[k])
 
-    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True, key_base=0):
+    def _batches(self, args, batch_size, rs, fps_start, sampler, seed, with_live=True, key_base=0, with_samples=False):
         """`ParcelPlots.batches` over the whole set -- a batch may cut across parcels -- with one more key, "parcel": (B,) the
-        parcel of every plot, on the host (non-decreasing)."""
+        parcel of every plot, on the host (non-decreasing); with_samples: and "col_base" (B) int32 on the device."""
+        if with_samples:
+            if self.point_start is None:
+                raise ValueError("ParcelSet.batches(with_samples=True) needs point_start (prepare_parcels sets it)")
+            col_base = torch.from_numpy(np.asarray(self.point_start, dtype=np.int64)[self.parcel_of].astype(np.int32)).to(self.raw.device)
         b0 = 0
-        for d in super()._batches(args, batch_size, rs, fps_start, sampler, seed, with_live, key_base):
+        for d in super()._batches(args, batch_size, rs, fps_start, sampler, seed, with_live, key_base, with_samples):
             b1 = b0 + len(d["plot_center"])
             d["parcel"] = self.parcel_of[b0:b1]
+            if with_samples:
+                d["col_base"] = col_base[b0:b1]
             b0 = b1
             yield d
 
@@ -506,9 +526,11 @@ def prepare_parcels(clouds, args, shapes=None, keeps=None, device=None, min_poin
             pc = ParcelClouds.from_clouds(clouds, device)
         out = _prepare_batched(pc, args, shapes, keeps, min_points, strict)
         if out is not None:
+            out.point_start = np.asarray(pc.point_start, dtype=np.int64).copy()
             return out
     if pc is not None:
         clouds = [pc.cloud(k) for k in range(K)]
+    point_start = np.concatenate([[0], np.cumsum([int(c.shape[1]) for c in clouds])]).astype(np.int64)
     parts = [prepare_parcel(cloud, args, keep=_keep_of(k, args, shapes, keeps), device=device, min_points=min_points)
              for k, cloud in enumerate(clouds)]
     dev = parts[0].raw.device
@@ -521,20 +543,25 @@ def prepare_parcels(clouds, args, shapes=None, keeps=None, device=None, min_poin
                      torch.cat([p.point_index for p in parts]), torch.cat([p.centers for p in parts]), n_points,
                      np.concatenate([p.plot_index for p in parts]), [i for p in parts for i in p.plot_ids],
                      np.concatenate([p.centers_host for p in parts]).astype(np.float32).reshape(-1, 2),
-                     np.repeat(np.arange(K, dtype=np.int64), counts), np.concatenate([[0], np.cumsum(counts)]))
+                     np.repeat(np.arange(K, dtype=np.int64), counts), np.concatenate([[0], np.cumsum(counts)]), point_start)
 
 
 def predict_parcels(model, clouds, args, shapes=None, batch_size: int = 512, sampler="device", seed=None,
-                    fps_start: Optional[int] = None, prefetch: int = 3, n_live: bool = True, rs=np.random, batched=None):
+                    fps_start: Optional[int] = None, prefetch: int = 3, n_live: bool = True, rs=np.random, batched=None,
+                    points: bool = False):
     """K parcels predicted in shared batches: `prepare_parcels` (batched: as there), a `MosaicAtlas` with one canvas per parcel, and
     `inference.predict_parcel`'s prefetching loop over the set's batches, which cut across parcels -- each batch ends in ONE
     `atlas.add` -> (MosaicAtlas, ParcelSet).  `atlas.report(shapes)` gives every parcel's cropped bands and band means with one
     device-to-host read.  Canvas k holds the bytes of `predict_parcel_cloud(model, clouds[k], ..., key_base=k << 32)`'s mosaic
-    (an eval forward of a plot does not depend on the batch it is in)."""
+    (an eval forward of a plot does not depend on the batch it is in).
+    points=True: -> (MosaicAtlas, ParcelSet, `inference.PointScores`) over the columns of the whole cloud arena (`plots.point_start`);
+    `scores.parcel(k)` holds the bytes of that parcel's own `predict_parcel_cloud(..., key_base=k << 32, points=True)` scores."""
     check_sampler(sampler)
     plots = prepare_parcels(clouds, args, shapes=shapes, batched=batched)
     atlas = MosaicAtlas.for_plots(plots, args)
+    scores = PointScores(int(plots.point_start[-1]), plots.raw.device, plots.point_start) if points else None
     if len(plots):
-        predict_batches(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live), args,
-                        lambda rasters, cur: atlas.add(rasters, cur["plot_center"], cur["parcel"]), prefetch=prefetch)
-    return atlas, plots
+        predict_batches(model, plots.batches(args, batch_size, rs, fps_start, sampler, seed, n_live, with_samples=points), args,
+                        lambda rasters, cur: atlas.add(rasters, cur["plot_center"], cur["parcel"]), prefetch=prefetch,
+                        point_sink=scores.add if points else None)
+    return (atlas, plots, scores) if points else (atlas, plots)
