@@ -854,6 +854,56 @@ int sn2_atlas_crop_stats(float *bands, int C, int K, const long long *canvas_hos
                          const double *edges, const int *edge_start_host, const int *edge_start_dev, void *ws, double *mean,
                          long long *count, void *stream);
 
+/* ---- Admissibility band (csrc/admissibility.hip; the rule's functions: csrc/admissibility_rules.h): the fifth band of the
+ * reference's parcel product and the source of PRED_ADM -- insert_admissibility_raster (inference/geotiff_raster.py:149-196):
+ * rasterio `sieve` of the hard medium-vegetation band, `shapes` of its ones, a shapely buffer of -1.5, `geometry_mask`, then
+ * max(Vb, Vm_soft) with the masked pixels set to 0.  Those libraries cannot be run beside this one, so the rule below is OURS: what
+ * that chain comes to on a pixel grid (the reference passes an identity transform: its 1.5 m are 1.5 px), with the two places that
+ * are a reading and not a pinned fact marked UNPINNED.  It works on one canvas of H x W pixels, on the five bands of the
+ * finalisation [Vb, Vm_soft, Vh, Vm_hard, weights], BEFORE the crop (merge_geotiff_rasters finalises at :215, crops at :216).
+ *   1 valid(p) = !isnan(Vm_hard(p)) (the finalisation makes the five bands NaN together);  h(p) = Vm_hard(p) > 0.
+ *   2 SIEVE with size threshold s, 4-connectivity (the single pass of GDAL's sieve filter as we read it).  s <= 1: S = h.
+ *     A region is a 4-connected component of valid pixels of equal h; id(R) = its smallest row-major pixel index, size(R) = its
+ *     pixel count.  Two regions are neighbours when they hold 4-adjacent pixels; an invalid pixel is nobody's neighbour.
+ *     big(R), for a region of size < s: the neighbour of largest size, ties to the SMALLEST id; none without a neighbour.
+ *     The walk R -> big(R) -> big(big(R)) ... stops with target T at the first region of size >= s; it fails at a region without a
+ *     big, or when a region comes up a second time.  Sizes are the original ones throughout: nothing cascades.
+ *     S(p) = h(T) on the pixels of a small region whose walk found T;  S(p) = h(p) everywhere else.
+ *     UNPINNED: s.  The reference calls sieve(..., 5, mask=isnan(...)); by rasterio's documentation a mask value of False EXCLUDES
+ *     a pixel, so as written the valid pixels are excluded and nothing inside the parcel changes (s = 0); the comment beside the
+ *     call, "Eliminate zones < 5 pixels", states the intent (s = 5).  Neither can be run here: s is the caller's, no default.
+ *   3 H'(p) = 1 where !valid(p) (the reference sets the outside to one "to avoid border effects"), else min(h(p), S(p)): small
+ *     patches of ones disappear, small holes of zeros stay zeros.
+ *   4 inacc(p) iff H'(q) = 1 for every q at offset (dx,dy) with max(2|dx|-1,0)^2 + max(2|dy|-1,0)^2 < 9 (4 x the squared distance
+ *     from p's centre to q's pixel square against 4 x 1.5^2); a q outside the canvas counts as 0.  In effect the 3 x 3 neighbourhood.
+ *     UNPINNED: the tie.  The offsets (+-2,0), (0,+-2) sit at exactly 1.5 px, the centre ON the buffered outline; `<` counts it as
+ *     inside (inaccessible).  GDAL's scanline fill treats the four sides differently.  The comparison is adm_offset_tested's.
+ *   5 Adm(p) = NaN where !valid(p), 0 where inacc(p), else the larger of Vb(p), Vm_soft(p) in fp32.
+ *   6 out (6,H,W) = [Vb, Vm_soft, Vh, Vm_hard, Adm, weights], the reference's band order; bands 0-3 and 5 carry the bits of the
+ *     input, band 3 the UNSIEVED hard band as in the reference.
+ * stats (K,4) int64 on the device, per canvas: regions, regions of size < s, pixels with S != h, valid inaccessible pixels.
+ * ws: 8-byte aligned, SN2_ADM_WS_WORDS(pixels) 32-bit words for `pixels` = H W (the atlas: the sum over its canvases), no
+ * initialisation: a head (the single-canvas call's one-row canvas table) and SN2_ADM_WS_WORDS_PER_PIXEL words per pixel -- union-find
+ * parent, region size, sieve bit, H', and the 64-bit neighbour key.
+ * PHASES, separate launches on `stream`, no cross-workgroup waiting, nothing read back (capturable): labelling by union-find with
+ * atomicMin on the roots (a root is its tree's smallest index: the labels do not depend on the order of the atomics) -> flatten and
+ * sizes (integer adds) -> big (one 64-bit atomicMax of (size << 32) | (0xFFFFFFFF - id) per adjacency) -> walk (one thread per
+ * small region, repeat detection that terminates on any input) -> H' -> the offsets test and the six bands.  wave64; vector
+ * stores and vector integer atomics only; no floating-point atomic: DETERMINISTIC, the same input gives the same bytes.
+ * sn2_atlas_admissibility: bands5_arena / bands6_arena hold canvas k's (5,H_k,W_k) / (6,H_k,W_k) at word 5 base_k / 6 base_k.
+ * CONTRACT: canvas k's six bands and stats are the bytes sn2_mosaic_admissibility gives on that canvas's view.
+ * ERRORS, before any launch: SN2_EINVAL on a NULL pointer, H or W <= 0, K <= 0, sieve_size < 0, a misaligned ws or a table that is
+ * not sn2_atlas_canvas_table's; SN2_ELIMIT on H W >= 2^31.
+ * (The size helper returns its value through a pointer, as sn2_atlas_finalize_ws_words does.) */
+#define SN2_ADM_WS_HEAD_WORDS (4 * SN2_ATLAS_CANVAS_COLS)
+#define SN2_ADM_WS_WORDS_PER_PIXEL 6
+#define SN2_ADM_WS_WORDS(pixels) (SN2_ADM_WS_HEAD_WORDS + SN2_ADM_WS_WORDS_PER_PIXEL * (size_t)(pixels))
+int sn2_admissibility_ws_words(long long pixels, size_t *words);
+int sn2_mosaic_admissibility(const float *bands5, int H, int W, int sieve_size, void *ws, float *bands6, long long *stats,
+                             void *stream);
+int sn2_atlas_admissibility(const float *bands5_arena, int K, const long long *canvas_host, const long long *canvas_dev,
+                            int sieve_size, void *ws, float *bands6_arena, long long *stats, void *stream);
+
 /* ---- Per-point scores of a parcel cloud (csrc/points.hip; the rule's functions: csrc/point_rules.h): the network's OWN pointwise
  * outputs of every batch -- what utils/visualize_predictions.py shows per plot as "Pointwise prediction" and "Score for
  * most-likely strata" -- scattered back onto the parcel's points and merged over the overlapping plots by the mosaic's radial

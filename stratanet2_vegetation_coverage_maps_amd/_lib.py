@@ -25,6 +25,7 @@ CONSTANTS = {
     "SN2_NET_GRAD_IMAGES": 32, "SN2_METER_TERMS": 4, "SN2_PARCELS_COLS": 16, "SN2_PARCELS_BBOX_CHUNK": 4096,
     "SN2_CV_SLICE_PLOTS": 1024, "SN2_CV_COLUMNS": 30, "SN2_CV_STATS_DOUBLES": 2 * 30 + 2 * 3 * 8 * 8 + 1, "SN2_CV_MAX_PLOTS": 1 << 24,
     "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8, "SN2_POINTS_ACC_WORDS": 9,
+    "SN2_ADM_WS_HEAD_WORDS": 32, "SN2_ADM_WS_WORDS_PER_PIXEL": 6,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
@@ -235,6 +236,10 @@ SIGNATURES = {
     "sn2_atlas_finalize": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_atlas_crop_stats": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p],
+    # the admissibility band (csrc/admissibility.hip); canvas_host is a host pointer
+    "sn2_admissibility_ws_words": [c_longlong, POINTER(ctypes.c_size_t)],
+    "sn2_mosaic_admissibility": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sn2_atlas_admissibility": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     # the per-point scores of a parcel cloud (csrc/points.hip)
     "sn2_points_merge": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_double,
                          c_void_p, c_void_p, c_long, c_void_p],

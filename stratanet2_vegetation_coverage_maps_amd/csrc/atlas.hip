@@ -7,26 +7,14 @@
 #include <cmath>
 #include <cstring>
 
+#include "atlas_table.h"
 #include "common.h"
 #include "mosaic_rules.h"
 
 namespace {
-constexpr int COLS = SN2_ATLAS_CANVAS_COLS;
+constexpr int COLS = ATLAS_COLS;
 constexpr int SEG = SN2_ATLAS_SEG_COLS;
 constexpr int FIN_WORDS = SN2_ATLAS_FINALIZE_CANVAS_WORDS;
-
-// the last row r of [0, n) with table[r * stride + col] <= blk (rows are non-decreasing in that column, row 0 holds 0).
-// Every argument is uniform over the workgroup: the loads are scalar.
-template <typename T>
-__device__ __forceinline__ int last_row_at_or_below(const T* __restrict__ table, int stride, int col, int n, long long blk) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((long long)table[(size_t)mid * stride + col] <= blk) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 // ---- merge: grid (workgroups of all runs, 3 bands); a workgroup owns a 4 x 64 pixel tile of its run's window ----------------
 __global__ __launch_bounds__(256) void atlas_merge_kernel(const float* __restrict__ rasters, const float* __restrict__ weights,
@@ -130,52 +118,6 @@ __global__ __launch_bounds__(CROP_T) void atlas_crop_fold_kernel(const double* _
     mosaic_crop_fold(psum + first, pcnt + first, C, (int)(cv[COLS + 4] - cv[4]), mean + (size_t)k * C, count + (size_t)k * C);
 }
 
-long long bits_of(double v) {
-    long long b;
-    std::memcpy(&b, &v, 8);
-    return b;
-}
-double double_of(long long b) {
-    double v;
-    std::memcpy(&v, &b, 8);
-    return v;
-}
-
-// row k of the table from the row before it; SN2_EINVAL / SN2_ELIMIT as the entry points answer them
-int canvas_row(long long H, long long W, double x_min, double y_max, const long long* prev, long long* row) {
-    if (H <= 0 || W <= 0 || H > 0x7fffffffLL || W > 0x7fffffffLL) return SN2_EINVAL;
-    if (!std::isfinite(x_min) || !std::isfinite(y_max)) return SN2_EINVAL;
-    if (H * W >= (1LL << 31)) return SN2_ELIMIT;
-    row[0] = prev[0];
-    row[1] = H;
-    row[2] = W;
-    row[3] = prev[3];
-    row[4] = prev[4];
-    row[5] = bits_of(x_min);
-    row[6] = bits_of(y_max);
-    row[7] = 0;
-    row[COLS + 0] = prev[0] + H * W;
-    row[COLS + 3] = prev[3] + (long long)SN2_ATLAS_FINALIZE_BLOCKS(H, W);
-    row[COLS + 4] = prev[4] + (long long)SN2_MOSAIC_CROP_BLOCKS(H, W);
-    return 0;
-}
-
-// a host table is taken only if it is what sn2_atlas_canvas_table writes: the kernels index the arenas by it
-int check_table(int K, const long long* t) {
-    if (!t || K <= 0) return SN2_EINVAL;
-    if (t[0] != 0 || t[3] != 0 || t[4] != 0) return SN2_EINVAL;
-    long long want[2 * COLS];
-    for (int k = 0; k < K; ++k) {
-        const long long* r = t + (size_t)k * COLS;
-        const int rc = canvas_row(r[1], r[2], double_of(r[5]), double_of(r[6]), r, want);
-        if (rc) return rc;
-        if (r[7] != 0 || r[COLS + 0] != want[COLS + 0] || r[COLS + 3] != want[COLS + 3] || r[COLS + 4] != want[COLS + 4]) return SN2_EINVAL;
-        if (r[COLS + 3] > 0x7fffffffLL || r[COLS + 4] > 0x7fffffffLL) return SN2_ELIMIT;     // a grid of at most 2^31 - 1 workgroups
-    }
-    const long long* last = t + (size_t)K * COLS;
-    if (last[1] != 0 || last[2] != 0 || last[5] != 0 || last[6] != 0 || last[7] != 0) return SN2_EINVAL;
-    return 0;
-}
 }  // namespace
 
 extern "C" int sn2_atlas_canvas_table(int K, const int* H, const int* W, const double* x_min, const double* y_max, long long* table) {
@@ -184,7 +126,7 @@ extern "C" int sn2_atlas_canvas_table(int K, const int* H, const int* W, const d
     for (int k = 0; k < K; ++k) {
         long long* r = table + (size_t)k * COLS;
         long long row[2 * COLS] = {0};
-        const int rc = canvas_row(H[k], W[k], x_min ? x_min[k] : 0.0, y_max ? y_max[k] : 0.0, r, row);
+        const int rc = atlas_canvas_row(H[k], W[k], x_min ? x_min[k] : 0.0, y_max ? y_max[k] : 0.0, r, row);
         if (rc) return rc;
         std::memcpy(r, row, sizeof(long long) * COLS);
         r[COLS + 0] = row[COLS + 0];
@@ -206,7 +148,7 @@ extern "C" int sn2_atlas_merge(const float* rasters, const float* weights, const
                                int S, float* mean, float* wsum, void* stream) {
     if (!rasters || !weights || !place || !canvas_host || !canvas_dev || !seg_host || !seg_dev || !mean || !wsum) return SN2_EINVAL;
     if (B <= 0 || D <= 0 || K <= 0 || S <= 0 || S > B) return SN2_EINVAL;
-    const int rc = check_table(K, canvas_host);
+    const int rc = atlas_check_table(K, canvas_host);
     if (rc) return rc;
     // the runs: canvases ascending, plots [0, B) cut in order, every window inside its canvas, the workgroup prefix as stated
     long long wg = 0;
@@ -233,7 +175,7 @@ extern "C" int sn2_atlas_finalize(const float* mean, const float* wsum, int K, c
                                   const long long* canvas_dev, void* ws, float* thr, float* bands, void* stream) {
     if (!mean || !wsum || !canvas_host || !canvas_dev || !ws || !thr || !bands || K <= 0) return SN2_EINVAL;
     if (((uintptr_t)ws & 7) != 0) return SN2_EINVAL;
-    const int rc = check_table(K, canvas_host);
+    const int rc = atlas_check_table(K, canvas_host);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)canvas_host[(size_t)K * COLS + 3];
@@ -259,7 +201,7 @@ extern "C" int sn2_atlas_crop_stats(float* bands, int C, int K, const long long*
         limit = limit || E > SN2_MOSAIC_CROP_MAX_EDGES;
     }
     if ((edge_start_host[K] == 0) != (edges == nullptr)) return SN2_EINVAL;
-    const int rc = check_table(K, canvas_host);
+    const int rc = atlas_check_table(K, canvas_host);
     if (rc) return rc;
     if (limit) return SN2_ELIMIT;
     hipStream_t st = (hipStream_t)stream;

@@ -1931,6 +1931,58 @@ def atlas_crop_stats(bands, C: int, table: AtlasTable, pix: float, edges=None, o
     return mean, count
 
 
+# ---- the admissibility band (include/strata_hip.h, "Admissibility band"; csrc/admissibility.hip) --------------------------------
+def admissibility_ws_words(pixels: int) -> int:
+    """SN2_ADM_WS_WORDS of include/strata_hip.h (32-bit words) for a canvas, or an atlas, of `pixels` pixels."""
+    words = ctypes.c_size_t()
+    check(_lib.load().sn2_admissibility_ws_words(int(pixels), ctypes.byref(words)), "sn2_admissibility_ws_words")
+    return int(words.value)
+
+
+def _sieve_size(sieve_size) -> int:
+    if isinstance(sieve_size, bool) or int(sieve_size) != sieve_size:
+        raise ValueError(f"sieve_size: expected an integer >= 0, got {sieve_size!r}")
+    return int(sieve_size)
+
+
+def mosaic_admissibility(bands5: torch.Tensor, sieve_size: int, out=None):
+    """include/strata_hip.h: sn2_mosaic_admissibility.  bands5 (5,H,W) fp32 = [Vb, Vm_soft, Vh, Vm_hard, weights] as
+    `mosaic_finalize` leaves them, BEFORE any crop -> (bands6 (6,H,W) = [Vb, Vm_soft, Vh, Vm_hard, Adm, weights], stats (4) int64 =
+    regions, regions smaller than sieve_size, sieved pixels, valid inaccessible pixels), both on the device.  The rule is the
+    header's -- ours, not a pinned reference output.  sieve_size has NO default: 5 is the reading by the reference's comment
+    ("Eliminate zones < 5 pixels"), 0 the reading by its call as written (the mask excludes the valid pixels: nothing is sieved).
+    out: a (bands6, stats) pair of device tensors to write into.  A few launches on the current stream, no read-back; the same
+    input gives the same bytes."""
+    _chk(bands5, F32, None, "bands5")
+    if bands5.dim() != 3 or bands5.shape[0] != 5:
+        raise ValueError(f"bands5: expected (5,H,W), got {tuple(bands5.shape)}")
+    _, H, W = bands5.shape
+    s, dev = _sieve_size(sieve_size), bands5.device
+    ws = torch.empty(admissibility_ws_words(H * W) // 2, dtype=F64, device=dev)
+    if out is None:
+        bands6, stats = torch.empty(6, H, W, dtype=F32, device=dev), torch.empty(4, dtype=I64, device=dev)
+    else:
+        bands6, stats = _chk(out[0], F32, (6, H, W), "out[0]"), _chk(out[1], I64, (4,), "out[1]")
+    _call("sn2_mosaic_admissibility", _ptr(bands5), H, W, s, _ptr(ws), _ptr(bands6), _ptr(stats), _stream())
+    return bands6, stats
+
+
+def atlas_admissibility(bands5, table: AtlasTable, sieve_size: int, out=None):
+    """include/strata_hip.h: sn2_atlas_admissibility.  bands5: the (5 pixels,) arena of `atlas_finalize` -> (bands6: the
+    (6 pixels,) arena, canvas k's (6,H_k,W_k) = `table.view(bands6, 6, k)`; stats (K,4) int64), on the device: canvas by canvas
+    the bytes `mosaic_admissibility` gives on that canvas's view.  out: a (bands6, stats) pair to write into."""
+    _arena(bands5, 5, table, "bands5")
+    s, dev, K = _sieve_size(sieve_size), bands5.device, table.K
+    ws = torch.empty(admissibility_ws_words(table.pixels) // 2, dtype=F64, device=dev)
+    if out is None:
+        bands6, stats = torch.empty(6 * table.pixels, dtype=F32, device=dev), torch.empty(K, 4, dtype=I64, device=dev)
+    else:
+        bands6, stats = _arena(out[0], 6, table, "out[0]"), _chk(out[1], I64, (K, 4), "out[1]")
+    _call("sn2_atlas_admissibility", _ptr(bands5), K, table.host.ctypes.data, _ptr(table.dev), s, _ptr(ws), _ptr(bands6), _ptr(stats),
+          _stream())
+    return bands6, stats
+
+
 # ---- the per-point scores of a parcel cloud (include/strata_hip.h, "Per-point scores"; csrc/points.hip) -------------------------
 POINTS_ACC_WORDS = _lib.SN2_POINTS_ACC_WORDS
 

@@ -1,6 +1,7 @@
 """Parcel inference on the device -- counterpart of the reference loop `predict.py:96-141` +
 `inference/predict_utils.py:94-116` + the raster merge of `inference/geotiff_raster.py`, without the GIS file I/O
-(GDAL / rasterio / shapefile are out of scope: DESIGN.md section 7).
+(GDAL / rasterio / shapefile are out of scope: DESIGN.md section 7).  The admissibility band and PRED_ADM are built on the
+device by a stated rule of this project's, on request: `finalize(admissibility=s)`, `report(..., admissibility=s)`.
 
     per batch of plots:  eval forward -> (B*N,4) coverages -> fixed-grid max rasters (B,3,D,D)   [project_to_2d_rasters]
                          -> radial weight band                                                  [add_weights_band_to_rasters]
@@ -11,6 +12,7 @@ Pixel placement follows `get_geotransform` (geotiff_raster.py:46-61): a plot's t
 (center_x - diam_meters//2, center_y + diam_meters//2) and a pixel is diam_meters/diam_pix metres wide.
 """
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -69,14 +71,18 @@ class ParcelMosaic:
         first of the three identical weight layers)."""
         return torch.cat([self.mean, self.wsum[:1]], 0)
 
-    def finalize(self):
-        """`finalize_merged_raster` (geotiff_raster.py:262-285) without its last, GIS step (the admissibility band needs
-        rasterio sieve / shapely buffers): (5,H,W) = [Vb, Vm_soft, Vh, Vm_hard, weights] and the hard-medium-vegetation
-        threshold that `insert_hard_med_veg_raster_band` (:119-144) searches for."""
+    def finalize(self, admissibility=None):
+        """`finalize_merged_raster` (geotiff_raster.py:262-285): (5,H,W) = [Vb, Vm_soft, Vh, Vm_hard, weights] and the
+        hard-medium-vegetation threshold that `insert_hard_med_veg_raster_band` (:119-144) searches for.
+        admissibility: None (the default) stops there, before the reference's last, GIS step.  An integer s >= 0 adds that step
+        by this project's stated rule (`ADMISSIBILITY` below): (6,H,W) = [Vb, Vm_soft, Vh, Vm_hard, Adm, weights], the reference's
+        band order, with the sieve size s."""
         out, thr = ops.mosaic_finalize(self.mean.contiguous(), self.wsum[0].contiguous())
+        if admissibility is not None:
+            out, _ = ops.mosaic_admissibility(out, admissibility)
         return out, thr
 
-    def report(self, rings=None) -> "ParcelReport":
+    def report(self, rings=None, admissibility=None) -> "ParcelReport":
         """`finalize()`, then the crop of `crop_merged_raster` (geotiff_raster.py:238-253) on its (5,H,W) output in place --
         every pixel whose centre is not inside the parcel polygon becomes NaN --, then the band-wise means of the cropped
         mosaic that `get_parcel_predicted_values` (predict_utils.py:124-146) writes into the shapefile.  rings: every ring of
@@ -85,29 +91,49 @@ class ParcelMosaic:
         sn2_mosaic_crop_stats); None: no crop, the means of the whole mosaic.  Everything stays on the device but ONE
         device-to-host read of the threshold, the means and the counts together.
 
-        There is no PRED_ADM: the admissibility band (`insert_admissibility_raster`) is rasterio's `sieve` / `shapes`, a
-        shapely negative buffer and `geometry_mask`, whose rule turns on ties that cannot be pinned without those libraries.
+        admissibility: None (the default): five bands, the means of REPORT_BANDS, no PRED_ADM.  An integer s >= 0: the
+        admissibility band is inserted before the crop, as the reference does (`ADMISSIBILITY` below: the rule is ours, s and the
+        1.5 px tie are readings, not pinned facts); the report then has six bands, the means of REPORT_BANDS_ADM -- PRED_ADM among
+        them -- and `admissibility_stats`, still with the ONE read.
         Where it differs from the reference: the reference sends the fp32-cast coordinates of the outside pixels back through
         `rowcol` (geotiff_raster.py:244-251), which at Lambert-93 magnitudes (an fp32 step of 0.5 m) masks a neighbouring
         pixel now and then -- here the pixel that was tested is masked; and the means are fp64 sums, not numpy's fp32
         pairwise `nanmean`."""
-        C = 5
-        pack = torch.empty(1 + 2 * C, dtype=torch.int64, device=self.mean.device)     # threshold + index | means | counts
-        thr, means, counts = pack[:1].view(torch.float32), pack[1:1 + C].view(torch.float64), pack[1 + C:]
+        adm = admissibility is not None
+        C = 6 if adm else 5
+        # threshold + index | means | counts | the admissibility statistics
+        pack = torch.empty(1 + 2 * C + (4 if adm else 0), dtype=torch.int64, device=self.mean.device)
+        thr, means, counts = pack[:1].view(torch.float32), pack[1:1 + C].view(torch.float64), pack[1 + C:1 + 2 * C]
         bands, _ = ops.mosaic_finalize(self.mean.contiguous(), self.wsum[0].contiguous(), thr=thr)
+        if adm:
+            six = torch.empty((6,) + tuple(bands.shape[1:]), dtype=torch.float32, device=bands.device)
+            bands, _ = ops.mosaic_admissibility(bands, admissibility, out=(six, pack[1 + 2 * C:]))
         edges = None
         if rings is not None:
             from .parcel import polygon_edges
             edges = polygon_edges(rings)
         ops.mosaic_crop_stats(bands, self.x_min, self.y_max, self.pix, edges, out=(means, counts))
         host = pack.cpu().numpy()                                                      # the one read
-        m, n = host[1:1 + C].view(np.float64).copy(), host[1 + C:].copy()
+        m, n = host[1:1 + C].view(np.float64).copy(), host[1 + C:1 + 2 * C].copy()
+        names = REPORT_BANDS_ADM if adm else REPORT_BANDS
         return ParcelReport(bands, float(host[:1].view(np.float32)[0]),
-                            {k: float(m[i]) for i, k in enumerate(REPORT_BANDS)}, {k: int(n[i]) for i, k in enumerate(REPORT_BANDS)},
-                            m, n)
+                            {k: float(m[i]) for i, k in enumerate(names)}, {k: int(n[i]) for i, k in enumerate(names)},
+                            m, n, C, host[1 + 2 * C:].copy() if adm else None)
 
 
 REPORT_BANDS = ("PRED_BASSE", "PRED_INTER", "PRED_HAUTE", "hard_med")          # bands 0..3 of `finalize()`; band 4 = weights
+# bands 0..4 of `finalize(admissibility=s)`; band 5 = weights.  The four PRED_ names are the reference's shapefile fields
+REPORT_BANDS_ADM = ("PRED_BASSE", "PRED_INTER", "PRED_HAUTE", "hard_med", "PRED_ADM")
+
+ADMISSIBILITY = """The admissibility band (include/strata_hip.h, "Admissibility band"; DESIGN.md section 6m) restates
+`insert_admissibility_raster` (geotiff_raster.py:149-196) on the pixel grid: sieve the hard medium-vegetation band, call a pixel
+inaccessible when everything within 1.5 px of its centre is hard medium vegetation (or outside the mosaic's data), and give every
+other pixel max(Vb, Vm_soft).  The reference does this with rasterio `sieve` / `shapes`, a shapely buffer of -1.5 and
+`geometry_mask`, which cannot be run beside this package, so the rule is OURS and two of its choices are readings, not pinned facts:
+  the sieve size s -- 5 by the reference's comment ("Eliminate zones < 5 pixels"), 0 by its call as written (the mask it passes
+      excludes the valid pixels, so nothing inside the parcel is sieved): s is an explicit argument without a default;
+  the tie -- a pixel centre exactly 1.5 px from a pixel that is not hard medium vegetation (two columns or two rows away) lies ON
+      the buffered outline; we count it as inaccessible (csrc/admissibility_rules.h: adm_offset_tested)."""
 
 
 @dataclass
@@ -115,13 +141,18 @@ class ParcelReport:
     """`ParcelMosaic.report`: bands (5,H,W) on the device = [Vb, Vm_soft, Vh, Vm_hard, weights], NaN outside the parcel polygon
     (and wherever no plot has data); threshold of the hard medium-vegetation band; means / counts: per name of REPORT_BANDS the
     mean over, and the number of, the band's pixels that are not NaN; band_means (5) fp64 / band_counts (5) int64: the same for
-    all five bands in order."""
+    all five bands in order.  With `report(..., admissibility=s)`: n_bands = 6, bands (6,H,W) = [Vb, Vm_soft, Vh, Vm_hard, Adm,
+    weights], the names are REPORT_BANDS_ADM -- means["PRED_ADM"] is the mean of band 4 over its pixels that are not NaN after
+    the crop --, band_means / band_counts have six entries and admissibility_stats (4) int64 = the uncropped canvas's regions,
+    regions smaller than s, sieved pixels and inaccessible pixels."""
     bands: torch.Tensor
     threshold: float
     means: dict
     counts: dict
     band_means: np.ndarray
     band_counts: np.ndarray
+    n_bands: int = 5
+    admissibility_stats: Optional[np.ndarray] = None
 
 
 @torch.no_grad()
@@ -285,19 +316,29 @@ class MosaicAtlas:
             return None
         return self.table.view(self.mean, 3, k), self.table.view(self.wsum, 3, k)
 
-    def finalize(self):
-        """`ParcelMosaic.finalize` of every canvas at once: (the (5,H_k,W_k) band arena, thr (K,2))."""
-        return ops.atlas_finalize(self.mean, self.wsum, self.table)
+    def finalize(self, admissibility=None):
+        """`ParcelMosaic.finalize` of every canvas at once: (the (5,H_k,W_k) band arena, thr (K,2)); with an integer
+        admissibility = s the (6,H_k,W_k) arena, the admissibility band inserted canvas by canvas."""
+        bands, thr = ops.atlas_finalize(self.mean, self.wsum, self.table)
+        if admissibility is not None:
+            bands, _ = ops.atlas_admissibility(bands, self.table, admissibility)
+        return bands, thr
 
-    def report(self, shapes=None) -> "AtlasReport":
+    def report(self, shapes=None, admissibility=None) -> "AtlasReport":
         """`ParcelMosaic.report` of all K parcels: one finalisation, one crop and one statistics pass over the atlas, and ONE
         device-to-host read of the K thresholds, means and counts together.  shapes: None (no crop), or per parcel the rings of
-        its polygon or None."""
-        C, K = 5, self.K
-        pack = torch.empty(K + 2 * K * C, dtype=torch.int64, device=self.mean.device)     # thresholds + indices | means | counts
+        its polygon or None.  admissibility: as `ParcelMosaic.report` takes it -- None: five bands; an integer s >= 0: six, the
+        admissibility band inserted in every canvas before the crop, its statistics in the same read."""
+        adm = admissibility is not None
+        C, K = (6 if adm else 5), self.K
+        # thresholds + indices | means | counts | the admissibility statistics
+        pack = torch.empty(K + 2 * K * C + (4 * K if adm else 0), dtype=torch.int64, device=self.mean.device)
         thr = pack[:K].view(torch.float32).view(K, 2)
-        means, counts = pack[K:K + K * C].view(torch.float64).view(K, C), pack[K + K * C:].view(K, C)
+        means, counts = pack[K:K + K * C].view(torch.float64).view(K, C), pack[K + K * C:K + 2 * K * C].view(K, C)
         bands, _ = ops.atlas_finalize(self.mean, self.wsum, self.table, thr=thr)
+        if adm:
+            six = torch.empty(6 * self.table.pixels, dtype=torch.float32, device=bands.device)
+            bands, _ = ops.atlas_admissibility(bands, self.table, admissibility, out=(six, pack[K + 2 * K * C:].view(K, 4)))
         edges = None
         if shapes is not None:
             from .parcel import polygon_edges
@@ -308,29 +349,35 @@ class MosaicAtlas:
         host = pack.cpu().numpy()                                                          # the one read
         thresholds = host[:K].view(np.float32).reshape(K, 2)[:, 0].astype(np.float64)
         thresholds[np.asarray(self.empty, dtype=bool)] = np.nan
-        return AtlasReport(thresholds, host[K:K + K * C].view(np.float64).reshape(K, C).copy(), host[K + K * C:].reshape(K, C).copy(),
-                           bands, self.table, list(self.empty))
+        return AtlasReport(thresholds, host[K:K + K * C].view(np.float64).reshape(K, C).copy(),
+                           host[K + K * C:K + 2 * K * C].reshape(K, C).copy(), bands, self.table, list(self.empty), C,
+                           host[K + 2 * K * C:].reshape(K, 4).copy() if adm else None)
 
 
 @dataclass
 class AtlasReport:
     """`MosaicAtlas.report`: thresholds (K) fp64, band_means (K,5) fp64 and band_counts (K,5) int64 on the host, the cropped band
     arena on the device.  bands(k): parcel k's (5,H,W) view; parcel(k): its `ParcelReport`.  A parcel without plots has None
-    bands, a NaN threshold, NaN means and zero counts."""
+    bands, a NaN threshold, NaN means and zero counts.  With `report(..., admissibility=s)`: n_bands = 6 -- six bands per canvas,
+    six columns of means and counts -- and admissibility_stats (K,4) int64 (zeros for a parcel without plots)."""
     thresholds: np.ndarray
     band_means: np.ndarray
     band_counts: np.ndarray
     band_arena: torch.Tensor
     table: object
     empty: list
+    n_bands: int = 5
+    admissibility_stats: Optional[np.ndarray] = None
 
     def __len__(self):
         return len(self.thresholds)
 
     def bands(self, k: int):
-        return None if self.empty[k] else self.table.view(self.band_arena, 5, k)
+        return None if self.empty[k] else self.table.view(self.band_arena, self.n_bands, k)
 
     def parcel(self, k: int) -> ParcelReport:
         m, n = self.band_means[k], self.band_counts[k]
-        return ParcelReport(self.bands(k), float(self.thresholds[k]), {b: float(m[i]) for i, b in enumerate(REPORT_BANDS)},
-                            {b: int(n[i]) for i, b in enumerate(REPORT_BANDS)}, m, n)
+        names = REPORT_BANDS_ADM if self.n_bands == 6 else REPORT_BANDS
+        return ParcelReport(self.bands(k), float(self.thresholds[k]), {b: float(m[i]) for i, b in enumerate(names)},
+                            {b: int(n[i]) for i, b in enumerate(names)}, m, n, self.n_bands,
+                            None if self.admissibility_stats is None else self.admissibility_stats[k])
