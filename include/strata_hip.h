@@ -701,7 +701,13 @@ int sn2_fp_bn_sums(const sn2_fp *p, const float *gamma, const float *beta, const
  * 0,2,3 (first point wins ties), bare soil = 1 - low-veg max, mean over occupied pixels.
  * cloud_xy: plot b's normalised x row at cloud_xy + b*plot_stride, y row at + b*plot_stride + N.
  * keys (B*D*D*3) u64 workspace; pix (B*N) int32 out (x_pix*D + y_pix, bit-exact); arg (B*D*D*3) int32 out;
- * nocc (B) int32 out; pred (B,4) out. */
+ * nocc (B) int32 out; pred (B,4) out.
+ * DOMAIN of the tie rule (every entry point that scatters coverages: this one, _pix, sn2_raster_project,
+ * sn2_projected_loss_forward, sn2_plot_losses): finite values, no NaN -- that is what "largest value, lowest point index
+ * among the points that attain it" is proven on (tests/test_gpu_projection_loss.py).  The maximum is taken on the key
+ * (ordered bits of the value << 32 | ~point), in which -0.0 orders BELOW +0.0 (torch_scatter's loop compares them equal and
+ * keeps the first of the two) and a NaN orders by its bit pattern.  The network's coverages are sigmoid outputs, so
+ * neither occurs there.  The ids are not range-checked: 0 <= pix < D*D is the caller's to keep. */
 int sn2_plot_project_forward(const float *pred_pointwise, const float *cloud_xy, long plot_stride, int B, int N,
                              int D, unsigned long long *keys, int *pix, int *arg, int *nocc, float *pred,
                              void *stream);
