@@ -944,6 +944,55 @@ int sn2_points_merge(const float *cov, const float *proba, const float *xyz, con
                      int *hits, long T, void *stream);
 int sn2_points_finalize(const long long *acc, const int *hits, long T, float *scores, float *weight, void *stream);
 
+/* ---- LAS point records (csrc/las.hip; the rule's functions: csrc/las_rules.h; host side las.py): the point-record block of a LAS
+ * file, as the file holds it, to the ten fp32 rows of the reference's load_las_file (utils/load_data.py:149-184).  The file's
+ * header stays on the host (las.read_header); `records` starts at the first record.
+ * The reference reads its files through laspy 1.x (`laspy.file.File`), which laspy 2 removed and which cannot be run beside this
+ * library.  So the LAYOUT below is OURS: a reading of the ASPRS LAS 1.0-1.4 specification, pinned by records typed out by hand
+ * (tests/test_las_host.py) and not by the reference's library.  The arithmetic of the `reference` mode is load_las_file's own.
+ *
+ * RECORD LAYOUT.  Little-endian, record stride L bytes (the header's "point data record length").
+ *     format   least L   fields beyond the base
+ *       0        20      base
+ *       1        28      + GPS time
+ *       2        26      + RGB at 20
+ *       3        34      + GPS time, RGB at 28
+ *       6        30      base
+ *       7        36      + RGB at 30
+ *       8        38      + RGB at 30, NIR at 36
+ *     4 / 5 / 9 / 10:  57 / 63 / 59 / 67, the waveform formats: their leading fields are those of 1 / 3 / 6 / 8.
+ *   X, Y, Z: int32 at bytes 0, 4, 8.  Intensity: uint16 at byte 12.  Red, green, blue, NIR: uint16 each.
+ *   Formats 0-5:  byte 14 = return number in bits 0-2, number of returns in bits 3-5; classification = byte 15.
+ *   Formats 6-10: byte 14 = return number in bits 0-3, number of returns in bits 4-7; classification = byte 16.
+ *   L may exceed the least length (extra bytes) and may be odd.
+ * ROWS.  out[r row_stride + col0 + i], r = 0..9, of record i, all fp32: x, y, z, red, green, blue, nir, intensity, return_num,
+ *   num_returns (the reference's order).  Colour rows the format does not have are written as 0.0f: four rows for formats 0, 1, 4,
+ *   6, 9, the nir row for 2, 3, 5, 7.  The integer fields convert exactly.
+ * COORDINATES, two modes.
+ *   SN2_LAS_COORDS_REFERENCE: (float)((double)((long long)X - X0) / 100.0), the division a correctly rounded fp64 quotient; raw0 =
+ *     X0, Y0, Z0 in raw integer units (host, 3 values; NULL = 0, 0, 0 = load_las_file: `las.X / 100`, then the cast of np.asarray).
+ *     The header's scale and offset are NOT used, exactly as the reference ignores them.
+ *   SN2_LAS_COORDS_HEADER: (float)((((double)X scale) + offset) - origin), each operation rounded to fp64 on its own (no fused
+ *     multiply-add); xform (host, 9 doubles) = scale xyz, offset xyz, origin xyz in metres.  With origin 0 this is laspy's `.x`.
+ *   raw0 / origin: fp32 has a step of 0.5 m at Lambert-93 northings; subtracting an origin BEFORE the rounding keeps centimetres.
+ * CLASSIFICATION (optional, NULL = not wanted): classification[col0 + i] = the classification byte as the record holds it (in
+ *   formats 0-5 with its three flag bits).  Nothing is filtered or compacted: a caller masks on the device.
+ * ONE launch on `stream`: no atomics, no synchronisation, nothing read back, safe to capture; the same bytes in give the same
+ * bytes out.  No load touches a byte at or beyond T L.  Records of at most 128 bytes are staged through LDS with 16-byte loads,
+ * 256 consecutive records per workgroup; longer ones are read field by field.
+ * ERRORS, before any launch: SN2_EINVAL on a NULL records / out, T <= 0, a compressed file (bit 7 or 6 of `format` set), a format
+ * above 10, L below the format's least length or above 65535, n_bytes < T L, records not 16-byte aligned, col0 < 0 or
+ * col0 + T > row_stride, an unknown mode, the header mode without xform, |raw0| > 2^52; SN2_ELIMIT on T >= 2^31.
+ * sn2_las_record_min_length: host-only, the table above, or SN2_EINVAL.  sn2_debug_las_form(1) sends every later call through the
+ * field-by-field form (measurements: scripts/bench_las.py), 0 restores the rule. */
+#define SN2_LAS_COORDS_REFERENCE 0
+#define SN2_LAS_COORDS_HEADER 1
+#define SN2_LAS_ROWS 10
+int sn2_las_record_min_length(int format);
+int sn2_las_decode(const void *records, size_t n_bytes, int format, int L, long T, int mode, const double *xform,
+                   const long long *raw0, float *out, long row_stride, long col0, unsigned char *classification, void *stream);
+int sn2_debug_las_form(int form);
+
 /* ---- loss block of the timed training step: learning/loss_functions.py:9-57 combined as learning/train.py:58-62,
  *   total = get_absolute_loss(pred, gt) + m * get_NLL_loss(proba, pdf_all) + e * get_entropy_loss(proba)
  * pred (B,4) fp32 plot-wise coverages, gt (B,4) fp64, proba (R,4) fp32 pointwise class probabilities, pdf (R,3) fp64 the

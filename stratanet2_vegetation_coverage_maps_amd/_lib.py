@@ -26,6 +26,7 @@ CONSTANTS = {
     "SN2_CV_SLICE_PLOTS": 1024, "SN2_CV_COLUMNS": 30, "SN2_CV_STATS_DOUBLES": 2 * 30 + 2 * 3 * 8 * 8 + 1, "SN2_CV_MAX_PLOTS": 1 << 24,
     "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8, "SN2_POINTS_ACC_WORDS": 9,
     "SN2_ADM_WS_HEAD_WORDS": 32, "SN2_ADM_WS_WORDS_PER_PIXEL": 6,
+    "SN2_LAS_COORDS_REFERENCE": 0, "SN2_LAS_COORDS_HEADER": 1, "SN2_LAS_ROWS": 10,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
@@ -244,6 +245,11 @@ SIGNATURES = {
     "sn2_points_merge": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_double,
                          c_void_p, c_void_p, c_long, c_void_p],
     "sn2_points_finalize": [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
+    # the LAS decoder (csrc/las.hip); xform and raw0 are host pointers
+    "sn2_las_record_min_length": [c_int],
+    "sn2_las_decode": [c_void_p, ctypes.c_size_t, c_int, c_int, c_long, c_int, POINTER(c_double), POINTER(c_longlong), c_void_p, c_long,
+                       c_long, c_void_p, c_void_p],
+    "sn2_debug_las_form": [c_int],
     "sn2_kde_lookup": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "sn2_kde_fit": [c_void_p, c_long, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_loss_forward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,

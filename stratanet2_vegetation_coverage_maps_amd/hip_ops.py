@@ -2033,6 +2033,48 @@ def points_finalize(acc, hits, out=None):
     return scores, weight
 
 
+# ---- the LAS decoder (include/strata_hip.h, "LAS point records"; csrc/las.hip) ---------------------------------------------------
+LAS_COORDS = {"reference": _lib.SN2_LAS_COORDS_REFERENCE, "header": _lib.SN2_LAS_COORDS_HEADER}
+
+
+def las_record_min_length(point_format: int) -> int:
+    """sn2_las_record_min_length: the least record length of a LAS point format (ValueError for a format the decoder refuses)."""
+    n = _lib.host_value("sn2_las_record_min_length", int(point_format))
+    if n <= 0:
+        raise ValueError(f"LAS point format {point_format}: not an uncompressed format 0..10")
+    return n
+
+
+def las_decode(raw, point_format: int, record_length: int, T: int, coords: str = "reference", xform=None, raw0=None, out=None,
+               col0: int = 0, classification=None):
+    """include/strata_hip.h: sn2_las_decode.  raw: uint8 device tensor that starts at the first record (16-byte aligned, at least
+    T * record_length bytes) -> out (10, >= col0 + T) fp32, columns col0 .. col0 + T written (a new (10,T) tensor when None).
+    coords "reference": raw0 = (X0, Y0, Z0) integers or None; "header": xform = 9 floats, scale xyz, offset xyz, origin xyz.
+    classification: a uint8 tensor of out's row length (column col0 + i written) or None.  One launch on the current stream."""
+    _chk(raw, torch.uint8, None, "raw")
+    if raw.dim() != 1:
+        raise ValueError(f"raw: expected a 1-D byte tensor, got {tuple(raw.shape)}")
+    if coords not in LAS_COORDS:
+        raise ValueError(f"coords: expected 'reference' or 'header', got {coords!r}")
+    T, col0 = int(T), int(col0)
+    if out is None:
+        out = torch.empty(_lib.SN2_LAS_ROWS, T, dtype=F32, device=raw.device)
+    row_stride = _chk_rows(out, F32, _lib.SN2_LAS_ROWS, col0 + T, "out", align=1)
+    if out.device != raw.device:
+        raise ValueError("out: must be on raw's device")
+    if classification is not None:
+        _chk(classification, torch.uint8, None, "classification")
+        if classification.dim() != 1 or classification.shape[0] < col0 + T or classification.device != raw.device:
+            raise ValueError(f"classification: expected (>= {col0 + T},) uint8 on raw's device")
+    if T == 0:
+        return out
+    xf = None if xform is None else (ctypes.c_double * 9)(*[float(v) for v in xform])
+    r0 = None if raw0 is None else (ctypes.c_longlong * 3)(*[int(v) for v in raw0])
+    _call("sn2_las_decode", _ptr(raw), raw.numel(), int(point_format), int(record_length), T, LAS_COORDS[coords], xf, r0, _ptr(out),
+          row_stride, col0, _ptr(classification), _stream())
+    return out
+
+
 LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS
 
 

@@ -408,6 +408,23 @@ class ParcelClouds:
         starts_dev, state = ops.pack_upload([starts, ops.parcels_bbox_identity(len(T))], dev)
         return cls(arena, starts[0].copy(), starts, starts_dev, state)
 
+    @classmethod
+    def from_arena(cls, arena: torch.Tensor, counts) -> "ParcelClouds":
+        """An arena that is already filled -- (10, sum counts) fp32 on the device, parcel k in the next counts[k] > 0 columns (e.g.
+        las.load_parcel_clouds decodes each file into its columns) -- with the bookkeeping of `from_clouds` and no concatenation:
+        the arena is taken as it is, not copied."""
+        T = np.asarray(counts, dtype=np.int64).reshape(-1)
+        if len(T) == 0 or (T <= 0).any():
+            raise ValueError("ParcelClouds: every parcel needs T > 0 points")
+        if T.sum() >= 2 ** 31:
+            raise ValueError("ParcelClouds: at most 2^31 - 1 points in all")
+        if (not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.float32 or not arena.is_contiguous()
+                or tuple(arena.shape) != (10, int(T.sum()))):
+            raise ValueError(f"ParcelClouds: expected a contiguous (10,{int(T.sum())}) fp32 device tensor")
+        starts = ops.parcels_bbox_starts(T)
+        starts_dev, state = ops.pack_upload([starts, ops.parcels_bbox_identity(len(T))], arena.device)
+        return cls(arena, starts[0].copy(), starts, starts_dev, state)
+
     def cloud(self, k: int) -> torch.Tensor:
         """parcel k's (10,T_k) view of the arena"""
         return self.arena[:, int(self.point_start[k]):int(self.point_start[k + 1])]
