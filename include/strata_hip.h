@@ -993,6 +993,64 @@ int sn2_las_decode(const void *records, size_t n_bytes, int format, int L, long 
                    const long long *raw0, float *out, long row_stride, long col0, unsigned char *classification, void *stream);
 int sn2_debug_las_form(int form);
 
+/* ---- Parcel cut (csrc/cut.hip; the rule's functions: csrc/cut_rules.h; host side parcel.cut_parcels, las.load_parcels): the points
+ * of a LAS tile cut into K parcel clouds by the parcels' polygons buffered by b metres -- what the reference's
+ * `parcelles_dataset_20m` holds as one file per parcel (b = 20, inference/prepare_utils.py:148).
+ *
+ * THE RULE, that of parcel.polygon_keep (numpy, fp64).  Point i has (px, py) = its fp32 x, y widened to fp64.  Parcel k has the edges
+ * (ax, ay, bx, by) in fp64 that parcel.polygon_edges lists: all rings, holes and further parts, closing edges included.
+ * b2 = b * b in fp64.  Point i belongs to parcel k iff
+ *   inside: the number of edges with (ay > py) != (by > py) and px < ax + ((py - ay) * (bx - ax)) / (by - ay) is odd (the
+ *           quotient evaluated only where the edge crosses), or
+ *   near:   for some edge, with dx = bx - ax, dy = by - ay, l2 = dx*dx + dy*dy, t = l2 > 0 ? ((px - ax)*dx + (py - ay)*dy) / l2 : 0
+ *           clamped to [0, 1], ex = (ax + t*dx) - px, ey = (ay + t*dy) - py:  ex*ex + ey*ey < b2  (strict).
+ * Every operation is rounded to fp64 on its own, in that association (no fused multiply-add): the boolean is numpy's, bit for bit.
+ * A lane stops at its first edge within b (the answer is an OR).  A NaN or infinite x or y belongs to no parcel (numpy's
+ * comparisons say so; the device gives such a point no grid cell).  A point in two parcels' buffers is copied into both.  With a
+ * classification (T) uint8 and a 256-bit drop set (8 words, bit c of word c / 32), a point whose class is in the set belongs to
+ * no parcel.  The buffer inherits polygon_keep's deviation from shapely (exact round joins, not 16 segments per quarter circle).
+ *
+ * CANDIDATE TABLE (sn2_cut_table), built on the host (hip_ops.CutTable), every array on the host AND on the device:
+ *   a uniform grid of GX x GY square cells as CSR: cell_start (GX GY + 1), cell_items (n_items) parcel ids, ascending inside a cell;
+ *   cell of a coordinate = floor((v - g0) * inv), the same fp64 expression on both sides.  The host lists parcel k in every cell
+ *   from cell(lo_k) to cell(hi_k) of its vertices' bounding box expanded by strictly more than b; the expression is monotonic, so a
+ *   point's cell list is a superset of the parcels that keep it.  The rule decides membership, the grid only prunes.
+ *   edge_start (K + 1) into edges (n_edges, 4) fp64.  T: the points of the cloud.  L: points per row (a wave walks one row).
+ * Before any launch every entry point checks the HOST copy (else SN2_EINVAL): K >= 1, T >= 1, b finite and >= 0, GX, GY >= 1, g0
+ * finite, inv finite and > 0, both starts begin at 0, never decrease and end at n_items / n_edges, every id in [0, K) and strictly
+ * ascending inside its cell, every edge coordinate finite (and at most 1e100 in magnitude: no product of the rule overflows), L a
+ * positive multiple of 64.  SN2_ELIMIT: T >= 2^31, more than 2^22 cells, 2^24 list entries, 2^26 edges or 2^28 (parcel, row)
+ * entries.  So no index a kernel derives from the table leaves its arrays.
+ *
+ * cloud (10, T) fp32, channel-major, contiguous (a ParcelClouds arena of tiles is one such cloud).
+ * sn2_cut_ws_words: host only -> the 32-bit words of sn2_cut_count's workspace (the scan's block sums + K rows counts).
+ * sn2_cut_count: clear + ONE pass (a wave per row of L points, 64 at a time; the wave visits its lanes' candidate parcels in
+ *   ascending id and the lanes that have parcel m as a candidate run m's edges together, so the edge addresses are wave-uniform;
+ *   the ballot's popcount goes to entry m rows + row) + one scan + a gather: prefix (K rows + 1) int32, parcel_start (K + 2) int64 =
+ *   the first slot of every parcel, the total, and the scan's own total word.  ws 8-byte aligned.
+ * sn2_cut_fill: ONE launch over the same rows in the same order.  parcel_base (K) int32, INT_MIN = parcel skipped; slot =
+ *   parcel_base[m] + the entry's cursor + rank (mbcnt over the ballot); the cursor is advanced by the row's own wave only.  Ten rows
+ *   are copied per hit into out (10, sum_n) and point_index[slot] = i.  A parcel's points are in ascending tile index: byte for
+ *   byte cloud[:, mask_k].  Integer atomics on the row's own cursor only, no floating-point atomics: the same input gives the same
+ *   bytes.  prefix is consumed.  sum_n >= 2^31: SN2_ELIMIT.
+ * classification and drop are both NULL or both given (drop: host, 8 words). */
+#define SN2_CUT_MAX_CELLS (1 << 22)
+#define SN2_CUT_MAX_ITEMS (1 << 24)
+typedef struct {
+    int K, GX, GY, L;
+    long long T, n_items, n_edges;
+    double gx0, gy0, inv, buffer;
+    const int *cell_start, *cell_items, *edge_start;                    /* host copies: what the checks read */
+    const double *edges;
+    const int *cell_start_dev, *cell_items_dev, *edge_start_dev;        /* device copies: what the kernels read */
+    const double *edges_dev;
+} sn2_cut_table;
+int sn2_cut_ws_words(const sn2_cut_table *table, size_t *words);
+int sn2_cut_count(const float *cloud, const unsigned char *classification, const unsigned *drop, const sn2_cut_table *table, int *ws,
+                  size_t ws_words, int *prefix, long long *parcel_start, void *stream);
+int sn2_cut_fill(const float *cloud, const unsigned char *classification, const unsigned *drop, const sn2_cut_table *table,
+                 int *prefix, const int *parcel_base, long sum_n, float *out, int *point_index, void *stream);
+
 /* ---- loss block of the timed training step: learning/loss_functions.py:9-57 combined as learning/train.py:58-62,
  *   total = get_absolute_loss(pred, gt) + m * get_NLL_loss(proba, pdf_all) + e * get_entropy_loss(proba)
  * pred (B,4) fp32 plot-wise coverages, gt (B,4) fp64, proba (R,4) fp32 pointwise class probabilities, pdf (R,3) fp64 the

@@ -26,7 +26,7 @@ CONSTANTS = {
     "SN2_CV_SLICE_PLOTS": 1024, "SN2_CV_COLUMNS": 30, "SN2_CV_STATS_DOUBLES": 2 * 30 + 2 * 3 * 8 * 8 + 1, "SN2_CV_MAX_PLOTS": 1 << 24,
     "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8, "SN2_POINTS_ACC_WORDS": 9,
     "SN2_ADM_WS_HEAD_WORDS": 32, "SN2_ADM_WS_WORDS_PER_PIXEL": 6,
-    "SN2_LAS_COORDS_REFERENCE": 0, "SN2_LAS_COORDS_HEADER": 1, "SN2_LAS_ROWS": 10,
+    "SN2_LAS_COORDS_REFERENCE": 0, "SN2_LAS_COORDS_HEADER": 1, "SN2_LAS_ROWS": 10, "SN2_CUT_MAX_CELLS": 1 << 22, "SN2_CUT_MAX_ITEMS": 1 << 24,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
@@ -132,6 +132,13 @@ class NetIO(Structure):  # sn2_net_io
     _fields_ = [("cloud", c_void_p), ("fps_start", c_void_p), ("fps_status", c_void_p), ("gl_xchg", c_void_p), ("gl_ctl", c_void_p),
                 ("stream_b", c_void_p), ("stream_c", c_void_p), ("stream_pack", c_void_p), ("ctx", c_void_p), ("flags", c_int),
                 ("training", c_int), ("fps_live", c_void_p), ("fps_live1", c_void_p)]
+
+
+class CutTable(Structure):  # sn2_cut_table
+    _fields_ = [("K", c_int), ("GX", c_int), ("GY", c_int), ("L", c_int), ("T", c_longlong), ("n_items", c_longlong),
+                ("n_edges", c_longlong), ("gx0", c_double), ("gy0", c_double), ("inv", c_double), ("buffer", c_double)] + [
+                    (n, c_void_p) for n in ("cell_start", "cell_items", "edge_start", "edges", "cell_start_dev", "cell_items_dev",
+                                            "edge_start_dev", "edges_dev")]
 
 
 # name -> argtypes; every entry point returns int (0 ok, >0 hipError_t, <0 argument error; the route predicates: 0 / 1)
@@ -250,6 +257,10 @@ SIGNATURES = {
     "sn2_las_decode": [c_void_p, ctypes.c_size_t, c_int, c_int, c_long, c_int, POINTER(c_double), POINTER(c_longlong), c_void_p, c_long,
                        c_long, c_void_p, c_void_p],
     "sn2_debug_las_form": [c_int],
+    # the parcel cut (csrc/cut.hip); drop is a host pointer, the table holds host and device pointers
+    "sn2_cut_ws_words": [POINTER(CutTable), POINTER(ctypes.c_size_t)],
+    "sn2_cut_count": [c_void_p, c_void_p, c_void_p, POINTER(CutTable), c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],
+    "sn2_cut_fill": [c_void_p, c_void_p, c_void_p, POINTER(CutTable), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
     "sn2_kde_lookup": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "sn2_kde_fit": [c_void_p, c_long, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_loss_forward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,

@@ -2075,6 +2075,171 @@ def las_decode(raw, point_format: int, record_length: int, T: int, coords: str =
     return out
 
 
+# ---- the parcel cut (include/strata_hip.h, "Parcel cut"; csrc/cut.hip) -------------------------------------------------------------
+CUT_ROW_POINTS = 2048         # points per wave of the count / fill passes (parcel.ROW_POINTS)
+CUT_MAX_TABLE = 1 << 26       # (parcel, row) entries of the count table before rows get longer (parcel.MAX_TABLE)
+CUT_CELL_SIDE = 32.0          # metres: the least cell side of the candidate grid
+
+
+def cut_boxes(edge_lists, buffer_m: float) -> np.ndarray:
+    """(K,4) fp64 = x_lo, y_lo, x_hi, y_hi: the bounding box of every parcel's vertices expanded by STRICTLY more than buffer_m --
+    by buffer_m + 2^-40 (A + buffer_m + 1) with A the largest |coordinate| of the set, 4096 ulps of the largest quantity the rule
+    or the differences `min - reach`, `max + reach` round.  A point the rule keeps lies inside."""
+    b = float(buffer_m)
+    lo = np.array([[e[:, 0].min(), e[:, 1].min()] for e in edge_lists], dtype=np.float64).reshape(-1, 2)
+    hi = np.array([[e[:, 0].max(), e[:, 1].max()] for e in edge_lists], dtype=np.float64).reshape(-1, 2)
+    amax = max(float(np.abs(lo).max()), float(np.abs(hi).max())) if len(lo) else 0.0
+    reach = b + 2.0 ** -40 * (amax + b + 1.0)
+    return np.concatenate([lo - reach, hi + reach], axis=1)
+
+
+def cut_cell(v, g0: float, inv: float):
+    """The cell of a coordinate along one axis, the kernels' floor((v - g0) * inv) in fp64 (monotonic in v)."""
+    return np.floor((np.asarray(v, dtype=np.float64) - np.float64(g0)) * np.float64(inv))
+
+
+class CutTable:
+    """The candidate table of sn2_cut_count / sn2_cut_fill for K parcels and a cloud of T points, built on the host.
+    edge_lists: per parcel its (E_k,4) fp64 edges (`parcel.polygon_edges`); buffer_m: b.  A uniform grid over the union of the
+    expanded boxes (`cut_boxes`), parcel k listed in every cell from cell(lo_k) to cell(hi_k), ids ascending inside a cell; the
+    cell side starts at max(cell_side, extent / 2048) and doubles until the grid has at most SN2_CUT_MAX_CELLS cells and
+    SN2_CUT_MAX_ITEMS list entries (StrataHipError SN2_ELIMIT where one cell per axis still lists too many).  L: points per row,
+    max(2048, ceil(K T / max_table) rounded up to 64).  `host`: the numpy arrays, `dev`: their device copies once `upload` ran;
+    `struct()`: the sn2_cut_table.  The library checks the table before every launch; `ws_words` asks it once here."""
+
+    def __init__(self, edge_lists, T: int, buffer_m: float, max_table: int = CUT_MAX_TABLE, cell_side: float = CUT_CELL_SIDE):
+        edge_lists = [np.ascontiguousarray(np.asarray(e, dtype=np.float64).reshape(-1, 4)) for e in edge_lists]
+        K, T, b = len(edge_lists), int(T), float(buffer_m)
+        if K < 1 or any(len(e) == 0 for e in edge_lists):
+            raise ValueError("CutTable: at least one parcel, and every parcel needs edges")
+        if T < 1:
+            raise ValueError("CutTable: the cloud holds no point")
+        if not (math.isfinite(b) and b >= 0.0):
+            raise ValueError(f"CutTable: buffer_m must be finite and >= 0, got {buffer_m}")
+        if int(max_table) < 1 or not float(cell_side) > 0.0:
+            raise ValueError("CutTable: max_table and cell_side must be positive")
+        edges = np.concatenate(edge_lists, axis=0)
+        if not np.isfinite(edges).all():
+            raise ValueError("CutTable: a polygon vertex is not finite")
+        boxes = cut_boxes(edge_lists, b)
+        gx0, gy0 = float(boxes[:, 0].min()), float(boxes[:, 1].min())
+        extent = max(float(boxes[:, 2].max()) - gx0, float(boxes[:, 3].max()) - gy0)
+        side = max(float(cell_side), extent / 2048)
+        while True:
+            inv = 1.0 / side
+            ix0, ix1 = cut_cell(boxes[:, 0], gx0, inv).astype(np.int64), cut_cell(boxes[:, 2], gx0, inv).astype(np.int64)
+            iy0, iy1 = cut_cell(boxes[:, 1], gy0, inv).astype(np.int64), cut_cell(boxes[:, 3], gy0, inv).astype(np.int64)
+            GX, GY = int(ix1.max()) + 1, int(iy1.max()) + 1
+            per = (ix1 - ix0 + 1) * (iy1 - iy0 + 1)
+            if GX * GY <= _lib.SN2_CUT_MAX_CELLS and int(per.sum()) <= _lib.SN2_CUT_MAX_ITEMS:
+                break
+            if GX == 1 and GY == 1:
+                raise StrataHipError(f"CutTable failed: SN2_ELIMIT {_lib.SN2_ELIMIT} ({K} parcels in one cell)")
+            side *= 2.0
+        # parcel k's cells, parcel after parcel; the stable sort by cell keeps the ids ascending inside a cell
+        ids = np.repeat(np.arange(K, dtype=np.int64), per)
+        first = np.concatenate([[0], np.cumsum(per)])[:-1]
+        j = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(first, per)
+        w = np.repeat(ix1 - ix0 + 1, per)
+        cell = (np.repeat(iy0, per) + j // w) * GX + np.repeat(ix0, per) + j % w
+        order = np.argsort(cell, kind="stable")
+        cell_start = np.zeros(GX * GY + 1, dtype=np.int64)
+        np.cumsum(np.bincount(cell, minlength=GX * GY), out=cell_start[1:])
+        edge_start = np.concatenate([[0], np.cumsum([len(e) for e in edge_lists])])
+        if edge_start[-1] >= 2 ** 31:
+            raise StrataHipError(f"CutTable failed: SN2_ELIMIT {_lib.SN2_ELIMIT} ({edge_start[-1]} edges)")
+        L = max(CUT_ROW_POINTS, (-(-(K * T) // int(max_table)) + 63) // 64 * 64)
+        if L >= 2 ** 31:
+            raise StrataHipError(f"CutTable failed: SN2_ELIMIT {_lib.SN2_ELIMIT} (row length {L})")
+        self.K, self.T, self.buffer, self.L, self.GX, self.GY = K, T, b, int(L), GX, GY
+        self.gx0, self.gy0, self.inv = gx0, gy0, inv
+        self.rows = -(-T // self.L)
+        self.boxes = boxes
+        self.host = [cell_start.astype(np.int32), ids[order].astype(np.int32), edge_start.astype(np.int32), np.ascontiguousarray(edges)]
+        self.dev = None
+        self.ws_words = self._ws_words()
+
+    def struct(self) -> "_lib.CutTable":
+        t = _lib.CutTable()
+        t.K, t.GX, t.GY, t.L, t.T = self.K, self.GX, self.GY, self.L, self.T
+        t.n_items, t.n_edges = len(self.host[1]), len(self.host[3])
+        t.gx0, t.gy0, t.inv, t.buffer = self.gx0, self.gy0, self.inv, self.buffer
+        t.cell_start, t.cell_items, t.edge_start, t.edges = (a.ctypes.data for a in self.host)
+        if self.dev is not None:
+            t.cell_start_dev, t.cell_items_dev, t.edge_start_dev, t.edges_dev = (_ptr(d) for d in self.dev)
+        return t
+
+    def _ws_words(self) -> int:
+        n = ctypes.c_size_t()
+        check(_lib.load().sn2_cut_ws_words(ctypes.byref(self.struct()), ctypes.byref(n)), "sn2_cut_ws_words")
+        return n.value
+
+    def upload(self, device):
+        """the four arrays to `device` in one copy"""
+        self.dev = pack_upload(self.host, device)
+        return self
+
+
+def cut_drop_words(drop_classes) -> np.ndarray:
+    """The 256-bit drop set of sn2_cut_count / _fill as 8 uint32 words: bit c of word c // 32 for every class c in 0..255."""
+    w = np.zeros(8, dtype=np.uint32)
+    for c in drop_classes:
+        if int(c) != c or not 0 <= int(c) <= 255:
+            raise ValueError(f"drop_classes: a LAS class is an integer in 0..255, got {c!r}")
+        w[int(c) >> 5] |= np.uint32(1 << (int(c) & 31))
+    return w
+
+
+def _chk_cut(cloud, table: CutTable, classification, drop):
+    _chk(cloud, F32, (10, table.T), "cloud")
+    if table.dev is None:
+        raise ValueError("table: not uploaded (CutTable.upload)")
+    for d, a, name in zip(table.dev, table.host, ("cell_start", "cell_items", "edge_start", "edges")):
+        _chk(d, torch.from_numpy(a).dtype, a.shape, f"table.{name}")
+        if d.device != cloud.device:
+            raise ValueError(f"table.{name}: must be on the cloud's device")
+    if (classification is None) != (drop is None):
+        raise ValueError("classification and drop: both or neither")
+    if classification is not None:
+        _chk(classification, torch.uint8, (table.T,), "classification")
+        if classification.device != cloud.device:
+            raise ValueError("classification: must be on the cloud's device")
+        drop = np.ascontiguousarray(drop, dtype=np.uint32)
+        if drop.shape != (8,):
+            raise ValueError("drop: expected 8 uint32 words (cut_drop_words)")
+    return drop
+
+
+def cut_count(cloud: torch.Tensor, table: CutTable, classification: Optional[torch.Tensor] = None, drop=None):
+    """include/strata_hip.h: sn2_cut_count.  cloud (10,T) f32; classification (T) u8 and drop (8 words, `cut_drop_words`) or neither
+    -> (prefix (K rows + 1) i32, parcel_start (K+1) i64 with the total last)."""
+    drop = _chk_cut(cloud, table, classification, drop)
+    dev = cloud.device
+    ws = torch.empty(table.ws_words + 4, dtype=I32, device=dev)
+    prefix = torch.empty(table.K * table.rows + 1, dtype=I32, device=dev)
+    starts = torch.empty(table.K + 2, dtype=I64, device=dev)               # parcel_start, then the scan's own total word
+    _call("sn2_cut_count", _ptr(cloud), _ptr(classification), None if drop is None else drop.ctypes.data, ctypes.byref(table.struct()),
+          _ptr(ws), table.ws_words, _ptr(prefix), _ptr(starts), _stream())
+    return prefix, starts[:table.K + 1]
+
+
+def cut_fill(cloud: torch.Tensor, table: CutTable, prefix: torch.Tensor, parcel_base: torch.Tensor, sum_n: int,
+             classification: Optional[torch.Tensor] = None, drop=None):
+    """include/strata_hip.h: sn2_cut_fill.  prefix: cut_count's (consumed); parcel_base (K) i32, INT_MIN = parcel skipped
+    -> out (10,sum_n) f32, point_index (sum_n) i32: the cloud's column of every column of out."""
+    drop = _chk_cut(cloud, table, classification, drop)
+    _chk(prefix, I32, (table.K * table.rows + 1,), "prefix")
+    _chk(parcel_base, I32, (table.K,), "parcel_base")
+    sum_n = int(sum_n)
+    if not 0 < sum_n < 2 ** 31:
+        raise ValueError(f"sum_n: expected 1 .. 2^31 - 1, got {sum_n}")
+    out = torch.empty(10, sum_n, dtype=F32, device=cloud.device)
+    pidx = torch.empty(sum_n, dtype=I32, device=cloud.device)
+    _call("sn2_cut_fill", _ptr(cloud), _ptr(classification), None if drop is None else drop.ctypes.data, ctypes.byref(table.struct()),
+          _ptr(prefix), _ptr(parcel_base), sum_n, _ptr(out), _ptr(pidx), _stream())
+    return out, pidx
+
+
 LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS
 
 

@@ -152,15 +152,18 @@ def load_plot(path, args, device=None, coords: str = "reference", origin=None):
     return cloud
 
 
-def load_parcel_clouds(paths, device=None, coords: str = "reference", origin=None):
+def load_parcel_clouds(paths, device=None, coords: str = "reference", origin=None, classification=False, headers=None):
     """K parcel files -> ParcelClouds: the K headers are read first, ONE (10, sum T) arena is allocated, and file k is decoded
     into the columns point_start[k] ..: one upload and one launch per file, the clouds' memory held once.  origin: one triple
-    for every file (so the parcels keep their relative positions) or None."""
+    for every file (so the parcels keep their relative positions) or None.  classification=True: (ParcelClouds, (sum T) uint8),
+    the class byte of every arena column.  headers: the files' `read_header` results where the caller already has them."""
     from .parcel import ParcelClouds
     paths = list(paths)
     if not paths:
         raise ValueError("load_parcel_clouds: no file")
-    heads = [read_header(p) for p in paths]
+    heads = [read_header(p) for p in paths] if headers is None else list(headers)
+    if len(heads) != len(paths):
+        raise ValueError("load_parcel_clouds: one header per file")
     counts = [h.n_points for h in heads]
     if min(counts) == 0:
         raise ValueError(f"load_parcel_clouds: {paths[counts.index(0)]} holds no point")
@@ -168,11 +171,54 @@ def load_parcel_clouds(paths, device=None, coords: str = "reference", origin=Non
         raise ValueError("load_parcel_clouds: at most 2^31 - 1 points in all")
     dev = _device(device)
     arena = torch.empty(10, sum(counts), dtype=torch.float32, device=dev)
+    cls = torch.empty(sum(counts), dtype=torch.uint8, device=dev) if classification else None
     pinned = torch.empty(max(h.n_bytes for h in heads), dtype=torch.uint8, pin_memory=True)
     col0 = 0
     for p, h in zip(paths, heads):
         raw, pinned = _upload_points(p, h, dev, pinned)
-        decode(raw, h, coords, origin, out=arena, col0=col0)
+        decode(raw, h, coords, origin, out=arena, col0=col0, classification=cls if classification else False)
         torch.cuda.current_stream(dev).synchronize()      # the next file overwrites the staging buffer
         col0 += h.n_points
-    return ParcelClouds.from_arena(arena, counts)
+    pc = ParcelClouds.from_arena(arena, counts)
+    return (pc, cls) if classification else pc
+
+
+def load_parcels(paths, shapes, buffer_m: float = 20, coords: str = "reference", origin=None, drop_classes=(), device=None):
+    """LAS tiles + K parcel polygons -> `parcel.ParcelCut`: `load_parcel_clouds(paths)` over the tiles, their classification byte
+    into one (T_all) buffer when drop_classes is given, then `parcel.cut_parcels` over the arena -- no host pass over points.
+    `point_index` of the result indexes the columns of the arena of the tiles READ, in the order of `paths`.
+
+    shapes: K ring lists in the FILES' frame (metres, e.g. Lambert-93).  origin: the triple `load_parcel_clouds` takes -- raw
+    integer units (centimetres) in the "reference" mode, metres in the "header" mode --; the same shift, in metres, is subtracted
+    from the shapes, so cloud and polygons stay in one frame and `shapes_kept` comes back in the cloud's.
+    coords="header": a tile whose header box (`read_header`'s mins / maxs) misses every parcel's expanded bounding box is not read
+    at all, a host test that trusts the header's extents (a file whose writer left them empty loses its points).
+    coords="reference" ignores the header's scale and offset, so there every tile is read."""
+    from .parcel import ParcelCut, cut_parcels, polygon_edges, shift_rings
+    paths, shapes = list(paths), list(shapes)
+    if not paths:
+        raise ValueError("load_parcels: no file")
+    if not shapes:
+        raise ValueError("load_parcels: no parcel")
+    o = (0.0, 0.0, 0.0) if origin is None else tuple(origin)
+    shift = (float(o[0]), float(o[1])) if coords == "header" else (int(o[0]) / 100, int(o[1]) / 100)
+    heads = [read_header(p) for p in paths]
+    dev = _device(device)
+    if coords == "header":
+        boxes = ops.cut_boxes([polygon_edges(r) for r in shift_rings(shapes, shift)], buffer_m)
+        keep = []
+        for h in heads:
+            lo, hi = np.array(h.mins[:2]) - shift, np.array(h.maxs[:2]) - shift
+            slack = 2.0 ** -22 * max(float(np.abs(lo).max()), float(np.abs(hi).max()))       # the decoder rounds x, y to fp32
+            keep.append(h.n_points > 0 and bool(((boxes[:, 0] <= hi[0] + slack) & (boxes[:, 2] >= lo[0] - slack) &
+                                                 (boxes[:, 1] <= hi[1] + slack) & (boxes[:, 3] >= lo[1] - slack)).any()))
+        paths, heads = [p for p, k in zip(paths, keep) if k], [h for h, k in zip(heads, keep) if k]
+        if not paths:
+            return ParcelCut(None, np.zeros(0, dtype=np.int64), np.zeros(len(shapes), dtype=np.int64),
+                             torch.empty(0, dtype=torch.int32, device=dev), [])
+    drop = tuple(drop_classes)
+    if drop:
+        pc, cls = load_parcel_clouds(paths, dev, coords, origin, classification=True, headers=heads)
+    else:
+        pc, cls = load_parcel_clouds(paths, dev, coords, origin, headers=heads), None
+    return cut_parcels(pc, shapes, buffer_m, origin=shift, classification=cls, drop_classes=drop)

@@ -436,6 +436,83 @@ class ParcelClouds:
         return ops.parcels_bbox_decode(state.cpu().numpy())
 
 
+@dataclass
+class ParcelCut:
+    """What `cut_parcels` makes of a tile and K polygons.  clouds: a `ParcelClouds` over the parcels that got points (None when
+    no parcel got any); parcel_index: their shape ids, ascending (host int64); counts (K,): points per shape, zeros included;
+    point_index: device int32, the tile column of every arena column; shapes_kept: the kept parcels' rings in the cloud's frame,
+    ready for `prepare_parcels(cut.clouds, args, shapes=cut.shapes_kept)` and `predict_parcels`."""
+    clouds: Optional[ParcelClouds]
+    parcel_index: np.ndarray
+    counts: np.ndarray
+    point_index: torch.Tensor
+    shapes_kept: list
+
+
+def shift_rings(shapes, origin=None):
+    """K ring lists -> the same as fp64 (V,2) arrays, `origin` = (x0, y0) subtracted in fp64 from every vertex (None: nothing)."""
+    o = np.zeros(2, dtype=np.float64) if origin is None else np.asarray(origin, dtype=np.float64).reshape(-1)[:2]
+    if o.shape != (2,) or not np.isfinite(o).all():
+        raise ValueError("origin: expected finite (x0, y0)")
+    return [[np.asarray(r, dtype=np.float64).reshape(-1, 2) - o for r in rings] for rings in shapes]
+
+
+def cut_parcels(cloud, shapes, buffer_m: float = LAS_PARCEL_BUFFER, origin=None, classification=None, drop_classes=(), device=None,
+                max_table: int = MAX_TABLE) -> ParcelCut:
+    """The points of a LAS tile cut into one cloud per parcel on the device (csrc/cut.hip): parcel k gets every point that
+    `polygon_keep(shapes[k], buffer_m)` keeps -- inside the polygon by even-odd, or nearer than buffer_m to its boundary in fp64
+    --, in ascending tile index, byte for byte `tile[:, mask_k]`.  A point in two parcels' buffers is copied into both.
+
+    cloud: a (10,T) device tensor (las.load_las), or a `ParcelClouds` of tiles (las.load_parcel_clouds): its arena is taken as ONE
+    cloud and `point_index` then indexes arena columns.  shapes: K ring lists ([exterior, *holes, *further parts], each (V,2)), as
+    `prepare_parcels(shapes=...)` takes them.  The cloud and the shapes MUST be in one frame: origin = (x0, y0) is subtracted in
+    fp64 from every ring vertex on the host, so polygons in Lambert-93 metres meet a cloud decoded with las.load_las(origin=...)
+    (in its "reference" mode that origin is in raw centimetres: pass (X0 / 100, Y0 / 100) here).  classification: (T) uint8 on
+    the device (las.decode(classification=...)); a point whose class is in drop_classes belongs to no parcel.  max_table: the
+    (parcel, row) entries up to which a row is 2048 points.
+    One packed upload, count, ONE device-to-host read (the K + 1 parcel starts), fill; more than 2^31 - 1 hits raise ValueError.
+    The buffer inherits `polygon_keep`'s deviation from shapely's 16-segment round joins."""
+    if isinstance(cloud, ParcelClouds):
+        cloud = cloud.arena
+    if not isinstance(cloud, torch.Tensor):
+        cloud = torch.from_numpy(np.ascontiguousarray(np.asarray(cloud, dtype=np.float32))).to(
+            torch.device("cuda") if device is None else torch.device(device))
+    elif device is not None and cloud.device != torch.device(device):
+        cloud = cloud.to(device)
+    if cloud.dim() != 2 or cloud.shape[0] != 10 or cloud.shape[1] == 0:
+        raise ValueError(f"cut_parcels: expected a (10,T) cloud with T > 0, got {tuple(cloud.shape)}")
+    cloud = cloud.contiguous()
+    shapes = list(shapes)
+    K = len(shapes)
+    if K == 0:
+        raise ValueError("cut_parcels: no parcel")
+    rings = shift_rings(shapes, origin)
+    drop = ops.cut_drop_words(drop_classes)
+    if classification is None and drop.any():
+        raise ValueError("cut_parcels: drop_classes needs the points' classification")
+    if classification is None or not drop.any():
+        classification, drop = None, None                         # an empty drop set: the pass without a mask
+    dev = cloud.device
+    table = ops.CutTable([polygon_edges(r) for r in rings], cloud.shape[1], buffer_m, max_table=max_table)
+    with torch.cuda.device(dev):
+        table.upload(dev)
+        prefix, starts_dev = ops.cut_count(cloud, table, classification, drop)
+        starts = starts_dev.cpu().numpy()                                                # the one read
+        if starts[-1] >= 2 ** 31:
+            raise ValueError(f"cut_parcels: {starts[-1]} points in all parcels, at most 2^31 - 1 in one cut")
+        counts = np.diff(starts).astype(np.int64)
+        kept = counts > 0
+        if not kept.any():
+            return ParcelCut(None, np.zeros(0, dtype=np.int64), counts, torch.empty(0, dtype=torch.int32, device=dev), [])
+        offsets = np.concatenate([[0], np.cumsum(counts[kept])])
+        base = np.full(K, INT_MIN, dtype=np.int64)
+        base[kept] = offsets[:-1] - starts[:-1][kept]
+        base_dev, = ops.pack_upload([base.astype(np.int32)], dev)
+        out, pidx = ops.cut_fill(cloud, table, prefix, base_dev, int(offsets[-1]), classification, drop)
+    ids = np.nonzero(kept)[0].astype(np.int64)
+    return ParcelCut(ParcelClouds.from_arena(out, counts[kept]), ids, counts, pidx, [rings[k] for k in ids])
+
+
 def _keep_of(k, args, shapes, keeps):
     keep = keeps[k] if keeps is not None else None
     if keep is None and shapes is not None and shapes[k] is not None:
