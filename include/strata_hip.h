@@ -638,7 +638,7 @@ int sn2_debug_global_spin_limit(unsigned sweeps);
  * f (R,34) pre-BN with affine (fa,fc); coverages (R,4), proba (R,4). */
 /* The loss gradient that sn2_head_backward can compute itself (the fused route, sn2_head_loss_route): what
  * sn2_projected_loss_backward takes, minus the two (R,4) buffers it writes.  The head backward then evaluates d loss / d proba and
- * d loss / d coverages of a row where it consumes them (csrc/loss_grad.h: the same two device functions as
+ * d loss / d coverages of a row where it consumes them (csrc/loss_rules.h: the same two device functions as
  * sn2_projected_loss_backward's kernel, so the same bits) and the 32 B per point never travel through memory. */
 #define SN2_HEAD_LOSS_MAX_PLOTS 128  /* its per-plot table (gx, gz, gw, 1/nocc) lives in what the head backward's LDS leaves free */
 typedef struct sn2_loss_grad {

@@ -6,7 +6,7 @@
 // head_fwd_turn).  The rows' accessors, WAVE_LDS_SYNC, the row side's input stream and arithmetic (fp_row_quad, fp_table_rows)
 // and the source table come from fp_rows.h.
 #include "fp_rows.h"
-#include "loss_grad.h"
+#include "loss_rules.h"
 
 namespace {
 
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd_mfma_kernel(int R, const floa
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // the fused route (sn2_head.loss; wave-uniform, as dcov / dproba / drop_mask are): the incoming gradients of a row are
-    // computed in its one-row-per-lane phase from the loss's own inputs (loss_grad.h) instead of being read
+    // computed in its one-row-per-lane phase from the loss's own inputs (loss_rules.h) instead of being read
     const bool loss = lg.proba != nullptr;
     float* st = smem + wave * HB_WAVE_FLOATS;
     float4* st4 = reinterpret_cast<float4*>(st);

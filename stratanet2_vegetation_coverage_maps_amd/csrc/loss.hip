@@ -7,46 +7,21 @@
 // (gt and the KDE densities are fp64 numpy arrays), the entropy terms in fp32.  Sums are per-workgroup partials added in
 // a fixed order: deterministic.
 #include "common.h"
+#include "loss_rules.h"
 
 namespace {
 
 constexpr int LOSS_BLOCKS = SN2_LOSS_BLOCKS;
-constexpr float EPS_F = 0.0001f;
-constexpr double EPS_D = 0.0001;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // one row per lane: 16 B of probabilities + 24 B of densities, both contiguous across the wave.  NLL / ENT: which of the two
-// pointwise terms are wanted (a term whose weight is zero is SKIPPED, not multiplied by zero: a caller that asks for the entropy
-// of rows that are no probability vectors -- the reference's docstring says "coverage raster" -- must not get 0 * log(<= 0) =
-// NaN from a likelihood nobody asked for, and the densities need not exist)
+// pointwise terms are wanted (pl_row_terms)
 template <bool NLL, bool ENT>
 __global__ __launch_bounds__(256) void loss_point_kernel(const float4* __restrict__ proba, const double* __restrict__ pdf,
                                                          int R, double* __restrict__ partials) {
     __shared__ double s_part[2][4];
     double nll = 0.0, ent = 0.0;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < R; i += gridDim.x * 256) {
-        const float4 p = proba[i];
-        if constexpr (NLL) {
-            const double f0 = pdf[3 * (size_t)i], f1 = pdf[3 * (size_t)i + 1], f2 = pdf[3 * (size_t)i + 2];
-            const float pg = p.x + p.y;                               // pred[:, :2].sum(1) in fp32 (:44)
-            const double lik = ((double)pg * f0 + (double)p.z * f1) + (double)p.w * f2;
-            nll -= log(lik);
-        }
-        if constexpr (ENT) {
-            const float e2 = p.z * logf(p.z + EPS_F) + (1.f - p.z) * logf(1.f - p.z + EPS_F);
-            const float e3 = p.w * logf(p.w + EPS_F) + (1.f - p.w) * logf(1.f - p.w + EPS_F);
-            ent -= (double)e2 + (double)e3;
-        }
-    }
-    nll = wave_sum_f64(nll);
-    ent = wave_sum_f64(ent);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_part[0][w] = nll; s_part[1][w] = ent; }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < R; i += gridDim.x * 256) pl_row_terms<NLL, ENT>(proba[i], pdf, (size_t)i, nll, ent);
+    pl_wave_partials(s_part, nll, ent);
     __syncthreads();
     if (threadIdx.x == 0) {
         partials[2 * blockIdx.x] = (s_part[0][0] + s_part[0][1]) + (s_part[0][2] + s_part[0][3]);
@@ -61,29 +36,12 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
     __shared__ double s[3][256];
     double nll = 0.0, ent = 0.0, ab = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) { nll += partials[2 * i]; ent += partials[2 * i + 1]; }
-    for (int i = threadIdx.x; i < 3 * B; i += 256) {                   // strata low, medium, high = columns 0, 2, 3 (:12)
-        const int b = i / 3, c = i - 3 * b, col = c == 0 ? 0 : c + 1;
-        const double d = (double)pred[4 * b + col] - gt[4 * b + col];
-        ab += sqrt(d * d + EPS_D);
+    for (int i = threadIdx.x; i < 3 * B; i += 256) {
+        const int b = i / 3, col = pl_stratum_col(i - 3 * b);
+        ab += pl_abs_term(pred[4 * b + col], gt[4 * b + col]);
     }
-    s[0][threadIdx.x] = nll; s[1][threadIdx.x] = ent; s[2][threadIdx.x] = ab;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            s[0][threadIdx.x] += s[0][threadIdx.x + o];
-            s[1][threadIdx.x] += s[1][threadIdx.x + o];
-            s[2][threadIdx.x] += s[2][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double l_abs = B > 0 ? s[2][0] / (3.0 * B) : 0.0, l_nll = nblocks > 0 ? s[0][0] / R : 0.0;
-        const double l_ent = nblocks > 0 ? (double)(float)(s[1][0] / (2.0 * R)) : 0.0;      // the reference's entropy is an fp32 tensor
-        out[0] = l_abs + m * l_nll + e * l_ent;
-        out[1] = l_abs;
-        out[2] = l_nll;
-        out[3] = l_ent;
-    }
+    pl_block_sum3(s, nll, ent, ab);
+    if (threadIdx.x == 0) pl_outputs(B > 0 ? s[2][0] / (3.0 * B) : 0.0, s[0][0], s[1][0], nblocks > 0, R, m, e, out);
 }
 
 // d loss / d proba, d loss / d pred for the upstream gradient g of the TOTAL loss (device scalar)
@@ -93,38 +51,15 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
                                                        double m, double e, const double* __restrict__ gout,
                                                        float* __restrict__ dpred, float4* __restrict__ dproba) {
     const double g = gout[0];
-    const double cn = R > 0 ? g * m / R : 0.0, ce = R > 0 ? g * e / (2.0 * R) : 0.0;
+    double cn = 0.0, ce = 0.0;
+    if (R > 0) pl_row_coeffs(g, m, e, (size_t)R, cn, ce);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < R; i += gridDim.x * 256) {
-        const float4 p = proba[i];
-        double d0 = 0.0, d2 = 0.0, d3 = 0.0;
-        if constexpr (NLL) {
-            const double f0 = pdf[3 * (size_t)i], f1 = pdf[3 * (size_t)i + 1], f2 = pdf[3 * (size_t)i + 2];
-            const float pg = p.x + p.y;
-            const double lik = ((double)pg * f0 + (double)p.z * f1) + (double)p.w * f2;
-            const double il = -cn / lik;
-            d0 = il * f0, d2 = il * f1, d3 = il * f2;
-        }
-        if constexpr (ENT) {
-            const float h2 = -(logf(p.z + EPS_F) + p.z / (p.z + EPS_F) - logf(1.f - p.z + EPS_F) - (1.f - p.z) / (1.f - p.z + EPS_F));
-            const float h3 = -(logf(p.w + EPS_F) + p.w / (p.w + EPS_F) - logf(1.f - p.w + EPS_F) - (1.f - p.w) / (1.f - p.w + EPS_F));
-            d2 += ce * (double)h2, d3 += ce * (double)h3;
-        }
-        float4 d;
-        d.x = d.y = (float)d0;
-        d.z = (float)d2;
-        d.w = (float)d3;
-        dproba[i] = d;
+        double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+        if constexpr (NLL) f0 = pdf[3 * (size_t)i], f1 = pdf[3 * (size_t)i + 1], f2 = pdf[3 * (size_t)i + 2];
+        dproba[i] = pl_row_dproba(NLL, ENT, proba[i], f0, f1, f2, cn, ce);
     }
     if (blockIdx.x == 0 && dpred) {
-        for (int i = threadIdx.x; i < 4 * B; i += 256) {
-            const int col = i & 3;
-            float r = 0.f;
-            if (col != 1) {
-                const double d = (double)pred[i] - gt[i];
-                r = (float)(g * d / sqrt(d * d + EPS_D) / (3.0 * B));
-            }
-            dpred[i] = r;
-        }
+        for (int i = threadIdx.x; i < 4 * B; i += 256) dpred[i] = (i & 3) != 1 ? pl_pred_grad(pred[i], gt[i], B, g) : 0.f;
     }
 }
 
@@ -178,9 +113,9 @@ extern "C" int sn2_loss_forward(const float* pred, const double* gt, int B, cons
     const int nb = (nll || ent) ? loss_grid(R) : 0;
     hipStream_t st = (hipStream_t)stream;
     const float4* p4 = reinterpret_cast<const float4*>(proba);
-    if (nll && ent) hipLaunchKernelGGL((loss_point_kernel<true, true>), dim3(nb), dim3(256), 0, st, p4, pdf, R, partials);
-    else if (nll) hipLaunchKernelGGL((loss_point_kernel<true, false>), dim3(nb), dim3(256), 0, st, p4, pdf, R, partials);
-    else if (ent) hipLaunchKernelGGL((loss_point_kernel<false, true>), dim3(nb), dim3(256), 0, st, p4, pdf, R, partials);
+    pl_for_terms(nll, ent, [&](auto NLL, auto ENT) {
+        if constexpr (NLL() || ENT()) hipLaunchKernelGGL((loss_point_kernel<NLL(), ENT()>), dim3(nb), dim3(256), 0, st, p4, pdf, R, partials);
+    });
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, pred, gt, B, (const double*)partials, nb, R > 0 ? R : 1, m, e, out);
     SN2_RETURN_LAUNCH();
 }
@@ -196,10 +131,9 @@ extern "C" int sn2_loss_backward(const float* pred, const double* gt, int B, con
     const float4* p4 = reinterpret_cast<const float4*>(proba);
     float4* d4 = reinterpret_cast<float4*>(dproba);
     float* dp = B > 0 ? dpred : nullptr;
-    if (nll && ent) hipLaunchKernelGGL((loss_bwd_kernel<true, true>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, R, m, e, grad_total, dp, d4);
-    else if (nll) hipLaunchKernelGGL((loss_bwd_kernel<true, false>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, R, m, e, grad_total, dp, d4);
-    else if (ent) hipLaunchKernelGGL((loss_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, R, m, e, grad_total, dp, d4);
-    else hipLaunchKernelGGL((loss_bwd_kernel<false, false>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, R, m, e, grad_total, dp, d4);
+    pl_for_terms(nll, ent, [&](auto NLL, auto ENT) {
+        hipLaunchKernelGGL((loss_bwd_kernel<NLL(), ENT()>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, R, m, e, grad_total, dp, d4);
+    });
     SN2_RETURN_LAUNCH();
 }
 

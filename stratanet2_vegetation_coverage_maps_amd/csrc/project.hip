@@ -6,33 +6,15 @@
 // point on ties as torch_scatter's CPU loop -- LDS atomics per workgroup slice, then one global atomic per touched
 // pixel -- and a tiny per-plot finalisation.  HBM-bound: 8 B (xy) + 16 B (coverages) read per point.
 #include "common.h"
-#include "loss_grad.h"
+#include "loss_rules.h"
 #include "mosaic_rules.h"
+#include "projection_rules.h"
 
 namespace {
 
 constexpr int MAX_CELLS = PL_MAX_CELLS;  // diam_pix <= 45: the D*D*3 keys of a workgroup fit the default 48 KiB dynamic LDS
 
-// project_to_2d.py:16-22   floor((xy - min) / (max - min + 0.0001) * diam_pix).int()
-__device__ __forceinline__ int p2_pix(float v, float mn, float mx, int D) {
-#pragma clang fp contract(off)
-    const float num = v - mn;
-    const float den = (mx - mn) + 0.0001f;
-    const float q = num / den;
-    const float s = q * (float)D;
-    int i = (int)floorf(s);
-    return i < 0 ? 0 : (i > D - 1 ? D - 1 : i);
-}
-
-// project_to_2d.py:68-78   clip(floor((xy + 0.0001) * scaling_factor + diam_meters // 2).int(), 0, diam_pix - 1)
-__device__ __forceinline__ int p1_pix(float v, float sf, float off, int D) {
-#pragma clang fp contract(off)
-    const float t = v + 0.0001f;
-    const float m = t * sf;
-    const float s = m + off;
-    int i = (int)floorf(s);
-    return i < 0 ? 0 : (i > D - 1 ? D - 1 : i);
-}
+// (the pixel of a point, the key, the scatter of a slice and the finalisation of a plot: projection_rules.h)
 
 // also clears the plot's (pixel, channel) key table for the scatter kernel that follows (see sn2_fill_words in common.h
 // for why this is not a hipMemsetAsync)
@@ -100,7 +82,7 @@ __global__ __launch_bounds__(1024) void scatter_max_kernel(const float* __restri
     extern __shared__ unsigned long long s_keys[];  // D*D*3
     const int b = blockIdx.y;
     const int ncell3 = D * D * 3;
-    for (int i = threadIdx.x; i < ncell3; i += 1024) s_keys[i] = 0ull;
+    pj_clear(s_keys, ncell3);
     __syncthreads();
     const float* x = xy + (size_t)b * plot_stride;
     const float* y = x + N;
@@ -111,8 +93,8 @@ __global__ __launch_bounds__(1024) void scatter_max_kernel(const float* __restri
         ymn = mm[b * 4 + 2];
         ymx = mm[b * 4 + 3];
     }
-    const int per = (N + gridDim.x - 1) / gridDim.x;
-    const int lo = blockIdx.x * per, hi = min(N, lo + per);
+    int lo, hi;
+    pj_slice(N, gridDim.x, blockIdx.x, lo, hi);
     for (int n = lo + threadIdx.x; n < hi; n += 1024) {
         int cell;
         if (MODE == 0) {
@@ -121,18 +103,10 @@ __global__ __launch_bounds__(1024) void scatter_max_kernel(const float* __restri
             cell = p1_pix(y[n], sf, off, D) * D + p1_pix(x[n], sf, off, D);
         }
         pix[(size_t)b * N + n] = cell;
-        const float4 v = reinterpret_cast<const float4*>(vals)[(size_t)b * N + n];
-        const unsigned long long tag = (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
-        atomicMax(&s_keys[cell * 3 + 0], ((unsigned long long)f2ord(v.x) << 32) | tag);
-        atomicMax(&s_keys[cell * 3 + 1], ((unsigned long long)f2ord(v.z) << 32) | tag);
-        atomicMax(&s_keys[cell * 3 + 2], ((unsigned long long)f2ord(v.w) << 32) | tag);
+        pj_push(s_keys, cell, reinterpret_cast<const float4*>(vals)[(size_t)b * N + n], n);
     }
     __syncthreads();
-    unsigned long long* g = keys + (size_t)b * ncell3;
-    for (int i = threadIdx.x; i < ncell3; i += 1024) {
-        const unsigned long long k = s_keys[i];
-        if (k) atomicMax(&g[i], k);
-    }
+    pj_copy_out<true>(s_keys, ncell3, keys + (size_t)b * ncell3);
 }
 
 // The pixel id of every point depends on the plot's x, y only (project_to_2d.py:16-22): a training loop that runs its
@@ -146,31 +120,15 @@ __global__ __launch_bounds__(1024) void plot_pixels_kernel(const float* __restri
     const float* x = xy + (size_t)b * plot_stride;
     const float* y = x + N;
     const float xmn = mm[b * 4 + 0], xmx = mm[b * 4 + 1], ymn = mm[b * 4 + 2], ymx = mm[b * 4 + 3];
-    const int per = (N + gridDim.x - 1) / gridDim.x;
-    const int lo = blockIdx.x * per, hi = min(N, lo + per);
+    int lo, hi;
+    pj_slice(N, gridDim.x, blockIdx.x, lo, hi);
     for (int n = lo + threadIdx.x; n < hi; n += 1024) pix[(size_t)b * N + n] = p2_pix(x[n], xmn, xmx, D) * D + p2_pix(y[n], ymn, ymx, D);
 }
 
 __global__ __launch_bounds__(1024) void scatter_max_pix_kernel(const float* __restrict__ vals, const int* __restrict__ pix, int N,
                                                                int D, unsigned long long* __restrict__ keys_part) {
     extern __shared__ unsigned long long s_keys[];  // D*D*3
-    const int b = blockIdx.y;
-    const int ncell3 = D * D * 3;
-    for (int i = threadIdx.x; i < ncell3; i += 1024) s_keys[i] = 0ull;
-    __syncthreads();
-    const int per = (N + gridDim.x - 1) / gridDim.x;
-    const int lo = blockIdx.x * per, hi = min(N, lo + per);
-    for (int n = lo + threadIdx.x; n < hi; n += 1024) {
-        const int cell = pix[(size_t)b * N + n];
-        const float4 v = reinterpret_cast<const float4*>(vals)[(size_t)b * N + n];
-        const unsigned long long tag = (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
-        atomicMax(&s_keys[cell * 3 + 0], ((unsigned long long)f2ord(v.x) << 32) | tag);
-        atomicMax(&s_keys[cell * 3 + 1], ((unsigned long long)f2ord(v.z) << 32) | tag);
-        atomicMax(&s_keys[cell * 3 + 2], ((unsigned long long)f2ord(v.w) << 32) | tag);
-    }
-    __syncthreads();
-    unsigned long long* g = keys_part + ((size_t)b * gridDim.x + blockIdx.x) * ncell3;
-    for (int i = threadIdx.x; i < ncell3; i += 1024) g[i] = s_keys[i];
+    pj_scatter_slice(s_keys, vals, pix, N, D, blockIdx.y, gridDim.x, blockIdx.x, keys_part);
 }
 
 // P2: pred[b] = mean over occupied pixels of [low, 1-low, med, high]   (project_to_2d.py:41-53)
@@ -181,55 +139,11 @@ __global__ __launch_bounds__(256) void p2_finalize_kernel(const unsigned long lo
                                                           float* __restrict__ pred) {
     __shared__ float s[5][4];
     const int b = blockIdx.x;
-    const int ncell = D * D;
-    float lo = 0.f, so = 0.f, me = 0.f, hi = 0.f, cnt = 0.f;
-    for (int c = threadIdx.x; c < ncell; c += 256) {
-        const size_t base = ((size_t)b * ncell + c) * 3;
-        const unsigned long long* kp = keys + ((size_t)b * parts * ncell + c) * 3;
-        unsigned long long k0 = kp[0], k1 = kp[1], k2 = kp[2];
-        for (int q = 1; q < parts; ++q) {
-            const unsigned long long* kq = kp + (size_t)q * ncell * 3;
-            const unsigned long long a0 = kq[0], a1 = kq[1], a2 = kq[2];
-            k0 = a0 > k0 ? a0 : k0;
-            k1 = a1 > k1 ? a1 : k1;
-            k2 = a2 > k2 ? a2 : k2;
-        }
-        if (k0) {
-            const float l = ord2f((uint32_t)(k0 >> 32));
-            lo += l;
-            so += 1.0f - l;
-            me += ord2f((uint32_t)(k1 >> 32));
-            hi += ord2f((uint32_t)(k2 >> 32));
-            cnt += 1.f;
-            arg[base + 0] = (int)(0xFFFFFFFFu - (uint32_t)(k0 & 0xFFFFFFFFull));
-            arg[base + 1] = (int)(0xFFFFFFFFu - (uint32_t)(k1 & 0xFFFFFFFFull));
-            arg[base + 2] = (int)(0xFFFFFFFFu - (uint32_t)(k2 & 0xFFFFFFFFull));
-        } else {
-            arg[base + 0] = arg[base + 1] = arg[base + 2] = -1;
-        }
-    }
-    lo = wave_sum(lo);
-    so = wave_sum(so);
-    me = wave_sum(me);
-    hi = wave_sum(hi);
-    cnt = wave_sum(cnt);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s[0][w] = lo;
-        s[1][w] = so;
-        s[2][w] = me;
-        s[3][w] = hi;
-        s[4][w] = cnt;
-    }
-    __syncthreads();
+    float t[5];
+    pj_finalize_plot<true>(keys, b, D, parts, arg, s, t);
     if (threadIdx.x == 0) {
-        float t[5];
-        for (int q = 0; q < 5; ++q) t[q] = (s[q][0] + s[q][1]) + (s[q][2] + s[q][3]);
         const float n = fmaxf(t[4], 1.f);
-        pred[b * 4 + 0] = t[0] / n;
-        pred[b * 4 + 1] = t[1] / n;
-        pred[b * 4 + 2] = t[2] / n;
-        pred[b * 4 + 3] = t[3] / n;
+        for (int q = 0; q < 4; ++q) pred[b * 4 + q] = t[q] / n;
         nocc[b] = (int)t[4];
     }
 }
@@ -262,13 +176,8 @@ __global__ void p1_finalize_kernel(const unsigned long long* __restrict__ keys, 
     const int cell = rem / 3, slot = rem - cell * 3;
     const int y = cell / D, x = cell - y * D;
     const unsigned long long k = keys[i];
-    const float v = k ? ord2f((uint32_t)(k >> 32)) : __uint_as_float(0x7FC00000u);
+    const float v = k ? pj_key_value(k) : __uint_as_float(0x7FC00000u);
     rasters[(((size_t)b * 3 + slot) * D + (D - 1 - y)) * D + x] = v;
-}
-
-int grid_slices(int N) {
-    int s = sn2_cdiv(N, 4096);
-    return s < 1 ? 1 : (s > 64 ? 64 : s);
 }
 
 }  // namespace
@@ -320,23 +229,19 @@ extern "C" int sn2_plot_project_forward_pix(const float* pred_pointwise, const i
 //   loss = get_absolute_loss(pred, gt) + m get_NLL_loss(proba, pdf) + e get_entropy_loss(proba)   learning/loss_functions.py:9-57
 // and their gradients.  The chip's floor for ANY launch is ~4.5 us (an empty kernel), the seven kernels were 4-7 us each:
 //   launch 1  two independent jobs side by side: workgroups [0, parts B) scatter the coverages into per-slice key tables
-//             (scatter_max_pix_kernel's body), the rest sum the pointwise loss terms (loss_point_kernel's body);
-//   launch 2  per plot: maximum over the slices, arg-max points, mean over occupied pixels (p2_finalize_kernel's body) -- and
-//             the workgroup that leaves last adds the loss up (loss_final_kernel's body); the B x 5 words it needs from its
-//             peers travel as agent-scope atomics, complete before their ticket;
-//   backward  one pass over the points: d loss / d proba (loss_bwd_kernel's body) and d loss / d coverages (p2_backward_kernel's,
-//             with the B x 3 values of d loss / d pred it needs recomputed from pred and gt by every thread).
-// Same arithmetic per element as the separate kernels: the same pred, arg, dcov, dproba bits; the loss sums are grouped by
-// 1024 instead of 256 rows per workgroup (fp64: 1e-16).
+//             (pj_scatter_slice, as scatter_max_pix_kernel), the rest sum the pointwise loss terms (pl_row_terms, as
+//             loss_point_kernel);
+//   launch 2  per plot: maximum over the slices, arg-max points, mean over occupied pixels (pj_finalize_plot, as
+//             p2_finalize_kernel) -- and the workgroup that leaves last adds the loss up (pl_abs_term, pl_block_sum3 and
+//             pl_outputs, as loss_final_kernel); the B x 5 words it needs from its peers travel as agent-scope atomics,
+//             complete before their ticket;
+//   backward  one pass over the points: d loss / d proba (pl_row_dproba, as loss_bwd_kernel) and d loss / d coverages (as
+//             p2_backward_kernel, with the B x 3 values of d loss / d pred it needs recomputed from pred and gt by every thread).
+// The same device functions per element as the separate kernels: the same pred, arg, dcov, dproba bits; the loss sums are
+// grouped by 1024 instead of 256 rows per workgroup (fp64: 1e-16).
 // ------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int PL_LOSS_BLOCKS = 512;          // (PL_EPS_F, PL_EPS_D: loss_grad.h)
-
-__device__ __forceinline__ double pl_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+constexpr int PL_LOSS_BLOCKS = 512;
 
 template <bool NLL, bool ENT>
 __global__ __launch_bounds__(1024) void projected_loss_scatter_kernel(const float* __restrict__ vals, const int* __restrict__ pix,
@@ -348,23 +253,8 @@ __global__ __launch_bounds__(1024) void projected_loss_scatter_kernel(const floa
     extern __shared__ unsigned long long s_keys[];  // D*D*3 (the scatter workgroups)
     const int n_scatter = parts * B;
     if ((int)blockIdx.x < n_scatter) {
-        const int b = blockIdx.x / parts, part = blockIdx.x - b * parts;
-        const int ncell3 = D * D * 3;
-        for (int i = threadIdx.x; i < ncell3; i += 1024) s_keys[i] = 0ull;
-        __syncthreads();
-        const int per = (N + parts - 1) / parts;
-        const int lo = part * per, hi = min(N, lo + per);
-        for (int n = lo + threadIdx.x; n < hi; n += 1024) {
-            const int cell = pix[(size_t)b * N + n];
-            const float4 v = reinterpret_cast<const float4*>(vals)[(size_t)b * N + n];
-            const unsigned long long tag = (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
-            atomicMax(&s_keys[cell * 3 + 0], ((unsigned long long)f2ord(v.x) << 32) | tag);
-            atomicMax(&s_keys[cell * 3 + 1], ((unsigned long long)f2ord(v.z) << 32) | tag);
-            atomicMax(&s_keys[cell * 3 + 2], ((unsigned long long)f2ord(v.w) << 32) | tag);
-        }
-        __syncthreads();
-        unsigned long long* g = keys_part + ((size_t)b * parts + part) * ncell3;
-        for (int i = threadIdx.x; i < ncell3; i += 1024) g[i] = s_keys[i];
+        const int b = blockIdx.x / parts;
+        pj_scatter_slice(s_keys, vals, pix, N, D, b, parts, blockIdx.x - b * parts, keys_part);
         return;
     }
     // ---- the pointwise loss terms: one row per lane, 16 B of probabilities + 24 B of densities
@@ -372,31 +262,10 @@ __global__ __launch_bounds__(1024) void projected_loss_scatter_kernel(const floa
     if (lb == 0 && threadIdx.x == 0) *ticket = 0u;                  // the finalisation's arrival counter (next launch)
     __shared__ double s_part[2][16];
     double nll = 0.0, ent = 0.0;
-    for (int i = lb * 1024 + threadIdx.x; i < R; i += n_loss_blocks * 1024) {
-        const float4 p = proba[i];
-        if constexpr (NLL) {
-            const double f0 = pdf[3 * (size_t)i], f1 = pdf[3 * (size_t)i + 1], f2 = pdf[3 * (size_t)i + 2];
-            const float pg = p.x + p.y;
-            const double lik = ((double)pg * f0 + (double)p.z * f1) + (double)p.w * f2;
-            nll -= log(lik);
-        }
-        if constexpr (ENT) {
-            const float e2 = p.z * logf(p.z + PL_EPS_F) + (1.f - p.z) * logf(1.f - p.z + PL_EPS_F);
-            const float e3 = p.w * logf(p.w + PL_EPS_F) + (1.f - p.w) * logf(1.f - p.w + PL_EPS_F);
-            ent -= (double)e2 + (double)e3;
-        }
-    }
-    nll = pl_wave_sum_f64(nll);
-    ent = pl_wave_sum_f64(ent);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) s_part[0][w] = nll, s_part[1][w] = ent;
+    for (int i = lb * 1024 + threadIdx.x; i < R; i += n_loss_blocks * 1024) pl_row_terms<NLL, ENT>(proba[i], pdf, (size_t)i, nll, ent);
+    pl_wave_partials(s_part, nll, ent);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, c = 0.0;
-        for (int k = 0; k < 16; ++k) a += s_part[0][k], c += s_part[1][k];
-        partials[2 * lb] = a;
-        partials[2 * lb + 1] = c;
-    }
+    if (threadIdx.x == 0) pl_store_partials16(s_part, partials + 2 * lb);
 }
 
 __global__ __launch_bounds__(256) void projected_loss_finalize_kernel(const unsigned long long* __restrict__ keys, int B, int D,
@@ -409,44 +278,9 @@ __global__ __launch_bounds__(256) void projected_loss_finalize_kernel(const unsi
     __shared__ int s_last;
     __shared__ double s3[3][256];
     const int b = blockIdx.x;
-    const int ncell = D * D;
-    float lo = 0.f, so = 0.f, me = 0.f, hi = 0.f, cnt = 0.f;
-    for (int c = threadIdx.x; c < ncell; c += 256) {
-        const size_t base = ((size_t)b * ncell + c) * 3;
-        const unsigned long long* kp = keys + ((size_t)b * parts * ncell + c) * 3;
-        unsigned long long k0 = kp[0], k1 = kp[1], k2 = kp[2];
-        for (int q = 1; q < parts; ++q) {
-            const unsigned long long* kq = kp + (size_t)q * ncell * 3;
-            const unsigned long long a0 = kq[0], a1 = kq[1], a2 = kq[2];
-            k0 = a0 > k0 ? a0 : k0;
-            k1 = a1 > k1 ? a1 : k1;
-            k2 = a2 > k2 ? a2 : k2;
-        }
-        if (k0) {
-            const float l = ord2f((uint32_t)(k0 >> 32));
-            lo += l;
-            so += 1.0f - l;
-            me += ord2f((uint32_t)(k1 >> 32));
-            hi += ord2f((uint32_t)(k2 >> 32));
-            cnt += 1.f;
-            arg[base + 0] = (int)(0xFFFFFFFFu - (uint32_t)(k0 & 0xFFFFFFFFull));
-            arg[base + 1] = (int)(0xFFFFFFFFu - (uint32_t)(k1 & 0xFFFFFFFFull));
-            arg[base + 2] = (int)(0xFFFFFFFFu - (uint32_t)(k2 & 0xFFFFFFFFull));
-        } else {
-            arg[base + 0] = arg[base + 1] = arg[base + 2] = -1;
-        }
-    }
-    lo = wave_sum(lo);
-    so = wave_sum(so);
-    me = wave_sum(me);
-    hi = wave_sum(hi);
-    cnt = wave_sum(cnt);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) s[0][w] = lo, s[1][w] = so, s[2][w] = me, s[3][w] = hi, s[4][w] = cnt;
-    __syncthreads();
+    float t[5];
+    pj_finalize_plot<true>(keys, b, D, parts, arg, s, t);
     if (threadIdx.x == 0) {
-        float t[5];
-        for (int q = 0; q < 5; ++q) t[q] = (s[q][0] + s[q][1]) + (s[q][2] + s[q][3]);
         const float n = fmaxf(t[4], 1.f);
         // (agent-scope stores: the workgroup that adds the loss up reads them from another CU, maybe another XCD)
         for (int q = 0; q < 4; ++q)
@@ -458,33 +292,16 @@ __global__ __launch_bounds__(256) void projected_loss_finalize_kernel(const unsi
     }
     __syncthreads();
     if (!s_last) return;
-    // ---- the last workgroup out: the loss value (loss_final_kernel)
+    // ---- the last workgroup out: the loss value (as loss_final_kernel)
     double nll = 0.0, ent = 0.0, ab = 0.0;
     for (int i = threadIdx.x; i < n_loss_blocks; i += 256) nll += partials[2 * i], ent += partials[2 * i + 1];
     for (int i = threadIdx.x; i < 3 * B; i += 256) {
-        const int bb = i / 3, c = i - 3 * bb, col = c == 0 ? 0 : c + 1;
+        const int bb = i / 3, col = pl_stratum_col(i - 3 * bb);
         const float pv = __uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned*>(pred) + 4 * bb + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        const double d = (double)pv - gt[4 * bb + col];
-        ab += sqrt(d * d + PL_EPS_D);
+        ab += pl_abs_term(pv, gt[4 * bb + col]);
     }
-    s3[0][threadIdx.x] = nll, s3[1][threadIdx.x] = ent, s3[2][threadIdx.x] = ab;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            s3[0][threadIdx.x] += s3[0][threadIdx.x + o];
-            s3[1][threadIdx.x] += s3[1][threadIdx.x + o];
-            s3[2][threadIdx.x] += s3[2][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double l_abs = s3[2][0] / (3.0 * B), l_nll = n_loss_blocks > 0 ? s3[0][0] / R : 0.0;
-        const double l_ent = n_loss_blocks > 0 ? (double)(float)(s3[1][0] / (2.0 * R)) : 0.0;
-        out[0] = l_abs + m * l_nll + e * l_ent;
-        out[1] = l_abs;
-        out[2] = l_nll;
-        out[3] = l_ent;
-    }
+    pl_block_sum3(s3, nll, ent, ab);
+    if (threadIdx.x == 0) pl_outputs(s3[2][0] / (3.0 * B), s3[0][0], s3[1][0], n_loss_blocks > 0, R, m, e, out);
 }
 
 template <bool NLL, bool ENT>
@@ -494,7 +311,7 @@ __global__ __launch_bounds__(256) void projected_loss_bwd_kernel(const float* __
                                                                  const int* __restrict__ arg, const int* __restrict__ nocc,
                                                                  const int* __restrict__ pix, float4* __restrict__ dcov,
                                                                  float4* __restrict__ dproba) {
-    // (the arithmetic lives in loss_grad.h: the head backward's fused route evaluates the same two functions)
+    // (the arithmetic lives in loss_rules.h: the head backward's fused route evaluates the same two functions)
     const size_t R = (size_t)B * N;
     const double g = gout[0];
     double cn, ce;
@@ -531,10 +348,10 @@ extern "C" int sn2_projected_loss_forward(const float* coverages, const int* pix
     const int grid = parts * B + (nlb > 0 ? nlb : 1);              // (at least one loss workgroup: it clears the ticket)
     const size_t lds = (size_t)D * D * 3 * 8;
     const float4* p4 = reinterpret_cast<const float4*>(proba);
-    if (nll && ent) hipLaunchKernelGGL((projected_loss_scatter_kernel<true, true>), dim3(grid), dim3(1024), lds, st, coverages, pix, B, N, D, parts, keys, p4, pdf, nlb > 0 ? R : 0, partials, nlb > 0 ? nlb : 1, ticket);
-    else if (nll) hipLaunchKernelGGL((projected_loss_scatter_kernel<true, false>), dim3(grid), dim3(1024), lds, st, coverages, pix, B, N, D, parts, keys, p4, pdf, nlb > 0 ? R : 0, partials, nlb > 0 ? nlb : 1, ticket);
-    else if (ent) hipLaunchKernelGGL((projected_loss_scatter_kernel<false, true>), dim3(grid), dim3(1024), lds, st, coverages, pix, B, N, D, parts, keys, p4, pdf, nlb > 0 ? R : 0, partials, nlb > 0 ? nlb : 1, ticket);
-    else hipLaunchKernelGGL((projected_loss_scatter_kernel<false, false>), dim3(grid), dim3(1024), lds, st, coverages, pix, B, N, D, parts, keys, p4, pdf, 0, partials, 1, ticket);
+    pl_for_terms(nll, ent, [&](auto NLL, auto ENT) {        // (neither term: nlb = 0, no row is read)
+        hipLaunchKernelGGL((projected_loss_scatter_kernel<NLL(), ENT()>), dim3(grid), dim3(1024), lds, st, coverages, pix, B, N, D, parts,
+                           keys, p4, pdf, nlb > 0 ? R : 0, partials, nlb > 0 ? nlb : 1, ticket);
+    });
     hipLaunchKernelGGL(projected_loss_finalize_kernel, dim3(B), dim3(256), 0, st, (const unsigned long long*)keys, B, D, parts, arg, nocc,
                        pred, gt, (const double*)partials, nlb, R, m, e, ticket, out);
     SN2_RETURN_LAUNCH();
@@ -552,10 +369,10 @@ extern "C" int sn2_projected_loss_backward(const float* pred, const double* gt, 
     if (grid > 2048) grid = 2048;
     const float4* p4 = reinterpret_cast<const float4*>(proba);
     float4 *dc = reinterpret_cast<float4*>(dcoverages), *dp = reinterpret_cast<float4*>(dproba);
-    if (nll && ent) hipLaunchKernelGGL((projected_loss_bwd_kernel<true, true>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, N, D, m, e, grad_total, arg, nocc, pix, dc, dp);
-    else if (nll) hipLaunchKernelGGL((projected_loss_bwd_kernel<true, false>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, N, D, m, e, grad_total, arg, nocc, pix, dc, dp);
-    else if (ent) hipLaunchKernelGGL((projected_loss_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, N, D, m, e, grad_total, arg, nocc, pix, dc, dp);
-    else hipLaunchKernelGGL((projected_loss_bwd_kernel<false, false>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, N, D, m, e, grad_total, arg, nocc, pix, dc, dp);
+    pl_for_terms(nll, ent, [&](auto NLL, auto ENT) {
+        hipLaunchKernelGGL((projected_loss_bwd_kernel<NLL(), ENT()>), dim3(grid), dim3(256), 0, st, pred, gt, B, p4, pdf, N, D, m, e,
+                           grad_total, arg, nocc, pix, dc, dp);
+    });
     SN2_RETURN_LAUNCH();
 }
 
@@ -563,10 +380,12 @@ extern "C" int sn2_projected_loss_backward(const float* pred, const double* gt, 
 // Validation pass: the losses of EVERY PLOT of a batch on its own (learning/test.py:52-79 evaluates with batch_size = 1, so its
 // loss_abs / loss_log / loss_e / get_absolute_loss_by_strata are per-plot numbers that an AverageValueMeter then averages).
 //   launch 1  one workgroup per (plot, slice of PL_SLICE_ROWS rows): scatters its rows' coverages into its own key table
-//             (scatter_max_pix_kernel's body) AND sums the pointwise loss terms of the same rows (loss_point_kernel's body) -- the
-//             number of slices depends on N alone, so the pointwise pass of a single plot already is cdiv(N, 2048) workgroups;
-//   launch 2  one workgroup per plot: maximum over the slices and mean over occupied pixels (p2_finalize_kernel's arithmetic:
-//             the same pred bits), the plot's partial sums added slice 0, 1, 2, ... by one thread, the seven outputs.
+//             (pj_push, as scatter_max_pix_kernel) AND sums the pointwise loss terms of the same rows (pl_row_terms, as
+//             loss_point_kernel) -- the number of slices depends on N alone, so the pointwise pass of a single plot already is
+//             cdiv(N, 2048) workgroups;
+//   launch 2  one workgroup per plot: maximum over the slices and mean over occupied pixels (pj_finalize_plot, as
+//             p2_finalize_kernel: the same pred bits), the plot's partial sums added slice 0, 1, 2, ... by one thread, the seven
+//             outputs.
 // Nothing crosses a plot's boundary and every sum has one fixed order that depends on N and D only: a plot's row is the same
 // bytes at any position of any batch, run after run, and a NaN stays in its plot.  No atomics outside LDS (integer maxima).
 // ------------------------------------------------------------------------------------------------------------
@@ -584,50 +403,21 @@ __global__ __launch_bounds__(1024) void plot_losses_scatter_kernel(const float4*
     __shared__ double s_part[2][16];
     const int b = blockIdx.x / parts, part = blockIdx.x - b * parts;
     const int ncell3 = D * D * 3;
-    for (int i = threadIdx.x; i < ncell3; i += 1024) s_keys[i] = 0ull;
+    pj_clear(s_keys, ncell3);
     __syncthreads();
-    const int per = (N + parts - 1) / parts;
-    const int lo = part * per, hi = min(N, lo + per);
+    int lo, hi;
+    pj_slice(N, parts, part, lo, hi);
     double nll = 0.0, ent = 0.0;
     for (int n = lo + threadIdx.x; n < hi; n += 1024) {
         const size_t i = (size_t)b * N + n;
-        const int cell = pix[i];
-        const float4 v = vals[i];
-        const unsigned long long tag = (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
-        atomicMax(&s_keys[cell * 3 + 0], ((unsigned long long)f2ord(v.x) << 32) | tag);
-        atomicMax(&s_keys[cell * 3 + 1], ((unsigned long long)f2ord(v.z) << 32) | tag);
-        atomicMax(&s_keys[cell * 3 + 2], ((unsigned long long)f2ord(v.w) << 32) | tag);
-        if constexpr (NLL || ENT) {
-            const float4 p = proba[i];
-            if constexpr (NLL) {
-                const double f0 = pdf[3 * i], f1 = pdf[3 * i + 1], f2 = pdf[3 * i + 2];
-                const float pg = p.x + p.y;
-                const double lik = ((double)pg * f0 + (double)p.z * f1) + (double)p.w * f2;
-                nll -= log(lik);
-            }
-            if constexpr (ENT) {
-                const float e2 = p.z * logf(p.z + PL_EPS_F) + (1.f - p.z) * logf(1.f - p.z + PL_EPS_F);
-                const float e3 = p.w * logf(p.w + PL_EPS_F) + (1.f - p.w) * logf(1.f - p.w + PL_EPS_F);
-                ent -= (double)e2 + (double)e3;
-            }
-        }
+        pj_push(s_keys, pix[i], vals[i], n);
+        if constexpr (NLL || ENT) pl_row_terms<NLL, ENT>(proba[i], pdf, i, nll, ent);
     }
-    if constexpr (NLL || ENT) {
-        nll = pl_wave_sum_f64(nll);
-        ent = pl_wave_sum_f64(ent);
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) s_part[0][w] = nll, s_part[1][w] = ent;
-    }
+    if constexpr (NLL || ENT) pl_wave_partials(s_part, nll, ent);
     __syncthreads();
-    unsigned long long* g = keys_part + (size_t)blockIdx.x * ncell3;
-    for (int i = threadIdx.x; i < ncell3; i += 1024) g[i] = s_keys[i];
+    pj_copy_out<false>(s_keys, ncell3, keys_part + (size_t)blockIdx.x * ncell3);
     if constexpr (NLL || ENT) {
-        if (threadIdx.x == 0) {
-            double a = 0.0, c = 0.0;
-            for (int k = 0; k < 16; ++k) a += s_part[0][k], c += s_part[1][k];
-            partials[2 * (size_t)blockIdx.x] = a;
-            partials[2 * (size_t)blockIdx.x + 1] = c;
-        }
+        if (threadIdx.x == 0) pl_store_partials16(s_part, partials + 2 * (size_t)blockIdx.x);
     }
 }
 
@@ -638,63 +428,21 @@ __global__ __launch_bounds__(256) void plot_losses_finalize_kernel(const unsigne
                                                                    double* __restrict__ out) {
     __shared__ float s[5][4];
     const int b = blockIdx.x;
-    const int ncell = D * D;
-    float lo = 0.f, so = 0.f, me = 0.f, hi = 0.f, cnt = 0.f;
-    for (int c = threadIdx.x; c < ncell; c += 256) {
-        const unsigned long long* kp = keys + ((size_t)b * parts * ncell + c) * 3;
-        unsigned long long k0 = kp[0], k1 = kp[1], k2 = kp[2];
-        for (int q = 1; q < parts; ++q) {
-            const unsigned long long* kq = kp + (size_t)q * ncell * 3;
-            const unsigned long long a0 = kq[0], a1 = kq[1], a2 = kq[2];
-            k0 = a0 > k0 ? a0 : k0;
-            k1 = a1 > k1 ? a1 : k1;
-            k2 = a2 > k2 ? a2 : k2;
-        }
-        if (k0) {
-            const float l = ord2f((uint32_t)(k0 >> 32));
-            lo += l;
-            so += 1.0f - l;
-            me += ord2f((uint32_t)(k1 >> 32));
-            hi += ord2f((uint32_t)(k2 >> 32));
-            cnt += 1.f;
-        }
-    }
-    lo = wave_sum(lo);
-    so = wave_sum(so);
-    me = wave_sum(me);
-    hi = wave_sum(hi);
-    cnt = wave_sum(cnt);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) s[0][w] = lo, s[1][w] = so, s[2][w] = me, s[3][w] = hi, s[4][w] = cnt;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
     float t[5];
-    for (int q = 0; q < 5; ++q) t[q] = (s[q][0] + s[q][1]) + (s[q][2] + s[q][3]);
+    pj_finalize_plot<false>(keys, b, D, parts, nullptr, s, t);
+    if (threadIdx.x != 0) return;
     const float n = fmaxf(t[4], 1.f);
     float pv[4];
     for (int q = 0; q < 4; ++q) pred[b * 4 + q] = pv[q] = t[q] / n;
+    double* o = out + 7 * (size_t)b;
     double ab[3];
-    for (int c = 0; c < 3; ++c) {                       // strata low, medium, high = columns 0, 2, 3
-        const int col = c == 0 ? 0 : c + 1;
-        const double d = (double)pv[col] - gt[4 * b + col];
-        ab[c] = sqrt(d * d + PL_EPS_D);
-    }
+    for (int c = 0; c < 3; ++c) o[4 + c] = ab[c] = pl_abs_term(pv[pl_stratum_col(c)], gt[4 * b + pl_stratum_col(c)]);
     double nll = 0.0, ent = 0.0;
     if (pointwise) {
         const double* pp = partials + 2 * (size_t)b * parts;
         for (int q = 0; q < parts; ++q) nll += pp[2 * q], ent += pp[2 * q + 1];
     }
-    const double l_abs = ((ab[0] + ab[1]) + ab[2]) / 3.0;
-    const double l_nll = pointwise ? nll / N : 0.0;
-    const double l_ent = pointwise ? (double)(float)(ent / (2.0 * N)) : 0.0;       // the reference's entropy is an fp32 tensor
-    double* o = out + 7 * (size_t)b;
-    o[0] = l_abs + m * l_nll + e * l_ent;
-    o[1] = l_abs;
-    o[2] = l_nll;
-    o[3] = l_ent;
-    o[4] = ab[0];
-    o[5] = ab[1];
-    o[6] = ab[2];
+    pl_outputs(((ab[0] + ab[1]) + ab[2]) / 3.0, nll, ent, pointwise != 0, N, m, e, o);
 }
 }  // namespace
 
@@ -721,10 +469,9 @@ extern "C" int sn2_plot_losses(const float* coverages, const int* pix, const flo
     const float4* c4 = reinterpret_cast<const float4*>(coverages);
     const float4* p4 = reinterpret_cast<const float4*>(proba);
     const dim3 grid((unsigned)slices);
-    if (nll && ent) hipLaunchKernelGGL((plot_losses_scatter_kernel<true, true>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
-    else if (nll) hipLaunchKernelGGL((plot_losses_scatter_kernel<true, false>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
-    else if (ent) hipLaunchKernelGGL((plot_losses_scatter_kernel<false, true>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
-    else hipLaunchKernelGGL((plot_losses_scatter_kernel<false, false>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
+    pl_for_terms(nll, ent, [&](auto NLL, auto ENT) {
+        hipLaunchKernelGGL((plot_losses_scatter_kernel<NLL(), ENT()>), grid, dim3(1024), lds, st, c4, pix, p4, pdf, N, D, parts, keys, partials);
+    });
     hipLaunchKernelGGL(plot_losses_finalize_kernel, dim3(B), dim3(256), 0, st, (const unsigned long long*)keys, N, D, parts, gt,
                        (const double*)partials, (nll || ent) ? 1 : 0, m, e, pred, out);
     SN2_RETURN_LAUNCH();

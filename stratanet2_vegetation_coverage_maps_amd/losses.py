@@ -360,7 +360,7 @@ def projected_total_loss(coverages_pointwise, proba_pointwise, clouds, gt, pdf_a
     re-association.  Without them: the two calls.
     Where cov and proba are the two outputs of ONE network node whose model has `fuse_loss_backward` on, and the library takes the
     sizes (`ops.head_loss_route`), that backward pass is no launch at all: the head backward computes both gradients from the
-    loss's inputs (`PendingLossGrad`; the same gradient bits, csrc/loss_grad.h)."""
+    loss's inputs (`PendingLossGrad`; the same gradient bits, csrc/loss_rules.h)."""
     from .project_to_2d import project_to_plotwise_coverages
     pix = getattr(geometry, "p2_pix", None) if geometry is not None else None
     B = clouds.shape[0]
