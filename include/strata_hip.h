@@ -993,6 +993,59 @@ int sn2_las_decode(const void *records, size_t n_bytes, int format, int L, long 
                    const long long *raw0, float *out, long row_stride, long col0, unsigned char *classification, void *stream);
 int sn2_debug_las_form(int form);
 
+/* ---- LAS point records, written (csrc/las_write.hip; the rule's functions: csrc/las_write_rules.h; host side las.encode,
+ * las.write_scored, las.write_parcels): the inverse of the decoder.  The point records of a LAS file, as the file holds them, come
+ * back annotated with the network's per-point scores (sn2_points_finalize): NOTHING is re-encoded from the fp32 cloud -- every byte
+ * the source record holds (coordinates, GPS time, colours, the file's own extra bytes) is copied unchanged -- and only the
+ * classification field and appended extra bytes are new.  The layout is that of "LAS point records" above, OUR reading of the ASPRS
+ * LAS 1.0-1.4 specification, pinned by records typed out by hand (tests/test_las_write_host.py); the header, the VLRs and the Extra
+ * Bytes descriptors are written on the host (las.py).
+ *
+ * SOURCE AND DESTINATION.  Output record i, 0 <= i < T_out, has L_dst = L_src + E bytes.  Its source is record
+ *   s = point_index ? point_index[i] : i of the T_src records of L_src bytes at `src` (format 0..10, L_src >= the format's least
+ *   length; without point_index T_out <= T_src).  Its score column is c = col0 + i: scores[k score_stride + c] for rows k = 0..7 (the
+ *   four coverages, then the four class probabilities), weight[c], hits[c].
+ * COPIED BYTES.  Bytes [0, L_src) of the output are the source record's bytes, except the classification field.
+ * CLASSIFICATION.  class_mode 0 leaves the field alone.  class_mode 1 decides it from rows 4..7 of scores, the class probabilities
+ *   p[0..3] in the network's column order (low vegetation, bare soil, medium, high).  The point is scored iff hits[c] > 0.  Scored:
+ *   best = 0; for k = 1..3: if (p[k] > p[best]) best = k -- strict, so ties go to the lowest index and a NaN never wins --, code =
+ *   class_codes[best] (host, 4 ints).  Unscored: code = unscored_code; -1 leaves the byte as the source has it.
+ *   Formats 6-10: byte 16 = code.  Formats 0-5: byte 15 = (byte 15 & 0xE0) | code, the synthetic, key-point and withheld flags kept.
+ * EXTRA BYTES, chosen by the 10-bit field_mask and appended in ascending bit order.  Bits 0..7: rows 0..7 of scores, the fp32's own
+ *   four bytes (the NaN of an unscored point bit for bit; no arithmetic).  Bit 8: weight[c], fp32.  Bit 9: min(hits[c], 65535) as
+ *   uint16 (negative hits: 0).  E = 4 popcount(mask & 0x1FF) + 2 (mask >> 9 & 1): E need not be a multiple of 4.
+ * BAD INDEX.  With point_index, an s outside [0, T_src) reads nothing, gives L_dst zero bytes and adds 1 to n_bad.
+ * STATS.  SN2_LAS_STATS_BYTES of device memory, 8-byte aligned, INITIALISED BY THE CALLER (min = INT32_MAX, max = INT32_MIN, the rest
+ *   0), so several launches accumulate into one file's header:
+ *     byte   0  int32  min[3]         raw X, Y, Z of the records written
+ *     byte  12  int32  max[3]
+ *     byte  24  uint64 by_return[15]  the return number r of byte 14 (3 bits in formats 0-5, 4 bits in 6-10), bin r - 1 for 1 <= r <= 15
+ *     byte 144  uint64 n_bad
+ *     byte 152  uint64 n_scored       records with hits > 0 (hits NULL: none)
+ *   A bad record counts in n_bad alone.  Integer atomics only, after a reduction per wave and per workgroup: the same input gives
+ *   the same bytes.
+ * BOUNDS.  No store touches a byte at or beyond T_out L_dst, no load a source byte at or beyond T_src L_src, no load a score
+ *   column outside [col0, col0 + T_out).
+ * WITHOUT SCORES.  scores, weight and hits may be NULL exactly when field_mask == 0 and class_mode == 0: a pure gather or copy.
+ * ONE launch on `stream`, no synchronisation, nothing read back: safe to capture.  Records of at most
+ * sn2_las_encode_stage_max() = 120 output bytes are composed in LDS, 256 consecutive ones per workgroup, and leave with 16-byte
+ * stores (without point_index the source is staged with 16-byte loads as the decoder stages it; with it each lane fetches its own
+ * record); longer ones are written byte by byte.  sn2_debug_las_encode_form(1) sends every later call through the byte-by-byte
+ * form, 0 restores the rule.
+ * ERRORS, before any launch: SN2_EINVAL on a NULL src / dst / stats, T_out <= 0, T_src <= 0, a compressed file (bit 7 or 6 of
+ * `format`), a format above 10, L_src below the format's least length or above 65535, field_mask bits above bit 9, a class_mode other
+ * than 0 / 1, L_dst above 65535, src_bytes < T_src L_src, dst_bytes < T_out L_dst, src or dst not 16-byte aligned, stats not 8-byte
+ * aligned, T_out > T_src without point_index, col0 < 0 or col0 + T_out > score_stride, a NULL scores / weight / hits with a mask or
+ * class_mode 1, class_mode 1 with class_codes NULL, a code outside 0..255 (0..31 for formats 0-5; unscored_code also -1);
+ * SN2_ELIMIT on T_out or T_src >= 2^31. */
+#define SN2_LAS_STATS_BYTES 160
+#define SN2_LAS_FIELD_MASK_ALL 0x3FF
+int sn2_las_encode(const void *src, size_t src_bytes, int format, int L_src, long T_src, const int *point_index, long T_out,
+                   const float *scores, const float *weight, const int *hits, long score_stride, long col0, int field_mask,
+                   int class_mode, const int *class_codes, int unscored_code, void *dst, size_t dst_bytes, void *stats, void *stream);
+int sn2_las_encode_stage_max(void);
+int sn2_debug_las_encode_form(int form);
+
 /* ---- Parcel cut (csrc/cut.hip; the rule's functions: csrc/cut_rules.h; host side parcel.cut_parcels, las.load_parcels): the points
  * of a LAS tile cut into K parcel clouds by the parcels' polygons buffered by b metres -- what the reference's
  * `parcelles_dataset_20m` holds as one file per parcel (b = 20, inference/prepare_utils.py:148).

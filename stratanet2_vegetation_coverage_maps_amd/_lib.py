@@ -26,7 +26,8 @@ CONSTANTS = {
     "SN2_CV_SLICE_PLOTS": 1024, "SN2_CV_COLUMNS": 30, "SN2_CV_STATS_DOUBLES": 2 * 30 + 2 * 3 * 8 * 8 + 1, "SN2_CV_MAX_PLOTS": 1 << 24,
     "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8, "SN2_POINTS_ACC_WORDS": 9,
     "SN2_ADM_WS_HEAD_WORDS": 32, "SN2_ADM_WS_WORDS_PER_PIXEL": 6,
-    "SN2_LAS_COORDS_REFERENCE": 0, "SN2_LAS_COORDS_HEADER": 1, "SN2_LAS_ROWS": 10, "SN2_CUT_MAX_CELLS": 1 << 22, "SN2_CUT_MAX_ITEMS": 1 << 24,
+    "SN2_LAS_COORDS_REFERENCE": 0, "SN2_LAS_COORDS_HEADER": 1, "SN2_LAS_ROWS": 10, "SN2_LAS_STATS_BYTES": 160, "SN2_LAS_FIELD_MASK_ALL": 0x3FF,
+    "SN2_CUT_MAX_CELLS": 1 << 22, "SN2_CUT_MAX_ITEMS": 1 << 24,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
@@ -257,6 +258,11 @@ SIGNATURES = {
     "sn2_las_decode": [c_void_p, ctypes.c_size_t, c_int, c_int, c_long, c_int, POINTER(c_double), POINTER(c_longlong), c_void_p, c_long,
                        c_long, c_void_p, c_void_p],
     "sn2_debug_las_form": [c_int],
+    # the LAS encoder (csrc/las_write.hip); class_codes is a host pointer
+    "sn2_las_encode": [c_void_p, ctypes.c_size_t, c_int, c_int, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_long,
+                       c_int, c_int, POINTER(c_int), c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    "sn2_las_encode_stage_max": [],
+    "sn2_debug_las_encode_form": [c_int],
     # the parcel cut (csrc/cut.hip); drop is a host pointer, the table holds host and device pointers
     "sn2_cut_ws_words": [POINTER(CutTable), POINTER(ctypes.c_size_t)],
     "sn2_cut_count": [c_void_p, c_void_p, c_void_p, POINTER(CutTable), c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],

@@ -2075,6 +2075,112 @@ def las_decode(raw, point_format: int, record_length: int, T: int, coords: str =
     return out
 
 
+# ---- the LAS encoder (include/strata_hip.h, "LAS point records, written"; csrc/las_write.hip) -----------------------------------
+LAS_FIELDS = ("cov_low_veg", "cov_bare_soil", "cov_medium_veg", "cov_high_veg", "p_low_veg", "p_bare_soil", "p_medium_veg", "p_high_veg",
+              "weight", "hits")          # bit k of field_mask; all fp32 but hits, a uint16
+
+
+def las_field_mask(fields) -> int:
+    """names out of LAS_FIELDS (any order, or "all") -> the 10-bit field_mask of sn2_las_encode"""
+    if fields == "all":
+        return _lib.SN2_LAS_FIELD_MASK_ALL
+    if isinstance(fields, str):
+        fields = (fields,)
+    mask = 0
+    for f in fields:
+        if f not in LAS_FIELDS:
+            raise ValueError(f"fields: {f!r} is none of {', '.join(LAS_FIELDS)}")
+        mask |= 1 << LAS_FIELDS.index(f)
+    return mask
+
+
+def las_extra_bytes(field_mask: int) -> int:
+    """E of the rule: four bytes per fp32 field, two for hits"""
+    return 4 * bin(field_mask & 0x1FF).count("1") + 2 * ((field_mask >> 9) & 1)
+
+
+def las_encode_stage_max() -> int:
+    """sn2_las_encode_stage_max: the longest output record the encoder composes in LDS"""
+    return _lib.host_value("sn2_las_encode_stage_max")
+
+
+class LasEncodeStats:
+    """The statistics block of sn2_las_encode on the device (`buf`, SN2_LAS_STATS_BYTES uint8), initialised here -- min = INT32_MAX,
+    max = INT32_MIN, the counts 0 -- so that several launches can accumulate into it.  `read()` is ONE device-to-host copy and
+    fills mins, maxs (raw integer X, Y, Z; None when nothing was written), by_return (15), n_bad, n_scored."""
+    _LAYOUT = "<3i3i15QQQ"
+
+    def __init__(self, device):
+        import struct
+        assert struct.calcsize(self._LAYOUT) == _lib.SN2_LAS_STATS_BYTES
+        init = struct.pack(self._LAYOUT, *([2 ** 31 - 1] * 3), *([-2 ** 31] * 3), *([0] * 17))
+        self.buf = torch.from_numpy(np.frombuffer(init, dtype=np.uint8).copy()).to(device)
+        self.mins = self.maxs = self.by_return = self.n_bad = self.n_scored = None
+
+    def read(self) -> "LasEncodeStats":
+        import struct
+        v = struct.unpack(self._LAYOUT, self.buf.cpu().numpy().tobytes())
+        some = all(lo <= hi for lo, hi in zip(v[0:3], v[3:6]))
+        self.mins, self.maxs = (tuple(v[0:3]), tuple(v[3:6])) if some else (None, None)
+        self.by_return, self.n_bad, self.n_scored = tuple(v[6:21]), v[21], v[22]
+        return self
+
+
+def las_encode(raw, point_format: int, record_length: int, T_src: int, point_index=None, n_out=None, scores=None, weight=None,
+               hits=None, col0: int = 0, field_mask: int = 0, class_codes=None, unscored: int = -1, out=None, stats=None):
+    """include/strata_hip.h: sn2_las_encode.  raw: uint8 device tensor that starts at the first source record (16-byte aligned, at
+    least T_src * record_length bytes).  point_index: int32 (T_out) source record of every output record, or None = record i.
+    n_out: T_out (default: len(point_index), else T_src).  scores (8, >= col0 + T_out) fp32 with unit inner stride, weight fp32 and
+    hits int32 (>= col0 + T_out): output record i takes column col0 + i; all three None for a pure copy.  class_codes: None = the
+    classification stays, else the four codes of the classes (and `unscored`: the code of a point with hits == 0, -1 = its byte
+    stays).  out: uint8 (>= T_out * L_dst), 16-byte aligned, or None.  stats: a `LasEncodeStats` to accumulate into, or None = a
+    fresh one.  One launch on the current stream, no read-back.  -> (out[:T_out * L_dst], stats)"""
+    _chk(raw, torch.uint8, None, "raw")
+    if raw.dim() != 1:
+        raise ValueError(f"raw: expected a 1-D byte tensor, got {tuple(raw.shape)}")
+    T_src, col0, mask = int(T_src), int(col0), int(field_mask)
+    if point_index is not None:
+        _chk(point_index, I32, None, "point_index")
+        if point_index.dim() != 1 or point_index.device != raw.device:
+            raise ValueError("point_index: expected (T_out,) int32 on raw's device")
+    T_out = int(n_out) if n_out is not None else (point_index.shape[0] if point_index is not None else T_src)
+    if point_index is not None and point_index.shape[0] < T_out:
+        raise ValueError(f"point_index: {point_index.shape[0]} entries for {T_out} records")
+    if mask < 0 or mask > _lib.SN2_LAS_FIELD_MASK_ALL:
+        raise ValueError(f"field_mask: expected 10 bits, got {mask:#x}")
+    L_dst = int(record_length) + las_extra_bytes(mask)
+    given = [t is not None for t in (scores, weight, hits)]
+    if any(given) and not all(given):
+        raise ValueError("scores, weight, hits: all three or none")
+    if not any(given) and (mask or class_codes is not None):
+        raise ValueError("fields or a classification need scores, weight and hits")
+    stride = col0 + max(T_out, 1)
+    if all(given):
+        stride = _chk_rows(scores, F32, 8, col0 + T_out, "scores", align=1)
+        for t, dt, name in ((weight, F32, "weight"), (hits, I32, "hits")):
+            if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.shape[0] < col0 + T_out or t.stride(0) != 1
+                    or t.device != raw.device):
+                raise ValueError(f"{name}: expected (>= {col0 + T_out},) {dt} with unit stride on raw's device")
+        if scores.device != raw.device:
+            raise ValueError("scores: must be on raw's device")
+    if out is None:
+        out = torch.empty(max(T_out * L_dst, 16), dtype=torch.uint8, device=raw.device)
+    _chk(out, torch.uint8, None, "out")
+    if out.dim() != 1 or out.device != raw.device:
+        raise ValueError("out: expected a 1-D byte tensor on raw's device")
+    if stats is None:
+        stats = LasEncodeStats(raw.device)
+    if stats.buf.device != raw.device:
+        raise ValueError("stats: must be on raw's device")
+    if T_out == 0:
+        return out[:0], stats
+    codes = None if class_codes is None else (ctypes.c_int * 4)(*[int(c) for c in class_codes])
+    _call("sn2_las_encode", _ptr(raw), raw.numel(), int(point_format), int(record_length), T_src, _ptr(point_index), T_out,
+          _ptr(scores), _ptr(weight), _ptr(hits), stride, col0, mask, 0 if class_codes is None else 1, codes, int(unscored),
+          _ptr(out), out.numel(), _ptr(stats.buf), _stream())
+    return out[:T_out * L_dst], stats
+
+
 # ---- the parcel cut (include/strata_hip.h, "Parcel cut"; csrc/cut.hip) -------------------------------------------------------------
 CUT_ROW_POINTS = 2048         # points per wave of the count / fill passes (parcel.ROW_POINTS)
 CUT_MAX_TABLE = 1 << 26       # (parcel, row) entries of the count table before rows get longer (parcel.MAX_TABLE)

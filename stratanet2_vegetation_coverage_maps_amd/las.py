@@ -16,10 +16,21 @@ records"), pinned by hand-written records in the tests.  Two coordinate modes:
 An origin keeps centimetres where fp32 alone cannot: at Lambert-93 northings (6.5e6 m) fp32 has a step of 0.5 m.
 Nothing is filtered: the reference's three file-name-specific `clean` filters (utils/load_data.py:187-202) are the caller's, to
 be applied as a mask on the device.  LAZ is refused.
+
+Writing (csrc/las_write.hip; include/strata_hip.h, "LAS point records, written"): the way back for the per-point scores.
+
+    mosaic, plots, scores = predict_parcel_cloud(model, cloud, args, points=True)
+    las.write_scored(src, dst, scores, fields="all", classify=True)       # src's records + class byte + ten extra-byte fields
+    las.write_parcels(tile_paths, cut, dst_paths, result)                   # one file per kept parcel of a ParcelCut
+
+The records are NOT re-encoded from the fp32 cloud: `encode` copies every byte the source record holds and only sets the
+classification and appends extra bytes, in one launch.  The header, the VLRs and the Extra Bytes descriptors are patched on the
+host (`patch_header`, pure `struct`) -- like the record layout OUR reading of the specification: no third-party LAS reader can be
+run beside this package.
 """
 import os
 import struct
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Tuple
 
 import numpy as np
@@ -222,3 +233,272 @@ def load_parcels(paths, shapes, buffer_m: float = 20, coords: str = "reference",
     else:
         pc, cls = load_parcel_clouds(paths, dev, coords, origin, headers=heads), None
     return cut_parcels(pc, shapes, buffer_m, origin=shift, classification=cls, drop_classes=drop)
+
+
+# ---- writing: records annotated on the device (ops.las_encode), the header and the VLRs patched on the host -----------------------
+FIELDS = ops.LAS_FIELDS
+DEFAULT_CLASS_CODES = (3, 2, 4, 5)        # ASPRS standard classes: low vegetation, ground, medium vegetation, high vegetation
+VLR_HEADER_BYTES, EVLR_HEADER_BYTES, DESCRIPTOR_BYTES = 54, 60, 192
+EXTRA_BYTES_USER_ID, EXTRA_BYTES_RECORD_ID = b"LASF_Spec", 4
+_TYPE_BYTES = (0, 1, 1, 2, 2, 4, 4, 8, 8, 4, 8)      # Extra Bytes data types 1..10: u8 i8 u16 i16 u32 i32 u64 i64 f32 f64
+_FIELD_DESCRIPTIONS = ("coverage, low vegetation", "coverage, bare soil", "coverage, medium vegetation", "coverage, high vegetation",
+                       "probability, low vegetation", "probability, bare soil", "probability, medium vegetation",
+                       "probability, high vegetation", "sum of the plots' weights", "plots that sampled the point")      # 31 bytes at most
+
+
+def _scores_of(result):
+    """PointScores -> its finalize(); a PointScoreResult (anything with scores, weight, hits) as it is; None -> three Nones"""
+    if result is None:
+        return None, None, None
+    if hasattr(result, "finalize") and not hasattr(result, "scores"):
+        result = result.finalize()
+    return result.scores, result.weight, result.hits
+
+
+def encode(raw, header: LasHeader, result=None, *, point_index=None, col0: int = 0, n_out=None, fields=(), classify: bool = False,
+           class_codes=DEFAULT_CLASS_CODES, unscored=None, out=None, stats=None):
+    """Source records annotated with per-point scores, on the device, in one launch (ops.las_encode) -> (records uint8 on the
+    device: n_out records of header.record_length + E bytes, `ops.LasEncodeStats`).
+
+    raw: the source records as the file holds them (`read_records`), header.n_points of them.  result: an
+    `inference.PointScoreResult` or `PointScores` (None: a pure copy or gather).  Output record i is source record point_index[i]
+    (int32 on the device; None: record i) with score column col0 + i.  fields: names out of `FIELDS`, or "all": appended as extra
+    bytes in FIELDS' order, fp32 but `hits`, a uint16 that saturates at 65535.  classify: the classification becomes
+    class_codes[argmax of the four class probabilities] (ties to the lowest index) where hits > 0 and `unscored` elsewhere (None:
+    the source's class stays); formats 0-5 keep their three flag bits and take codes up to 31.  stats: a LasEncodeStats to
+    accumulate into (several launches for one file)."""
+    scores, weight, hits = _scores_of(result)
+    with torch.cuda.device(raw.device):
+        return ops.las_encode(raw, header.point_format, header.record_length, header.n_points, point_index=point_index, n_out=n_out,
+                              scores=scores, weight=weight, hits=hits, col0=col0, field_mask=ops.las_field_mask(fields),
+                              class_codes=tuple(class_codes) if classify else None, unscored=-1 if unscored is None else int(unscored),
+                              out=out, stats=stats)
+
+
+def read_records(path, device=None):
+    """-> (raw, header): the point-record block of a LAS file on the device as the file holds it (one pinned host-to-device copy,
+    what `load_las` does before it decodes) and its `read_header`."""
+    h = read_header(path)
+    dev = _device(device)
+    raw, pinned = _upload_points(path, h, dev)
+    torch.cuda.current_stream(dev).synchronize()          # the staging buffer goes away with this call
+    return raw, h
+
+
+def _descriptor(data_type: int, name: bytes, options: int = 0, description: bytes = b"") -> bytes:
+    """One 192-byte Extra Bytes descriptor: reserved[2], data_type, options, name[32], unused[4], no_data[24], min[24], max[24],
+    scale[24], offset[24], description[32]"""
+    d = bytearray(DESCRIPTOR_BYTES)
+    name, description = name[:31], description[:31]        # both NUL-terminated in their 32 bytes
+    d[2], d[3] = data_type, options
+    d[4:4 + len(name)] = name
+    d[160:160 + len(description)] = description
+    return bytes(d)
+
+
+def _descriptor_bytes(d: bytes) -> int:
+    """the bytes of a record that a descriptor covers: type 0 holds its size in `options`, 11..30 are 2- and 3-tuples of 1..10"""
+    t = d[2]
+    if t == 0:
+        return d[3]
+    if t > 30:
+        raise ValueError(f"Extra Bytes descriptor with data type {t}")
+    return (1 + (t - 1) // 10) * _TYPE_BYTES[(t - 1) % 10 + 1]
+
+
+def extra_bytes_descriptors(field_mask: int) -> bytes:
+    """the descriptors of the appended fields, in the order of the bytes: data type 9 (fp32), 3 (uint16) for hits"""
+    return b"".join(_descriptor(3 if k == 9 else 9, FIELDS[k].encode(), 0, _FIELD_DESCRIPTIONS[k].encode())
+                    for k in range(10) if (field_mask >> k) & 1)
+
+
+def _walk_vlrs(block: bytes, n: int):
+    """(start, end) of each of the n VLRs at the head of `block`"""
+    at, spans = 0, []
+    for _ in range(n):
+        if at + VLR_HEADER_BYTES > len(block):
+            raise ValueError("the VLRs run past the offset to the point data")
+        end = at + VLR_HEADER_BYTES + struct.unpack_from("<H", block, at + 20)[0]
+        if end > len(block):
+            raise ValueError("the VLRs run past the offset to the point data")
+        spans.append((at, end))
+        at = end
+    return spans
+
+
+def patch_header(src, n_points: int, field_mask: int = 0, stats=None):
+    """The frame of a written file around its point records -> (head, tail): `head` = the source's public header, patched, its
+    VLRs (the CRS among them) verbatim, the Extra Bytes VLR, and whatever else the source holds before its points; `tail` = the
+    source's EVLRs verbatim.  src: a path or the file's bytes.  n_points records of the source's length + E follow `head`.
+    stats: a read `ops.LasEncodeStats` (extents and by-return counts; None: zeros).
+
+    Patched: offset to points (96), number of VLRs (100), record length (105), legacy count (107) and legacy by-return (111) --
+    both zero where the source's legacy count was zero in a 1.4 file --, the extents at 179 (max X, min X, max Y, min Y, max Z, min
+    Z as raw * scale + offset in fp64); for 1.4 the first-EVLR offset (235), the 64-bit count (247) and the fifteen by-return counts
+    (255).  Extra Bytes VLR (user id LASF_Spec, record id 4): the source's is extended; source extra bytes that no descriptor
+    covers get a data-type-0 descriptor first, so ours line up with the appended bytes.  This is OUR reading of the
+    specification (tables 3, 4, 24-26 of LAS 1.4 R15); waveform packets are not followed."""
+    h = read_header(src)
+    E = ops.las_extra_bytes(field_mask)
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        blob = bytes(src)
+        front = blob[:h.offset_to_points]
+    else:
+        blob = None
+        with open(src, "rb") as f:
+            front = f.read(h.offset_to_points)
+    head = bytearray(front[:h.header_size])
+    block = front[h.header_size:]
+    n_vlr = struct.unpack_from("<I", head, 100)[0]
+    spans = _walk_vlrs(block, n_vlr)
+    vlrs = [block[a:b] for a, b in spans]
+    padding = block[spans[-1][1] if spans else 0:]
+    if E:
+        own = [i for i, v in enumerate(vlrs) if v[2:18].rstrip(b"\0") == EXTRA_BYTES_USER_ID and
+               struct.unpack_from("<H", v, 18)[0] == EXTRA_BYTES_RECORD_ID]
+        payload = vlrs[own[0]][VLR_HEADER_BYTES:] if own else b""
+        if len(payload) % DESCRIPTOR_BYTES:
+            raise ValueError("the source's Extra Bytes VLR is no whole number of descriptors")
+        covered = sum(_descriptor_bytes(payload[i:i + DESCRIPTOR_BYTES]) for i in range(0, len(payload), DESCRIPTOR_BYTES))
+        have = h.record_length - ops.las_record_min_length(h.point_format)
+        if covered > have:
+            raise ValueError(f"the source's Extra Bytes descriptors cover {covered} bytes, its records hold {have}")
+        gap = have - covered
+        while gap:                                         # `options` is one byte
+            payload += _descriptor(0, b"undocumented", min(gap, 255), b"the source's undocumented extra bytes")
+            gap -= min(gap, 255)
+        payload += extra_bytes_descriptors(field_mask)
+        if len(payload) > 65535:
+            raise ValueError("more Extra Bytes descriptors than one VLR holds")
+        if own:
+            v = bytearray(vlrs[own[0]][:VLR_HEADER_BYTES])
+        else:
+            v = bytearray(VLR_HEADER_BYTES)
+            v[2:2 + len(EXTRA_BYTES_USER_ID)] = EXTRA_BYTES_USER_ID
+            struct.pack_into("<H", v, 18, EXTRA_BYTES_RECORD_ID)
+            v[22:22 + 11] = b"Extra Bytes"
+        struct.pack_into("<H", v, 20, len(payload))
+        if own:
+            vlrs[own[0]] = bytes(v) + payload
+        else:
+            vlrs.append(bytes(v) + payload)
+    body = b"".join(vlrs) + padding
+    offset_to_points = h.header_size + len(body)
+    L_dst = h.record_length + E
+    is14 = h.version >= (1, 4) and h.header_size >= HEADER_BYTES_1_4
+    src_legacy = struct.unpack_from("<I", head, 107)[0]
+    by_return = (0,) * 15 if stats is None or stats.by_return is None else tuple(stats.by_return)
+    legacy = not (is14 and src_legacy == 0) and n_points < 2 ** 32 and max(by_return[:5]) < 2 ** 32
+    if not legacy and not is14:
+        raise ValueError(f"{n_points} points do not fit the 32-bit count of a LAS {h.version[0]}.{h.version[1]} header")
+    struct.pack_into("<II", head, 96, offset_to_points, len(vlrs))
+    struct.pack_into("<H", head, 105, L_dst)
+    struct.pack_into("<I5I", head, 107, *((n_points,) + by_return[:5] if legacy else (0,) * 6))
+    ext = [0.0] * 6
+    if stats is not None and stats.mins is not None:
+        for a in range(3):
+            ext[2 * a] = float(np.float64(stats.maxs[a]) * np.float64(h.scale[a]) + np.float64(h.offset[a]))
+            ext[2 * a + 1] = float(np.float64(stats.mins[a]) * np.float64(h.scale[a]) + np.float64(h.offset[a]))
+    struct.pack_into("<6d", head, 179, *ext)
+    tail = b""
+    if is14:
+        first_evlr, n_evlr = struct.unpack_from("<QI", head, 235)
+        if n_evlr:
+            if first_evlr < h.offset_to_points + h.n_bytes:
+                raise ValueError("the source's EVLRs start inside its point records")
+            if blob is not None:
+                tail = blob[first_evlr:]
+            else:
+                with open(src, "rb") as f:
+                    f.seek(first_evlr)
+                    tail = f.read()
+        struct.pack_into("<Q", head, 235, offset_to_points + n_points * L_dst if n_evlr else 0)
+        struct.pack_into("<Q15Q", head, 247, n_points, *by_return)
+    return bytes(head) + body, tail
+
+
+def _to_host(records: torch.Tensor) -> memoryview:
+    """the device bytes on the host: ONE device-to-host copy into pinned memory"""
+    pinned = torch.empty(max(records.numel(), 1), dtype=torch.uint8, pin_memory=True)
+    pinned[:records.numel()].copy_(records, non_blocking=True)
+    torch.cuda.current_stream(records.device).synchronize()
+    return memoryview(pinned.numpy())[:records.numel()]
+
+
+def _write_file(dst_path, head: bytes, records: memoryview, tail: bytes):
+    with open(dst_path, "wb") as f:
+        f.write(head)
+        f.write(records)
+        f.write(tail)
+
+
+def write_scored(src_path, dst_path, result, device=None, **kw):
+    """The whole-file case: src_path's records with `result`'s scores -- column i is record i, as `predict_parcel_cloud(load_las(
+    src_path), points=True)` gives them -- to dst_path.  Upload, `encode` (kw: fields, classify, class_codes, unscored, ...), one
+    device-to-host copy of the block and one of the statistics, then the file.  -> the read LasEncodeStats"""
+    raw, h = read_records(src_path, device)
+    records, stats = encode(raw, h, result, **kw)
+    n = records.numel() // (h.record_length + ops.las_extra_bytes(ops.las_field_mask(kw.get("fields", ()))))
+    host = _to_host(records)
+    stats.read()
+    if stats.n_bad:
+        raise ValueError(f"write_scored: {stats.n_bad} point_index entries outside the source's {h.n_points} records")
+    head, tail = patch_header(src_path, n, ops.las_field_mask(kw.get("fields", ())), stats)
+    _write_file(dst_path, head, host, tail)
+    return stats
+
+
+def write_parcels(tile_paths, cut, dst_paths, result=None, device=None, **kw):
+    """One LAS file per kept parcel of a `parcel.ParcelCut`, with the tiles' exact integer coordinates: parcel k's records are the
+    source records cut.point_index[point_start[k] : point_start[k+1]] of the arena of the tiles READ (tile_paths, in the order
+    `load_parcels` read them), its score columns the same range of `result` (what `predict_parcels(..., points=True)` returns over
+    cut.clouds; None: no scores, a pure gather).  The header, VLRs and EVLRs are the first tile's.  The tiles must agree in point
+    format, record length, scale and offset: ValueError names the first that differs.  A point_index entry outside the tiles
+    raises ValueError after the parcel's one read.  -> the parcels' read LasEncodeStats"""
+    tile_paths, dst_paths = list(tile_paths), list(dst_paths)
+    if not tile_paths:
+        raise ValueError("write_parcels: no tile")
+    K = 0 if cut.clouds is None else cut.clouds.K
+    if len(dst_paths) != K:
+        raise ValueError(f"write_parcels: {len(dst_paths)} paths for {K} kept parcels")
+    heads = [read_header(p) for p in tile_paths]
+    for p, h in zip(tile_paths[1:], heads[1:]):
+        for what in ("point_format", "record_length", "scale", "offset"):
+            if getattr(h, what) != getattr(heads[0], what):
+                raise ValueError(f"write_parcels: {p} differs from {tile_paths[0]} in {what}: {getattr(h, what)} != {getattr(heads[0], what)}")
+    if K == 0:
+        return []
+    total = sum(h.n_points for h in heads)
+    if total >= 2 ** 31:
+        raise ValueError("write_parcels: at most 2^31 - 1 points in all")
+    dev = cut.point_index.device if device is None else torch.device(device)
+    h0 = heads[0]
+    arena = torch.empty(max(total * h0.record_length, 16), dtype=torch.uint8, device=dev)
+    pinned = torch.empty(max(max(h.n_bytes for h in heads), 16), dtype=torch.uint8, pin_memory=True)
+    at = 0
+    for p, h in zip(tile_paths, heads):
+        if h.n_bytes:
+            view = memoryview(pinned.numpy())[:h.n_bytes]
+            with open(p, "rb") as f:
+                f.seek(h.offset_to_points)
+                got = f.readinto(view)
+            if got != h.n_bytes:
+                raise ValueError(f"{p}: read {got} of {h.n_bytes} bytes of point records")
+            arena[at:at + h.n_bytes].copy_(pinned[:h.n_bytes], non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()  # the next tile overwrites the staging buffer
+            at += h.n_bytes
+    h_all = replace(h0, n_points=total)
+    mask = ops.las_field_mask(kw.get("fields", ()))
+    start = np.asarray(cut.clouds.point_start, dtype=np.int64)
+    out = []
+    for k, dst in enumerate(dst_paths):
+        p0, p1 = int(start[k]), int(start[k + 1])
+        records, stats = encode(arena[:total * h0.record_length], h_all, result, point_index=cut.point_index[p0:p1], col0=p0, **kw)
+        host = _to_host(records)
+        stats.read()
+        if stats.n_bad:
+            raise ValueError(f"write_parcels: parcel {k}: {stats.n_bad} point_index entries outside the tiles' {total} records")
+        head, tail = patch_header(tile_paths[0], p1 - p0, mask, stats)
+        _write_file(dst, head, host, tail)
+        out.append(stats)
+    return out
