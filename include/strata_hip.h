@@ -1046,6 +1046,65 @@ int sn2_las_encode(const void *src, size_t src_bytes, int format, int L_src, lon
 int sn2_las_encode_stage_max(void);
 int sn2_debug_las_encode_form(int form);
 
+/* ---- GeoTIFF image data (csrc/tiff_pack.hip; the rule's functions: csrc/tiff_rules.h; host side geotiff.pack, geotiff.write_atlas,
+ * write_parcel, write_bands): the band arena of a mosaic atlas turned into the bytes its map files hold after their headers -- what
+ * the reference's merge_geotiff_rasters (inference/geotiff_raster.py:199-235) leaves to GDAL.  The header (IFD, GeoKeys, GDAL
+ * metadata) is assembled on the host with `struct` (geotiff.py); the layout is OUR reading of TIFF 6.0, TIFF Technical Note 3 and
+ * the GeoTIFF key directory, pinned by files typed out by hand and by libtiff reading them back (tests/test_geotiff_host.py).
+ * UNPINNED there: the text of the GDALMetadata tag (42112: band descriptions, STATISTICS_*), a reading of GDAL's format.
+ *
+ * SOURCE.  Canvas k has H x W pixels and C bands, 1 <= C <= SN2_MOSAIC_CROP_MAX_BANDS: the (C,H,W) view of a C-band arena at word
+ *   C base_k -- the atlas layout and the atlas canvas table above, as they are.
+ * IMAGE DATA BLOCK.  Exactly the bytes an uncompressed little-endian TIFF holds after its header, in one of two layouts:
+ *                          SN2_TIFF_LAYOUT_BAND (PlanarConfiguration 2)    SN2_TIFF_LAYOUT_PIXEL (PlanarConfiguration 1)
+ *     rows                 q = c H + r                                     q = r
+ *     floats per row wc    W                                               W C
+ *     float f of a row     bands[c][r][f]                                  bands[f % C][r][f / C]
+ *     stride               1                                               C
+ *   Row q occupies the 4 wc bytes at data_base_k + q 4 wc.
+ * PREDICTOR 1.  Byte j of a row is byte j % 4 of float j / 4: the fp32's own bytes -- NaN payloads, -0 and denormals bit for bit, no
+ *   arithmetic.
+ * PREDICTOR 3, the floating-point predictor of TIFF Technical Note 3 as libtiff's fpDiff applies it on a little-endian host:
+ *   t[j] = byte 3 - j / wc of float j % wc (plane 0 holds the sign and exponent bytes); out[j] = t[j] for j < stride, otherwise
+ *   (t[j] - t[j - stride]) mod 256.  Each row on its own: nothing carries from one row to the next.
+ *   PINNED for stride 1 (libtiff reads the files back bit for bit).  UNPINNED: stride C of the PIXEL layout -- no reader on hand
+ *   opens multi-sample float files; it rests on bytes typed out by hand and on the reading of fpDiff stated here.
+ * STATISTICS.  Per (k, c) SN2_TIFF_STATS_BYTES: uint64 count of the band's pixels that are not NaN; uint32 key of the smallest,
+ *   uint32 key of the largest of them, key = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) on the fp32's bit pattern, compared as
+ *   uint32: -0 < +0, the infinities are ordinary values.  bits = key ^ (key >> 31 ? 0x80000000 : 0xFFFFFFFF) gives the fp32 back.
+ *   INITIALISED BY THE CALLER on the stream: count 0, minimum 0xFFFFFFFF, maximum 0 -- an all-NaN band keeps them.  Integer
+ *   atomics only, after a reduction per wave and per workgroup: the same input gives the same bytes.
+ * PLACE TABLE.  (K+1) rows of SN2_TIFF_PLACE_COLS int64, written by sn2_tiff_place_table (host arithmetic, no device) from the
+ *   canvas table and K flags (skip[k] != 0: no file; skip NULL: none flagged):
+ *     [0] data_base_k, a multiple of 16: the blocks in canvas order, each rounded up to 16 bytes  [1] 1 = no file: no bytes, no
+ *     workgroups  [2] the exclusive prefix of the canvases' workgroups  [3] the block's bytes C H W 4 (0 without a file);
+ *     row K: [0] the offset of the statistics block, K C SN2_TIFF_STATS_BYTES bytes, canvas-major  [1] 0  [2] the workgroups in all
+ *     [3] the bytes in all.  ONE staging buffer holds every block and then the statistics: one copy fetches everything.  The padding
+ *   between blocks is never written.  Taken twice, `place_host` (checked before any launch) and `place_dev`, like the canvas table.
+ *   The cut into workgroups follows the kernel form, so a table is made and used under the same sn2_debug_tiff_pack_form.
+ * ONE launch on `stream` for all K canvases, no synchronisation, nothing read back: safe to capture.  Rows of at most
+ * sn2_tiff_pack_stage_max() = 16384 bytes (4 wc) are STAGED: a workgroup gathers as many consecutive image rows as fit 16 KiB
+ * of LDS from the C planes with coalesced loads, in row order, composes the byte planes and differences from LDS sixteen bytes at
+ * a time and stores 16-byte words (17 KiB with the skew that keeps the lanes off each other's banks: eight to a CU's 160 KiB).
+ * Longer rows take the DIRECT form: 16 KiB of a row
+ * per workgroup, every output byte a function of at most two source floats read from memory.  Both give identical bytes;
+ * sn2_debug_tiff_pack_form(1) sends every later table and call through the direct form, 0 restores the rule.
+ * wave64; vector stores only; no floating-point atomics; no cross-workgroup waiting.
+ * ERRORS, before any launch: SN2_EINVAL on a NULL pointer, K <= 0, C outside 1..SN2_MOSAIC_CROP_MAX_BANDS, an unknown layout or
+ * predictor (1 or 3), dst not 16-byte aligned or a statistics offset that is no multiple of 16, a canvas table that is not
+ * sn2_atlas_canvas_table's, a place table that is not sn2_tiff_place_table's, dst_bytes below the table's total; SN2_ELIMIT on a
+ * block or a total of 2^32 bytes or more (classic TIFF cannot address it) or more than 2^31 - 1 workgroups. */
+#define SN2_TIFF_LAYOUT_BAND 0
+#define SN2_TIFF_LAYOUT_PIXEL 1
+#define SN2_TIFF_PLACE_COLS 4
+#define SN2_TIFF_STATS_BYTES 16
+int sn2_tiff_place_table(int C, int K, const long long *canvas_host, int layout, const unsigned char *skip, long long *place);
+int sn2_tiff_pack(const float *bands, int C, int K, const long long *canvas_host, const long long *canvas_dev,
+                  const long long *place_host, const long long *place_dev, int layout, int predictor, void *dst, size_t dst_bytes,
+                  void *stream);
+int sn2_tiff_pack_stage_max(void);
+int sn2_debug_tiff_pack_form(int form);
+
 /* ---- Parcel cut (csrc/cut.hip; the rule's functions: csrc/cut_rules.h; host side parcel.cut_parcels, las.load_parcels): the points
  * of a LAS tile cut into K parcel clouds by the parcels' polygons buffered by b metres -- what the reference's
  * `parcelles_dataset_20m` holds as one file per parcel (b = 20, inference/prepare_utils.py:148).

@@ -27,6 +27,7 @@ CONSTANTS = {
     "SN2_CV_WS_SLICE_WORDS": 2 * 30 + 32 + 2 * 3 * 8 * 8, "SN2_POINTS_ACC_WORDS": 9,
     "SN2_ADM_WS_HEAD_WORDS": 32, "SN2_ADM_WS_WORDS_PER_PIXEL": 6,
     "SN2_LAS_COORDS_REFERENCE": 0, "SN2_LAS_COORDS_HEADER": 1, "SN2_LAS_ROWS": 10, "SN2_LAS_STATS_BYTES": 160, "SN2_LAS_FIELD_MASK_ALL": 0x3FF,
+    "SN2_TIFF_LAYOUT_BAND": 0, "SN2_TIFF_LAYOUT_PIXEL": 1, "SN2_TIFF_PLACE_COLS": 4, "SN2_TIFF_STATS_BYTES": 16,
     "SN2_CUT_MAX_CELLS": 1 << 22, "SN2_CUT_MAX_ITEMS": 1 << 24,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
@@ -263,6 +264,11 @@ SIGNATURES = {
                        c_int, c_int, POINTER(c_int), c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     "sn2_las_encode_stage_max": [],
     "sn2_debug_las_encode_form": [c_int],
+    # the GeoTIFF band packer (csrc/tiff_pack.hip); canvas_host, skip, place and place_host are host pointers
+    "sn2_tiff_place_table": [c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
+    "sn2_tiff_pack": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
+    "sn2_tiff_pack_stage_max": [],
+    "sn2_debug_tiff_pack_form": [c_int],
     # the parcel cut (csrc/cut.hip); drop is a host pointer, the table holds host and device pointers
     "sn2_cut_ws_words": [POINTER(CutTable), POINTER(ctypes.c_size_t)],
     "sn2_cut_count": [c_void_p, c_void_p, c_void_p, POINTER(CutTable), c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],

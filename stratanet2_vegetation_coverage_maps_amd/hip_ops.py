@@ -2181,6 +2181,103 @@ def las_encode(raw, point_format: int, record_length: int, T_src: int, point_ind
     return out[:T_out * L_dst], stats
 
 
+# ---- the GeoTIFF band packer (include/strata_hip.h, "GeoTIFF image data"; csrc/tiff_pack.hip) --------------------------------------
+TIFF_LAYOUTS = {"band": _lib.SN2_TIFF_LAYOUT_BAND, "pixel": _lib.SN2_TIFF_LAYOUT_PIXEL}
+
+
+def tiff_pack_stage_max() -> int:
+    """sn2_tiff_pack_stage_max: the longest row, in bytes (4 wc), the packer stages in LDS"""
+    return _lib.host_value("sn2_tiff_pack_stage_max")
+
+
+def tiff_layout(interleave) -> int:
+    if interleave not in TIFF_LAYOUTS:
+        raise ValueError(f"interleave: expected 'band' or 'pixel', got {interleave!r}")
+    return TIFF_LAYOUTS[interleave]
+
+
+def tiff_place_table(canvas_table: np.ndarray, C: int, layout: int, skip=None) -> np.ndarray:
+    """sn2_tiff_place_table: the (K+1, SN2_TIFF_PLACE_COLS) int64 place table of the K canvases of a canvas table (host) for C bands
+    in `layout`; skip: None or K flags, True = no file.  Host arithmetic, no device.  SN2_EINVAL / SN2_ELIMIT raise."""
+    canvas_table = np.ascontiguousarray(canvas_table, dtype=np.int64)
+    K = len(canvas_table) - 1
+    flags = None
+    if skip is not None:
+        flags = np.ascontiguousarray(np.asarray(skip, dtype=bool).reshape(-1).astype(np.uint8))
+        if len(flags) != K:
+            raise ValueError(f"skip: expected one flag per canvas ({K}), got {len(flags)}")
+    place = np.zeros((K + 1, _lib.SN2_TIFF_PLACE_COLS), dtype=np.int64)
+    check(_lib.load().sn2_tiff_place_table(int(C), K, canvas_table.ctypes.data, int(layout), None if flags is None else flags.ctypes.data,
+                                           place.ctypes.data), "sn2_tiff_place_table")
+    return place
+
+
+def tiff_key_bits(key: np.ndarray) -> np.ndarray:
+    """the fp32 bit pattern of a statistics key (csrc/tiff_rules.h: tiff_key_bits)"""
+    key = np.asarray(key, dtype=np.uint32)
+    return key ^ np.where(key >> 31, np.uint32(0x80000000), np.uint32(0xFFFFFFFF)).astype(np.uint32)
+
+
+class TiffPacked:
+    """What sn2_tiff_pack leaves on the device: `buf` (uint8) holds every canvas's image data block at place[k, 0] and then the
+    statistics.  `read()` is the ONE device-to-host copy; after it block(k) is canvas k's bytes (a uint8 view of the host copy, None
+    without a file), counts (K,C) uint64, min_bits / max_bits (K,C) uint32 the fp32 bit patterns of the extrema (meaningless where
+    the count is 0) and minimum / maximum (K,C) fp32 (NaN where the count is 0)."""
+
+    def __init__(self, buf, place, C, K, layout, predictor):
+        self.buf, self.place, self.C, self.K, self.layout, self.predictor = buf, place, C, K, layout, predictor
+        self.total = int(place[K, 3])
+        self.host = self.counts = self.min_bits = self.max_bits = self.minimum = self.maximum = None
+
+    def read(self) -> "TiffPacked":
+        if self.host is None:
+            self.host = self.buf[:self.total].cpu().numpy()
+            s = self.host[int(self.place[self.K, 0]):self.total].view(np.uint32).reshape(self.K, self.C, 4)
+            self.counts = np.ascontiguousarray(s[:, :, 0:2]).view(np.uint64).reshape(self.K, self.C)
+            self.min_bits, self.max_bits = tiff_key_bits(s[:, :, 2]), tiff_key_bits(s[:, :, 3])
+            some = self.counts > 0
+            self.minimum = np.where(some, self.min_bits.view(np.float32), np.float32(np.nan))
+            self.maximum = np.where(some, self.max_bits.view(np.float32), np.float32(np.nan))
+        return self
+
+    def block(self, k: int):
+        if self.host is None:
+            raise ValueError("TiffPacked.block: read() first")
+        if self.place[k, 1]:
+            return None
+        b = int(self.place[k, 0])
+        return self.host[b:b + int(self.place[k, 3])]
+
+
+def tiff_pack(band_arena, C: int, table: AtlasTable, layout: int = 0, predictor: int = 1, skip=None, out=None) -> TiffPacked:
+    """include/strata_hip.h: sn2_tiff_pack.  band_arena: the (C pixels,) fp32 arena of `table`'s canvases, left as it is.  skip: None or
+    K flags, True = that canvas gets no file.  out: None or a 1-D uint8 device tensor, 16-byte aligned, of at least the place
+    table's total.  The statistics block is initialised here, on the stream; then ONE launch, no read-back."""
+    C = int(C)
+    _arena(band_arena, C, table, "band_arena")
+    if table.dev is None or table.dev.device != band_arena.device:
+        raise ValueError("table: needs its device copy on the arena's device")
+    if predictor not in (1, 3):
+        raise ValueError(f"predictor: expected 1 or 3, got {predictor!r}")
+    place = tiff_place_table(table.host, C, layout, skip)
+    K = table.K
+    total, stats_off = int(place[K, 3]), int(place[K, 0])
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=band_arena.device)
+    _chk(out, torch.uint8, None, "out")
+    if out.dim() != 1 or out.device != band_arena.device or out.numel() < total:
+        raise ValueError(f"out: expected a 1-D byte tensor of at least {total} bytes on the arena's device")
+    stats = out[stats_off:total].view(torch.int32).view(K * C, 4)            # count (two words), key of the minimum, of the maximum
+    stats.zero_()
+    stats[:, 2].fill_(-1)
+    place_dev = torch.from_numpy(place).to(band_arena.device)
+    _call("sn2_tiff_pack", _ptr(band_arena), C, K, table.host.ctypes.data, _ptr(table.dev), place.ctypes.data, _ptr(place_dev),
+          int(layout), int(predictor), _ptr(out), out.numel(), _stream())
+    packed = TiffPacked(out, place, C, K, int(layout), int(predictor))
+    packed._place_dev = place_dev                                            # alive until the launch has run
+    return packed
+
+
 # ---- the parcel cut (include/strata_hip.h, "Parcel cut"; csrc/cut.hip) -------------------------------------------------------------
 CUT_ROW_POINTS = 2048         # points per wave of the count / fill passes (parcel.ROW_POINTS)
 CUT_MAX_TABLE = 1 << 26       # (parcel, row) entries of the count table before rows get longer (parcel.MAX_TABLE)
