@@ -685,8 +685,9 @@ int sn2_debug_head_backward_occupancy(int bf16, int with_loss);
 /* After sn2_head_backward: the gradients of the BatchNorm whose output the head reads (FP1's), obtained from lin1's weight
  * and bias gradients instead of a pass over all rows (derivation in head.hip).  gamma, beta, mean, invstd: that BatchNorm's
  * parameters and saved batch statistics; dgamma, dbeta: ACCUMULATED, complete on return.  *ok (device int) = 1 when the
- * identity was used, 0 when some |gamma| <= 1e-4 made it unusable and the kernel summed over the rows itself (p->f = the
- * BatchNorm's input rows, p->dy = the gradient of its output).  Hand `ok` to the producer's sn2_fp_backward as bn_sums_done. */
+ * identity was used, 0 when some channel's |gamma| <= 1e-4 or |beta| > 64 |gamma| made it unusable and the kernel summed
+ * over the rows itself (p->f = the BatchNorm's input rows, p->dy = the gradient of its output).  Hand `ok` to the producer's
+ * sn2_fp_backward as bn_sums_done. */
 int sn2_head_bn_sums(const sn2_head *p, const float *gamma, const float *beta, const float *mean, const float *invstd,
                      float *dgamma, float *dbeta, int *ok, void *stream);
 /* The same for the BatchNorm whose output an FP block interpolates (its columns 0..ca-1), after that block's
