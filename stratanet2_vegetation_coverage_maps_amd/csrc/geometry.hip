@@ -78,19 +78,49 @@ __device__ __forceinline__ int fps_live_count(const int* __restrict__ n_live, in
     n = n < 1 ? 1 : (n > N ? N : n);
     return __builtin_amdgcn_readfirstlane(n);
 }
+// A plot's output rows: idx (B, M), cpos_soa (B, 3, M), cpos_aos (B * M, 4).  THE statement of how a sample leaves: the bucketed
+// kernels and fps_fill_zero all write through `emit`.  A sample's `code` is its original index, or -1 - its sorted position where
+// a kernel defers the load of ord[] (`translate` at its end: in the sampling loop it would sit on the selecting wave's critical path).
+struct fps_rows {
+    int* idx_out;
+    float *cpos_soa, *cpos_aos;
+    int b, M;
+    // (the stores go through __restrict__ parameters: written on the members, which carry no such promise, they cost
+    // fps_bucket_kernel eight VGPRs -- <128, 16> a wave per SIMD -- and changed the registers of every fps_kernel)
+    static __device__ __forceinline__ void emit_to(int* __restrict__ idx_out, float* __restrict__ cpos_soa, float* __restrict__ cpos_aos,
+                                                   int b, int M, int at, float x, float y, float z, int code) {
+        idx_out[(size_t)b * M + at] = code;
+        cpos_soa[((size_t)b * 3 + 0) * M + at] = x;
+        cpos_soa[((size_t)b * 3 + 1) * M + at] = y;
+        cpos_soa[((size_t)b * 3 + 2) * M + at] = z;
+        reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M + at] = make_float4(x, y, z, 0.f);
+    }
+    __device__ __forceinline__ void emit(int at, float x, float y, float z, int code) const {
+        emit_to(idx_out, cpos_soa, cpos_aos, b, M, at, x, y, z, code);
+    }
+    // by all `nt` threads of the workgroup, behind a barrier.  log = nullptr: the samples are out, their codes become indices;
+    // log = the M samples (x, y, z, code) that fps_cluster_kernel kept in LDS: they leave here
+    __device__ __forceinline__ void translate(const int* __restrict__ ord, int tid, int nt, const float4* log) const {
+        for (int i = tid; i < M; i += nt) {
+            if (log) {
+                const float4 e = log[i];
+                const int code = __float_as_int(e.w);
+                emit(i, e.x, e.y, e.z, code < 0 ? ord[-1 - code] : code);
+            } else {
+                const int v = idx_out[(size_t)b * M + i];
+                if (v < 0) idx_out[(size_t)b * M + i] = ord[-1 - v];
+            }
+        }
+    }
+};
 // The plot's maximum reached 0 with `from` samples out: every point is at distance 0, the arg-max of an all-zero row is index 0,
 // and so is every later sample.  Called by all `nt` threads of the workgroup that writes the plot's samples.
 __device__ __forceinline__ void fps_fill_zero(const float* __restrict__ px, int N, int M, int b, int from, int tid, int nt,
                                               int* __restrict__ idx_out, float* __restrict__ cpos_soa,
                                               float* __restrict__ cpos_aos, int* __restrict__ n_live_out) {
     const float x0 = px[0], y0 = px[N], z0 = px[2 * (size_t)N];
-    for (int i = from + tid; i < M; i += nt) {
-        idx_out[(size_t)b * M + i] = 0;
-        cpos_soa[((size_t)b * 3 + 0) * M + i] = x0;
-        cpos_soa[((size_t)b * 3 + 1) * M + i] = y0;
-        cpos_soa[((size_t)b * 3 + 2) * M + i] = z0;
-        reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M + i] = make_float4(x0, y0, z0, 0.f);
-    }
+    const fps_rows out = {idx_out, cpos_soa, cpos_aos, b, M};
+    for (int i = from + tid; i < M; i += nt) out.emit(i, x0, y0, z0, 0);
     if (tid == 0 && n_live_out) n_live_out[b] = from;
 }
 template <int PPT, int T, bool ZLDS>
@@ -350,8 +380,7 @@ __global__ __launch_bounds__(NT) void spatial_order_chunk_kernel(const float* __
 
 // the plot's Morton order, sorted table and cell starts (+ the zeroed exchange area)
 static void launch_spatial_order(const float* pos, int B, int N, int* order, float4* sorted, int* grid, unsigned* xchg,
-                                 unsigned* ctl, const int* nl, hipStream_t st) {
-    int* rank = reinterpret_cast<int*>(ctl + FPS_CTL_WORDS);          // the last B*N words of the workspace
+                                 unsigned* ctl, int* rank, const int* nl, hipStream_t st) {
     if (sn2_small_sort_wg(B) && N <= 16 * 1024)          // many plots: 256 threads per plot (common.h)
         hipLaunchKernelGGL((spatial_order_chunk_kernel<16, 256>), dim3(B), dim3(256), 0, st, pos, N, order, sorted, grid, xchg, ctl, rank, nl);
     else if (N <= 8 * 1024)
@@ -401,6 +430,213 @@ extern "C" int sn2_debug_fps_stamps(unsigned long long* out) {
 #define STAMP(var)
 #endif
 
+// wave64 max with the DPP modifier fused into v_max_f32 (the update_dpp builtin of wave_max_dpp costs a v_mov, a v_mov_dpp, an
+// s_nop and the v_max per step: 24 instructions per reduction; this is 12).  All 64 lanes must be active.
+__device__ __forceinline__ float wave_max_fused(float v) {
+    asm("s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 1"
+        : "+v"(v));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The bucket phases, stated ONCE for the three bucketed kernels below (fps_bucket_kernel = route ROUND, fps_spec_kernel = SPEC
+// and the repair launch, fps_cluster_kernel = CLUSTER).  The kernels must agree bit for bit, so what they share is one text:
+// the plot's pointers and first sample, the rows a sample is written to, the bucket boxes, phase A's queue push, phase B's
+// entry update and the exact-tie search.  Where the callers differ they differ in a compile-time BUCKET VIEW (fps_buckets).
+// ------------------------------------------------------------------------------------------------------------
+// a plot's inputs: its SoA rows in the original order, the Morton order and the sorted table of spatial_order_chunk_kernel
+struct fps_plot {
+    const float *px, *py, *pz;
+    const int* ord;                                    // sorted position -> original index
+    float4* pts;                                       // sorted: (x, y, z, running distance = +inf from the sort; dead points: 0)
+    __device__ __forceinline__ fps_plot(const float* pos, const int* order, float4* sorted, int b, int N)
+        : px(pos + (size_t)b * 3 * N), py(px + N), pz(py + N), ord(order + (size_t)b * N), pts(sorted + (size_t)b * N) {}
+};
+// the first sample: start[b] clamped into the plot (0 without the array), wave-uniform
+__device__ __forceinline__ int fps_first(const int* __restrict__ start, int b, int N) {
+    int cur = start ? start[b] : 0;
+    cur = cur < 0 ? 0 : (cur >= N ? N - 1 : cur);
+    return __builtin_amdgcn_readfirstlane(cur);
+}
+// BUCKET VIEW: where the buckets of a workgroup of NW waves lie.  Its local bucket lb = slot * NW + wave is bucket lb * P + part
+// of the plot (P = 1: the workgroup owns the whole plot), and the bucket's 64 points are the sorted positions 64 * bucket + lane:
+// quads of the L2-resident table `pts`, or -- LP -- of the workgroup's own copy in LDS (s_pts, filled by `keep` while the boxes
+// are built: the updates of phase B then never leave the CU).
+template <int NW_, int P_ = 1, bool LP_ = false>
+struct fps_buckets {
+    static constexpr int NW = NW_, P = P_;
+    float4* pts;
+    int N, part;
+    float4* s_pts;
+    __device__ __forceinline__ int pos(int lb, int lane) const { return (lb * P + (P > 1 ? part : 0)) * 64 + lane; }
+    // the point of `lane` in local bucket lb; p = pos(lb, lane), which the caller has at hand
+    __device__ __forceinline__ float4 quad(int lb, int lane, int p) const {     // (a padding lane of the last bucket: any quad)
+        if constexpr (LP_) return s_pts[lb * 64 + lane]; else return pts[p < N ? p : 0];
+    }
+    __device__ __forceinline__ float dist(int lb, int lane, int p) const {      // of a real point
+        if constexpr (LP_) return s_pts[lb * 64 + lane].w; else return pts[p].w;
+    }
+    __device__ __forceinline__ void set_dist(int lb, int lane, int p, float v) const {
+        if constexpr (LP_) reinterpret_cast<float*>(s_pts + lb * 64 + lane)[3] = v; else fps_st_dist(pts, p, v);
+    }
+    __device__ __forceinline__ void keep(int lb, int lane, const float4& q) const {
+        if constexpr (LP_) s_pts[lb * 64 + lane] = q;
+    }
+};
+
+// the boxes of this wave's SPW buckets -> s_box, SoA rows [component][wave][slot]: lane j reads word j of its wave's row =>
+// conflict-free (an AoS box layout cost 32-way conflicts).  Returns the wave's row (+ component * SPW * NW + slot).
+template <int SPW, class View>
+__device__ __forceinline__ float* fps_bucket_boxes(const View& vw, float* s_box, int wave, int lane) {
+    constexpr int NBK = SPW * View::NW;
+    float* my_box = s_box + wave * SPW;
+    for (int k = 0; k < SPW; ++k) {
+        const int lb = k * View::NW + wave, p = vw.pos(lb, lane);
+        const bool v = p < vw.N;
+        const float4 q = v ? vw.pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+        vw.keep(lb, lane, q);
+        const float lx = -wave_max_fused(v ? -q.x : -INFINITY), ly = -wave_max_fused(v ? -q.y : -INFINITY),
+                    lz = -wave_max_fused(v ? -q.z : -INFINITY);
+        const float hx = wave_max_fused(v ? q.x : -INFINITY), hy = wave_max_fused(v ? q.y : -INFINITY),
+                    hz = wave_max_fused(v ? q.z : -INFINITY);
+        if (lane == 0) {
+            my_box[0 * NBK + k] = lx; my_box[1 * NBK + k] = ly; my_box[2 * NBK + k] = lz;
+            my_box[3 * NBK + k] = hx; my_box[4 * NBK + k] = hy; my_box[5 * NBK + k] = hz;
+        }
+    }
+    return my_box;
+}
+
+// phase A's push, by a whole wave: the lanes with a sample mask `sm` != 0 append (local bucket | sm << 11) to the workgroup's
+// queue -- one ballot, one atomicAdd per wave, the lane's slot from mbcnt
+__device__ __forceinline__ void fps_queue_push(unsigned* s_q, int* s_qn, unsigned sm, int lb, int lane) {
+    const unsigned long long bal = __ballot(sm != 0u);
+    if (bal) {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(s_qn, __popcll(bal));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (sm != 0u) s_q[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] =
+            (unsigned)lb | (sm << 11);
+    }
+}
+
+// phase B: the qn queue entries dealt out to the waves, four per wave in flight (8 measured no faster: the phase is VALU-bound):
+// new distances from the samples of the entry's mask (lanes 0.. of ax, ay, az); if the bucket's maximum (or its holder) moved,
+// the new (max, second max, arg-max point) go to LDS.  `stamp` (SN2_FPS_STAMPS builds): this wave counts its entries.
+// HOLD: an entry's sorted position stays in a register from its load to its update (as every kernel's own loop had it) instead of
+// being computed twice.  Four of them across the loads cost the kernels at 6 or 7 waves per SIMD one of those waves, so only
+// the rungs whose occupancy other registers set hold them: there the second computation was measured (profiles/fps_phases).
+template <bool HOLD, class View>
+__device__ __forceinline__ void fps_update_queue(const View& vw, int qn, int wave, int lane, float ax, float ay, float az,
+                                                 const unsigned* s_q, float* s_val, float* s_max2, float4* s_pt,
+                                                 [[maybe_unused]] bool stamp) {
+    constexpr int QD = 4;
+    for (int i0 = wave; i0 < qn; i0 += QD * View::NW) {
+        unsigned ent[QD];
+        [[maybe_unused]] int held[QD];
+        bool on[QD];
+        float4 q[QD];
+        float U[QD];
+#pragma unroll
+        for (int u = 0; u < QD; ++u) {
+            const int i = i0 + u * View::NW;
+            on[u] = i < qn;
+            ent[u] = s_q[on[u] ? i : 0];
+            const int lb = (int)(ent[u] & 2047u);
+            const int p = vw.pos(lb, lane);
+            if constexpr (HOLD) held[u] = p;
+            q[u] = vw.quad(lb, lane, p);
+            U[u] = s_val[lb];
+        }
+#pragma unroll
+        for (int u = 0; u < QD; ++u) {
+            if (!on[u]) continue;
+            const int lb = (int)(ent[u] & 2047u);
+            unsigned sm = ent[u] >> 11;
+            const float d0 = q[u].w;
+            float nd = d0;
+            while (sm) {
+                const int k = __ffs(sm) - 1;
+                sm &= sm - 1;
+                const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ax), k));
+                const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ay), k));
+                const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(az), k));
+                nd = fminf(nd, sn2_d2(q[u].x, q[u].y, q[u].z, sx, sy, sz));
+            }
+            int p;
+            if constexpr (HOLD) p = held[u]; else p = vw.pos(lb, lane);
+            const bool real = p < vw.N;
+            const bool changed = real && nd < d0;
+            if (changed) vw.set_dist(lb, lane, p, nd);
+#ifdef SN2_FPS_STAMPS
+            if (stamp && lane == 0) {
+                g_fps_dbg2[25] += 1;                                                     // entries
+                g_fps_dbg2[26] += __ballot(changed) != 0ull ? 1 : 0;                     // ... with a changed point
+                g_fps_dbg2[27] += (__ballot(changed && d0 == U[u]) == 0ull && U[u] != INFINITY) ? 0 : 1;   // ... slow path
+                g_fps_dbg2[28] += __popc(ent[u] >> 11);                                  // samples per entry
+                g_fps_dbg2[29] += __popcll(__ballot(changed));                           // changed points
+            }
+#endif
+            // five of six queue entries change no point at all (the box test is necessary, not sufficient: fps_stamps.py);
+            // a bucket's FIRST visit always takes its maximum (a bucket of dead points only changes nothing and holds 0)
+            if (__ballot(changed) == 0ull && U[u] != INFINITY) continue;
+            // nothing of the bucket's maximum moved (no changed point held it): its (max, point) stand, and its
+            // second-max entry stays an UPPER bound of the true one, which is all the acceptance tests need
+            if (__ballot(changed && d0 == U[u]) == 0ull && U[u] != INFINITY) continue;
+            if (!real) nd = -1.f;                               // padding lanes of the last bucket never win
+            const float m1 = wave_max_fused(nd);
+            const unsigned long long bal = __ballot(nd == m1);
+            const int first = __ffsll((long long)bal) - 1;
+            float m2 = m1;
+            if (__popcll(bal) == 1) m2 = wave_max_fused(nd == m1 ? -1.f : nd);
+            const float fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].x), first));
+            const float fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].y), first));
+            const float fz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].z), first));
+            if (lane == 0) {
+                s_val[lb] = m1;
+                s_max2[lb] = m2;
+                s_pt[lb] = make_float4(fx, fy, fz, __int_as_float(vw.pos(lb, first)));
+            }
+        }
+    }
+}
+
+// exact tie of the maximal distance V (duplicated points, ...): the lowest ORIGINAL index among this wave's points at V -> s_win
+// (atomicMin; the caller set it to 0xFFFFFFFF and puts a barrier behind).  at_max(h): slot 64 h + lane of this wave holds V.
+template <int SL, class View, class AtMax>
+__device__ __forceinline__ void fps_tie_search(const View& vw, const int* __restrict__ ord, int wave, int lane, float V,
+                                               unsigned* s_win, AtMax at_max) {
+#pragma unroll
+    for (int h = 0; h < SL; ++h) {
+        unsigned long long cand = __ballot(at_max(h));
+        while (cand) {
+            const int lb = (64 * h + __ffsll((long long)cand) - 1) * View::NW + wave;
+            cand &= cand - 1;
+            const int pp = vw.pos(lb, lane);
+            const float d = pp < vw.N ? vw.dist(lb, lane, pp) : -1.f;
+            unsigned oi = 0xFFFFFFFFu;
+            if (d == V) oi = (unsigned)ord[pp];
+            oi = wave_min_u32_dpp(oi);
+            if (lane == 0) atomicMin(s_win, oi);
+        }
+    }
+}
+
+// fps_bucket_kernel (route ROUND: waves = 1, instantiated for 16 waves only): one sample per arg-max round, as the comment above
+// the shared statements describes it.  Set-up, boxes, tie search and emission are those statements (view: P = 1, points in the
+// L2 table); the per-wave dirty test, the in-register bucket state and the one-barrier exchange of a round are its own.
 template <int SPW, int NW>
 __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __restrict__ pos, int N, int M,
                                                           const int* __restrict__ start, const int* __restrict__ order,
@@ -410,32 +646,19 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
     constexpr int NBK = SPW * NW;
     constexpr int SL = (SPW + 63) / 64;                // bucket slots per lane: slot s = 64 h + lane, h < SL
     static_assert(SPW <= 128 && NW <= 16, "at most two bucket slots per lane");
-    __shared__ float s_box[6 * NBK];                   // bucket boxes, [component][wave][slot]: lane j reads word j of its
-                                                       // wave's row => conflict-free (an AoS box layout cost 32-way conflicts)
+    __shared__ float s_box[6 * NBK];                   // bucket boxes (fps_bucket_boxes)
     __shared__ float4 s_xchg[2][2][NW];                // per wave: (max distance, tie flag, -, -) and (x, y, z, sorted position)
     __shared__ unsigned s_win;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const float* px = pos + (size_t)b * 3 * N;
-    const float* py = px + N;
-    const float* pz = py + N;
-    const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_chunk_kernel; dead: 0)
+    const fps_plot plot(pos, order, sorted, b, N);
+    const float *px = plot.px, *py = plot.py, *pz = plot.pz;
+    const int* ord = plot.ord;
+    float4* pts = plot.pts;
+    const fps_rows out = {idx_out, cpos_soa, cpos_aos, b, M};
+    const fps_buckets<NW> view = {pts, N, 0, nullptr};
     if (tid == 0 && n_live_out) n_live_out[b] = M;     // unless the maximum reaches 0 first (fps_fill_zero)
-    float* my_box = s_box + wave * SPW;                // + component * NBK + slot
-    for (int k = 0; k < SPW; ++k) {
-        const int p = (k * NW + wave) * 64 + lane;     // position in the sorted order (bucket k*NW + wave)
-        const bool v = p < N;
-        const float4 q = v ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float lx = -wave_max_dpp(v ? -q.x : -INFINITY), ly = -wave_max_dpp(v ? -q.y : -INFINITY),
-                    lz = -wave_max_dpp(v ? -q.z : -INFINITY);
-        const float hx = wave_max_dpp(v ? q.x : -INFINITY), hy = wave_max_dpp(v ? q.y : -INFINITY),
-                    hz = wave_max_dpp(v ? q.z : -INFINITY);
-        if (lane == 0) {
-            my_box[0 * NBK + k] = lx; my_box[1 * NBK + k] = ly; my_box[2 * NBK + k] = lz;
-            my_box[3 * NBK + k] = hx; my_box[4 * NBK + k] = hy; my_box[5 * NBK + k] = hz;
-        }
-    }
+    const float* my_box = fps_bucket_boxes<SPW>(view, s_box, wave, lane);
     // lane j < SPW keeps the state of bucket slot j of this wave in registers: its maximal running distance, the point
     // attaining it (lowest lane on ties) and whether several points share the maximum (then the lowest ORIGINAL index must
     // be found the slow way)
@@ -450,9 +673,7 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
         bpos[h] = 0;
         tiej[h] = false;
     }
-    int cur = start ? start[b] : 0;
-    cur = cur < 0 ? 0 : (cur >= N ? N - 1 : cur);
-    cur = __builtin_amdgcn_readfirstlane(cur);
+    int cur = fps_first(start, b, N);
     float cx = px[cur], cy = py[cur], cz = pz[cur];
     int cur_pos = -1;                                   // >= 0: the sample is sorted point cur_pos (index = ord[cur_pos])
     __syncthreads();
@@ -482,14 +703,7 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
     };
 
     for (int i = 0; i < M; ++i) {
-        if (tid == 0) {
-            const int oi = cur_pos >= 0 ? ord[cur_pos] : cur;
-            idx_out[(size_t)b * M + i] = oi;
-            cpos_soa[((size_t)b * 3 + 0) * M + i] = cx;
-            cpos_soa[((size_t)b * 3 + 1) * M + i] = cy;
-            cpos_soa[((size_t)b * 3 + 2) * M + i] = cz;
-            reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M + i] = make_float4(cx, cy, cz, 0.f);
-        }
+        if (tid == 0) out.emit(i, cx, cy, cz, cur_pos >= 0 ? ord[cur_pos] : cur);
         if (i == M - 1) break;
         STAMP(t0);
         // (a) which of this wave's buckets can change?  lane j tests slots j, j + 64, ...
@@ -579,20 +793,7 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
             // rare exact tie of the maximal distance (duplicated points): lowest ORIGINAL index among all candidates
             if (tid == 0) s_win = 0xFFFFFFFFu;
             __syncthreads();
-#pragma unroll
-            for (int h = 0; h < SL; ++h) {
-                unsigned long long cand = __ballot(mine[h] == V);
-                while (cand) {
-                    const int kk = 64 * h + __ffsll((long long)cand) - 1;
-                    cand &= cand - 1;
-                    const int pp = (kk * NW + wave) * 64 + lane;
-                    const float d = pp < N ? pts[pp].w : -1.f;
-                    unsigned oi = 0xFFFFFFFFu;
-                    if (d == V) oi = (unsigned)ord[pp];
-                    oi = wave_min_u32_dpp(oi);
-                    if (lane == 0) atomicMin(&s_win, oi);
-                }
-            }
+            fps_tie_search<SL>(view, ord, wave, lane, V, &s_win, [&](int h) { return mine[h] == V; });
             __syncthreads();
             cur = __builtin_amdgcn_readfirstlane((int)s_win);
             cur_pos = -1;
@@ -637,27 +838,9 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(const float* __rest
 // Per super-round: all waves test + update their dirty buckets and refresh (max, second max, arg-max point) of those
 // buckets in LDS; barrier; wave 0 alone extracts the K+1 largest maxima (three sorted heads per lane, DPP wave max),
 // runs the acceptance tests (lane e = candidate e), emits the samples; barrier.
+// Set-up, phases (A)'s push and (B), the tie search and the samples' way out are the shared statements above (view: P = 1,
+// the points in the L2-resident table); the box tests of (A) and phases (C) and (D) are this kernel's own.
 // ------------------------------------------------------------------------------------------------------------
-// wave64 max with the DPP modifier fused into v_max_f32 (the update_dpp builtin above costs a v_mov, a v_mov_dpp, an
-// s_nop and the v_max per step: 24 instructions per reduction; this is 12).  All 64 lanes must be active.
-__device__ __forceinline__ float wave_max_fused(float v) {
-    asm("s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 template <int SPW, int NW, int K>
 __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restrict__ pos, int N, int M,
                                                         const int* __restrict__ start, const int* __restrict__ order,
@@ -683,11 +866,12 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
     unsigned* s_win = reinterpret_cast<unsigned*>(s_ctl + 4);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const float* px = pos + (size_t)b * 3 * N;
-    const float* py = px + N;
-    const float* pz = py + N;
-    const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_chunk_kernel; dead: 0)
+    const fps_plot plot(pos, order, sorted, b, N);
+    const float *px = plot.px, *py = plot.py, *pz = plot.pz;
+    const int* ord = plot.ord;
+    float4* pts = plot.pts;
+    const fps_rows out = {idx_out, cpos_soa, cpos_aos, b, M};
+    const fps_buckets<NW> view = {pts, N, 0, nullptr};
     if (gate) {
         // REPAIR launch behind fps_cluster_kernel (gate = that launch's control words): nothing to do unless one of its waits
         // gave up (gate[1] = the count); then every plot is sampled again by this kernel, which waits for nobody.  The running
@@ -700,37 +884,17 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
         __threadfence_block();
         __syncthreads();
     }
-    float* my_box = s_box + wave * SPW;                // + component * NBK + slot; bucket of (wave, slot) = slot * NW + wave
-    for (int k = 0; k < SPW; ++k) {
-        const int p = (k * NW + wave) * 64 + lane;     // position in the sorted order (bucket k*NW + wave)
-        const bool v = p < N;
-        const float4 q = v ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float lx = -wave_max_fused(v ? -q.x : -INFINITY), ly = -wave_max_fused(v ? -q.y : -INFINITY),
-                    lz = -wave_max_fused(v ? -q.z : -INFINITY);
-        const float hx = wave_max_fused(v ? q.x : -INFINITY), hy = wave_max_fused(v ? q.y : -INFINITY),
-                    hz = wave_max_fused(v ? q.z : -INFINITY);
-        if (lane == 0) {
-            my_box[0 * NBK + k] = lx; my_box[1 * NBK + k] = ly; my_box[2 * NBK + k] = lz;
-            my_box[3 * NBK + k] = hx; my_box[4 * NBK + k] = hy; my_box[5 * NBK + k] = hz;
-        }
-    }
+    const float* my_box = fps_bucket_boxes<SPW>(view, s_box, wave, lane);     // bucket of (wave, slot) = slot * NW + wave
     for (int g = tid; g < NBK; g += NW * 64) {
         s_val[g] = g * 64 < N ? INFINITY : -1.f;       // every real bucket is dirty for the first sample
         s_max2[g] = -1.f;
     }
-    int cur = start ? start[b] : 0;
-    cur = cur < 0 ? 0 : (cur >= N ? N - 1 : cur);
-    cur = __builtin_amdgcn_readfirstlane(cur);
+    int cur = fps_first(start, b, N);
     // the accepted samples of the current super-round live in lanes 0..j-1 of (ax, ay, az) in EVERY wave
     float ax = px[cur], ay = py[cur], az = pz[cur];
     int j = 1, cnt = 1;
-    int* out_idx = idx_out + (size_t)b * M;            // sorted positions are stored as -1 - position and translated at the end
     if (tid == 0) {
-        out_idx[0] = cur;
-        cpos_soa[((size_t)b * 3 + 0) * M] = ax;
-        cpos_soa[((size_t)b * 3 + 1) * M] = ay;
-        cpos_soa[((size_t)b * 3 + 2) * M] = az;
-        reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M] = make_float4(ax, ay, az, 0.f);
+        out.emit(0, ax, ay, az, cur);
         s_ctl[3] = 0;
         if (n_live_out) n_live_out[b] = M;              // unless the maximum reaches 0 first (fps_fill_zero)
     }
@@ -757,86 +921,13 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
                     if (sn2_box_d2(b0, b1, b2, b3, b4, b5, sx, sy, sz) < mx) sm |= 1u << k;
                 }
             }
-            const unsigned long long bal = __ballot(sm != 0u);
-            if (bal) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&s_ctl[3], __popcll(bal));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (sm != 0u) s_q[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] =
-                    (unsigned)(sl * NW + wave) | (sm << 11);
-            }
+            fps_queue_push(s_q, &s_ctl[3], sm, sl * NW + wave, lane);
         }
         STAMP(t1);
         __syncthreads();
-        // (B) the queue, four entries per wave in flight: new distances; if the bucket's maximum (or its holder) moved, the
-        // new (max, second max, arg-max point) go to LDS
+        // (B) the queue: new distances and, where a bucket's maximum moved, its new (max, second max, arg-max point)
         const int qn = s_ctl[3];
-        constexpr int QD = 4;                            // queue entries per wave in flight (8 measured no faster: the phase is VALU-bound)
-        for (int i0 = wave; i0 < qn; i0 += QD * NW) {
-            unsigned ent[QD];
-            int p[QD];
-            bool on[QD];
-            float4 q[QD];
-            float U[QD];
-#pragma unroll
-            for (int u = 0; u < QD; ++u) {
-                const int i = i0 + u * NW;
-                on[u] = i < qn;
-                ent[u] = s_q[on[u] ? i : 0];
-                const int g = (int)(ent[u] & 2047u);
-                p[u] = g * 64 + lane;
-                q[u] = pts[p[u] < N ? p[u] : 0];
-                U[u] = s_val[g];
-            }
-#pragma unroll
-            for (int u = 0; u < QD; ++u) {
-                if (!on[u]) continue;
-                const int g = (int)(ent[u] & 2047u);
-                unsigned sm = ent[u] >> 11;
-                const float d0 = q[u].w;
-                float nd = d0;
-                while (sm) {
-                    const int k = __ffs(sm) - 1;
-                    sm &= sm - 1;
-                    const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ax), k));
-                    const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ay), k));
-                    const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(az), k));
-                    nd = fminf(nd, sn2_d2(q[u].x, q[u].y, q[u].z, sx, sy, sz));
-                }
-                const bool real = p[u] < N;
-                const bool changed = real && nd < d0;
-                if (changed) fps_st_dist(pts, p[u], nd);
-#ifdef SN2_FPS_STAMPS
-                if (b == 0 && wave == 0 && lane == 0) {
-                    g_fps_dbg2[25] += 1;                                                     // entries
-                    g_fps_dbg2[26] += __ballot(changed) != 0ull ? 1 : 0;                     // ... with a changed point
-                    g_fps_dbg2[27] += (__ballot(changed && d0 == U[u]) == 0ull && U[u] != INFINITY) ? 0 : 1;   // ... slow path
-                    g_fps_dbg2[28] += __popc(ent[u] >> 11);                                  // samples per entry
-                    g_fps_dbg2[29] += __popcll(__ballot(changed));                           // changed points
-                }
-#endif
-                // five of six queue entries change no point at all (the box test is necessary, not sufficient: fps_stamps.py);
-                // a bucket's FIRST visit always takes its maximum (a bucket of dead points only changes nothing and holds 0)
-                if (__ballot(changed) == 0ull && U[u] != INFINITY) continue;
-                // nothing of the bucket's maximum moved (no changed point held it): its (max, point) stand, and its
-                // second-max entry stays an UPPER bound of the true one, which is all the acceptance tests need
-                if (__ballot(changed && d0 == U[u]) == 0ull && U[u] != INFINITY) continue;
-                if (!real) nd = -1.f;                               // padding lanes of the last bucket never win
-                const float m1 = wave_max_fused(nd);
-                const unsigned long long bal = __ballot(nd == m1);
-                const int first = __ffsll((long long)bal) - 1;
-                float m2 = m1;
-                if (__popcll(bal) == 1) m2 = wave_max_fused(nd == m1 ? -1.f : nd);
-                const float fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].x), first));
-                const float fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].y), first));
-                const float fz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].z), first));
-                if (lane == 0) {
-                    s_val[g] = m1;
-                    s_max2[g] = m2;
-                    s_pt[g] = make_float4(fx, fy, fz, __int_as_float(g * 64 + first));
-                }
-            }
-        }
+        fps_update_queue<false>(view, qn, wave, lane, ax, ay, az, s_q, s_val, s_max2, s_pt, b == 0 && wave == 0);
         STAMP(t2);
         __syncthreads();
         STAMP(t3);
@@ -918,6 +1009,9 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
             nj = nj > rem ? rem : nj;
             if (jj == 0 && e < nj) {
                 s_acc[e] = make_float4(pte.x, pte.y, pte.z, 0.f);
+                // (phase D keeps its own stores, the text of fps_rows::emit: through `out` wave 0's critical path was longer,
+                // 16 x 32768 -> 1024 with 8 waves 1.3750 against 1.3703 ms, with these lines 1.3704: profiles/fps_phases)
+                int* out_idx = idx_out + (size_t)b * M;
                 out_idx[cnt + e] = -1 - __float_as_int(pte.w);
                 cpos_soa[((size_t)b * 3 + 0) * M + cnt + e] = pte.x;
                 cpos_soa[((size_t)b * 3 + 1) * M + cnt + e] = pte.y;
@@ -965,42 +1059,21 @@ __global__ __launch_bounds__(NW * 64) void fps_spec_kernel(const float* __restri
         } else {
             // exact tie of the maximal distance (duplicated points, ...): lowest ORIGINAL index among all points attaining it
             const float V = __int_as_float(s_ctl[2]);
-#pragma unroll
-            for (int h = 0; h < SL; ++h) {
+            fps_tie_search<SL>(view, ord, wave, lane, V, s_win, [&](int h) {
                 const int sl = 64 * h + lane;
-                unsigned long long cand = __ballot(sl < SPW && s_val[sl * NW + wave] == V);
-                while (cand) {
-                    const int kk = 64 * h + __ffsll((long long)cand) - 1;
-                    cand &= cand - 1;
-                    const int pp = (kk * NW + wave) * 64 + lane;
-                    const float d = pp < N ? pts[pp].w : -1.f;
-                    unsigned oi = 0xFFFFFFFFu;
-                    if (d == V) oi = (unsigned)ord[pp];
-                    oi = wave_min_u32_dpp(oi);
-                    if (lane == 0) atomicMin(s_win, oi);
-                }
-            }
+                return sl < SPW && s_val[sl * NW + wave] == V;
+            });
             __syncthreads();
             cur = __builtin_amdgcn_readfirstlane((int)*s_win);
             ax = px[cur]; ay = py[cur]; az = pz[cur];
-            if (tid == 0) {
-                out_idx[cnt] = cur;
-                cpos_soa[((size_t)b * 3 + 0) * M + cnt] = ax;
-                cpos_soa[((size_t)b * 3 + 1) * M + cnt] = ay;
-                cpos_soa[((size_t)b * 3 + 2) * M + cnt] = az;
-                reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M + cnt] = make_float4(ax, ay, az, 0.f);
-            }
+            if (tid == 0) out.emit(cnt, ax, ay, az, cur);
             j = 1;
         }
         cnt += j;
         if (done) break;
     }
-    // sorted positions -> original indices (kept out of the loop: the load would sit on wave 0's critical path)
     __syncthreads();
-    for (int i = tid; i < M; i += NW * 64) {
-        const int v = out_idx[i];
-        if (v < 0) out_idx[i] = ord[-1 - v];
-    }
+    out.translate(ord, tid, NW * 64, nullptr);
 }
 
 template <int SPW, int NW, int K>
@@ -1020,37 +1093,51 @@ struct fps_ws_parts {
     int* grid;           // B*GRID_WORDS ints
     unsigned* xchg;      // B*FPS_XCHG_WORDS + FPS_CTL_WORDS
     unsigned* ctl;
+    int* rank;           // B*N ints: the inverse of `order` (the last words of the workspace)
 };
 static fps_ws_parts fps_ws_carve(int* ws, int B, int N) {
     int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);
     return {ws, reinterpret_cast<float4*>(ws + (size_t)B * N), grid, reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS),
-            reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N))};
+            reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N)), ws + SN2_FPS_WS_RANK_OFFSET(B, N)};
+}
+// ... and the tables a reader of a filled workspace takes (sn2_ball_query)
+struct fps_ws_tables {
+    const int* order;
+    const float4* sorted;
+    const int* grid;
+};
+static fps_ws_tables fps_ws_carve(const int* ws, int B, int N) {
+    return {ws, reinterpret_cast<const float4*>(ws + (size_t)B * N), ws + SN2_FPS_WS_GRID_OFFSET(B, N)};
 }
 static void launch_spatial_order(const fps_call& a, const fps_ws_parts& w) {
-    launch_spatial_order(a.pos, a.B, a.N, w.order, w.sorted, w.grid, w.xchg, w.ctl, a.nl, a.st);
+    launch_spatial_order(a.pos, a.B, a.N, w.order, w.sorted, w.grid, w.xchg, w.ctl, w.rank, a.nl, a.st);
 }
 
+// SPEC.  repair = this launch follows fps_cluster_kernel on the same workspace: the tables are there, and the kernel returns at
+// once unless the control words say that the multi-workgroup pass gave up (the count then goes to the status word)
 template <int SPW, int NW = 16>
-static int launch_fps_bucket(const fps_call& a, bool speculate = true, bool repair = false) {
+static int launch_fps_spec(const fps_call& a, bool repair = false) {
     const fps_ws_parts w = fps_ws_carve(a.ws, a.B, a.N);
-    // repair = this launch follows fps_cluster_kernel on the same workspace: the tables are there, and the kernel returns at once
-    // unless the control words say that the multi-workgroup pass gave up (the count then goes to the status word)
     const unsigned* gate = repair ? w.ctl : nullptr;
     unsigned* status = repair ? a.status : nullptr;
     if (!repair) launch_spatial_order(a, w);
-    if (speculate) {
-        constexpr int K = SN2_FPS_K;
-        const size_t lds = fps_spec_lds_bytes<SPW, NW, K>();
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_spec_kernel<SPW, NW, K>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        // (Round 4 tried the FPS waves at the highest wave priority, `s_setprio 3`: beside the feature kernels a super-round takes
-        // three times as long as alone, and what the pass costs the step follows the time it is resident -- no effect, 0.7652
-        // against 0.762 ms per step; round 3 had tried the opposite, the feature kernels raised: none either.)
-        hipLaunchKernelGGL((fps_spec_kernel<SPW, NW, K>), dim3(a.B), dim3(NW * 64), lds, a.st, a.pos, a.N, a.M, a.start,
-                           (const int*)w.order, w.sorted, a.idx, a.cs, a.ca, gate, status, a.nl, a.nlo);
-        SN2_RETURN_LAUNCH();
-    }
-    hipLaunchKernelGGL((fps_bucket_kernel<SPW, NW>), dim3(a.B), dim3(NW * 64), 0, a.st, a.pos, a.N, a.M, a.start,
+    constexpr int K = SN2_FPS_K;
+    const size_t lds = fps_spec_lds_bytes<SPW, NW, K>();
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_spec_kernel<SPW, NW, K>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    // (Round 4 tried the FPS waves at the highest wave priority, `s_setprio 3`: beside the feature kernels a super-round takes
+    // three times as long as alone, and what the pass costs the step follows the time it is resident -- no effect, 0.7652
+    // against 0.762 ms per step; round 3 had tried the opposite, the feature kernels raised: none either.)
+    hipLaunchKernelGGL((fps_spec_kernel<SPW, NW, K>), dim3(a.B), dim3(NW * 64), lds, a.st, a.pos, a.N, a.M, a.start,
+                       (const int*)w.order, w.sorted, a.idx, a.cs, a.ca, gate, status, a.nl, a.nlo);
+    SN2_RETURN_LAUNCH();
+}
+// ROUND: 16 waves (sn2_fps_route), so this is the only place that names fps_bucket_kernel
+template <int SPW>
+static int launch_fps_round(const fps_call& a) {
+    const fps_ws_parts w = fps_ws_carve(a.ws, a.B, a.N);
+    launch_spatial_order(a, w);
+    hipLaunchKernelGGL((fps_bucket_kernel<SPW, 16>), dim3(a.B), dim3(16 * 64), 0, a.st, a.pos, a.N, a.M, a.start,
                        (const int*)w.order, w.sorted, a.idx, a.cs, a.ca, a.nlo);
     SN2_RETURN_LAUNCH();
 }
@@ -1061,7 +1148,8 @@ static int launch_fps_bucket(const fps_call& a, bool speculate = true, bool repa
 // (A) and the dirty-bucket updates (B: VALU-issue bound on one CU's four SIMDs).  Here P workgroups share a plot:
 //   * bucket g (64 consecutive points of the Morton order) belongs to workgroup g % P -- interleaved, so the ~17 buckets a
 //     new sample dirties spread evenly over the P workgroups; each workgroup keeps (max, second max, arg-max point) of
-//     its NBL = ceil(buckets / P) buckets in LDS and runs phases (A) and (B) of fps_spec_kernel on them;
+//     its NBL = ceil(buckets / P) buckets in LDS and runs phases (A) and (B) on them: the push and phase (B) are the statements
+//     fps_spec_kernel uses (fps_queue_push, fps_update_queue), under the view <NW, P, LP>; (A)'s box tests are its own;
 //   * per super-round ONE exchange through L2: wave 0 of every workgroup publishes its TP = 8 largest bucket maxima (value,
 //     second max, point) and a bound on everything it did not publish as 8-byte {tag = super-round, value} granules
 //     (agent-scope relaxed stores = `global_store_dwordx2 sc1`, the data is its own flag: cdna_hip_programming.md
@@ -1076,7 +1164,8 @@ static int launch_fps_bucket(const fps_call& a, bool speculate = true, bool repa
 //     survivors: eight wave-max rounds instead of the ranking);
 //   * acceptance tests, exact-tie search (lowest ORIGINAL index at the plot's TRUE maximum: two more granules per workgroup, its
 //     winner and the maximum of its own buckets -- the published records are its top by 64-ulp keys only) and emitted samples are
-//     those of fps_spec_kernel, bit for bit (tests/test_gpu_geometry.py holds all kernels to each other and to the oracle).
+//     those of fps_spec_kernel, bit for bit (tests/test_gpu_geometry.py holds all kernels to each other and to the oracle): the
+//     search inside a workgroup is fps_tie_search, a sample leaves through fps_rows (here by way of the LDS log);
 // Residency: a workgroup waits only for the P-1 peers of its plot.  Plots are handed out by a ticket counter in arrival
 // order (not by blockIdx), so the peers of every resident workgroup are resident too or are the very next workgroups to
 // start -- no dispatch-order assumption; every spin is bounded (`spin_limit` sweeps, then the kernel gives up, counts the
@@ -1212,52 +1301,28 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
     if (ticket < 0) return;
     const int b = ticket / P, part = ticket - b * P;
     const bool use_log = log_cap >= M;
-    const float* px = pos + (size_t)b * 3 * N;
-    const float* py = px + N;
-    const float* pz = py + N;
-    const int* ord = order + (size_t)b * N;
-    float4* pts = sorted + (size_t)b * N;              // (x, y, z, running distance = +inf from spatial_order_chunk_kernel)
+    const fps_plot plot(pos, order, sorted, b, N);
+    const float *px = plot.px, *py = plot.py, *pz = plot.pz;
+    const int* ord = plot.ord;
+    const fps_rows out = {idx_out, cpos_soa, cpos_aos, b, M};
+    const fps_buckets<NW, P, LP> view = {plot.pts, N, part, s_pts};
     fc_u64* xchg = xchg_all + (size_t)b * (2 * FC_COPY_U64);
-    float* my_box = s_box + wave * SPW;                // + component * NBL + slot
-    for (int k = 0; k < SPW; ++k) {
-        const int p = ((k * NW + wave) * P + part) * 64 + lane;       // sorted position: global bucket (k*NW + wave)*P + part
-        const bool v = p < N;
-        const float4 q = v ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (LP) s_pts[(k * NW + wave) * 64 + lane] = q;
-        const float lx = -wave_max_fused(v ? -q.x : -INFINITY), ly = -wave_max_fused(v ? -q.y : -INFINITY),
-                    lz = -wave_max_fused(v ? -q.z : -INFINITY);
-        const float hx = wave_max_fused(v ? q.x : -INFINITY), hy = wave_max_fused(v ? q.y : -INFINITY),
-                    hz = wave_max_fused(v ? q.z : -INFINITY);
-        if (lane == 0) {
-            my_box[0 * NBL + k] = lx; my_box[1 * NBL + k] = ly; my_box[2 * NBL + k] = lz;
-            my_box[3 * NBL + k] = hx; my_box[4 * NBL + k] = hy; my_box[5 * NBL + k] = hz;
-        }
-    }
+    const float* my_box = fps_bucket_boxes<SPW>(view, s_box, wave, lane);     // (LP: and the workgroup's points -> s_pts)
     for (int lb = tid; lb < NBL; lb += NW * 64) {
-        s_val[lb] = (lb * P + part) * 64 < N ? INFINITY : -1.f;     // every real bucket is dirty for the first sample
+        s_val[lb] = view.pos(lb, 0) < N ? INFINITY : -1.f;          // every real bucket is dirty for the first sample
         s_max2[lb] = -1.f;
     }
-    int cur = start ? start[b] : 0;
-    cur = cur < 0 ? 0 : (cur >= N ? N - 1 : cur);
-    cur = __builtin_amdgcn_readfirstlane(cur);
+    int cur = fps_first(start, b, N);
     // the accepted samples of the current super-round: s_acc[0..j-1], and lanes 0..j-1 of (ax, ay, az) in EVERY wave
     float ax = px[cur], ay = py[cur], az = pz[cur];
     int j = 1, cnt = 1;
     unsigned epoch = 0;
     float tau = -1.f;                                  // wave 0's threshold for the next selection
     bool gave_up = false;                              // a wait ran out: leave without writing (the repair launch samples the plot)
-    int* out_idx = idx_out + (size_t)b * M;
-    // one sample of the plot: (x, y, z) and its code = -1 - sorted position (translated at the end) or the original index
+    // one sample of the plot: into the LDS log where the plot's samples fit (they leave together at the end), else out at once
     auto emit = [&](int at, float x, float y, float z, int code) {
-        if (use_log) {
-            s_log[at] = make_float4(x, y, z, __int_as_float(code));
-        } else {
-            out_idx[at] = code;
-            cpos_soa[((size_t)b * 3 + 0) * M + at] = x;
-            cpos_soa[((size_t)b * 3 + 1) * M + at] = y;
-            cpos_soa[((size_t)b * 3 + 2) * M + at] = z;
-            reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M + at] = make_float4(x, y, z, 0.f);
-        }
+        if (use_log) s_log[at] = make_float4(x, y, z, __int_as_float(code));
+        else out.emit(at, x, y, z, code);
     };
     if (tid == 0) {
         if (part == 0) emit(0, ax, ay, az, cur);
@@ -1305,75 +1370,15 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
                 sm |= ((unsigned)(hb >> ((asl * KPL) & 63)) & ((1u << KPL) - 1u)) << k0;     // the KPL hits of this lane's slot
             }
             if (akk != 0 || !slot_ok) sm = 0u;           // one lane per slot pushes
-            const unsigned long long bal = __ballot(sm != 0u);
-            if (bal) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&s_ctl[3], __popcll(bal));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (sm != 0u) s_q[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] =
-                    (unsigned)(sl * NW + wave) | (sm << 11);
-            }
+            fps_queue_push(s_q, &s_ctl[3], sm, sl * NW + wave, lane);
         }
         FCSTAMP(t1);
         __syncthreads();
         FCSTAMP(t2);
-        // (B) the queue, four entries per wave in flight (fps_spec_kernel's phase B on this workgroup's buckets)
+        // (B) the queue: new distances and, where a bucket's maximum moved, its new (max, second max, arg-max point)
         const int qn = s_ctl[3];
-        constexpr int QD = 4;
-        for (int i0 = wave; i0 < qn; i0 += QD * NW) {
-            unsigned ent[QD];
-            int p[QD];
-            bool on[QD];
-            float4 q[QD];
-            float U[QD];
-#pragma unroll
-            for (int u = 0; u < QD; ++u) {
-                const int i = i0 + u * NW;
-                on[u] = i < qn;
-                ent[u] = s_q[on[u] ? i : 0];
-                const int lb = (int)(ent[u] & 2047u);
-                p[u] = (lb * P + part) * 64 + lane;
-                if constexpr (LP) q[u] = s_pts[lb * 64 + lane]; else q[u] = pts[p[u] < N ? p[u] : 0];
-                U[u] = s_val[lb];
-            }
-#pragma unroll
-            for (int u = 0; u < QD; ++u) {
-                if (!on[u]) continue;
-                const int lb = (int)(ent[u] & 2047u);
-                unsigned sm = ent[u] >> 11;
-                const float d0 = q[u].w;
-                float nd = d0;
-                while (sm) {
-                    const int k = __ffs(sm) - 1;
-                    sm &= sm - 1;
-                    const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ax), k));
-                    const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ay), k));
-                    const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(az), k));
-                    nd = fminf(nd, sn2_d2(q[u].x, q[u].y, q[u].z, sx, sy, sz));
-                }
-                const bool real = p[u] < N;
-                const bool changed = real && nd < d0;
-                if (changed) {
-                    if constexpr (LP) reinterpret_cast<float*>(s_pts + lb * 64 + lane)[3] = nd; else fps_st_dist(pts, p[u], nd);
-                }
-                if (__ballot(changed) == 0ull && U[u] != INFINITY) continue;       // (first visit: as in fps_spec_kernel)
-                if (__ballot(changed && d0 == U[u]) == 0ull && U[u] != INFINITY) continue;
-                if (!real) nd = -1.f;                               // padding lanes of the last bucket never win
-                const float m1 = wave_max_fused(nd);
-                const unsigned long long bal = __ballot(nd == m1);
-                const int first = __ffsll((long long)bal) - 1;
-                float m2 = m1;
-                if (__popcll(bal) == 1) m2 = wave_max_fused(nd == m1 ? -1.f : nd);
-                const float fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].x), first));
-                const float fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].y), first));
-                const float fz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[u].z), first));
-                if (lane == 0) {
-                    s_val[lb] = m1;
-                    s_max2[lb] = m2;
-                    s_pt[lb] = make_float4(fx, fy, fz, __int_as_float((lb * P + part) * 64 + first));
-                }
-            }
-        }
+        // (256 and more buckets per workgroup: the points are never in LDS, and the selection's registers set the occupancy)
+        fps_update_queue<(NBL >= 256)>(view, qn, wave, lane, ax, ay, az, s_q, s_val, s_max2, s_pt, false);
         FCSTAMP(t3);
         __syncthreads();
         FCSTAMP(t4);
@@ -1676,24 +1681,10 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
             if (lane == 0) atomicMax(s_win + 1, __float_as_uint(lmx));           // non-negative floats order as their bits
             __syncthreads();
             const float V = __uint_as_float(s_win[1]);
-#pragma unroll
-            for (int h = 0; h < SL; ++h) {
+            fps_tie_search<SL>(view, ord, wave, lane, V, s_win, [&](int h) {
                 const int sl = 64 * h + lane;
-                unsigned long long cand = __ballot(sl < SPW && s_val[sl * NW + wave] == V);
-                while (cand) {
-                    const int kk = 64 * h + __ffsll((long long)cand) - 1;
-                    cand &= cand - 1;
-                    const int pp = ((kk * NW + wave) * P + part) * 64 + lane;
-                    float d = -1.f;
-                    if (pp < N) {
-                        if constexpr (LP) d = s_pts[(kk * NW + wave) * 64 + lane].w; else d = pts[pp].w;
-                    }
-                    unsigned oi = 0xFFFFFFFFu;
-                    if (d == V) oi = (unsigned)ord[pp];
-                    oi = wave_min_u32_dpp(oi);
-                    if (lane == 0) atomicMin(s_win, oi);
-                }
-            }
+                return sl < SPW && s_val[sl * NW + wave] == V;
+            });
             __syncthreads();
             if (wave == 0) {
                 fc_u64* tg = xg + 6 * NE + P;           // two tie words per workgroup: its winner, its maximum
@@ -1755,20 +1746,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cluster_kernel(const float* __res
     // (after a give-up the log holds `cnt` samples and uninitialised LDS behind them: nothing is translated, nothing written)
     if (part != 0 || gave_up) return;
     __syncthreads();
-    for (int i = tid; i < M; i += NW * 64) {
-        if (use_log) {
-            const float4 e = s_log[i];
-            const int code = __float_as_int(e.w);
-            out_idx[i] = code < 0 ? ord[-1 - code] : code;
-            cpos_soa[((size_t)b * 3 + 0) * M + i] = e.x;
-            cpos_soa[((size_t)b * 3 + 1) * M + i] = e.y;
-            cpos_soa[((size_t)b * 3 + 2) * M + i] = e.z;
-            reinterpret_cast<float4*>(cpos_aos)[(size_t)b * M + i] = make_float4(e.x, e.y, e.z, 0.f);
-        } else {
-            const int v = out_idx[i];
-            if (v < 0) out_idx[i] = ord[-1 - v];
-        }
-    }
+    out.translate(ord, tid, NW * 64, use_log ? s_log : nullptr);
 }
 
 static bool fps_cluster_lds_points = getenv("SN2_FC_NO_LDS_POINTS") == nullptr;     // (diagnostic switches)
@@ -1849,7 +1827,7 @@ extern "C" int sn2_fps_route(int B, int N, int M, int waves, int have_ws, int cu
         // training loop the STEP is 2.4 % shorter (0.918 vs 0.940 ms; 4 waves: 2.07 ms alone, 0.922 ms per step).
         // waves = 4 (plots of at most 16 384 points): half the wave slots again, for passes that share the chip with MANY other
         // workgroups (the parcel loop: 512 plots per launch = two FPS workgroups per CU); larger plots take the 8-wave kernel
-        // (four waves at 32 768 points -- launch_fps_bucket<128, 4> -- were measured in the training loop: 0.773 against 0.769 ms
+        // (four waves at 32 768 points -- launch_fps_spec<128, 4> -- were measured in the training loop: 0.773 against 0.769 ms
         // per step with eight; not instantiated), and above 32 768 points there are 16 waves or none
         if (r.nw == 4 && N > 16384) r.nw = 8;
         if (r.nw == 8 && N > 32768) r.nw = 16;
@@ -1875,20 +1853,24 @@ static int launch_fps_brute(const fps_call& a, const sn2_fps_route_t& r) {
     }
 }
 // SPEC, ROUND (16 waves only) and the repair launch behind CLUSTER (SPEC, 16 waves, gated by the workspace's control words)
+template <int SPW>
+static int launch_fps_16(const fps_call& a, bool spec, bool repair) {
+    return spec ? launch_fps_spec<SPW>(a, repair) : launch_fps_round<SPW>(a);
+}
 static int launch_fps_single(const fps_call& a, int nw, int spw, bool spec, bool repair) {
     switch (nw * 1000 + spw) {
-    case 4032: return launch_fps_bucket<32, 4>(a);
-    case 4064: return launch_fps_bucket<64, 4>(a);
-    case 8008: return launch_fps_bucket<8, 8>(a);
-    case 8016: return launch_fps_bucket<16, 8>(a);
-    case 8032: return launch_fps_bucket<32, 8>(a);
-    case 8064: return launch_fps_bucket<64, 8>(a);
-    case 16004: return launch_fps_bucket<4>(a, spec, repair);
-    case 16008: return launch_fps_bucket<8>(a, spec, repair);
-    case 16016: return launch_fps_bucket<16>(a, spec, repair);
-    case 16032: return launch_fps_bucket<32>(a, spec, repair);
-    case 16064: return launch_fps_bucket<64>(a, spec, repair);
-    case 16128: return launch_fps_bucket<128>(a, spec, repair);
+    case 4032: return launch_fps_spec<32, 4>(a);
+    case 4064: return launch_fps_spec<64, 4>(a);
+    case 8008: return launch_fps_spec<8, 8>(a);
+    case 8016: return launch_fps_spec<16, 8>(a);
+    case 8032: return launch_fps_spec<32, 8>(a);
+    case 8064: return launch_fps_spec<64, 8>(a);
+    case 16004: return launch_fps_16<4>(a, spec, repair);
+    case 16008: return launch_fps_16<8>(a, spec, repair);
+    case 16016: return launch_fps_16<16>(a, spec, repair);
+    case 16032: return launch_fps_16<32>(a, spec, repair);
+    case 16064: return launch_fps_16<64>(a, spec, repair);
+    case 16128: return launch_fps_16<128>(a, spec, repair);
     default: return SN2_ELIMIT;
     }
 }
@@ -2301,9 +2283,10 @@ extern "C" int sn2_ball_query(const float* src_soa, int B, int N, const float* c
     const float r = sqrtf(r2);   // only used (enlarged) to bound the cell range; the hit test is d2 < r2
     if (fps_ws && N > 2048 && (((size_t)B * N) % 4 == 0)) {
         // the sources are the point set FPS just sorted: walk its cell lists instead of the whole plot
-        const int* order = fps_ws;
-        const float4* sorted = reinterpret_cast<const float4*>(fps_ws + (size_t)B * N);
-        const int* grid = fps_ws + (size_t)5 * B * N;
+        const fps_ws_tables w = fps_ws_carve(fps_ws, B, N);
+        const int* order = w.order;
+        const float4* sorted = w.sorted;
+        const int* grid = w.grid;
         const size_t lds = (size_t)4 * ((N + 31) / 32) * sizeof(unsigned);       // the dense-ball bitmaps: 64 KB at N = 131 072
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ball_query_grid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
