@@ -1164,6 +1164,63 @@ int sn2_cut_count(const float *cloud, const unsigned char *classification, const
 int sn2_cut_fill(const float *cloud, const unsigned char *classification, const unsigned *drop, const sn2_cut_table *table,
                  int *prefix, const int *parcel_base, long sum_n, float *out, int *point_index, void *stream);
 
+/* ---- Orthoimage colours (csrc/ortho.hip; the rule's functions: csrc/ortho_rules.h; host side ortho.py: colorize, colorize_ref): the
+ * rows of the (10,T) cloud that no LiDAR sensor measures -- red, green, blue, near infrared, rows 3..6 -- looked up per point in
+ * georeferenced orthoimages.  The reference's files had them painted on upstream, by tools that are not part of it: the rule is OURS.
+ *
+ * AN IMAGE is H x W pixels of C bands, north up, no rotation.  (x0, y0) is the OUTER corner of its top-left pixel (the x_min, y_max
+ * of geotiff.write_bands, the corner of a GDAL geotransform), px, py > 0 the pixel sizes in metres.  All images of a set share the
+ * pixel type (SN2_ORTHO_U8 / _U16 / _F32), C and the layout: SN2_ORTHO_CHUNKY (H,W,C) or SN2_ORTHO_PLANAR (C,H,W), contiguous.
+ *
+ * THE RULE, that of ortho.colorize_ref (numpy, fp64).  Point i has (x, y) = rows 0 and 1 of its column, fp32 widened to fp64.
+ *   u = (x - x0) / px      v = (y0 - y) / py          every operation rounded to fp64 on its own
+ *   inside  <=>  u >= 0 && u < W && v >= 0 && v < H    compared in fp64 before any conversion to int: NaN and inf are outside
+ *   col = (int)floor(u)    row = (int)floor(v)
+ * So the nearest pixel is the pixel whose area holds the point; a point exactly on an inner pixel edge belongs to the pixel to the
+ * east or to the south; x == x0 + W px is outside.  The images are tried in list order: the point takes the FIRST image that
+ * covers it and whose pixel is not nodata.  With has_nodata, a pixel is nodata iff every band SAMPLED there (band[0 .. n_map))
+ * equals `nodata`, the sample widened to fp64.  A point no image serves keeps the values it had and is counted as missing.  A
+ * served point gets, for k < n_map, row[k] = (float)pixel[band[k]] * scale: one fp32 product from the sample's exact fp32 value.
+ * Rows 0 and 1 are read and never written; the rows written are distinct and in 3..9.  A cloud in a shifted frame (the origin= of
+ * las.load_las / parcel.cut_parcels): the caller subtracts the shift in metres from x0, y0 in fp64 on the host; the kernel sees
+ * one frame.  UNPINNED against GDAL / pdal: the side a tie at a pixel edge falls to, and the default scale (ortho.py).
+ *
+ * sn2_ortho_colorize: ONE launch over the columns col0 .. col0 + T of a (10, row_stride) fp32 cloud (a ParcelClouds arena is one
+ *   such cloud: all K parcels in one launch).  The set travels BY VALUE in the kernel arguments, so an image's words are scalar
+ *   loads.  A lane holds one point, a wave walks the image list: the ballot of the lanes not yet served that lie inside image s
+ *   decides wave-uniformly whether image s is touched; a nodata pixel leaves its lane in the walk.  covered (T) uint8 or NULL:
+ *   the 1-based index of the serving image, 0 = missing, element i for column col0 + i.  missing: int64 device word, ADDED to --
+ *   one integer atomic per wave, the popcount of its unserved lanes.  No floating-point atomics: the same input gives the same bytes.
+ *   Pixel addresses are 64-bit.
+ * Before any launch the HOST copy of the set is checked, else SN2_EINVAL and no device work: set, cloud, missing non-NULL;
+ *   1 <= S <= SN2_ORTHO_MAX_IMAGES; C >= 1; dtype and layout known; 1 <= n_map <= SN2_ORTHO_MAX_MAP; 0 <= band[k] < C; row[k] in
+ *   3..9 and distinct; scale finite; nodata not NaN where has_nodata; per image: x0, y0 finite, px, py finite and > 0, W, H >= 1,
+ *   pixels non-NULL; T >= 0, col0 >= 0, col0 + T <= row_stride.  SN2_ELIMIT: W H C >= SN2_ORTHO_MAX_SAMPLES for an image, or
+ *   T >= 2^31.  T == 0 passes the checks and launches nothing. */
+#define SN2_ORTHO_MAX_IMAGES 32
+#define SN2_ORTHO_MAX_MAP 4
+#define SN2_ORTHO_MAX_SAMPLES (1LL << 40)
+#define SN2_ORTHO_U8 0
+#define SN2_ORTHO_U16 1
+#define SN2_ORTHO_F32 2
+#define SN2_ORTHO_CHUNKY 0
+#define SN2_ORTHO_PLANAR 1
+typedef struct {
+    double x0, y0, px, py;
+    const void *pixels;                                                 /* device */
+    int W, H;
+} sn2_ortho_image;
+typedef struct {
+    int S, C, dtype, layout, n_map, has_nodata;
+    int band[SN2_ORTHO_MAX_MAP], row[SN2_ORTHO_MAX_MAP];
+    double nodata;
+    float scale;
+    int reserved;
+    sn2_ortho_image image[SN2_ORTHO_MAX_IMAGES];
+} sn2_ortho_set;
+int sn2_ortho_colorize(float *cloud, long row_stride, long col0, long T, const sn2_ortho_set *set, unsigned char *covered,
+                       long long *missing, void *stream);
+
 /* ---- loss block of the timed training step: learning/loss_functions.py:9-57 combined as learning/train.py:58-62,
  *   total = get_absolute_loss(pred, gt) + m * get_NLL_loss(proba, pdf_all) + e * get_entropy_loss(proba)
  * pred (B,4) fp32 plot-wise coverages, gt (B,4) fp64, proba (R,4) fp32 pointwise class probabilities, pdf (R,3) fp64 the

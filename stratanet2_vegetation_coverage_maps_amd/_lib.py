@@ -29,6 +29,8 @@ CONSTANTS = {
     "SN2_LAS_COORDS_REFERENCE": 0, "SN2_LAS_COORDS_HEADER": 1, "SN2_LAS_ROWS": 10, "SN2_LAS_STATS_BYTES": 160, "SN2_LAS_FIELD_MASK_ALL": 0x3FF,
     "SN2_TIFF_LAYOUT_BAND": 0, "SN2_TIFF_LAYOUT_PIXEL": 1, "SN2_TIFF_PLACE_COLS": 4, "SN2_TIFF_STATS_BYTES": 16,
     "SN2_CUT_MAX_CELLS": 1 << 22, "SN2_CUT_MAX_ITEMS": 1 << 24,
+    "SN2_ORTHO_MAX_IMAGES": 32, "SN2_ORTHO_MAX_MAP": 4, "SN2_ORTHO_MAX_SAMPLES": 1 << 40, "SN2_ORTHO_U8": 0, "SN2_ORTHO_U16": 1, "SN2_ORTHO_F32": 2,
+    "SN2_ORTHO_CHUNKY": 0, "SN2_ORTHO_PLANAR": 1,
     "SN2_FP_FORM_SPLIT": 0, "SN2_FP_FORM_SOURCE_SIDE": 1, "SN2_FP_FORM_DENSE": 2,
     "SN2_FPS_FORM_BRUTE": 0, "SN2_FPS_FORM_ROUND": 1, "SN2_FPS_FORM_SPEC": 2, "SN2_FPS_FORM_CLUSTER": 3,
     "SN2_NET_FORK": 1, "SN2_NET_SHARED": 2, "SN2_NET_INVERTED": 4, "SN2_NET_DEFER_JOIN": 8, "SN2_NET_INPUT_ONLY": 16,
@@ -141,6 +143,16 @@ class CutTable(Structure):  # sn2_cut_table
                 ("n_edges", c_longlong), ("gx0", c_double), ("gy0", c_double), ("inv", c_double), ("buffer", c_double)] + [
                     (n, c_void_p) for n in ("cell_start", "cell_items", "edge_start", "edges", "cell_start_dev", "cell_items_dev",
                                             "edge_start_dev", "edges_dev")]
+
+
+class OrthoImage(Structure):  # sn2_ortho_image
+    _fields_ = [("x0", c_double), ("y0", c_double), ("px", c_double), ("py", c_double), ("pixels", c_void_p), ("W", c_int), ("H", c_int)]
+
+
+class OrthoSet(Structure):  # sn2_ortho_set
+    _fields_ = [(n, c_int) for n in ("S", "C", "dtype", "layout", "n_map", "has_nodata")] + [
+        ("band", c_int * CONSTANTS["SN2_ORTHO_MAX_MAP"]), ("row", c_int * CONSTANTS["SN2_ORTHO_MAX_MAP"]), ("nodata", c_double),
+        ("scale", c_float), ("reserved", c_int), ("image", OrthoImage * CONSTANTS["SN2_ORTHO_MAX_IMAGES"])]
 
 
 # name -> argtypes; every entry point returns int (0 ok, >0 hipError_t, <0 argument error; the route predicates: 0 / 1)
@@ -273,6 +285,8 @@ SIGNATURES = {
     "sn2_cut_ws_words": [POINTER(CutTable), POINTER(ctypes.c_size_t)],
     "sn2_cut_count": [c_void_p, c_void_p, c_void_p, POINTER(CutTable), c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],
     "sn2_cut_fill": [c_void_p, c_void_p, c_void_p, POINTER(CutTable), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
+    # the orthoimage colours (csrc/ortho.hip); the set is a host structure that holds device pointers
+    "sn2_ortho_colorize": [c_void_p, c_long, c_long, c_long, POINTER(OrthoSet), c_void_p, c_void_p, c_void_p],
     "sn2_kde_lookup": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "sn2_kde_fit": [c_void_p, c_long, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sn2_loss_forward": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,

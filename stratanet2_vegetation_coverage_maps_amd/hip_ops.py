@@ -2443,6 +2443,82 @@ def cut_fill(cloud: torch.Tensor, table: CutTable, prefix: torch.Tensor, parcel_
     return out, pidx
 
 
+# ---- the orthoimage colours (include/strata_hip.h, "Orthoimage colours"; csrc/ortho.hip) -------------------------------------------
+ORTHO_DTYPES = {"uint8": (_lib.SN2_ORTHO_U8, 1), "uint16": (_lib.SN2_ORTHO_U16, 2), "float32": (_lib.SN2_ORTHO_F32, 4)}
+ORTHO_LAYOUTS = {"chunky": _lib.SN2_ORTHO_CHUNKY, "planar": _lib.SN2_ORTHO_PLANAR}
+
+
+def ortho_check_mapping(C: int, bands, rows, scale):
+    """The (band, row) pairs of one call, checked before the library: 1 to SN2_ORTHO_MAX_MAP pairs, bands in [0, C), rows
+    distinct and in 3..9 (0 and 1 are the call's input), a finite scale."""
+    bands, rows = tuple(bands), tuple(rows)
+    if len(bands) != len(rows) or not 1 <= len(bands) <= _lib.SN2_ORTHO_MAX_MAP:
+        raise ValueError(f"bands, rows: 1 to {_lib.SN2_ORTHO_MAX_MAP} (band, row) pairs, got {len(bands)} bands and {len(rows)} rows")
+    for b in bands:
+        if int(b) != b or not 0 <= b < C:
+            raise ValueError(f"bands: band {b!r} of an image of {C}")
+    for r in rows:
+        if int(r) != r or not 3 <= r <= 9:
+            raise ValueError(f"rows: row {r!r}; the rows a call may write are 3..9 (0 and 1 are read)")
+    if len(set(rows)) != len(rows):
+        raise ValueError(f"rows: {rows} are not distinct")
+    if not math.isfinite(float(scale)):
+        raise ValueError(f"scale: expected a finite number, got {scale!r}")
+
+
+def ortho_set_struct(images, dtype: str, C: int, layout: str, bands, rows, scale: float, nodata=None) -> "_lib.OrthoSet":
+    """The sn2_ortho_set of one call.  images: up to SN2_ORTHO_MAX_IMAGES tuples (pixels: device address, x0, y0, px, py, W, H);
+    dtype: a key of ORTHO_DTYPES, layout: a key of ORTHO_LAYOUTS.  What can be refused without the library is refused here."""
+    images = list(images)
+    if dtype not in ORTHO_DTYPES:
+        raise ValueError(f"dtype: expected one of {tuple(ORTHO_DTYPES)}, got {dtype!r}")
+    if layout not in ORTHO_LAYOUTS:
+        raise ValueError(f"layout: expected one of {tuple(ORTHO_LAYOUTS)}, got {layout!r}")
+    if not 1 <= len(images) <= _lib.SN2_ORTHO_MAX_IMAGES:
+        raise ValueError(f"images: 1 to {_lib.SN2_ORTHO_MAX_IMAGES}, got {len(images)}")
+    if int(C) < 1:
+        raise ValueError(f"C: at least one band, got {C}")
+    ortho_check_mapping(C, bands, rows, scale)
+    if nodata is not None and math.isnan(float(nodata)):
+        raise ValueError("nodata: must not be NaN")
+    s = _lib.OrthoSet()
+    s.S, s.C, s.dtype, s.layout, s.n_map = len(images), int(C), ORTHO_DTYPES[dtype][0], ORTHO_LAYOUTS[layout], len(tuple(bands))
+    s.has_nodata, s.nodata, s.scale = int(nodata is not None), 0.0 if nodata is None else float(nodata), float(scale)
+    for k, (b, r) in enumerate(zip(bands, rows)):
+        s.band[k], s.row[k] = int(b), int(r)
+    for im, (ptr, x0, y0, px, py, W, H) in zip(s.image, images):
+        im.pixels, im.x0, im.y0, im.px, im.py, im.W, im.H = ptr, float(x0), float(y0), float(px), float(py), int(W), int(H)
+    return s
+
+
+def ortho_colorize(cloud: torch.Tensor, oset: "_lib.OrthoSet", col0: int = 0, T: Optional[int] = None, covered: Optional[torch.Tensor] = None,
+                   missing: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """include/strata_hip.h: sn2_ortho_colorize.  cloud (10, n) fp32 with unit stride along n (its row stride may be larger: a
+    column view of an arena); the columns col0 .. col0 + T (T None: all from col0) are coloured in place.  covered (T) u8 or None;
+    missing (1) i64, ADDED to (None: a fresh zero) -> missing.  The images' pixel buffers are the caller's to keep alive and to
+    size (W H C samples each)."""
+    if not isinstance(cloud, torch.Tensor) or not cloud.is_cuda or cloud.dtype != F32 or cloud.dim() != 2 or cloud.shape[0] != 10:
+        raise ValueError("cloud: expected a (10,T) fp32 tensor on the HIP device")
+    n = cloud.shape[1]
+    if n > 1 and cloud.stride(1) != 1:
+        raise ValueError("cloud: unit stride along the points")
+    row_stride = max(cloud.stride(0), n)
+    col0 = int(col0)
+    T = n - col0 if T is None else int(T)
+    if col0 < 0 or T < 0 or col0 + T > n:
+        raise ValueError(f"col0, T: columns {col0} .. {col0 + T} of a cloud of {n}")
+    if covered is not None:
+        _chk(covered, torch.uint8, (T,), "covered")
+    if missing is None:
+        missing = torch.zeros(1, dtype=I64, device=cloud.device)
+    _chk(missing, I64, (1,), "missing")
+    for t, name in ((covered, "covered"), (missing, "missing")):
+        if t is not None and t.device != cloud.device:
+            raise ValueError(f"{name}: must be on the cloud's device")
+    _call("sn2_ortho_colorize", _ptr(cloud), row_stride, col0, T, ctypes.byref(oset), _ptr(covered), _ptr(missing), _stream())
+    return missing
+
+
 LOSS_BLOCKS = _lib.SN2_LOSS_BLOCKS
 
 
