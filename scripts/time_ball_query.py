@@ -18,7 +18,7 @@ ref = {}
 for inflight in (1, 2, 4):
     so = os.path.join(ROOT, f"gpurun_out/libgq{inflight}.so")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared",
-                           f"-DSN2_GQ_INFLIGHT={inflight}", os.path.join(csrc, "geometry.hip"), "-o", so])
+                           f"-DSN2_GQ_INFLIGHT={inflight}", os.path.join(csrc, "ball_query.hip"), "-o", so])
     lib = ctypes.CDLL(so)
     lib.sn2_ball_query.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]

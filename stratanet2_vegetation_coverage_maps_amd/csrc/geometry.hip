@@ -1,4 +1,5 @@
-// geometry.hip -- position-only kernels: row packing, farthest point sampling, radius ball query, 3-NN.
+// geometry.hip -- position-only kernels: row packing and farthest point sampling (the radius ball query, the 3-NN searches and
+// the z-normalisation that stood here have units of their own: ball_query.hip, three_nn.hip, znorm.hip).
 // All discrete decisions use the canonical fp32 squared distance sn2_d2 (common.h) so that the index structures
 // are bit-identical to the oracle's.
 #include "common.h"
@@ -242,32 +243,7 @@ static int launch_fps(const fps_call& a) {
 //     index, as torch.argmax does on the unsorted array (candidates = lanes whose distance equals the global maximum).
 // Result: bit-identical indices to the brute-force kernel, with ~20x fewer distance evaluations after the first rounds.
 // ------------------------------------------------------------------------------------------------------------
-// 16 x 16 x 16 cells over the plot's bounding box, full 3-D Morton order.  (Measured on the synthetic plots: 19.6 of 512
-// buckets change per FPS round on average, against 27.7 for a 32 x 32 x 8 grid whose two top levels split x,y only.)
-constexpr int ORDER_GX = 16, ORDER_GZ = 16, ORDER_CELLS = ORDER_GX * ORDER_GX * ORDER_GZ;
-
-__device__ __forceinline__ unsigned morton_cell(unsigned cx, unsigned cy, unsigned cz) {
-    unsigned c = 0;
-#pragma unroll
-    for (int bit = 3; bit >= 0; --bit) c = (c << 3) | (((cx >> bit) & 1u) << 2) | (((cy >> bit) & 1u) << 1) | ((cz >> bit) & 1u);
-    return c;
-}
-
-// grid header per plot (32-bit words): [0..4096] first sorted position of every Morton cell (+ end), then lo.xyz, scale.xyz
-constexpr int GRID_WORDS = SN2_FPS_WS_GRID_WORDS;
-static_assert(GRID_WORDS == ORDER_CELLS + 1 + 6 + 1, "cell starts (+ end), lo.xyz, scale.xyz, padded to an even count");
-// exchange area of the multi-workgroup FPS (fps_cluster_kernel): per plot FPS_XCHG_WORDS words of tagged granules, then
-// FPS_CTL_WORDS control words per launch (ticket counter, timeout count).  Zeroed HERE, by the kernel in front of every FPS
-// launch (a kernel boundary: visible to every workgroup behind it; the tags count super-rounds from 1, so 0 = nothing yet).
-constexpr int FPS_XCHG_WORDS = SN2_FPS_WS_XCHG_WORDS, FPS_CTL_WORDS = SN2_FPS_WS_CTL_WORDS;
-// the Morton cell of a point (lo, sc: as the grid header keeps them)
-__device__ __forceinline__ unsigned order_cell(const float (&lo)[3], const float (&sc)[3], float x, float y, float z) {
-    int cx = (int)((x - lo[0]) * sc[0]), cy = (int)((y - lo[1]) * sc[1]), cz = (int)((z - lo[2]) * sc[2]);
-    cx = cx < 0 ? 0 : (cx > ORDER_GX - 1 ? ORDER_GX - 1 : cx);
-    cy = cy < 0 ? 0 : (cy > ORDER_GX - 1 ? ORDER_GX - 1 : cy);
-    cz = cz < 0 ? 0 : (cz > ORDER_GZ - 1 ? ORDER_GZ - 1 : cz);
-    return morton_cell((unsigned)cx, (unsigned)cy, (unsigned)cz);
-}
+#include "fps_ws.h"
 
 // One workgroup per plot walks the points three times (bounding box, histogram, scatter: the counting sort of plot_sort.h); a
 // trip fetches U points per thread before it touches the first (two trips per pass at N = 32 768 with U = 16 and 1024 threads:
@@ -1086,29 +1062,6 @@ static size_t fps_spec_lds_bytes() {
                           // with 12, 5.6 with 16 -- the prefix mostly ends at a candidate touched by an earlier one -- while
                           // the selection's cost grows with K)
 #endif
-// the parts of the workspace (include/strata_hip.h: SN2_FPS_WS_WORDS)
-struct fps_ws_parts {
-    int* order;          // B*N ints
-    float4* sorted;      // B*N float4 (16-byte aligned: B*N*4 bytes offset from a 16-byte aligned base with B*N % 4 == 0)
-    int* grid;           // B*GRID_WORDS ints
-    unsigned* xchg;      // B*FPS_XCHG_WORDS + FPS_CTL_WORDS
-    unsigned* ctl;
-    int* rank;           // B*N ints: the inverse of `order` (the last words of the workspace)
-};
-static fps_ws_parts fps_ws_carve(int* ws, int B, int N) {
-    int* grid = ws + SN2_FPS_WS_GRID_OFFSET(B, N);
-    return {ws, reinterpret_cast<float4*>(ws + (size_t)B * N), grid, reinterpret_cast<unsigned*>(grid + (size_t)B * GRID_WORDS),
-            reinterpret_cast<unsigned*>(ws + SN2_FPS_WS_CTL_OFFSET(B, N)), ws + SN2_FPS_WS_RANK_OFFSET(B, N)};
-}
-// ... and the tables a reader of a filled workspace takes (sn2_ball_query)
-struct fps_ws_tables {
-    const int* order;
-    const float4* sorted;
-    const int* grid;
-};
-static fps_ws_tables fps_ws_carve(const int* ws, int B, int N) {
-    return {ws, reinterpret_cast<const float4*>(ws + (size_t)B * N), ws + SN2_FPS_WS_GRID_OFFSET(B, N)};
-}
 static void launch_spatial_order(const fps_call& a, const fps_ws_parts& w) {
     launch_spatial_order(a.pos, a.B, a.N, w.order, w.sorted, w.grid, w.xchg, w.ctl, w.rank, a.nl, a.st);
 }
@@ -1919,16 +1872,10 @@ static int launch_fps_cluster_form(const fps_call& a, const sn2_fps_route_t& r) 
     }
 }
 
-static bool nn_grid_sources(int S) { return S >= 128 && S <= 8192; }      // what the per-plot x,y grid of three_nn_grid_kernel holds in LDS
-extern "C" int sn2_three_nn_uses_grid(int S, int T) { return nn_grid_sources(S) && T > 2048; }
-
 extern "C" size_t sn2_fps_ws_words(int B, int N) { return (size_t)SN2_FPS_WS_WORDS(B, N); }
 extern "C" size_t sn2_fps_ws_grid_offset(int B, int N) { return (size_t)SN2_FPS_WS_GRID_OFFSET(B, N); }
 extern "C" size_t sn2_fps_ws_ctl_offset(int B, int N) { return (size_t)SN2_FPS_WS_CTL_OFFSET(B, N); }
 extern "C" size_t sn2_fps_ws_rank_offset(int B, int N) { return (size_t)SN2_FPS_WS_RANK_OFFSET(B, N); }
-extern "C" size_t sn2_three_nn_ws_words(int B, int S) { return SN2_THREE_NN_WS_WORDS(B, S); }
-extern "C" size_t sn2_three_nn_xy_ws_words(int B, int S, int T) { return SN2_THREE_NN_XY_WS_WORDS(B, S, T); }
-extern "C" size_t sn2_znorm_ws_words(int n, long cells) { return SN2_ZNORM_WS_WORDS(n, cells); }
 
 extern "C" int sn2_fps_waves(const float* pos_soa, int B, int N, int M, const int* start, int* idx, float* cpos_soa,
                              float* cpos_aos, int* order_ws, int waves, void* stream) {
@@ -1958,887 +1905,4 @@ extern "C" int sn2_fps_live(const float* pos_soa, int B, int N, int M, const int
 extern "C" int sn2_fps(const float* pos_soa, int B, int N, int M, const int* start, int* idx, float* cpos_soa,
                        float* cpos_aos, int* order_ws, void* stream) {
     return sn2_fps_waves(pos_soa, B, N, M, start, idx, cpos_soa, cpos_aos, order_ws, 0, stream);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// ball_query: one wave owns TC centroids of one plot (coordinates and running counts wave-uniform -> SGPRs) and
-// streams the plot's points 64 at a time (coalesced SoA loads, L2-resident after the first wave); per centroid a
-// ballot + prefix popcount compacts the hits, so each list comes out in ascending source index and the stores of
-// one wave-instruction are contiguous.  Algorithmic HBM bytes: 12*(N+M) read + 4*E + 4*M written per plot.
-// ------------------------------------------------------------------------------------------------------------
-template <int TC>
-__global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict__ src, int B, int N,
-                                                         const float* __restrict__ cpos, int M, float r2, int cap,
-                                                         int* __restrict__ nbr, int* __restrict__ cnt,
-                                                         unsigned long long* __restrict__ total, int tiles_per_plot) {
-    const int lane = threadIdx.x & 63;
-    const int wg = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * 256 + threadIdx.x) >> 6));
-    const int b = wg / tiles_per_plot;
-    if (b >= B) return;
-    const int c0 = (wg - b * tiles_per_plot) * TC;
-    const float* px = src + (size_t)b * 3 * N;
-    const float* py = px + N;
-    const float* pz = py + N;
-    float cx[TC], cy[TC], cz[TC];
-    int n[TC];
-#pragma unroll
-    for (int t = 0; t < TC; ++t) {
-        const int ci = (c0 + t < M) ? c0 + t : M - 1;
-        cx[t] = cpos[((size_t)b * 3 + 0) * M + ci];
-        cy[t] = cpos[((size_t)b * 3 + 1) * M + ci];
-        cz[t] = cpos[((size_t)b * 3 + 2) * M + ci];
-        n[t] = 0;
-    }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int j0 = 0; j0 < N; j0 += 64) {
-        const int j = j0 + lane;
-        const bool valid = j < N;
-        const float x = valid ? px[j] : 0.f, y = valid ? py[j] : 0.f, z = valid ? pz[j] : 0.f;
-#pragma unroll
-        for (int t = 0; t < TC; ++t) {
-            const bool hit = valid && (sn2_d2(x, y, z, cx[t], cy[t], cz[t]) < r2);
-            const unsigned long long mask = __ballot(hit);
-            if (mask) {
-                const int p = n[t] + __popcll(mask & below);
-                if (hit && p < cap && c0 + t < M) nbr[((size_t)b * M + c0 + t) * cap + p] = j;
-                n[t] += __popcll(mask);
-            }
-        }
-    }
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int t = 0; t < TC; ++t) {
-        const int c = n[t] < cap ? n[t] : cap;
-        if (c0 + t < M) {
-            if (lane == 0) cnt[(size_t)b * M + c0 + t] = c;
-            sum += (unsigned long long)c;
-        }
-    }
-    (void)sum;
-    (void)total;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Grid ball query (exact): the sources were already sorted into 16^3 Morton cells by spatial_order_chunk_kernel (FPS level 1
-// runs on the same points).  One wave per centroid walks only the cells that can intersect the ball -- the cell range of
-// [c - r, c + r] per axis under the same monotone fp32 cell function, so no point with d2 < r2 is missed --, tests the
-// cells' points with the canonical sn2_d2, compacts the hits into a wave-private LDS list, rank-sorts them by ORIGINAL
-// index (the contract: ascending source index, first `cap` kept) and writes the list.  ~200 candidates per centroid
-// instead of 32 768.  A ball with more hits than the LDS list (GQ_LIST) falls back to the full scan for that centroid.
-// ------------------------------------------------------------------------------------------------------------
-constexpr int GQ_LIST = 512;
-#ifndef SN2_GQ_DENSE
-#define SN2_GQ_DENSE 512
-#endif
-constexpr int GQ_DENSE = SN2_GQ_DENSE;   // hits beyond which the bitmap path takes over from the rank sort (measured: switching at 192
-                                         // instead of 512 made the query slower at both sizes, 0.30 vs 0.26 ms at 8 x 131 072, 0.075 vs 0.054 at 16 x 32 768)
-static_assert(GQ_DENSE <= GQ_LIST, "the list holds the sparse balls");
-#ifndef SN2_GQ_BM_CAND
-#define SN2_GQ_BM_CAND 160
-#endif
-constexpr int GQ_BM_WORDS = 512, GQ_BM_CAND = SN2_GQ_BM_CAND;   // bitmap first: plots of <= 16 384 points, more candidates than this
-
-__global__ __launch_bounds__(256) void ball_query_grid_kernel(const float* __restrict__ src, int B, int N,
-                                                              const float* __restrict__ cpos, int M, float r, float r2,
-                                                              int cap, const int* __restrict__ order,
-                                                              const float4* __restrict__ sorted, const int* __restrict__ grid,
-                                                              int* __restrict__ nbr, int* __restrict__ cnt,
-                                                              unsigned long long* __restrict__ total, int xcd_aware) {
-    __shared__ int s_list[4][GQ_LIST];
-    extern __shared__ unsigned gq_bits[];              // [4][(N + 31) / 32]: one bit per source point, per wave (dense balls)
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    // XCD-aware placement (round 4): workgroups go to the eight XCDs round-robin, and every XCD has its own L2 -- with the
-    // centroids dealt out in index order all eight L2s fetched every plot's sorted table (PMC: 5.2 x the compulsory bytes at
-    // 16 x 32 768).  Plot b is worked on by the workgroups of XCD b % 8 only: workgroup w = (XCD w & 7, turn w >> 3), the turns
-    // of an XCD walk its plots one after the other, (M + 3) / 4 workgroups of four centroids per plot.
-    // (xcd_aware = 0: fewer plots than that balances -- a single plot would run on one XCD --: workgroup w takes plot w / bpp)
-    const int bpp = (M + 3) >> 2;
-    const int turn = xcd_aware ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int pb = xcd_aware ? (int)(blockIdx.x & 7u) + 8 * (turn / bpp) : turn / bpp;
-    const int pm = (turn % bpp) * 4 + wib;
-    if (pb >= B || pm >= M) return;
-    const int ci = __builtin_amdgcn_readfirstlane(pb * M + pm);
-    const int nwords = (N + 31) >> 5;
-    unsigned* bits = gq_bits + (size_t)wib * nwords;
-    // (Round 4 tried working the centroids in the order of their Morton cells instead of FPS order -- consecutive waves then
-    // walk the same cells while those are in L1 / L2 --: no gain at 16 x 32 768 (step 0.7661 against 0.7656 ms) and a small loss
-    // in the parcel loop (51.2 against 52.2 k plots/s): the kernel is bound by its instructions per candidate, not by where the
-    // candidates come from.)
-    const int b = ci / M, m = ci - b * M;
-    const float cx = cpos[((size_t)b * 3 + 0) * M + m], cy = cpos[((size_t)b * 3 + 1) * M + m],
-                cz = cpos[((size_t)b * 3 + 2) * M + m];
-    const int* gb = grid + (size_t)b * GRID_WORDS;
-    const float* gf = reinterpret_cast<const float*>(gb + ORDER_CELLS + 1);
-    const int* ord = order + (size_t)b * N;
-    const float4* pts = sorted + (size_t)b * N;
-    int* list = s_list[wib];
-    // conservative cell range: slightly enlarged radius, same cell function as the sort (monotone in the coordinate)
-    const float rr = r * 1.0001f + 1e-6f;
-    int lo3[3], hi3[3];
-    {
-        const float cc[3] = {cx, cy, cz};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const int G = a < 2 ? ORDER_GX : ORDER_GZ;
-            int l = (int)(((cc[a] - rr) - gf[a]) * gf[3 + a]), h = (int)(((cc[a] + rr) - gf[a]) * gf[3 + a]);
-            // (int) truncates toward zero: a negative argument must still map to cell 0 -> clamp covers it
-            lo3[a] = l < 0 ? 0 : (l > G - 1 ? G - 1 : l);
-            hi3[a] = h < 0 ? 0 : (h > G - 1 ? G - 1 : h);
-            if ((cc[a] - rr) - gf[a] < 0.f) lo3[a] = 0;
-        }
-    }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int h = 0;
-    // one lane per candidate cell: all cell bounds arrive with ONE round trip, then the candidates of all cells form one
-    // flat sequence that the wave walks 64 at a time (a cell-by-cell walk serialised ~50 dependent loads per centroid)
-    const int ncx = hi3[0] - lo3[0] + 1, ncy = hi3[1] - lo3[1] + 1, ncz = hi3[2] - lo3[2] + 1;
-    const int ncell = ncx * ncy * ncz;
-    bool overflow = ncell > 64;
-    bool dense = false;                                // more hits than the list holds: the bitmap path below
-    if (!overflow) {
-        __shared__ int s_pre[4][65], s_p0[4][64];
-        int p0 = 0, len = 0;
-        if (lane < ncell) {
-            const int ix = lo3[0] + lane % ncx, iy = lo3[1] + (lane / ncx) % ncy, iz = lo3[2] + lane / (ncx * ncy);
-            const unsigned cell = morton_cell((unsigned)ix, (unsigned)iy, (unsigned)iz);
-            p0 = gb[cell];
-            len = gb[cell + 1] - p0;
-        }
-        const int incl = wave_scan_incl(len);
-        const int T = __shfl(incl, 63);
-        s_pre[wib][lane + 1] = incl;   // exclusive prefix of cell i = s_pre[i]
-        if (lane == 0) s_pre[wib][0] = 0;
-        s_p0[wib][lane] = p0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        // four blocks of 64 candidates per turn, their positions AND original indices all requested before the first test:
-        // one round trip per 256 candidates (block by block, with the index fetched for the hits only, a centroid with 250
-        // candidates waited for eight dependent loads: 54 us per launch at 16 x 32 768)
-#ifndef SN2_GQ_INFLIGHT
-#define SN2_GQ_INFLIGHT 4
-#endif
-        constexpr int GQ_INFLIGHT = SN2_GQ_INFLIGHT;
-        // (a ball with few candidates -- the parcel loop's 10 000-point plots put ~70 into the 27 cells -- takes the same turn
-        // with one or two blocks: the cell search and the tests of empty blocks were a fifth of the kernel's instructions)
-        auto turn = [&](auto nb, int t0) {
-            constexpr int NB = decltype(nb)::value;
-            float4 qv[NB];
-            int oi[NB];
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                const int t = t0 + 64 * c + lane;
-                // the cell of candidate t: largest i with s_pre[i] <= t (binary search over <= 64 entries)
-                int lo_i = 0;
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1) {
-                    const int mid = lo_i + step;
-                    if (mid < ncell && s_pre[wib][mid] <= t) lo_i = mid;
-                }
-                const int p = t < T ? s_p0[wib][lo_i] + (t - s_pre[wib][lo_i]) : 0;
-                qv[c] = pts[p];
-                oi[c] = ord[p];
-            }
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                const bool in = t0 + 64 * c + lane < T;
-                const bool hit = in && (sn2_d2(qv[c].x, qv[c].y, qv[c].z, cx, cy, cz) < r2);
-                const unsigned long long mask = __ballot(hit);
-                if (mask && !dense) {
-                    const int nh = __popcll(mask);
-                    if (h + nh > GQ_DENSE) {
-                        dense = true;
-                    } else {
-                        if (hit) list[h + __popcll(mask & below)] = oi[c];
-                        h += nh;
-                    }
-                }
-            }
-        };
-        // Small plots with many candidates (the parcel loop: 10 000 points, r = sqrt 2: ~500 candidates and ~150 hits per centroid)
-        // go to the bitmap at once: it is N / 32 words (5 trips of the wave to clear, 5 to read) whatever the count, while
-        // rank-sorting h hits is h^2 / 64 steps -- 1.3 ms of the 5.5 ms a launch of 256 plots takes went into those sorts --, and
-        // deciding it before the first walk saves the second one.  Same lists: ascending original index either way.
-        if (nwords <= GQ_BM_WORDS && T > GQ_BM_CAND) dense = true;
-        else if (T <= 64) turn(std::integral_constant<int, 1>{}, 0);
-        else if (T <= 128) turn(std::integral_constant<int, 2>{}, 0);
-        else
-            for (int t0 = 0; t0 < T && !dense; t0 += 64 * GQ_INFLIGHT) turn(std::integral_constant<int, GQ_INFLIGHT>{}, t0);
-        if (dense) {
-            // A dense ball (the ground layer of a 131 072-point plot puts ~700 points into a 1 m ball): rank-sorting h hits
-            // costs h^2 / 64 steps and the old fallback re-scanned the whole plot (2048 steps per centroid: 0.78 ms at
-            // BASELINE config 5).  Instead: one bit per source point in LDS, the candidates walked once more to set the
-            // hits' bits, then the bitmap read in order -- ascending original index by construction, no sort, any count.
-            for (int i = lane; i < nwords; i += 64) bits[i] = 0u;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            for (int t0 = 0; t0 < T; t0 += 64 * GQ_INFLIGHT) {
-                float4 qv[GQ_INFLIGHT];
-                int oi[GQ_INFLIGHT];
-#pragma unroll
-                for (int c = 0; c < GQ_INFLIGHT; ++c) {
-                    const int t = t0 + 64 * c + lane;
-                    int lo_i = 0;
-#pragma unroll
-                    for (int step = 32; step > 0; step >>= 1) {
-                        const int mid = lo_i + step;
-                        if (mid < ncell && s_pre[wib][mid] <= t) lo_i = mid;
-                    }
-                    const int p = t < T ? s_p0[wib][lo_i] + (t - s_pre[wib][lo_i]) : 0;
-                    qv[c] = pts[p];
-                    oi[c] = ord[p];
-                }
-#pragma unroll
-                for (int c = 0; c < GQ_INFLIGHT; ++c)
-                    if (t0 + 64 * c + lane < T && (sn2_d2(qv[c].x, qv[c].y, qv[c].z, cx, cy, cz) < r2))
-                        atomicOr(&bits[oi[c] >> 5], 1u << (oi[c] & 31));
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            int* outd = nbr + (size_t)ci * cap;
-            int n = 0;
-            for (int w0 = 0; w0 < nwords; w0 += 64) {
-                unsigned word = (w0 + lane < nwords) ? bits[w0 + lane] : 0u;
-                const int c = __popc(word);
-                if (__ballot(c != 0) == 0ull) continue;
-                const int incl = wave_scan_incl(c);
-                int pos = n + incl - c;
-                while (word) {
-                    const int bit = __ffs(word) - 1;
-                    word &= word - 1;
-                    if (pos < cap) outd[pos] = (w0 + lane) * 32 + bit;
-                    ++pos;
-                }
-                n += __shfl(incl, 63);
-            }
-            if (lane == 0) cnt[ci] = n < cap ? n : cap;
-            return;
-        }
-    }
-    int* out = nbr + (size_t)ci * cap;
-    if (!overflow) {
-        // rank sort by original index (indices are distinct), keep the first `cap`
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int i0 = 0; i0 < h; i0 += 64) {
-            const int i = i0 + lane;
-            const int mine = i < h ? list[i] : 0x7FFFFFFF;
-            int rank = 0;
-            for (int j = 0; j < h; ++j) rank += list[j] < mine ? 1 : 0;
-            if (i < h && rank < cap) out[rank] = mine;
-        }
-        const int c = h < cap ? h : cap;
-        if (lane == 0) cnt[ci] = c;
-    } else {
-        // dense ball: full scan of the plot in index order (identical to ball_query_kernel for one centroid)
-        const float* px = src + (size_t)b * 3 * N;
-        const float* py = px + N;
-        const float* pz = py + N;
-        int n = 0;
-        for (int j0 = 0; j0 < N; j0 += 64) {
-            const int j = j0 + lane;
-            const bool valid = j < N;
-            const float x = valid ? px[j] : 0.f, y = valid ? py[j] : 0.f, z = valid ? pz[j] : 0.f;
-            const bool hit = valid && (sn2_d2(x, y, z, cx, cy, cz) < r2);
-            const unsigned long long mask = __ballot(hit);
-            if (mask) {
-                const int p = n + __popcll(mask & below);
-                if (hit && p < cap) out[p] = j;
-                n += __popcll(mask);
-            }
-        }
-        const int c = n < cap ? n : cap;
-        if (lane == 0) cnt[ci] = c;
-    }
-}
-
-// *total = sum of cnt (one workgroup; thousands of same-address atomics from the query waves cost 0.2 ms)
-// (grouped: workgroup h sums the n counts of batch h into total[h * tstride] -- sn2_count_sum_group)
-__global__ __launch_bounds__(1024) void count_sum_kernel(const int* __restrict__ cnt_all, int n, unsigned long long* __restrict__ total_all,
-                                                         size_t tstride = 0) {
-    __shared__ unsigned long long s_tot;
-    const int* __restrict__ cnt = cnt_all + (size_t)blockIdx.x * n;
-    unsigned long long* __restrict__ total = total_all + (size_t)blockIdx.x * tstride;
-    unsigned long long acc = 0;
-    // sixteen counts per lane in flight (one dependent load per trip: 0.19 ms for the parcel loop's 640 000 counts)
-    const int n16 = (reinterpret_cast<uintptr_t>(cnt) & 15) == 0 ? n / 16 : 0;
-    const int4* c4 = reinterpret_cast<const int4*>(cnt);
-    for (int i = threadIdx.x; i < n16; i += 1024) {
-        int4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = c4[(size_t)i * 4 + u];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc += (unsigned long long)((long)v[u].x + v[u].y + v[u].z + v[u].w);
-    }
-    for (int i = n16 * 16 + threadIdx.x; i < n; i += 1024) acc += (unsigned long long)cnt[i];
-    if (threadIdx.x == 0) s_tot = 0ull;
-    __syncthreads();
-    atomicAdd(&s_tot, acc);
-    __syncthreads();
-    if (threadIdx.x == 0) *total = s_tot;
-}
-
-extern "C" int sn2_ball_query(const float* src_soa, int B, int N, const float* cpos_soa, int M, float r2, int cap,
-                              int* nbr, int* cnt, unsigned long long* total, const int* fps_ws, void* stream) {
-    if (!src_soa || !cpos_soa || !nbr || !cnt || B <= 0 || N <= 0 || M <= 0 || cap <= 0 || !(r2 > 0.f)) return SN2_EINVAL;
-    const float r = sqrtf(r2);   // only used (enlarged) to bound the cell range; the hit test is d2 < r2
-    if (fps_ws && N > 2048 && (((size_t)B * N) % 4 == 0)) {
-        // the sources are the point set FPS just sorted: walk its cell lists instead of the whole plot
-        const fps_ws_tables w = fps_ws_carve(fps_ws, B, N);
-        const int* order = w.order;
-        const float4* sorted = w.sorted;
-        const int* grid = w.grid;
-        const size_t lds = (size_t)4 * ((N + 31) / 32) * sizeof(unsigned);       // the dense-ball bitmaps: 64 KB at N = 131 072
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ball_query_grid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        // grid: eight XCDs x the plots of the fullest XCD x the workgroups of a plot (ball_query_grid_kernel: placement)
-        // (plots per XCD must balance: a multiple of 8 plots, or so many that the remainder does not matter)
-        static const bool gq_no_xcd = getenv("SN2_GQ_NO_XCD") != nullptr;        // (diagnostic switch)
-        const int xcd_aware = (!gq_no_xcd && (B % 8 == 0 || B >= 64)) ? 1 : 0;
-        const long gq_blocks = xcd_aware ? 8L * sn2_cdiv(B, 8) * sn2_cdiv(M, 4) : (long)B * sn2_cdiv(M, 4);
-        if (gq_blocks >= (1L << 31)) return SN2_ELIMIT;
-        hipLaunchKernelGGL(ball_query_grid_kernel, dim3((unsigned)gq_blocks), dim3(256), lds, (hipStream_t)stream, src_soa,
-                           B, N, cpos_soa, M, r, r2, cap, order, sorted, grid, nbr, cnt, total, xcd_aware);
-        if (total) hipLaunchKernelGGL(count_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int*)cnt, B * M, total);
-        SN2_RETURN_LAUNCH();
-    }
-    constexpr int TC = 8;
-    const int tiles = sn2_cdiv(M, TC);
-    const long waves = (long)B * tiles;
-    hipLaunchKernelGGL((ball_query_kernel<TC>), dim3(sn2_cdiv(waves, 4)), dim3(256), 0, (hipStream_t)stream, src_soa, B,
-                       N, cpos_soa, M, r2, cap, nbr, cnt, total, tiles);
-    if (total) hipLaunchKernelGGL(count_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int*)cnt, B * M, total);
-    SN2_RETURN_LAUNCH();
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// three_nn: one lane per target point, the plot's source positions staged through LDS in tiles of 1024 (AoS4, every
-// lane reads the same address -> broadcast), ascending source index with strict '<' insertion so ties keep the
-// lowest index (oracle: stable sort).  Writes idx (B*T,3), w (B*T,3) = 1/max(d2,1e-16); unused slots w = 0.
-// ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void three_nn_kernel(const float* __restrict__ src, int S, const float* __restrict__ dst,
-                                                       int T, int k, int* __restrict__ idx, float* __restrict__ w) {
-    __shared__ float4 s_src[1024];
-    const int b = blockIdx.y;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = t < T;
-    const float* sx = src + (size_t)b * 3 * S;
-    const float* dx = dst + (size_t)b * 3 * T;
-    const float qx = valid ? dx[t] : 0.f, qy = valid ? dx[(size_t)T + t] : 0.f, qz = valid ? dx[2 * (size_t)T + t] : 0.f;
-    float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
-    int i0 = -1, i1 = -1, i2 = -1;
-    for (int s0 = 0; s0 < S; s0 += 1024) {
-        const int tn = (S - s0) < 1024 ? (S - s0) : 1024;
-        __syncthreads();
-        for (int i = threadIdx.x; i < tn; i += 256)
-            s_src[i] = make_float4(sx[s0 + i], sx[(size_t)S + s0 + i], sx[2 * (size_t)S + s0 + i], 0.f);
-        __syncthreads();
-        for (int i = 0; i < tn; ++i) {
-            const float4 p = s_src[i];
-            const float dd = sn2_d2(p.x, p.y, p.z, qx, qy, qz);
-            if (dd < d2) {
-                if (dd < d1) {
-                    d2 = d1;
-                    i2 = i1;
-                    if (dd < d0) {
-                        d1 = d0;
-                        i1 = i0;
-                        d0 = dd;
-                        i0 = s0 + i;
-                    } else {
-                        d1 = dd;
-                        i1 = s0 + i;
-                    }
-                } else {
-                    d2 = dd;
-                    i2 = s0 + i;
-                }
-            }
-        }
-    }
-    if (!valid) return;
-    const size_t o = ((size_t)b * T + t) * 3;
-    const bool u1 = (k >= 2) && (i1 >= 0), u2 = (k >= 3) && (i2 >= 0);
-    idx[o + 0] = i0;
-    idx[o + 1] = u1 ? i1 : i0;
-    idx[o + 2] = u2 ? i2 : i0;
-    w[o + 0] = 1.0f / fmaxf(d0, 1e-16f);
-    w[o + 1] = u1 ? 1.0f / fmaxf(d1, 1e-16f) : 0.f;
-    w[o + 2] = u2 ? 1.0f / fmaxf(d2, 1e-16f) : 0.f;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Grid 3-NN (exact), for targets that FPS already put into Morton order (FP1: the targets are the plot's points).
-// The plot's S sources are binned once into a G x G grid over their x,y bounding box (nn_grid_build_kernel: LDS counting
-// sort -> a table of (x, y, z, source index) in cell order + the cell starts).  One wave takes 64 consecutive SORTED
-// targets -- neighbours in space -- and treats them as one query box: it visits the cells under the box, then square
-// rings of growing radius rho around it, every lane testing every visited source (wave-uniform loops, LDS broadcast
-// reads; a per-lane walk of each lane's own cells was tried first and lost to the brute-force scan: a wave runs as long
-// as its worst lane at every cell).  It stops when the largest k-th best squared distance of its lanes is below what any
-// unvisited source can reach: such a source lies in a cell more than rho columns or rows away from the cells of ALL the
-// wave's targets, so its x or y gap -- hence its distance -- to each of them exceeds rho cell widths (taken 0.1 % short
-// and minus 1e-4 m, which covers the fp32 rounding of the cell assignment and of sn2_d2).  Candidates arrive in arbitrary
-// index order, so the running best three are kept in (d2, index) lexicographic order: exactly the brute-force scan's
-// "ascending index, strict <" result, bit for bit.  ~50-150 distance evaluations per target instead of S = 1024.
-// ------------------------------------------------------------------------------------------------------------
-constexpr int NN_GMAX = 32;
-constexpr int NN_HDR = NN_GMAX * NN_GMAX + 1 + 7;   // cell starts (G*G+1), then x0, y0, inv_x, inv_y, min cell width, G (as int), pad
-
-__global__ __launch_bounds__(256) void nn_grid_build_kernel(const float* __restrict__ src, int S, int G,
-                                                            float4* __restrict__ tbl, int* __restrict__ hdr) {
-    __shared__ int s_hist[NN_GMAX * NN_GMAX + 1];
-    __shared__ float s_mm[4][4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* sx = src + (size_t)b * 3 * S;
-    const float* sy = sx + S;
-    const float* sz = sy + S;
-    auto load = [&](int i) { return make_float3(sx[i], sy[i], sz[i]); };
-    float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
-    for_plot_points<1, 256>(S, load, [&](int, float3 v) {
-        lo[0] = fminf(lo[0], v.x); hi[0] = fmaxf(hi[0], v.x);
-        lo[1] = fminf(lo[1], v.y); hi[1] = fmaxf(hi[1], v.y);
-    });
-    block_minmax<256, 2>(lo, hi, s_mm);
-    const float x0 = lo[0], y0 = lo[1];
-    const float ex = fmaxf(hi[0] - x0, 1e-6f), ey = fmaxf(hi[1] - y0, 1e-6f);
-    const float ix = (float)G / ex, iy = (float)G / ey;
-    int* hb = hdr + (size_t)b * NN_HDR;
-    if (tid == 0) {
-        float* hf = reinterpret_cast<float*>(hb + NN_GMAX * NN_GMAX + 1);
-        hf[0] = x0; hf[1] = y0; hf[2] = ix; hf[3] = iy; hf[4] = fminf(ex, ey) / (float)G;
-        hb[NN_GMAX * NN_GMAX + 1 + 5] = G;
-    }
-    float4* tb = tbl + (size_t)b * S;
-    plot_counting_sort<1, 256, NN_GMAX * NN_GMAX, true>(
-        s_hist, G * G, S, load,
-        [&](float3 v) {
-            int cx = (int)((v.x - x0) * ix), cy = (int)((v.y - y0) * iy);
-            cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
-            cy = cy < 0 ? 0 : (cy > G - 1 ? G - 1 : cy);
-            return cy * G + cx;
-        },
-        [&](int cell, int start) { hb[cell] = start; },       // cell starts + end word (= S)
-        [&](int i, int p, float3 v) { tb[p] = make_float4(v.x, v.y, v.z, __int_as_float(i)); });
-}
-
-#ifdef SN2_NN_STAMPS
-// diagnostic build only (never shipped): per wave {cycles, candidates tested, final ring, query box cells}
-__device__ unsigned long long g_nn_dbg[4 * 16384];
-extern "C" int sn2_debug_nn_stamps(unsigned long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_dbg), sizeof(unsigned long long) * n);
-}
-#endif
-__global__ __launch_bounds__(256) void three_nn_grid_kernel(const float4* __restrict__ tbl, const int* __restrict__ hdr, int S,
-                                                            int T, int k, const int* __restrict__ dst_order,
-                                                            const float4* __restrict__ dst_sorted,
-                                                            int* __restrict__ idx, float* __restrict__ w, int B, int gx,
-                                                            int* __restrict__ idx_sorted, float* __restrict__ w_sorted) {
-    extern __shared__ __attribute__((aligned(16))) float4 s_tbl[];      // S entries, then the cell starts
-    // XCD-aware placement (as ball_query_grid_kernel): with B = 0 the grid is (gx, plots) as before; with B > 0 it is one-
-    // dimensional, workgroup w = (XCD w & 7, turn w >> 3), and plot b is worked on by XCD b % 8 only -- the results go to the
-    // targets' ORIGINAL rows, 24 bytes each into lines that ten waves share, and only waves behind the same L2 merge them
-    // there before they are written back
-    int b = blockIdx.y, bx = blockIdx.x;
-    if (B > 0) {
-        const int turn = (int)(blockIdx.x >> 3);
-        b = (int)(blockIdx.x & 7u) + 8 * (turn / gx);
-        bx = turn % gx;
-        if (b >= B) return;
-    }
-    const int lane = threadIdx.x & 63;
-    const int* hb = hdr + (size_t)b * NN_HDR;
-    const int G = __builtin_amdgcn_readfirstlane(hb[NN_GMAX * NN_GMAX + 1 + 5]);
-    int* s_cell = reinterpret_cast<int*>(s_tbl + S);
-    for (int i = threadIdx.x; i < S; i += 256) s_tbl[i] = tbl[(size_t)b * S + i];
-    for (int i = threadIdx.x; i <= G * G; i += 256) s_cell[i] = hb[i];
-    __syncthreads();
-    const int p = bx * 256 + threadIdx.x;                                // sorted position
-    if (p - lane >= T) return;                                           // whole wave past the end
-    const bool valid = p < T;
-    const float* hf = reinterpret_cast<const float*>(hb + NN_GMAX * NN_GMAX + 1);
-    const float x0 = hf[0], y0 = hf[1], ix = hf[2], iy = hf[3], cw = hf[4];
-    const float4 q = dst_sorted[(size_t)b * T + (valid ? p : T - 1)];
-    const float qx = q.x, qy = q.y, qz = q.z;
-    // the cells under the wave's targets (clamped like the sources' cells; the cell function is monotone)
-    auto cell1 = [&](float v, float o, float inv) {
-        int c = (int)((v - o) * inv);
-        return (v - o < 0.f || c < 0) ? 0 : (c > G - 1 ? G - 1 : c);
-    };
-    const int bx0 = __builtin_amdgcn_readfirstlane(cell1(wave_min(qx), x0, ix)),
-              bx1 = __builtin_amdgcn_readfirstlane(cell1(wave_max(qx), x0, ix));
-    const int by0 = __builtin_amdgcn_readfirstlane(cell1(wave_min(qy), y0, iy)),
-              by1 = __builtin_amdgcn_readfirstlane(cell1(wave_max(qy), y0, iy));
-    constexpr unsigned long long KINF = (0x7F800000ull << 32) | 0x7FFFFFFFull;     // (+inf, no index)
-    unsigned long long k0 = KINF, k1 = KINF, k2 = KINF;
-    const int kk = k < S ? k : S;          // slots that will be filled
-#ifdef SN2_NN_STAMPS
-    unsigned long long t_begin;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_begin)::"memory");
-    unsigned n_cand = 0;
-    int rho_last = 0;
-#endif
-    for (int rho = 0;; ++rho) {
-#ifdef SN2_NN_STAMPS
-        rho_last = rho;
-#endif
-        const int xl = bx0 - rho, xh = bx1 + rho, yl = by0 - rho, yh = by1 + rho;
-        const int cxl = xl < 0 ? 0 : xl, cxh = xh > G - 1 ? G - 1 : xh;
-        for (int cy = (yl < 0 ? 0 : yl); cy <= (yh > G - 1 ? G - 1 : yh); ++cy) {
-            // a new row of the rectangle is one segment of contiguous cells; an old row contributes its two new end cells
-            const bool whole = rho == 0 || cy == yl || cy == yh;
-            for (int sg = 0; sg < (whole ? 1 : 2); ++sg) {
-                int c_lo, c_hi;
-                if (whole) {
-                    c_lo = cy * G + cxl; c_hi = cy * G + cxh;
-                } else if (sg == 0) {
-                    if (xl < 0) continue;
-                    c_lo = c_hi = cy * G + xl;
-                } else {
-                    if (xh > G - 1) continue;
-                    c_lo = c_hi = cy * G + xh;
-                }
-                // wave-uniform bounds in SGPRs: scalar loop control and one broadcast LDS read per candidate; the common
-                // case (the candidate beats nobody's third best) is 8 VALU ops, one compare and one branch.  (Written
-                // inline, not as a lambda: called through a closure the best-three state ended up in scratch memory.)
-                const int p_lo = __builtin_amdgcn_readfirstlane(s_cell[c_lo]), p_hi = __builtin_amdgcn_readfirstlane(s_cell[c_hi + 1]);
-#ifdef SN2_NN_STAMPS
-                n_cand += p_hi - p_lo;
-#endif
-// the running best three as 64-bit keys (d2 bits << 32 | source index): d2 >= 0, so the unsigned order of the keys IS the
-// lexicographic (d2, index) order, and an insertion is three branch-free min/max steps.  (With 64 lanes per query box
-// nearly every candidate is a hit for SOME lane, so the nested-if insertion ran, divergent, for most candidates.)
-#define NN_INSERT(DD, CW)                                                                                  \
-    {                                                                                                      \
-        const unsigned long long kn_ = ((unsigned long long)__float_as_uint(DD) << 32) | (unsigned)__float_as_int(CW); \
-        k2 = kn_ < k2 ? kn_ : k2;                                                                          \
-        const unsigned long long a_ = k1 < k2 ? k1 : k2, b_ = k1 < k2 ? k2 : k1;                           \
-        k1 = a_; k2 = b_;                                                                                  \
-        const unsigned long long c_ = k0 < k1 ? k0 : k1, e_ = k0 < k1 ? k1 : k0;                           \
-        k0 = c_; k1 = e_;                                                                                  \
-    }
-                int sp = p_lo;
-                for (; sp + 4 <= p_hi; sp += 4) {
-                    const float4 c0 = s_tbl[sp], c1 = s_tbl[sp + 1], c2 = s_tbl[sp + 2], c3 = s_tbl[sp + 3];
-                    const float e0 = sn2_d2(c0.x, c0.y, c0.z, qx, qy, qz), e1 = sn2_d2(c1.x, c1.y, c1.z, qx, qy, qz);
-                    const float e2 = sn2_d2(c2.x, c2.y, c2.z, qx, qy, qz), e3 = sn2_d2(c3.x, c3.y, c3.z, qx, qy, qz);
-                    if (fminf(fminf(e0, e1), fminf(e2, e3)) <= __uint_as_float((unsigned)(k2 >> 32))) {
-                        NN_INSERT(e0, c0.w)
-                        NN_INSERT(e1, c1.w)
-                        NN_INSERT(e2, c2.w)
-                        NN_INSERT(e3, c3.w)
-                    }
-                }
-                for (; sp < p_hi; ++sp) {
-                    const float4 c = s_tbl[sp];
-                    const float dd = sn2_d2(c.x, c.y, c.z, qx, qy, qz);
-                    NN_INSERT(dd, c.w)
-                }
-#undef NN_INSERT
-            }
-        }
-        if (xl <= 0 && yl <= 0 && xh >= G - 1 && yh >= G - 1) break;     // the whole grid has been visited
-        const float reach = (float)rho * cw * 0.999f - 1e-4f;           // nothing unvisited is closer than this
-        const float dk = __uint_as_float((unsigned)((kk >= 3 ? k2 : (kk == 2 ? k1 : k0)) >> 32));
-        const float worst = wave_max(valid ? dk : 0.f);
-        if (reach > 0.f && worst < reach * reach) break;
-    }
-    const float d0 = __uint_as_float((unsigned)(k0 >> 32)), d1 = __uint_as_float((unsigned)(k1 >> 32)),
-                d2 = __uint_as_float((unsigned)(k2 >> 32));
-    const int i0 = (int)(unsigned)k0, i1 = (int)(unsigned)k1, i2 = (int)(unsigned)k2;
-#ifdef SN2_NN_STAMPS
-    {
-        unsigned long long t_end;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_end)::"memory");
-        const int wid = (b * gx + bx) * 4 + (threadIdx.x >> 6);
-        if (lane == 0 && wid < 16384) {
-            g_nn_dbg[4 * wid + 0] = t_end - t_begin;
-            g_nn_dbg[4 * wid + 1] = n_cand;
-            g_nn_dbg[4 * wid + 2] = rho_last;
-            g_nn_dbg[4 * wid + 3] = (unsigned long long)((bx1 - bx0 + 1) * (by1 - by0 + 1));
-        }
-    }
-#endif
-    if (!valid) return;
-    const int t = dst_order[(size_t)b * T + p];
-    const size_t o = ((size_t)b * T + t) * 3;
-    const bool u1 = (k >= 2) && (i1 != 0x7FFFFFFF), u2 = (k >= 3) && (i2 != 0x7FFFFFFF);
-    const int j1 = u1 ? i1 : i0, j2 = u2 ? i2 : i0;
-    const float w0 = 1.0f / fmaxf(d0, 1e-16f), w1 = u1 ? 1.0f / fmaxf(d1, 1e-16f) : 0.f, w2 = u2 ? 1.0f / fmaxf(d2, 1e-16f) : 0.f;
-    idx[o + 0] = i0;
-    idx[o + 1] = j1;
-    idx[o + 2] = j2;
-    w[o + 0] = w0;
-    w[o + 1] = w1;
-    w[o + 2] = w2;
-    // the same row once more at its SORTED position (sn2_three_nn_xy_copy): 24 bytes per lane, contiguous across the wave --
-    // the table in the order the inverted index is built in (interp_index.hip)
-    if (idx_sorted) {
-        const size_t q = ((size_t)b * T + p) * 3;
-        idx_sorted[q + 0] = i0;
-        idx_sorted[q + 1] = j1;
-        idx_sorted[q + 2] = j2;
-        w_sorted[q + 0] = w0;
-        w_sorted[q + 1] = w1;
-        w_sorted[q + 2] = w2;
-    }
-}
-
-extern "C" int sn2_count_sum_group(const int* cnt, int G, int n, unsigned long long* total, size_t total_stride, void* stream) {
-    if (!cnt || !total || G <= 0 || n <= 0 || (G > 1 && total_stride < 1)) return SN2_EINVAL;
-    hipLaunchKernelGGL(count_sum_kernel, dim3(G), dim3(1024), 0, (hipStream_t)stream, cnt, n, total, total_stride);
-    SN2_RETURN_LAUNCH();
-}
-
-extern "C" int sn2_count_sum(const int* cnt, int n, unsigned long long* total, void* stream) {
-    if (!cnt || !total || n <= 0) return SN2_EINVAL;
-    hipLaunchKernelGGL(count_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, cnt, n, total);
-    SN2_RETURN_LAUNCH();
-}
-
-// The targets of a plot in the order of the SOURCE grid's cells (rows of cells walked in a snake, so that consecutive cells
-// are always neighbours): counting sort in LDS, one workgroup per plot.  A wave of three_nn_grid_kernel then holds 64
-// targets of one or two adjacent cells -- a 1-2 cell query box for every wave.  (In the order sn2_fps leaves, a 3-D
-// Morton order of a 16^3 grid, the boxes averaged 7 cells and reached 72: 162 candidates per wave on average, 726 in
-// the slowest, and the slowest wave is the kernel.)  The order inside a cell is whatever the cursor atomics give: the
-// search is exact, so its results do not depend on it.
-// U loads per coordinate in flight (a loop of one point per thread and trip spends a trip of dependent loads per point and
-// pass: 54 us at T = 32 768).  A target below the sources' box on an axis (vx < 0) goes to the first cell of that axis.
-template <int U, int NT>
-__global__ __launch_bounds__(NT) void nn_target_sort_chunk_kernel(const float* __restrict__ dst, int T, const int* __restrict__ hdr,
-                                                                    int* __restrict__ order, float4* __restrict__ sorted) {
-    __shared__ int s_hist[NN_GMAX * NN_GMAX];
-    __shared__ int s_wsum[NT / 64];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* dx = dst + (size_t)b * 3 * T;
-    const float* dy = dx + T;
-    const float* dz = dy + T;
-    const int* hb = hdr + (size_t)b * NN_HDR;
-    const int G = hb[NN_GMAX * NN_GMAX + 1 + 5];
-    const float* hf = reinterpret_cast<const float*>(hb + NN_GMAX * NN_GMAX + 1);
-    const float x0 = hf[0], y0 = hf[1], ix = hf[2], iy = hf[3];
-    auto key_of = [&](float px_, float py_) {
-        const float vx = px_ - x0, vy = py_ - y0;
-        int cx = (int)(vx * ix), cy = (int)(vy * iy);
-        cx = (vx < 0.f || cx < 0) ? 0 : (cx > G - 1 ? G - 1 : cx);
-        cy = (vy < 0.f || cy < 0) ? 0 : (cy > G - 1 ? G - 1 : cy);
-        return cy * G + ((cy & 1) ? G - 1 - cx : cx);
-    };
-    for (int i = tid; i < G * G; i += NT) s_hist[i] = 0;
-    __syncthreads();
-    // (plot_sort.h's loader written out: through it the 256-thread form measured 3 % slower, profiles/plot_sort)
-    for (int i0 = 0; i0 < T; i0 += NT * U) {
-        float vx[U], vy[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * NT + tid, ii = i < T ? i : T - 1;
-            vx[u] = dx[ii]; vy[u] = dy[ii];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (i0 + u * NT + tid < T) atomicAdd(&s_hist[key_of(vx[u], vy[u])], 1);
-    }
-    __syncthreads();
-    block_scan_cells<NT, NN_GMAX * NN_GMAX, false>(s_hist, G * G, s_wsum, [](int, int) {});
-    int* ob = order + (size_t)b * T;
-    float4* sb = sorted + (size_t)b * T;
-    for (int i0 = 0; i0 < T; i0 += NT * U) {
-        float vx[U], vy[U], vz[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * NT + tid, ii = i < T ? i : T - 1;
-            vx[u] = dx[ii]; vy[u] = dy[ii]; vz[u] = dz[ii];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * NT + tid;
-            if (i < T) {
-                const int p = atomicAdd(&s_hist[key_of(vx[u], vy[u])], 1);
-                ob[p] = i;
-                sb[p] = make_float4(vx[u], vy[u], vz[u], 0.f);
-            }
-        }
-    }
-}
-
-// the workspace of sn2_three_nn_xy, in 32-bit words:  tbl [4 B S] | sorted [4 B T] | hdr [B NN_HDR] | order [B T] |
-// idx_sorted [3 B T] | w_sorted [3 B T]
-static_assert(NN_HDR == 1032, "SN2_THREE_NN_XY_WS_WORDS counts 1032 header words per plot");
-extern "C" int sn2_three_nn_xy_order_offset(int B, int S, int T, size_t* order_words, size_t* copy_words) {
-    if (B <= 0 || S <= 0 || T <= 0 || !order_words) return SN2_EINVAL;
-    *order_words = (size_t)B * (4 * (size_t)S + 4 * (size_t)T + NN_HDR);
-    if (copy_words) *copy_words = *order_words + (size_t)B * T;
-    return 0;
-}
-
-extern "C" int sn2_three_nn_xy_copy(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
-                                    void* ws, int sorted_copy, void* stream) {
-    if (!src_soa || !dst_soa || !idx || !w || !ws || B <= 0 || S <= 0 || T <= 0 || k < 1 || k > 3) return SN2_EINVAL;
-    if (!nn_grid_sources(S) || (((size_t)ws) % 16) != 0) return SN2_ELIMIT;
-    hipStream_t st = (hipStream_t)stream;
-    int G = (int)sqrtf((float)S / 4.f);   // about 4 sources per cell
-    G = G < 2 ? 2 : (G > NN_GMAX ? NN_GMAX : G);
-    float4* tbl = reinterpret_cast<float4*>(ws);
-    float4* sorted = tbl + (size_t)B * S;
-    int* hdr = reinterpret_cast<int*>(sorted + (size_t)B * T);
-    int* order = hdr + (size_t)B * NN_HDR;
-    int* idx_sorted = sorted_copy ? order + (size_t)B * T : nullptr;
-    float* w_sorted = sorted_copy ? reinterpret_cast<float*>(idx_sorted + (size_t)3 * B * T) : nullptr;
-    hipLaunchKernelGGL(nn_grid_build_kernel, dim3(B), dim3(256), 0, st, src_soa, S, G, tbl, hdr);
-    if (sn2_small_sort_wg(B) && T <= 16 * 1024)        // many plots: 256 threads per plot (common.h)
-        hipLaunchKernelGGL((nn_target_sort_chunk_kernel<16, 256>), dim3(B), dim3(256), 0, st, dst_soa, T, (const int*)hdr, order, sorted);
-    else if (T <= 8 * 1024)
-        hipLaunchKernelGGL((nn_target_sort_chunk_kernel<8, 1024>), dim3(B), dim3(1024), 0, st, dst_soa, T, (const int*)hdr, order, sorted);
-    else
-        hipLaunchKernelGGL((nn_target_sort_chunk_kernel<16, 1024>), dim3(B), dim3(1024), 0, st, dst_soa, T, (const int*)hdr, order, sorted);
-    const size_t lds = (size_t)S * 16 + (size_t)(G * G + 1) * 4;
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&three_nn_grid_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    {
-        const int gx = sn2_cdiv(T, 256);
-        static const bool no_xcd = getenv("SN2_NN_NO_XCD") != nullptr;      // (diagnostic switch)
-        if (!no_xcd && (B % 8 == 0 || B >= 64))      // plots balance over the XCDs: XCD-aware placement
-            hipLaunchKernelGGL(three_nn_grid_kernel, dim3(8 * sn2_cdiv(B, 8) * gx), dim3(256), lds, st, (const float4*)tbl,
-                               (const int*)hdr, S, T, k, (const int*)order, (const float4*)sorted, idx, w, B, gx, idx_sorted,
-                               w_sorted);
-        else
-            hipLaunchKernelGGL(three_nn_grid_kernel, dim3(gx, B), dim3(256), lds, st, (const float4*)tbl,
-                               (const int*)hdr, S, T, k, (const int*)order, (const float4*)sorted, idx, w, 0, gx, idx_sorted,
-                               w_sorted);
-    }
-    SN2_RETURN_LAUNCH();
-}
-
-extern "C" int sn2_three_nn_xy(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
-                               void* ws, void* stream) {
-    return sn2_three_nn_xy_copy(src_soa, B, S, dst_soa, T, k, idx, w, ws, 0, stream);
-}
-
-extern "C" int sn2_three_nn(const float* src_soa, int B, int S, const float* dst_soa, int T, int k, int* idx, float* w,
-                            void* ws, const int* dst_fps_ws, void* stream) {
-    if (!src_soa || !dst_soa || !idx || !w || B <= 0 || S <= 0 || T <= 0 || k < 1 || k > 3) return SN2_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    // grid search: needs the targets in the spatial order sn2_fps built for them (workspace laid out as there)
-    if (ws && dst_fps_ws && sn2_three_nn_uses_grid(S, T) && (((size_t)B * T) % 4 == 0) && (((size_t)ws) % 16 == 0)) {
-        int G = (int)sqrtf((float)S / 4.f);   // about 4 sources per cell (2, 3, 8 and 12 per cell measured slower)
-        G = G < 2 ? 2 : (G > NN_GMAX ? NN_GMAX : G);
-        float4* tbl = reinterpret_cast<float4*>(ws);
-        int* hdr = reinterpret_cast<int*>(tbl + (size_t)B * S);
-        hipLaunchKernelGGL(nn_grid_build_kernel, dim3(B), dim3(256), 0, st, src_soa, S, G, tbl, hdr);
-        const size_t lds = (size_t)S * 16 + (size_t)(G * G + 1) * 4;
-        if (lds > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&three_nn_grid_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(three_nn_grid_kernel, dim3(sn2_cdiv(T, 256), B), dim3(256), lds, st, (const float4*)tbl,
-                           (const int*)hdr, S, T, k, dst_fps_ws, reinterpret_cast<const float4*>(dst_fps_ws + (size_t)B * T),
-                           idx, w, 0, sn2_cdiv(T, 256), (int*)nullptr, (float*)nullptr);
-        SN2_RETURN_LAUNCH();
-    }
-    dim3 grid(sn2_cdiv(T, 256), B);
-    hipLaunchKernelGGL(three_nn_kernel, grid, dim3(256), 0, st, src_soa, S, dst_soa, T, k, idx, w);
-    SN2_RETURN_LAUNCH();
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// z-normalisation of a raw plot: z_i - min{ z_j : |xy_i - xy_j| <= r }  -- normalize_z_with_minz_in_a_radius,
-// /root/reference/utils/load_data.py:237-249 (an sklearn kd-tree radius query over x,y, then a python loop over all points).
-// sklearn works on the float64 copies of the coordinates and keeps neighbours with reduced distance
-// (dx*dx + dy*dy, summed in that order) <= r*r, inclusive: the same test is made here in fp64 without contraction.
-// Points are binned into square cells of side r (counting sort through global memory: a raw plot is one variable-length
-// cloud), every point then scans the 3 x 3 cells around its own.
-// ------------------------------------------------------------------------------------------------------------
-namespace {
-__global__ __launch_bounds__(256) void znorm_cell_kernel(const float* __restrict__ x, const float* __restrict__ y, int n,
-                                                         float x0, float y0, float inv, int GX, int GY,
-                                                         int* __restrict__ cell, int* __restrict__ hist) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int cx = (int)((x[i] - x0) * inv), cy = (int)((y[i] - y0) * inv);
-    cx = cx < 0 ? 0 : (cx > GX - 1 ? GX - 1 : cx);
-    cy = cy < 0 ? 0 : (cy > GY - 1 ? GY - 1 : cy);
-    const int c = cy * GX + cx;
-    cell[i] = c;
-    atomicAdd(&hist[c], 1);
-}
-
-// exclusive scan of hist (ncell <= 2^20) by one workgroup; start[c], and cursor[c] = start[c] for the scatter
-__global__ __launch_bounds__(1024) void znorm_scan_kernel(const int* __restrict__ hist, int ncell, int* __restrict__ start,
-                                                          int* __restrict__ cursor) {
-    __shared__ int s_wsum[16];
-    const int tid = threadIdx.x;
-    const int per = (ncell + 1023) / 1024;
-    int sum = 0;
-    for (int k = 0; k < per; ++k) {
-        const int c = tid * per + k;
-        if (c < ncell) sum += hist[c];
-    }
-    int run = block_scan_excl<1024>(sum, s_wsum);
-    for (int k = 0; k < per; ++k) {
-        const int c = tid * per + k;
-        if (c < ncell) {
-            start[c] = run;
-            cursor[c] = run;
-            run += hist[c];
-        }
-    }
-    if (tid == 1023) start[ncell] = run;
-}
-
-__global__ __launch_bounds__(256) void znorm_scatter_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                            const float* __restrict__ z, int n, const int* __restrict__ cell,
-                                                            int* __restrict__ cursor, float4* __restrict__ sorted) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int p = atomicAdd(&cursor[cell[i]], 1);
-    sorted[p] = make_float4(x[i], y[i], z[i], 0.f);
-}
-
-__global__ __launch_bounds__(256) void znorm_query_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                          const float* __restrict__ z, int n, const int* __restrict__ cell,
-                                                          const int* __restrict__ start, const float4* __restrict__ sorted,
-                                                          int GX, int GY, double r2, float* __restrict__ zmin,
-                                                          float* __restrict__ z_out) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double qx = (double)x[i], qy = (double)y[i];
-    const int c = cell[i], cx = c % GX, cy = c / GX;
-    float best = z[i];                                    // the point is its own neighbour (distance 0)
-    for (int yy = (cy > 0 ? cy - 1 : 0); yy <= (cy < GY - 1 ? cy + 1 : GY - 1); ++yy) {
-        const int c_lo = yy * GX + (cx > 0 ? cx - 1 : 0), c_hi = yy * GX + (cx < GX - 1 ? cx + 1 : GX - 1);
-        for (int p = start[c_lo]; p < start[c_hi + 1]; ++p) {     // three adjacent cells of a row are contiguous
-            const float4 s = sorted[p];
-            const double dx = qx - (double)s.x, dy = qy - (double)s.y;
-            const double d2 = dx * dx + dy * dy;
-            if (d2 <= r2) best = fminf(best, s.z);
-        }
-    }
-    if (zmin) zmin[i] = best;
-    if (z_out) z_out[i] = (float)((double)z[i] - (double)best);   // float32 array minus a python list of minima: fp64, then cast
-}
-}  // namespace
-
-extern "C" int sn2_znorm(const float* x, const float* y, const float* z, int n, float radius, float x_min, float y_min,
-                         float x_max, float y_max, int* ws, float* zmin, float* z_out, void* stream) {
-    if (!x || !y || !z || !ws || (!zmin && !z_out) || n <= 0 || !(radius > 0.f) || !(x_max >= x_min) || !(y_max >= y_min))
-        return SN2_EINVAL;
-    // cells of side >= radius (a point's neighbours are then within the 3 x 3 block around its cell)
-    const float inv = 1.0f / (radius * 1.0001f);
-    const long gx = (long)((x_max - x_min) * inv) + 1, gy = (long)((y_max - y_min) * inv) + 1;
-    if (gx * gy > (1L << 20)) return SN2_ELIMIT;
-    const int GX = (int)gx, GY = (int)gy, ncell = GX * GY;
-    hipStream_t st = (hipStream_t)stream;
-    int* cell = ws;                                  // n
-    int* hist = cell + n;                            // ncell
-    int* start = hist + ncell;                       // ncell + 1
-    int* cursor = start + ncell + 1;                 // ncell
-    float4* sorted = reinterpret_cast<float4*>(ws + (((size_t)n + 3 * (size_t)ncell + 1 + 3) & ~(size_t)3));   // 16-byte aligned
-    sn2_fill_words(hist, 0u, (size_t)ncell, st);
-    const int blocks = sn2_cdiv(n, 256);
-    hipLaunchKernelGGL(znorm_cell_kernel, dim3(blocks), dim3(256), 0, st, x, y, n, x_min, y_min, inv, GX, GY, cell, hist);
-    hipLaunchKernelGGL(znorm_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)hist, ncell, start, cursor);
-    hipLaunchKernelGGL(znorm_scatter_kernel, dim3(blocks), dim3(256), 0, st, x, y, z, n, (const int*)cell, cursor, sorted);
-    const double r2 = (double)radius * (double)radius;
-    hipLaunchKernelGGL(znorm_query_kernel, dim3(blocks), dim3(256), 0, st, x, y, z, n, (const int*)cell, (const int*)start,
-                       (const float4*)sorted, GX, GY, r2, zmin, z_out);
-    SN2_RETURN_LAUNCH();
 }

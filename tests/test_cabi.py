@@ -33,6 +33,17 @@ def test_library_builds_loads_and_exports_everything():
     assert set(_lib.SIZE_HELPERS) == set(_declared("size_t")), "ctypes binding and header disagree on the size helpers"
 
 
+def test_build_lists_every_unit_and_header_of_csrc():
+    """HEADERS drives the stale-object check of the build: a header missing from it means silently stale objects, a unit missing
+    from SOURCES entry points that never reach the library."""
+    from stratanet2_vegetation_coverage_maps_amd import _build
+    files = os.listdir(_build.CSRC)
+    assert sorted(f for f in files if f.endswith(".hip")) == sorted(_build.SOURCES)
+    assert sorted(f for f in files if f.endswith(".h")) == sorted(h for h in _build.HEADERS if os.sep not in h)
+    assert len(set(_build.SOURCES)) == len(_build.SOURCES) and len(set(_build.HEADERS)) == len(_build.HEADERS)
+    assert {"ball_query.hip", "three_nn.hip", "znorm.hip"} <= set(_build.SOURCES) and "fps_ws.h" in _build.HEADERS
+
+
 def test_struct_layouts_match_the_header_abi():
     """sizeof of the ctypes mirrors == what a C compiler computes for the header's structs."""
     import subprocess

@@ -1,5 +1,5 @@
-"""The per-plot counting sorts of csrc/geometry.hip (csrc/plot_sort.h) against their definitions, in every template form of
-the kernels and at the smallest sizes that cross a trip boundary of the point loader.  Everything is equality."""
+"""The per-plot counting sorts of csrc/geometry.hip and csrc/three_nn.hip (csrc/plot_sort.h) against their definitions, in every
+template form of the kernels and at the smallest sizes that cross a trip boundary of the point loader.  Everything is equality."""
 import numpy as np
 import pytest
 import torch
