@@ -1106,6 +1106,54 @@ int sn2_tiff_pack(const float *bands, int C, int K, const long long *canvas_host
 int sn2_tiff_pack_stage_max(void);
 int sn2_debug_tiff_pack_form(int form);
 
+/* ---- Parcel shapefiles (host side shp.py: shp.read, shp.write_predictions; the device half below): the ESRI shapefile triple the
+ * reference's parcel job starts from (`shapefile.Reader`, inference/prepare_utils.py:33) and ends with
+ * (`update_shapefile_with_predictions`, inference/predict_utils.py:149-177).  The layout is OUR reading of the ESRI Shapefile
+ * Technical Description (July 1998) and of dBase III, PINNED BY FILES TYPED OUT BY HAND (tests/_shp_cases.py), NOT BY pyshp: neither
+ * pyshp nor shapely was at hand.
+ *
+ * .shp.  A header of 100 bytes: file code 9994, big-endian int32, at byte 0; the file's length in 16-bit words, big-endian int32, at
+ *   byte 24; version 1000, little-endian int32, at byte 28; the shape type, little-endian int32, at byte 32 (the boxes at 36..99 are
+ *   not read).  Then the records.  A record header is 8 bytes, both big-endian int32: the 1-based record number and the content
+ *   length in words.  The content is little-endian: int32 shape type; for a polygon four doubles (the box: x_min, y_min, x_max,
+ *   y_max), int32 NumParts, int32 NumPoints, NumParts int32 Parts[] (the first vertex of every part), NumPoints pairs of doubles
+ *   (x, y).  Shape types read: 0 (null: the content is the type alone), 5 (Polygon), 15 (PolygonZ), 25 (PolygonM); the Z and M blocks
+ *   that follow the points of 15 and 25 are skipped by the content length, not decoded.  Any other type is refused.  The record
+ *   offsets come from walking the .shp itself; the .shx (the same header, then per record the offset and the content length in
+ *   words, big-endian) is not needed to read and is only copied on write.
+ * .dbf.  byte 0 the version, bytes 1..3 the date (YY MM DD), uint32 LE at byte 4 the record count, uint16 LE at byte 8 the header's
+ *   length, uint16 LE at byte 10 the record length L.  From byte 32 field descriptors of 32 bytes: the name (11 bytes, NUL-padded), the
+ *   type at byte 11 (C N F L D), the length at byte 16, the decimals at byte 17; the table ends with 0x0D, which is the header's last
+ *   byte.  Then K records of L bytes, each begun by the deletion flag (' ' or '*'); a trailing 0x1A is optional.  The record count
+ *   equals the .shp's.
+ * WRITTEN.  .shp, .shx, .prj and .cpg are copied byte for byte.  The .dbf header is the source's with header_len += 32 n,
+ *   record_len += n size and n descriptors of type F (length `size`, `decimal` decimals) before the 0x0D; the date stays, so the same
+ *   input gives the same bytes.  Every record is the source's L bytes followed by the n fields below; one 0x1A closes the file.
+ *
+ * dBase records, annotated (csrc/dbf.hip; the rule's functions: csrc/dbf_rules.h; host side hip_ops.dbf_annotate).
+ * OUTPUT.  Record k, 0 <= k < K, has Ld = L + n size bytes: bytes [0, L) are source record k's, then field f = 0..n-1 in `size` bytes.
+ * VALUE.  row = row_of[k] (device, K int32); row < 0 or row >= R: v = missing; else v = values[row C + cols[f]] (values: device, (R,C)
+ *   fp64; cols: HOST, n ints, any order).
+ * FIELD.  text = the decimal expansion of the EXACT binary value of v rounded half-to-even at `decimal` places -- what CPython's
+ *   format(v, ".<decimal>f") and glibc's printf("%.<decimal>f") print -- made with integer arithmetic only (mantissa and exponent
+ *   from the bits, a 64 x 64 -> 128-bit product, shifts, divisions by constants): no floating-point operation touches v.  The sign is
+ *   '-' whenever the sign bit is set: -0.0 and a negative that rounds to zero print -0.000...  decimal = 0 prints no point.  A NaN
+ *   prints nan (either sign), the infinities inf and -inf.  field = text[:size] right-justified with spaces.  A finite
+ *   |v| >= 2^53 fills the field with '*' (the dBase overflow convention; CPython would print such a value exactly, we do not) and
+ *   adds 1 to the overflow count.
+ * DST.  16-byte aligned; K Ld bytes of records, then on the next multiple of 8 the uint64 overflow count, INITIALISED BY THE CALLER
+ *   (0) on the stream: dst_bytes >= (K Ld rounded up to 8) + 8, and ONE device-to-host read fetches records and count.  The padding
+ *   before the counter is never written.
+ * ONE launch on `stream`, ONE kernel form: the output is a stream of K Ld bytes cut into tiles of 16 KiB; a workgroup composes its
+ * tile in LDS (the copied bytes by consecutive lanes on consecutive bytes, a lane per field) and the tile leaves with 16-byte
+ * stores.  wave64; vector stores only; no floating-point atomics; the count is one integer atomic per workgroup after a per-wave
+ * reduction; no cross-workgroup waiting; nothing read back: safe to capture.
+ * ERRORS, before any launch: SN2_EINVAL on a NULL pointer, K <= 0, R <= 0, C <= 0, L outside 1..65535, size outside 1..254,
+ * decimal outside 0..15 or decimal + 2 > size, n outside 1..255, a cols entry outside [0, C), L + n size > 65535, dst not 16-byte
+ * aligned, dst_bytes too small; SN2_ELIMIT on K > 2^40, R >= 2^31 or more than 2^31 - 1 tiles. */
+int sn2_dbf_annotate(const void *src_records, long K, int L, const double *values, long R, int C, const int *row_of, const int *cols,
+                     int n, int size, int decimal, double missing, void *dst, size_t dst_bytes, void *stream);
+
 /* ---- Parcel cut (csrc/cut.hip; the rule's functions: csrc/cut_rules.h; host side parcel.cut_parcels, las.load_parcels): the points
  * of a LAS tile cut into K parcel clouds by the parcels' polygons buffered by b metres -- what the reference's
  * `parcelles_dataset_20m` holds as one file per parcel (b = 20, inference/prepare_utils.py:148).

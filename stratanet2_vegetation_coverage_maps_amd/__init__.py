@@ -20,6 +20,7 @@ from .las import LasHeader, load_las, load_parcel_clouds, load_parcels, load_plo
 from . import geotiff  # noqa: F401
 from . import ortho  # noqa: F401
 from .ortho import ColorizeResult, OrthoImage, OrthoSet  # noqa: F401
+from . import shp  # noqa: F401
 
 __all__ = ["PointNet2", "project_to_plotwise_coverages", "project_to_2d_rasters", "project_batch_to_2d_rasters", "ParcelPlots",
            "parcel_plot_centers", "polygon_keep", "prepare_parcel", "predict_parcel_cloud", "subsample", "subsample_form",
@@ -27,4 +28,4 @@ __all__ = ["PointNet2", "project_to_plotwise_coverages", "project_to_2d_rasters"
            "pseudo_label_parcel", "pretrain_split", "ParcelSet", "ParcelClouds", "prepare_parcels", "predict_parcels", "MosaicAtlas", "AtlasReport",
            "evaluate_table", "kfold_indices", "indicators", "CrossValReport", "cross_validate", "las", "LasHeader",
            "load_las", "load_plot", "load_parcel_clouds", "ParcelCut", "cut_parcels", "load_parcels", "geotiff", "ortho",
-           "OrthoImage", "OrthoSet", "ColorizeResult"]
+           "OrthoImage", "OrthoSet", "ColorizeResult", "shp"]

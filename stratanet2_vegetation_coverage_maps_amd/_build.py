@@ -16,9 +16,9 @@ LIB = os.path.join(CSRC, "libstrata_hip.so")
 VARIANT_DIR = os.path.join(os.path.dirname(HERE), "build", "variants")      # (build/ is ignored by git)
 SOURCES = ["geometry.hip", "ball_query.hip", "three_nn.hip", "znorm.hip", "sa.hip", "sa_mfma.hip", "fp.hip", "interp_index.hip", "global_level.hip", "global_level_bwd.hip", "head.hip", "project.hip",
            "loss.hip", "misc.hip", "net.hip", "parcel.hip", "parcels.hip", "sample.hip", "kde.hip", "feed.hip", "plotset.hip", "atlas.hip", "indicators.hip", "points.hip",
-           "admissibility.hip", "las.hip", "cut.hip", "las_write.hip", "tiff_pack.hip", "ortho.hip"]
+           "admissibility.hip", "las.hip", "cut.hip", "las_write.hip", "tiff_pack.hip", "ortho.hip", "dbf.hip"]
 HEADERS = ["common.h", "philox.h", "mlp.h", "fp_rows.h", "global_level.h", "loss_rules.h", "mosaic_rules.h", "projection_rules.h", "parcel_rules.h", "plot_sort.h", "fps_ws.h", "point_rules.h",
-           "atlas_table.h", "admissibility_rules.h", "las_rules.h", "cut_rules.h", "las_write_rules.h", "tiff_rules.h", "ortho_rules.h", os.path.join("..", "..", "include", "strata_hip.h")]
+           "atlas_table.h", "admissibility_rules.h", "las_rules.h", "cut_rules.h", "las_write_rules.h", "tiff_rules.h", "ortho_rules.h", "dbf_rules.h", os.path.join("..", "..", "include", "strata_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"] + os.environ.get("SN2_EXTRA_HIPCC_FLAGS", "").split()
 
 

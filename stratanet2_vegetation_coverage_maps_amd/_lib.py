@@ -281,6 +281,9 @@ SIGNATURES = {
     "sn2_tiff_pack": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     "sn2_tiff_pack_stage_max": [],
     "sn2_debug_tiff_pack_form": [c_int],
+    # the dBase record annotator (csrc/dbf.hip); cols is a host pointer
+    "sn2_dbf_annotate": [c_void_p, c_long, c_int, c_void_p, c_long, c_int, c_void_p, POINTER(c_int), c_int, c_int, c_int, c_double, c_void_p,
+                         ctypes.c_size_t, c_void_p],
     # the parcel cut (csrc/cut.hip); drop is a host pointer, the table holds host and device pointers
     "sn2_cut_ws_words": [POINTER(CutTable), POINTER(ctypes.c_size_t)],
     "sn2_cut_count": [c_void_p, c_void_p, c_void_p, POINTER(CutTable), c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],

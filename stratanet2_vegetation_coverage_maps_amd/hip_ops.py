@@ -2278,6 +2278,57 @@ def tiff_pack(band_arena, C: int, table: AtlasTable, layout: int = 0, predictor:
     return packed
 
 
+# ---- the dBase record annotator (include/strata_hip.h, "dBase records, annotated"; csrc/dbf.hip) ------------------------------------
+class DbfAnnotated:
+    """What sn2_dbf_annotate leaves on the device: `buf` (uint8) holds the K records of Ld bytes and, on the next multiple of 8, the
+    uint64 overflow count.  `read()` is the ONE device-to-host copy; after it `records` is the (K, Ld) uint8 view of the host copy
+    and `overflow` the number of fields filled with '*'."""
+
+    def __init__(self, buf, K, Ld):
+        self.buf, self.K, self.Ld = buf, K, Ld
+        self.counter_at = (K * Ld + 7) // 8 * 8
+        self.total = self.counter_at + 8
+        self.host = self.records = self.overflow = None
+
+    def read(self) -> "DbfAnnotated":
+        if self.host is None:
+            self.host = self.buf[:self.total].cpu().numpy()
+            self.records = self.host[:self.K * self.Ld].reshape(self.K, self.Ld)
+            self.overflow = int(self.host[self.counter_at:self.total].view(np.uint64)[0])
+        return self
+
+
+def dbf_annotate(records, values, row_of, cols, size: int = 50, decimal: int = 10, missing: float = -1.0, out=None) -> DbfAnnotated:
+    """include/strata_hip.h: sn2_dbf_annotate.  records (K,L) uint8, values (R,C) fp64, row_of (K,) int32 (-1 = no row: `missing`),
+    all contiguous on one device; cols: n host ints, the column of `values` each appended field is formatted from.  out: None or a
+    1-D uint8 device tensor, 16-byte aligned, of at least K (L + n size) rounded up to 8, plus 8 bytes.  The overflow count is
+    zeroed here, on the stream; then ONE launch, no read-back."""
+    _chk(records, torch.uint8, None, "records")
+    if records.dim() != 2 or records.shape[0] < 1 or records.shape[1] < 1:
+        raise ValueError(f"records: expected (K,L) uint8 with K, L >= 1, got {tuple(records.shape)}")
+    _chk(values, torch.float64, None, "values")
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1 or values.device != records.device:
+        raise ValueError(f"values: expected (R,C) fp64 with R, C >= 1 on the records' device, got {tuple(values.shape)}")
+    K, L = records.shape
+    R, C = values.shape
+    _chk(row_of, I32, (K,), "row_of")
+    if row_of.device != records.device:
+        raise ValueError("row_of: must be on the records' device")
+    cols = [int(c) for c in cols]
+    n, size, decimal = len(cols), int(size), int(decimal)
+    Ld = L + n * size
+    counter_at = (K * Ld + 7) // 8 * 8
+    if out is None:
+        out = torch.empty(counter_at + 8, dtype=torch.uint8, device=records.device)
+    _chk(out, torch.uint8, None, "out")
+    if out.dim() != 1 or out.device != records.device or out.numel() < counter_at + 8:
+        raise ValueError(f"out: expected a 1-D byte tensor of at least {counter_at + 8} bytes on the records' device")
+    out[counter_at:counter_at + 8].zero_()
+    _call("sn2_dbf_annotate", _ptr(records), K, L, _ptr(values), R, C, _ptr(row_of), (ctypes.c_int * max(n, 1))(*cols), n, size, decimal,
+          float(missing), _ptr(out), out.numel(), _stream())
+    return DbfAnnotated(out, K, Ld)
+
+
 # ---- the parcel cut (include/strata_hip.h, "Parcel cut"; csrc/cut.hip) -------------------------------------------------------------
 CUT_ROW_POINTS = 2048         # points per wave of the count / fill passes (parcel.ROW_POINTS)
 CUT_MAX_TABLE = 1 << 26       # (parcel, row) entries of the count table before rows get longer (parcel.MAX_TABLE)
